@@ -337,6 +337,20 @@ def aggregate(dt, units_local, dist=None, device="cpu"):
     return float(t.item()), int(round(float(u.item())))
 
 
+def dump_outputs(out_dir, arrays, max_bytes=64 * 10**6):
+    """--dump-outputs: every [B, ...] array as out_dir/<name>.npy in float32 (the token ids are exact in float32).  When the arrays
+    hold more than max_bytes in all, the same fixed, seeded sample of the B rows is written for every array."""
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    B = len(next(iter(host.values())))
+    keep = min(B, (max_bytes - 4096) // sum(v[0].nbytes for v in host.values()))
+    rows = np.sort(np.random.RandomState(0).choice(B, keep, replace=False)) if keep < B else np.arange(B)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in host.items():
+        np.save(os.path.join(out_dir, k + ".npy"), v[rows])
+    log(f"outputs of the last timed step -> {out_dir}: " + ", ".join(f"{k}{list(v[rows].shape)}" for k, v in host.items())
+        + ("" if keep == B else f" ({keep} of {B} rows, seeded sample)"))
+
+
 def main():
     if "--workload" in sys.argv:
         wl = sys.argv[sys.argv.index("--workload") + 1]
@@ -366,7 +380,11 @@ def main():
     ap.add_argument("--no-train-leg", action="store_true", help="skip the short training-step leg (bench_train.py in child ranks) that fills `train_step`")
     ap.add_argument("--workload", default="t2i", help="t2i (default, the headline metric) | train (bench_train.py: stage-1 step time) | "
                     "t2i512 | mmu (bench_configs.py: BASELINE configs[2] / configs[3])")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned (image tokens, decoded images) as "
+                    "DIR/<name>.npy in float32, for output-for-output comparison of two builds on the same seeded inputs")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     self_launch(a.gpus, __file__)
     if dry_run():
         return dry_main(a)
@@ -408,16 +426,16 @@ def main():
         toks = model.t2i_generate(input_ids=ids, uncond_input_ids=iu_d, attention_mask=mask_d, temperature=1.0, timesteps=18,
                                   guidance_scale=5.0, generator=gen, config=cfg, use_graph=a.graph, reuse_prefix=not a.no_prefix_reuse)
         toks = torch.clamp(toks, max=codebook - 1, min=0)
-        return vq.decode_code(toks)
+        return toks, vq.decode_code(toks)
 
     img = None
     for i in range(a.warmup):
         t1 = time.time()
-        img = step()
+        _, img = step()
         torch.cuda.synchronize()
         log(f"warmup step {i}: {time.time() - t1:.2f}s")
     if img is None:
-        img = step()
+        _, img = step()
     assert tuple(img.shape) == (B, 3, 256, 256) and torch.isfinite(img).all()
 
     def barrier():
@@ -431,10 +449,13 @@ def main():
     barrier()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        step()
+        last = step()
     barrier()
     dt = time.perf_counter() - t0
     log(f"timed {a.steps} steps in {dt:.2f}s")
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, dict(zip(("tokens", "images"), last)))
+    del last
     dt, images = aggregate(dt, B * a.steps, dist, "cuda")
     # ---- roofline leg (same process, right after): the same steps with every n-th launch of each kernel kind bracketed by HIP
     # events on the launch stream; event timing makes the engine launch eagerly (a graph replay has no per-kernel events)

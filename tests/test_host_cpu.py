@@ -435,10 +435,33 @@ def test_bench_gpus_flag_fails_loudly_without_enough_gpus():
         r = subprocess.run([sys.executable, os.path.join(ROOT, script), "--gpus", "64", "--steps", "1", "--warmup", "0"], env=env,
                            capture_output=True, text=True, timeout=300)
         assert r.returncode != 0 and "--gpus 64 requested" in (r.stderr + r.stdout), (script, r.stderr[-500:])
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0"], env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode != 0 and "--steps must be at least 1" in r.stderr
     env["WORLD_SIZE"] = "2"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "1", "--warmup", "0"], env=env,
                        capture_output=True, text=True, timeout=300)
     assert r.returncode != 0 and "WORLD_SIZE=2" in (r.stderr + r.stdout)
+
+
+def test_bench_dump_outputs_float32_within_budget(tmp_path):
+    """--dump-outputs: each array as <name>.npy in float32; over the byte budget, the same seeded rows of every array"""
+    import sys
+    sys.path.insert(0, util.ROOT)
+    import bench
+    toks = torch.arange(6 * 4, dtype=torch.int64).view(6, 4)
+    img = torch.randn(6, 3, 8, 8)
+    bench.dump_outputs(str(tmp_path / "all"), {"tokens": toks, "images": img})
+    t, i = np.load(tmp_path / "all" / "tokens.npy"), np.load(tmp_path / "all" / "images.npy")
+    assert t.dtype == np.float32 and i.dtype == np.float32
+    assert np.array_equal(t, toks.numpy()) and np.array_equal(i, img.numpy())
+    row = 4 * 4 + 3 * 8 * 8 * 4
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"tokens": toks, "images": img}, max_bytes=4096 + 3 * row)
+    ta, ia = np.load(tmp_path / "a" / "tokens.npy"), np.load(tmp_path / "a" / "images.npy")
+    assert ta.shape == (3, 4) and ia.shape == (3, 3, 8, 8)
+    assert np.array_equal(ta, np.load(tmp_path / "b" / "tokens.npy")) and np.array_equal(ia, np.load(tmp_path / "b" / "images.npy"))
+    rows = (ta[:, 0] // 4).astype(int)  # the sampled rows, the same for both arrays
+    assert np.array_equal(ia, img.numpy()[rows])
 
 
 def test_bench_training_leg_child_launch(monkeypatch):

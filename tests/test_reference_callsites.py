@@ -22,7 +22,7 @@ from util import O
 
 REF = "/root/reference"
 SCRIPTS = ["inference_t2i.py", "inference_mmu.py", "training/train.py", "training/train_w_clip_vit.py"]
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree is only present in the build container")
+needs_reference = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree is only present in the build container")
 
 # reference module -> where the name lives in this package; names of a mapped module that are control plane
 # (config loading, logging meters) stay the reference's own and are listed as such
@@ -180,6 +180,7 @@ def _walk_script(path, objs, P):
     return problems, seen
 
 
+@needs_reference
 def test_every_reference_call_site_binds_against_showo_amd():
     P = util.pkg()
     objs = _instances()
@@ -222,6 +223,7 @@ def test_noise_schedule_and_prompting_objects_behave_as_the_scripts_use_them():
     assert m.showo.model.embed_tokens.weight.dtype == torch.float32
 
 
+@needs_reference
 def test_the_walker_reports_a_broken_surface(monkeypatch):
     """non-vacuity: with a keyword of `mmu_generate` renamed, an attribute of the model dropped and a special token missing, the walk
     names the reference lines that would break"""
