@@ -102,11 +102,39 @@ def showo_state_spec(d: ShowoDims):
     return sp
 
 
-def make_showo_state(d: ShowoDims, seed: int = 0, dtype=np.float32):
+def make_showo_state(d: ShowoDims, seed: int = 0, dtype=np.float32, profile: str = "default"):
+    """profile "default": N(std, mean) per tensor (the golden fixtures depend on this stream).  "heavy": the same draw, then
+    heavy_tails() on top -- activations at the fp16 range limit for the precision-2 edge tests."""
+    if profile not in ("default", "heavy"):
+        raise ValueError(f"unknown weight profile {profile!r}")
     rs = np.random.RandomState(seed)
     sd = OrderedDict()
     for k, (shape, std, mean) in showo_state_spec(d).items():
         sd[k] = (rs.standard_normal(size=shape) * std + mean).astype(dtype)
+    if profile == "heavy":
+        heavy_tails(sd, d, seed)
+    return sd
+
+
+HEAVY_CHANNELS = 3  # outlier hidden channels of the "heavy" profile
+
+
+def heavy_tails(sd, d: ShowoDims, seed: int = 0):
+    """In place: the activation statistics of a trained LLM that random N(0, 0.02) weights lack, from a stream of its own (the
+    default draw is untouched).  A few outlier hidden channels (x100 in the embedding and in the fc2 rows that write them), LayerNorm
+    gains >> 1 on those channels (the LayerNorm outputs h, and through them v and fc1, reach the fp16 limit of 65504), and a peaked
+    lm_head (a few vocabulary rows x20)."""
+    rs = np.random.RandomState(seed + 7919)
+    H = d.hidden
+    ch = rs.choice(H, size=HEAVY_CHANNELS, replace=False)
+    sd["showo.model.embed_tokens.weight"][:, ch] *= 100.0
+    for i in range(d.layers):
+        p = f"showo.model.layers.{i}."
+        sd[p + "mlp.fc2.weight"][ch, :] *= 100.0
+        sd[p + "input_layernorm.weight"][ch] *= np.float32(4000.0 * (1 + i))
+    sd["showo.model.final_layernorm.weight"][ch] *= 50.0
+    rows = rs.choice(d.vocab, size=8, replace=False)
+    sd["showo.lm_head.weight"][rows] *= 20.0
     return sd
 
 

@@ -69,12 +69,15 @@ __device__ inline uint32_t pack_bf2(float lo, float hi) {
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
 constexpr float F16_MAX = 65504.0f;
-// one v_med3_f32 per value.  (A NaN comes out as -65504 -- v_med3 returns the minimum when an input is NaN; the fp32 residual stream and
-// the fp32 GEMM accumulators are never converted, so a NaN that reaches x still reaches the logits; the range check counts |x| = 65504.)
+// one v_med3_f32 per value plus a NaN pass-through: v_med3 returns the minimum when an input is NaN, and a NaN born in a 16-bit
+// activation must reach the logits as a NaN, not as -65504 (the range check counts |x| = 65504, inf and NaN).
 #if defined(SHOWO_F16_NOSAT)  // A/B build only (what the saturation costs); never the shipped library
 __device__ inline float sat_f16(float x) { return x; }
 #else
-__device__ inline float sat_f16(float x) { return __builtin_amdgcn_fmed3f(x, -F16_MAX, F16_MAX); }
+__device__ inline float sat_f16(float x) {
+    const float c = __builtin_amdgcn_fmed3f(x, -F16_MAX, F16_MAX);
+    return x != x ? x : c;
+}
 #endif
 template <bool F16>
 struct Op16;
@@ -98,8 +101,9 @@ struct Op16<true> {
         const f32x2_t v = {sat_f16(lo), sat_f16(hi)};
         return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, f16x2_t));  // the compiler's own fptrunc (RNE), visible to the hazard recognizer
     }
-    // values bounded by construction (soft-max numerators <= e^8, convex combinations of already converted values): no clamp --
-    // in the attention kernels the clamp of P cost 5 % of the kernel (profiles/r6_f16_saturation_ab.txt)
+    // values bounded by construction (soft-max numerators <= e^8): no clamp -- in the attention kernels the clamp of P cost 5 % of the
+    // kernel (profiles/r6_f16_saturation_ab.txt).  NOT for the attention output: P is rounded while the denominator sums the unrounded
+    // numerators, so O = sum(P V) / l can exceed max|V| by a rounding step and overflow at |V| near 65504 (O stores use pack2).
     static __device__ __forceinline__ uint32_t pack2_bounded(float lo, float hi) {
         const f32x2_t v = {lo, hi};
         return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, f16x2_t));

@@ -505,8 +505,9 @@ extern "C" int showo_engine_batch_begin(showo_engine* e, int nb, int cap_tokens)
         TRY(e->alloc(&d->vt, need));
         d->elems = need;
         // zeroed ONCE, when the caches are (re)allocated (the two memsets -- 600 MB at cfg4 -- ran on every call): columns of
-        // V^T beyond a sequence's live length only ever meet probabilities that are exactly 0, so they must be FINITE, not zero, and
-        // whatever an earlier batch left there is (a cache row is written by prefill / decode steps of finite activations)
+        // V^T beyond a sequence's live length only ever meet probabilities that are exactly 0, so they must be FINITE, not zero; what an
+        // earlier batch left there need not be (a NaN activation), so each prefill re-zeroes the columns its last key tile reads
+        // (engine_prefill_into), and the decode steps never multiply columns beyond the live length
         SHOWO_CHECK_HIP(hipMemset(d->k, 0, (size_t)need * sizeof(bf16_t)));
         SHOWO_CHECK_HIP(hipMemset(d->vt, 0, (size_t)need * sizeof(bf16_t)));
     }

@@ -52,6 +52,11 @@ __global__ void rows_index_kernel(int32_t* rows, int nseq, int L, int img_start,
 __global__ void set_iv_kernel(int32_t* iv, int a, int b, int c, int d) {
     if (threadIdx.x == 0) { iv[0] = a; iv[1] = b; iv[2] = c; iv[3] = d; }
 }
+// V^T columns [c0, c1) of every (layer, head, d) row of one sequence's cache: grid (nH * 64 rows, layers), row pitch = Lp
+__global__ void zero_vt_cols_kernel(bf16_t* vt, int64_t lstride, int Lp, int c0, int c1) {
+    bf16_t* r = vt + blockIdx.y * lstride + (int64_t)blockIdx.x * Lp;
+    for (int c = c0 + threadIdx.x; c < c1; c += blockDim.x) r[c] = 0;
+}
 // ---- t2i prefix reuse: rows [0, prefix) of every sequence (pads + text; causal, never see an image column) are step-invariant
 __global__ void gather_ids_kernel(const int64_t* __restrict__ all, int64_t* __restrict__ act, int nseq, int L, int prefix) {
     const int La = L - prefix;
@@ -192,6 +197,7 @@ static int cast_w(showo_engine* e, const std::string& key, bf16_t* dst, bf16_t* 
                   bool is_head = false) {
     if (n != expect) return set_error_msg(2, "engine_load: element count mismatch");
     if ((e->precision == 1 || (e->precision == 2 && is_head)) && dst_lo) {
+        if (!is_head) e->img_f16 = false;  // the hi half is a bf16 image (a precision-2 engine switched to 1 must not keep the fp16 flag)
         int rc = showo_split_f32_bf16(src, dst, dst_lo, n, s);
         if (!rc) e->lo_loaded.insert(key);
         return rc;
@@ -982,7 +988,10 @@ extern "C" int showo_engine_t2i_generate(showo_engine* e, int64_t* ids_cond, int
     // once (first-use attributes, GEMM tile tuning) outside the capture; step 0 always runs eagerly.  Not combined with per-launch
     // event timing.
     const int n_eager = reuse ? 2 : 1;
-    const bool graph = (use_graph & 1) && steps > n_eager && !showo::g_prof_on_query() && (e->precision == 0 || e->precision == 2 || pfast);
+    // A registered range-check counter forces the eager path: its launches (and the caller's counter pointer) must not be baked into a
+    // cached graph that later plain calls replay, and a replayed cached graph would skip them.
+    const bool graph = (use_graph & 1) && steps > n_eager && !showo::g_prof_on_query() && (e->precision == 0 || e->precision == 2 || pfast) &&
+                       !(e->range_count && e->precision == 2);
     if (!graph) {
         for (int step = 0; step < steps; ++step) TRY(denoise_step(step, step == 0 || !reuse));
     } else {
@@ -1119,6 +1128,18 @@ int engine_prefill_into(showo_engine* e, const int64_t* ids, const float* embeds
         iv = e->iv; flag = e->flag;
     } else if (e->ext_iv) {  // caller-built intervals (showo_engine_use_intervals, e.g. from showo_mask_mmu_vit)
         iv = e->ext_iv; flag = e->ext_flag;
+    }
+    // The prefill attention multiplies the V^T columns of its last 64-key tile beyond L by P = 0, which is 0 only if they are finite.
+    // The projection epilogue of >= 256-row prefills writes columns [0, L) alone, and a cache is zeroed once, when it is allocated: an
+    // earlier, longer prompt with a NaN activation may have left NaN in [L, 64 * ceil(L / 64)).
+    const int c1 = ((L + 63) / 64) * 64 < cap ? ((L + 63) / 64) * 64 : cap;
+    if (c1 > L) {
+        zero_vt_cols_kernel<<<dim3(e->nH * 64, e->nL), 64, 0, s>>>(vt, v_lstride, cap, L, c1);
+        SHOWO_CHECK_HIP(hipGetLastError());
+        if (vt_lo) {
+            zero_vt_cols_kernel<<<dim3(e->nH * 64, e->nL), 64, 0, s>>>(vt_lo, v_lstride, cap, L, c1);
+            SHOWO_CHECK_HIP(hipGetLastError());
+        }
     }
     TRY(run_layers(e, 1, L, 0, KVDest{k, vt, k_lstride, v_lstride, cap, cap, k_lo, vt_lo}, iv, flag, mask, s));
     if (iv) {
