@@ -632,6 +632,12 @@ int showo_train_backward(showo_trainer* t, const int64_t* labels, int b_t2i, int
  * exchange of a finished bucket while the next phase runs */
 int showo_train_backward_head(showo_trainer* t, const int64_t* labels, int b_t2i, int b_lm, int b_mmu, int max_seq_len,
                               float g_t2i, float g_lm, float g_mmu, void* stream);
+/* showo_train_backward_head with the three loss weights read from device memory g3 fp32 [3] = (g_t2i, g_lm, g_mmu) instead of host
+ * scalars: the autograd path, where they are the incoming gradients of the three losses (training/train.py:600 builds the weighted
+ * loss, :612 calls accelerator.backward on it) and the host never reads them.  Same as showo_train_backward_head without an announced
+ * d(logits) (showo_train_set_loss_weights): its own cross-entropy pass, bit-identical d(logits) for equal weight values. */
+int showo_train_backward_head_dev(showo_trainer* t, const int64_t* labels, int b_t2i, int b_lm, int b_mmu, int max_seq_len,
+                                  const float* g3, void* stream);
 int showo_train_backward_layer(showo_trainer* t, int layer, void* stream);
 int showo_train_backward_embed(showo_trainer* t, void* stream);
 /* Announce the loss weights (training/train.py:600: loss = w_t2i*loss_t2i + w_lm*loss_lm + w_mmu*loss_mmu) BEFORE the forward:
@@ -646,6 +652,9 @@ int showo_train_bucket(showo_trainer* t, int bucket, float** ptr, int64_t* n);
 int showo_train_grad(showo_trainer* t, const char* key, float** ptr, int64_t* n);
 int showo_train_grad_copy(showo_trainer* t, const char* key, float* dst, int64_t n, void* stream);
 int showo_train_losses(showo_trainer* t, float* out3, void* stream);
+/* number of training forwards started on this trainer (showo_train_forward / _embeds): a host-driven backward checks that the
+ * saved activations are still those of its own forward; -1 for a NULL handle */
+int64_t showo_train_generation(showo_trainer* t);
 /* optimizer (torch.optim.AdamW with the reference's two parameter groups, training/train.py:205-231): register the fp32
  * master tensor and the two moment buffers of a state-dict key once, then one call per step updates every parameter from
  * the gradients of the last backward and refreshes the engine's bf16 weight images. */

@@ -66,6 +66,7 @@ _PROTOS = {
     "showo_train_input_grad": [c_p, c_p, c_i64, c_p],
     "showo_train_backward": [c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_p],
     "showo_train_backward_head": [c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_f, c_f, c_p],
+    "showo_train_backward_head_dev": [c_p, c_p, c_i, c_i, c_i, c_i, c_p, c_p],
     "showo_train_backward_layer": [c_p, c_i, c_p],
     "showo_train_backward_embed": [c_p, c_p],
     "showo_train_set_loss_weights": [c_p, c_f, c_f, c_f, c_i],
@@ -187,7 +188,7 @@ _PROTOS = {
     "showo_prof_set_stride": [c_i],
     "showo_prof_totals": [c_i, c_p, c_p],
 }
-_I64 = {"showo_gemm_tiled_elems": [c_i, c_i], "showo_conv3t_launches": []}
+_I64 = {"showo_gemm_tiled_elems": [c_i, c_i], "showo_conv3t_launches": [], "showo_train_generation": [c_p]}
 _VOID = {"showo_engine_destroy": [c_p], "showo_vq_destroy": [c_p], "showo_train_destroy": [c_p], "showo_clip_destroy": [c_p], "showo_projector_destroy": [c_p]}
 EXPORTED_SYMBOLS = sorted(list(_PROTOS) + list(_VOID) + list(_I64) + ["showo_last_error"])
 

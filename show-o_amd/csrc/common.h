@@ -308,4 +308,8 @@ struct AdamSeg { float *p, *m, *v; const float* g; bf16_t* dst16; float* dst32; 
 constexpr int64_t ADAM_CHUNK = 65536;  // elements per block
 int adamw_multi_launch(const AdamSeg* segs, const int* seg_of, const int64_t* start_of, int nchunks, float lr, float beta1, float beta2,
                        float eps, float weight_decay, int step, hipStream_t s);
+// cross-entropy backward pass with the three loss weights read from device memory g3[3] (train_kernels.hip)
+int ce_loss_dev_weights(const float* logits, int ldl, const int64_t* labels, int B, int L, int V, int b_t2i, int b_lm, int b_mmu,
+                        int max_seq_len, const float* g3, void* rows_ws, int* counts, float* rowloss, uint16_t* dlogits, int ldd,
+                        hipStream_t s);
 }  // namespace showo

@@ -77,6 +77,7 @@ struct showo_trainer {
     // state of the last forward
     int B = 0, Lq = 0;
     bool have_fwd = false;
+    uint64_t generation = 0;  // training forwards started (showo_train_generation)
     bool has_mask = false;
     bool from_embeds = false;  // last forward started from caller-provided embeddings: d(loss)/d(embeddings) = dy
     bool weights_synced = false;
@@ -271,6 +272,7 @@ static int train_forward_impl(showo_trainer* t, const int64_t* ids, const float*
                               void* stream) {
     hipStream_t s = (hipStream_t)stream;
     if (!t || ((ids == nullptr) == (embeds == nullptr))) return set_error_msg(1, "train_forward: exactly one of ids / embeds");
+    ++t->generation;
     showo_engine* e = t->e;
     if (showo_engine_missing(e) != 0) return set_error_msg(4, "train: weights missing");
     if (B > t->maxB || L > t->maxL || (int64_t)B * L > t->Tmax) return set_error_msg(5, "train: batch exceeds the trainer workspace");
@@ -396,17 +398,9 @@ extern "C" int showo_train_input_grad(showo_trainer* t, float* out, int64_t n, v
     const int32_t* iv = t->has_mask ? e->iv : nullptr;                                                                \
     (void)F; (void)V; (void)nH; (void)Vp; (void)Tp; (void)Lp; (void)iv; (void)s;
 
-extern "C" int showo_train_backward_head(showo_trainer* t, const int64_t* labels, int b_t2i, int b_lm, int b_mmu, int max_seq_len,
-                                         float g_t2i, float g_lm, float g_mmu, void* stream) {
+// the head phase after d(logits) is in t->dlogits: lm_head weight / bias gradients, d(final LayerNorm), dy of the top block
+static int backward_head_from_dlogits(showo_trainer* t, void* stream) {
     BW_PROLOGUE
-    if (!labels) return set_error_msg(1, "train_backward: labels required");
-    // ---- loss + head
-    const bool have_dl = t->dl_valid && t->dl_labels == labels && t->dl_g[0] == g_t2i && t->dl_g[1] == g_lm && t->dl_g[2] == g_mmu &&
-                         t->dl_split[0] == b_t2i && t->dl_split[1] == b_lm && t->dl_split[2] == b_mmu && t->dl_split[3] == max_seq_len;
-    t->dl_valid = false;  // dlogits^T below reuses nothing of it, but a second backward must not trust a consumed flag blindly
-    if (!have_dl)
-        TRY(showo_ce_loss(t->logits, V, labels, B, L, V, b_t2i, b_lm, b_mmu, max_seq_len, g_t2i, g_lm, g_mmu, t->ce_rows, t->counts,
-                          t->rowloss, t->dlogits, Vp, nullptr, s));
     if (train_tn()) {
         TRY(showo_colsum_bf16(t->dlogits, Vp, T, Vp, t->colpart, t->gblm, 0, s));                                        // lm_head bias grad
         TRY(showo_gemm_tn_bf16(t->dlogits, Vp, e->hf, H, t->gwlm, H, V, H, T, 0, 1, s));                                    // dWlm [V,H]
@@ -423,6 +417,36 @@ extern "C" int showo_train_backward_head(showo_trainer* t, const int64_t* labels
     TRY(showo_ln_bwd(e->x, e->fln_w, t->dh, t->dy, t->dy, t->dy16, t->lnpart, t->gfln, T, H, e->cfg.ln_eps, s));
     return 0;
 }
+
+extern "C" int showo_train_backward_head(showo_trainer* t, const int64_t* labels, int b_t2i, int b_lm, int b_mmu, int max_seq_len,
+                                         float g_t2i, float g_lm, float g_mmu, void* stream) {
+    BW_PROLOGUE
+    if (!labels) return set_error_msg(1, "train_backward: labels required");
+    // ---- loss + head
+    const bool have_dl = t->dl_valid && t->dl_labels == labels && t->dl_g[0] == g_t2i && t->dl_g[1] == g_lm && t->dl_g[2] == g_mmu &&
+                         t->dl_split[0] == b_t2i && t->dl_split[1] == b_lm && t->dl_split[2] == b_mmu && t->dl_split[3] == max_seq_len;
+    t->dl_valid = false;  // dlogits^T below reuses nothing of it, but a second backward must not trust a consumed flag blindly
+    if (!have_dl)
+        TRY(showo_ce_loss(t->logits, V, labels, B, L, V, b_t2i, b_lm, b_mmu, max_seq_len, g_t2i, g_lm, g_mmu, t->ce_rows, t->counts,
+                          t->rowloss, t->dlogits, Vp, nullptr, s));
+    return backward_head_from_dlogits(t, stream);
+}
+
+// the same with the three loss weights in device memory g3[3] (the autograd path: they are the incoming gradients of the three loss
+// outputs, training/train.py:600,612, and are never read on the host).  Always runs its own cross-entropy pass over the logits.
+extern "C" int showo_train_backward_head_dev(showo_trainer* t, const int64_t* labels, int b_t2i, int b_lm, int b_mmu, int max_seq_len,
+                                             const float* g3, void* stream) {
+    BW_PROLOGUE
+    if (!labels || !g3) return set_error_msg(1, "train_backward_head_dev: labels and g3 required");
+    t->dl_valid = false;
+    TRY(showo::ce_loss_dev_weights(t->logits, V, labels, B, L, V, b_t2i, b_lm, b_mmu, max_seq_len, g3, t->ce_rows, t->counts, t->rowloss,
+                                   t->dlogits, Vp, s));
+    return backward_head_from_dlogits(t, stream);
+}
+
+// number of training forwards this trainer has started (showo_train_forward / _embeds, whether or not they succeeded): a backward
+// driven from the host checks that the saved activations still belong to its own forward
+extern "C" int64_t showo_train_generation(showo_trainer* t) { return t ? (int64_t)t->generation : -1; }
 
 extern "C" int showo_train_backward_layer(showo_trainer* t, int i, void* stream) {
     BW_PROLOGUE

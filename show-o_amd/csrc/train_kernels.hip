@@ -413,11 +413,16 @@ __global__ void ce_rows_kernel(const int64_t* __restrict__ labels, CeRow* __rest
     rows[r] = o;
 }
 
+// kDevW: the three loss weights come from device memory g3[3] (the autograd path, where they are the incoming gradients of the three
+// loss outputs and the host never reads them); the scalar arguments are then ignored.  Same arithmetic on the same values either way.
+template <bool kDevW>
 __global__ __launch_bounds__(256) void ce_kernel(const float* __restrict__ logits, int ldl, const CeRow* __restrict__ rows,
                                                  const int* __restrict__ counts, float g_t2i, float g_lm, float g_mmu,
+                                                 const float* __restrict__ g3,
                                                  bf16_t* __restrict__ dlogits, int ldd, float* __restrict__ rowloss, int V) {
     __shared__ float sred[4];
     __shared__ float sbc;
+    if constexpr (kDevW) { g_t2i = g3[0]; g_lm = g3[1]; g_mmu = g3[2]; }
     const int r = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const CeRow cr = rows[r];
     const float* z = logits + (int64_t)r * ldl;
@@ -846,8 +851,24 @@ extern "C" int showo_ce_loss(const float* logits, int ldl, const int64_t* labels
     CeRow* rows = reinterpret_cast<CeRow*>(rows_ws);
     SHOWO_CHECK_HIP(hipMemsetAsync(counts, 0, 3 * sizeof(int), s));
     ce_rows_kernel<<<dim3((R + 255) / 256), dim3(256), 0, s>>>(labels, rows, counts, B, L, b_t2i, b_lm, b_mmu, max_seq_len);
-    ce_kernel<<<dim3(R), dim3(256), 0, s>>>(logits, ldl, rows, counts, g_t2i, g_lm, g_mmu, dlogits, ldd, rowloss, V);
+    ce_kernel<false><<<dim3(R), dim3(256), 0, s>>>(logits, ldl, rows, counts, g_t2i, g_lm, g_mmu, nullptr, dlogits, ldd, rowloss, V);
     if (losses) ce_finalize_kernel<<<dim3(1), dim3(256), 0, s>>>(rowloss, rows, counts, losses, R);
+    SHOWO_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// showo_ce_loss with the loss weights in device memory g3[3] and d(logits) always written (the backward's pass of
+// showo_train_backward_head_dev); the losses are not finalised (the forward did that)
+int showo::ce_loss_dev_weights(const float* logits, int ldl, const int64_t* labels, int B, int L, int V, int b_t2i, int b_lm, int b_mmu,
+                               int max_seq_len, const float* g3, void* rows_ws, int* counts, float* rowloss, uint16_t* dlogits, int ldd,
+                               hipStream_t s) {
+    if (B <= 0 || L <= 0) return 0;
+    if (!g3 || !dlogits || (ldd % 8) || ldd < V) return set_error_msg(1, "ce_loss_dev_weights: g3 and dlogits (ldd % 8 == 0, >= V) required");
+    const int R = B * L;
+    CeRow* rows = reinterpret_cast<CeRow*>(rows_ws);
+    SHOWO_CHECK_HIP(hipMemsetAsync(counts, 0, 3 * sizeof(int), s));
+    ce_rows_kernel<<<dim3((R + 255) / 256), dim3(256), 0, s>>>(labels, rows, counts, B, L, b_t2i, b_lm, b_mmu, max_seq_len);
+    ce_kernel<true><<<dim3(R), dim3(256), 0, s>>>(logits, ldl, rows, counts, 0.f, 0.f, 0.f, g3, dlogits, ldd, rowloss, V);
     SHOWO_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -109,13 +109,120 @@ class _PhiForCausalLMParams(nn.Module):
         return self.model.embed_tokens
 
 
-class _ShowoTrainFn(torch.autograd.Function):
-    """Showo.forward with labels (reference models/modeling_showo.py:80-102) as one autograd node: forward runs the HIP
-    training forward (activations stay in the trainer), backward runs the HIP backward for the incoming loss weights
-    and hands the parameter gradients (reference names and shapes) back to autograd."""
+class _TrainRun:
+    """What the autograd nodes of ONE labelled Showo.forward share: the model, the trainer handle and generation of the HIP forward
+    they belong to (showo_train_generation), the arguments of the backward and the gradient layout of the trainer's buckets."""
+
+    def __init__(self, model):
+        self.model, self.tr, self.gen = model, None, None
+
+    def check(self, node):
+        """the trainer still holds this forward's activations: no other training forward ran since (a labelled forward, Trainer.step)"""
+        tr = self.model.__dict__.get("_trainer")
+        if self.gen is None or tr is not self.tr or _lib.load().showo_train_generation(tr) != self.gen:
+            raise RuntimeError(f"Showo backward ({node}): another training forward ran on this model after the one this loss comes from, "
+                               "so its saved activations are gone; call backward() before the next labelled forward")
+
+    def hand_out(self, bucket):
+        """ONE device copy of gradient bucket `bucket` into a fresh tensor, returned as views shaped like its parameters (in the order of
+        _train_param_groups): autograd / DDP may keep them, the next backward overwrites only the trainer's own buffer"""
+        n, src, parts = self.layout[bucket]
+        buf = torch.empty(n, dtype=torch.float32, device=src.device)
+        buf.copy_(src)
+        return [buf[o:o + k].view(shape) for o, k, shape in parts]
+
+
+def _train_param_groups(model):
+    """model.showo's parameters per gradient bucket of the trainer (include/showo_hip.h showo_train_bucket): 0 = embedding, 1 + i = block i,
+    nL + 1 = final LayerNorm + lm_head; (state-dict key, parameter) pairs"""
+    ph = model.showo
+    groups = [[("showo.model.embed_tokens.weight", ph.model.embed_tokens.weight)]]
+    for i, layer in enumerate(ph.model.layers):
+        groups.append([(f"showo.model.layers.{i}.{n}", p) for n, p in layer.named_parameters()])
+    groups.append([("showo.model.final_layernorm." + n, p) for n, p in ph.model.final_layernorm.named_parameters()] +
+                  [("showo.lm_head." + n, p) for n, p in ph.lm_head.named_parameters()])
+    return groups
+
+
+def _grad_layout(model, tr, groups, device):
+    """per bucket: (element count, zero-copy view of the trainer's bucket, [(offset, numel, shape) of each parameter's gradient]) --
+    offsets from showo_train_grad; cached for the lifetime of the trainer handle"""
+    cached = model.__dict__.get("_grad_layout_cache")
+    if cached is not None and cached[0] is tr:
+        return cached[1]
+    import ctypes as C
+    from .training import device_view
+    lib = _lib.load()
+    if lib.showo_train_num_buckets(tr) != len(groups):
+        raise RuntimeError("trainer buckets do not match the model's parameter groups")
+    layout = []
+    for b, group in enumerate(groups):
+        bp, bn = C.c_void_p(), C.c_int64()
+        _lib.check(lib.showo_train_bucket(tr, b, C.byref(bp), C.byref(bn)), "showo_train_bucket")
+        parts = []
+        for name, p in group:
+            gp, gn = C.c_void_p(), C.c_int64()
+            _lib.check(lib.showo_train_grad(tr, name.encode(), C.byref(gp), C.byref(gn)), "showo_train_grad")
+            off = (gp.value - bp.value) // 4
+            if gn.value != p.numel() or off < 0 or off + gn.value > bn.value:
+                raise RuntimeError(f"{name}: gradient outside its bucket {b}")
+            parts.append((off, gn.value, tuple(p.shape)))
+        layout.append((bn.value, device_view(bp.value, bn.value, device), parts))
+    model.__dict__["_grad_layout_cache"] = (tr, layout)
+    return layout
+
+
+class _EmbedNode(torch.autograd.Function):
+    """bucket 0 of the chain Showo.forward(labels=...) builds (embedding -> block 0 .. nL-1 -> head): launches nothing forward; its
+    backward, last of the chain, runs the embedding phase of the HIP backward and hands out the embedding-table gradient and, for the
+    `input_embeddings` flow (reference modeling_showo.py:77-78), d(loss)/d(input_embeddings) to the caller's graph (`anchor`)."""
 
     @staticmethod
-    def forward(ctx, model, input_ids, input_embeddings, attention_mask, labels, b_t2i, b_lm, b_mmu, max_seq_length, *params):
+    def forward(ctx, run, anchor, embed_w):
+        ctx.run = run
+        return embed_w.new_empty(0)
+
+    @staticmethod
+    def backward(ctx, g_tok):
+        run = ctx.run
+        run.check("embedding")
+        _lib.call("showo_train_backward_embed", run.tr, _lib.stream())
+        (g_w,) = run.hand_out(0)
+        g_emb = None
+        if run.emb_shape is not None and ctx.needs_input_grad[1]:
+            g_emb = torch.empty(run.emb_shape[0], dtype=torch.float32, device=g_w.device)
+            _lib.call("showo_train_input_grad", run.tr, _lib.ptr(g_emb), g_emb.numel(), _lib.stream())
+            g_emb = g_emb.to(run.emb_shape[1])
+        return None, g_emb, g_w
+
+
+class _BlockNode(torch.autograd.Function):
+    """block i (bucket 1 + i): no forward work; the backward runs showo_train_backward_layer(i) and hands out the block's gradients, so
+    their AccumulateGrad hooks (DDP's bucket readiness) fire while the blocks below are still to be queued."""
+
+    @staticmethod
+    def forward(ctx, run, i, tok, *params):
+        ctx.run, ctx.i = run, i
+        return tok.new_empty(0)
+
+    @staticmethod
+    def backward(ctx, g_tok):
+        run = ctx.run
+        run.check(f"block {ctx.i}")
+        _lib.call("showo_train_backward_layer", run.tr, ctx.i, _lib.stream())
+        grads = run.hand_out(1 + ctx.i)
+        return (None, None, g_tok.new_empty(0)) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[3:]))
+
+
+class _HeadNode(torch.autograd.Function):
+    """Showo.forward with labels (reference models/modeling_showo.py:80-102): the forward runs the whole HIP training forward (ONE call;
+    activations stay in the trainer) and returns logits + the three losses; the backward -- first of the chain -- runs the loss + head
+    phase for the incoming loss gradients read on the device (no host synchronisation) and hands out the final LayerNorm and lm_head
+    gradients (bucket nL + 1)."""
+
+    @staticmethod
+    def forward(ctx, run, input_ids, attention_mask, labels, b_t2i, b_lm, b_mmu, max_seq_length, tok, *params):
+        model = run.model
         tr = model.trainer()
         lab = labels.to(torch.int64).contiguous()
         B, L = lab.shape
@@ -126,42 +233,55 @@ class _ShowoTrainFn(torch.autograd.Function):
         logits = torch.empty((B, L, model.vocab_size), dtype=torch.float32, device=lab.device)
         losses = torch.empty(3, dtype=torch.float32, device=lab.device)
         try:
-            if input_embeddings is None:
+            if run.emb is None:
                 ids = input_ids.to(torch.int64).contiguous()
                 _lib.call("showo_train_forward", tr, _lib.ptr(ids), _lib.ptr(mask), _lib.ptr(lab), B, L, b_t2i, b_lm, b_mmu,
                           max_seq_length, _lib.ptr(logits), _lib.ptr(losses), _lib.stream())
             else:  # `inputs_embeds` flow of the w_clip_vit trainer (reference modeling_showo.py:77-78)
-                emb = input_embeddings.detach().float().contiguous()
+                emb = run.emb.float().contiguous()
                 if tuple(emb.shape) != (B, L, model.arch["hidden_size"]):
                     raise ValueError(f"input_embeddings should be {(B, L, model.arch['hidden_size'])}, got {tuple(emb.shape)}")
                 _lib.call("showo_train_forward_embeds", tr, _lib.ptr(emb), _lib.ptr(mask), _lib.ptr(lab), B, L, b_t2i, b_lm, b_mmu,
                           max_seq_length, _lib.ptr(logits), _lib.ptr(losses), _lib.stream())
         finally:
             _lib.call("showo_trainer_use_intervals", tr, None, None)
-        ctx.model, ctx.lab, ctx.meta = model, lab, (b_t2i, b_lm, b_mmu, max_seq_length)
-        ctx.emb_shape = None if input_embeddings is None else (tuple(input_embeddings.shape), input_embeddings.dtype)
-        ctx.names = ["showo." + n for n, _ in model.showo.named_parameters()]
-        ctx.shapes = [tuple(p.shape) for p in params]
+        run.tr, run.gen = tr, _lib.load().showo_train_generation(tr)
+        run.layout = _grad_layout(model, tr, run.groups, lab.device)
+        run.lab, run.meta = lab, (b_t2i, b_lm, b_mmu, max_seq_length)
+        ctx.run = run
         ctx.mark_non_differentiable(logits)
+        ctx.set_materialize_grads(False)  # no [B, L, V] zeros for the logits; an unused loss arrives as None (weight 0)
         return logits, losses[0].clone(), losses[1].clone(), losses[2].clone()
 
     @staticmethod
     def backward(ctx, g_logits, g_t2i, g_lm, g_mmu):
-        model = ctx.model
-        g = [0.0 if x is None else float(x) for x in (g_t2i, g_lm, g_mmu)]
-        b_t2i, b_lm, b_mmu, msl = ctx.meta
-        _lib.call("showo_train_backward", model._trainer, _lib.ptr(ctx.lab), b_t2i, b_lm, b_mmu, msl, g[0], g[1], g[2], _lib.stream())
-        grads = []
-        for name, shape in zip(ctx.names, ctx.shapes):
-            t = torch.empty(shape, dtype=torch.float32, device=ctx.lab.device)
-            _lib.call("showo_train_grad_copy", model._trainer, name.encode(), _lib.ptr(t), t.numel(), _lib.stream())
-            grads.append(t)
-        g_emb = None
-        if ctx.emb_shape is not None and ctx.needs_input_grad[2]:
-            g_emb = torch.empty(ctx.emb_shape[0], dtype=torch.float32, device=ctx.lab.device)
-            _lib.call("showo_train_input_grad", model._trainer, _lib.ptr(g_emb), g_emb.numel(), _lib.stream())
-            g_emb = g_emb.to(ctx.emb_shape[1])
-        return (None, None, g_emb) + (None,) * 6 + tuple(grads)
+        run = ctx.run
+        run.check("head")
+        dev = run.lab.device
+        g3 = torch.stack([torch.zeros((), dtype=torch.float32, device=dev) if g is None else g.detach().reshape(()).float()
+                          for g in (g_t2i, g_lm, g_mmu)])  # the loss weights stay on the device (training/train.py:600)
+        b_t2i, b_lm, b_mmu, msl = run.meta
+        _lib.call("showo_train_backward_head_dev", run.tr, _lib.ptr(run.lab), b_t2i, b_lm, b_mmu, msl, _lib.ptr(g3), _lib.stream())
+        grads = run.hand_out(len(run.groups) - 1)
+        return ((None,) * 8 + (torch.empty(0, device=dev),)
+                + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[9:])))
+
+
+def _train_forward(model, input_ids, input_embeddings, attention_mask, labels, b_t2i, b_lm, b_mmu, max_seq_length):
+    """Showo.forward with labels as a chain of autograd nodes, one per gradient bucket (embedding -> blocks -> head): autograd
+    runs their backwards head -> block nL-1 .. 0 -> embedding and accumulates every bucket's gradients as soon as its phase is queued,
+    which is when DDP (accelerator.prepare, training/train.py:449) starts that bucket's all-reduce.  The tok tensors are empty: they
+    only carry the graph edges."""
+    run = _TrainRun(model)
+    run.groups = _train_param_groups(model)
+    run.emb = None if input_embeddings is None else input_embeddings.detach()
+    run.emb_shape = None if input_embeddings is None else (tuple(input_embeddings.shape), input_embeddings.dtype)
+    (embed_w,) = [p for _, p in run.groups[0]]
+    tok = _EmbedNode.apply(run, input_embeddings, embed_w)
+    for i, group in enumerate(run.groups[1:-1]):
+        tok = _BlockNode.apply(run, i, tok, *[p for _, p in group])
+    return _HeadNode.apply(run, input_ids, attention_mask, labels, b_t2i, b_lm, b_mmu, max_seq_length, tok,
+                           *[p for _, p in run.groups[-1]])
 
 
 class _ProjectorFn(torch.autograd.Function):
@@ -546,9 +666,8 @@ class Showo(PretrainedMixin, nn.Module):
                 batch_size_t2i=0, batch_size_lm=0, batch_size_mmu=0, max_seq_length=128, labels_mask_text=None,
                 labels_mask_image=None, **kwargs):
         if labels is not None:
-            params = [p for _, p in self.showo.named_parameters()]
-            return _ShowoTrainFn.apply(self, input_ids, input_embeddings, attention_mask, labels, int(batch_size_t2i),
-                                       int(batch_size_lm), int(batch_size_mmu), int(max_seq_length), *params)
+            return _train_forward(self, input_ids, input_embeddings, attention_mask, labels, int(batch_size_t2i), int(batch_size_lm),
+                                  int(batch_size_mmu), int(max_seq_length))
         eng = self.engine()
         if input_embeddings is None:
             B, L = input_ids.shape
