@@ -4,6 +4,8 @@ One "step" = one pass of the hot path over one batch: Showo.t2i_generate (18 mas
 [16,387] CFG batch) followed by MAGVITv2.decode_code of the 8 results (BASELINE.json configs[1]).
 Inputs (ids, mask) are resident in HBM before the timed region.  Prints ONE JSON line (rank 0).
 Multi-GPU: images are independent -> N replicas, no data-path collective ("weak" scaling).
+A plain run sets up, warms up, times the steps, dumps (--dump-outputs) and prints the headline line.  The other legs -- roofline,
+measured ceilings, accuracy / fp16 modes, the other BASELINE configs, the training step, the CPU baselines -- run with --full.
 """
 import argparse
 import ctypes as C
@@ -382,9 +384,15 @@ def main():
                     "t2i512 | mmu (bench_configs.py: BASELINE configs[2] / configs[3])")
     ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned (image tokens, decoded images) as "
                     "DIR/<name>.npy in float32, for output-for-output comparison of two builds on the same seeded inputs")
+    ap.add_argument("--full", action="store_true", help="after the headline, run every other leg (roofline, measured ceilings, accuracy and "
+                    "fp16 modes, VQ HBM, the other BASELINE configs, the training step, CPU baselines); the --no-* options and "
+                    "--roofline-steps select among them")
     a = ap.parse_args()
     if a.steps < 1:
         ap.error("--steps must be at least 1")
+    if not a.full:  # a plain run does only what the headline figure needs
+        a.no_cpu_baseline = a.no_train_leg = a.no_accuracy_leg = a.no_config_legs = True
+        a.roofline_steps = 0
     self_launch(a.gpus, __file__)
     if dry_run():
         return dry_main(a)
@@ -597,7 +605,7 @@ def main():
             model.set_precision(0)
     ceilings = None
     vq_hbm = None
-    if rank == 0:
+    if rank == 0 and a.full:
         try:
             ceilings = measured_ceilings(L)
             log(f"ceilings of this run: {ceilings}")
@@ -611,6 +619,23 @@ def main():
                 vq_hbm = {"error": repr(ex)}
     if rank == 0:
         value = images / dt
+        out = {
+            "metric": "t2i images/sec @256x256 (18 denoise steps)", "value": value, "unit": "images/s", "n_gpus": world,
+            "steps": a.steps, "warmup": a.warmup, "ms_per_step": dt / a.steps * 1e3, "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": {0: "bf16", 1: "bf16x3 (split-bf16 hi+lo operands, fp32-class)", 2: "f16"}[a.precision], "data": "synthetic",
+            "config": {"workload": (f"BASELINE cfg{2 if B == 8 else 1}{'' if B in (1, 8) else ' shape'}: configs/showo_demo.yaml t2i 256x256, batch {B} prompt{'s' if B > 1 else ''}, "
+                                    f"CFG 5.0 (forward on [{2 * B},387]), 18 mask-predict steps + MAGVITv2.decode_code; random-init Show-o 1.45B + MAGVIT-v2 95M"),
+                       "global_batch": B * world, "seq_len": 387, "parallelism": f"replicas x{world}",
+                       "launch_mode": ("hipGraph replay of the denoise steps (cached on the engine)" if a.graph else "eager"),
+                       "precision": {0: "bf16 operands, fp32 accumulation", 1: "accuracy mode (split-bf16 GEMMs, fp32 attention)",
+                                     2: "fp16 operands, fp32 accumulation, split-bf16 lm_head"}[a.precision],
+                       # SURVEY.md §8d counts the REFERENCE's flops (38.4 TFLOP per image: text rows recomputed every step, lm_head over
+                       # the full vocabulary); the path skips most of that work (prefix reuse, restricted head), so this rate is NOT MFMA
+                       # utilisation -- `roofline.frac` is
+                       "algorithmic_tflop_per_image": 38.4, "reference_flops_rate_tflops_skipped_work_included": value * 38.4},
+            "roofline": None,
+        }
+    if rank == 0 and a.full:
         peak = 2500.0  # TFLOP/s dense bf16 MFMA (MI355X_MICROARCH.md)
         # HBM bytes per GEMM launch: PMC counters cannot be read from inside this process; they come from the separate
         # rocprofv3 --pmc passes over this same command (scripts/gpu_pmc.sh -> profiles/pmc/bench_traffic.json)
@@ -642,35 +667,20 @@ def main():
         except (OSError, KeyError, TypeError, ValueError):
             pass
         ach = fl_gemm.value / (ms_gemm.value * 1e-3) / 1e12 if ms_gemm.value > 0 else 0.0
-        out = {
-            "metric": "t2i images/sec @256x256 (18 denoise steps)", "value": value, "unit": "images/s", "n_gpus": world,
-            "steps": a.steps, "warmup": a.warmup, "ms_per_step": dt / a.steps * 1e3, "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": {0: "bf16", 1: "bf16x3 (split-bf16 hi+lo operands, fp32-class)", 2: "f16"}[a.precision], "data": "synthetic",
-            "config": {"workload": (f"BASELINE cfg{2 if B == 8 else 1}{'' if B in (1, 8) else ' shape'}: configs/showo_demo.yaml t2i 256x256, batch {B} prompt{'s' if B > 1 else ''}, "
-                                    f"CFG 5.0 (forward on [{2 * B},387]), 18 mask-predict steps + MAGVITv2.decode_code; random-init Show-o 1.45B + MAGVIT-v2 95M"),
-                       "global_batch": B * world, "seq_len": 387, "parallelism": f"replicas x{world}",
-                       "launch_mode": ("hipGraph replay of the denoise steps (cached on the engine)" if a.graph else "eager"),
-                       "precision": {0: "bf16 operands, fp32 accumulation", 1: "accuracy mode (split-bf16 GEMMs, fp32 attention)",
-                                     2: "fp16 operands, fp32 accumulation, split-bf16 lm_head"}[a.precision],
-                       # SURVEY.md §8d counts the REFERENCE's flops (38.4 TFLOP per image: text rows recomputed every step, lm_head over
-                       # the full vocabulary); the path skips most of that work (prefix reuse, restricted head), so this rate is NOT MFMA
-                       # utilisation -- `roofline.frac` is
-                       "algorithmic_tflop_per_image": 38.4, "reference_flops_rate_tflops_skipped_work_included": value * 38.4},
-            "roofline": {"bound": "mfma", "kernel": "gemm3w_kernel / gemm2p_kernel (one template family; the tuner picks the weight-ring form gemm3w for both layer launches at this shape) -- 16-bit MFMA GEMM; per layer ONE [Wqkv;W1] projection with the QKV / GELU split epilogue and ONE K-concatenated dense|fc2 residual GEMM; lm_head rows)",
-                         "achieved": ach, "peak": peak, "unit": "TFLOP/s", "frac": ach / peak, "measured_peak": measured_peak, "mfma_busy_pmc_from_profiles_not_this_run": mfma_pmc, "traffic": traffic, "traffic_measured_in": "a separate rocprofv3 --pmc pass of this command on the builder's box (profiles/pmc/), NOT this run; null when the GEMM sources changed since", "traffic_unit": "bytes per launch (PMC FETCH_SIZE x2 + WRITE_SIZE)",
-                         "traffic_source": traffic_src,
-                         "launches": int(n_all.value), "timed_launches": int(n_gemm.value),
-                         "avg_launch_ms": ms_gemm.value / max(1, n_gemm.value),
-                         "measured_in": f"{n_evt} extra eager steps with HIP events after the timed region ({dt_evt / n_evt * 1e3:.1f} ms per step)" if n_evt else None,
-                         "time_share_of_step": (fl_all.value / max(1e-9, ach * 1e12)) / dt_evt if (ach > 0 and n_evt) else None,
-                         # at small batches the forward approaches the weight-streaming roof (2.90 GB of bf16 weights per
-                         # forward, 18 forwards per image batch): printed so that a --batch 1 line (BASELINE cfg1 shape) can be read
-                         "weight_stream": {"bytes_per_forward": 2.896e9, "forwards_per_step": 18,
-                                           "TBps_if_weights_streamed_once_per_forward": 18 * 2.896e9 / (dt / a.steps) / 1e12,
-                                           "frac_of_8TBps": 18 * 2.896e9 / (dt / a.steps) / 8e12, "token_rows_per_forward": 2 * B * 387},
-                         "attention": {"achieved": fl_attn.value / max(1e-9, ms_attn.value * 1e-3) / 1e12},
-                         "vq_conv": {"achieved": fl_conv.value / max(1e-9, ms_conv.value * 1e-3) / 1e12}},
-        }
+        out["roofline"] = {"bound": "mfma", "kernel": "gemm3w_kernel / gemm2p_kernel (one template family; the tuner picks the weight-ring form gemm3w for both layer launches at this shape) -- 16-bit MFMA GEMM; per layer ONE [Wqkv;W1] projection with the QKV / GELU split epilogue and ONE K-concatenated dense|fc2 residual GEMM; lm_head rows)",
+                           "achieved": ach, "peak": peak, "unit": "TFLOP/s", "frac": ach / peak, "measured_peak": measured_peak, "mfma_busy_pmc_from_profiles_not_this_run": mfma_pmc, "traffic": traffic, "traffic_measured_in": "a separate rocprofv3 --pmc pass of this command on the builder's box (profiles/pmc/), NOT this run; null when the GEMM sources changed since", "traffic_unit": "bytes per launch (PMC FETCH_SIZE x2 + WRITE_SIZE)",
+                           "traffic_source": traffic_src,
+                           "launches": int(n_all.value), "timed_launches": int(n_gemm.value),
+                           "avg_launch_ms": ms_gemm.value / max(1, n_gemm.value),
+                           "measured_in": f"{n_evt} extra eager steps with HIP events after the timed region ({dt_evt / n_evt * 1e3:.1f} ms per step)" if n_evt else None,
+                           "time_share_of_step": (fl_all.value / max(1e-9, ach * 1e12)) / dt_evt if (ach > 0 and n_evt) else None,
+                           # at small batches the forward approaches the weight-streaming roof (2.90 GB of bf16 weights per
+                           # forward, 18 forwards per image batch): printed so that a --batch 1 line (BASELINE cfg1 shape) can be read
+                           "weight_stream": {"bytes_per_forward": 2.896e9, "forwards_per_step": 18,
+                                             "TBps_if_weights_streamed_once_per_forward": 18 * 2.896e9 / (dt / a.steps) / 1e12,
+                                             "frac_of_8TBps": 18 * 2.896e9 / (dt / a.steps) / 8e12, "token_rows_per_forward": 2 * B * 387},
+                           "attention": {"achieved": fl_attn.value / max(1e-9, ms_attn.value * 1e-3) / 1e12},
+                           "vq_conv": {"achieved": fl_conv.value / max(1e-9, ms_conv.value * 1e-3) / 1e12}}
     # ---- training-step leg: BASELINE.json's metric is "t2i images/sec + train step-time, 1/2/4/8 MI355X", and the t2i replicas above
     # exchange nothing, so the data-parallel half (RCCL all-reduce of the gradient buckets overlapped with backward) is measured here:
     # every rank runs bench_train.py as a CHILD process (own process group on MASTER_PORT + 101, bounded by a timeout, so that a
@@ -688,7 +698,7 @@ def main():
         # every BASELINE config in the driver's record: cfg3 / cfg4 (and cfg1 = --batch 1) as short child runs under a ~90 s budget
         if world == 1 and not a.no_config_legs:
             others = {}
-            for key, argv in (("cfg1_t2i256_batch1", ["--batch", "1", "--steps", "3", "--warmup", "1", "--roofline-steps", "1"]),
+            for key, argv in (("cfg1_t2i256_batch1", ["--batch", "1", "--steps", "3", "--warmup", "1", "--full", "--roofline-steps", "1"]),
                               ("cfg3_t2i512_inpaint_batch4", ["--workload", "t2i512", "--steps", "1", "--warmup", "1"]),
                               ("cfg4_mmu_decode", ["--workload", "mmu", "--steps", "1", "--warmup", "1"])):
                 t1 = time.time()

@@ -8,6 +8,7 @@ cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 for step in "$@"; do
   name=${step%%:*}; arg=""; [ "$step" != "$name" ] && arg=${step#*:}
+  case $name in bench|batch1|prof-t2i) arg="--full $arg" ;; esac  # these steps record the whole line: every leg of bench.py --full
   case $name in
     tests)
       if [ -f "$arg" ]; then sel="$arg"; kexpr=""; else sel="tests"; kexpr="$arg"; fi

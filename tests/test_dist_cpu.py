@@ -105,7 +105,7 @@ def test_no_decay_rule_is_the_reference_rule():
 
 
 def test_bench_gpus_2_launch_plumbing_with_two_real_processes():
-    """`python bench.py --gpus 2` end to end with REAL processes (no monkeypatching): bench.self_launch re-execs the
+    """`python bench.py --gpus 2 --full` end to end with REAL processes (no monkeypatching): bench.self_launch re-execs the
     command as 2 ranks under torch.distributed.run, the ranks rendezvous (gloo here, RCCL on the GPU box), aggregate MAX time / SUM
     units, and every rank starts bench_train.py as a child whose ranks rendezvous among themselves on MASTER_PORT + 101 without the
     launcher's agent store.  SHOWO_BENCH_DRYRUN=1 removes the GPU work only; launch code, environment handling and aggregation are the
@@ -115,7 +115,7 @@ def test_bench_gpus_2_launch_plumbing_with_two_real_processes():
     env = dict(os.environ, SHOWO_BENCH_DRYRUN="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR", "TORCHELASTIC_USE_AGENT_STORE"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "0", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "0", "--full", "--no-cpu-baseline"],
                        env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, (r.stdout[-800:], r.stderr[-1500:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{") and '"metric"' in l]
@@ -137,3 +137,21 @@ def test_bench_gpus_2_launch_plumbing_with_two_real_processes():
     assert r.returncode == 0, (r.stdout[-800:], r.stderr[-1500:])
     d2 = json.loads([l for l in r.stdout.splitlines() if l.startswith("{") and '"metric"' in l][0])
     assert d2["n_gpus"] == 2 and d2["dryrun"]["allreduce_sum"] == 3.0
+
+
+def test_bench_plain_run_leaves_the_other_legs_to_full():
+    """a plain `python bench.py` times the headline only: its line has no training step (no bench_train.py child is started)
+    and no CPU baseline; those legs run with --full (test above)"""
+    import json
+    import subprocess
+    env = dict(os.environ, SHOWO_BENCH_DRYRUN="1")
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR", "TORCHELASTIC_USE_AGENT_STORE"):
+        env.pop(k, None)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "0"],
+                       env=env, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, (r.stdout[-800:], r.stderr[-1500:])
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{") and '"metric"' in l]
+    assert len(lines) == 1, r.stdout[-800:]
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["n_gpus"] == 1 and d["value"] > 0
+    assert d["train_step"] is None and d["cpu_baseline"] is None and "training leg" not in r.stderr
