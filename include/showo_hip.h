@@ -559,12 +559,28 @@ int showo_engine_decode_greedy(showo_engine* e, int64_t* tok, int n_steps, int64
  *   showo_engine_batch_prefill(e, b, ...): showo_engine_prefill of sequence b into its slot (own length, own mask);
  *   showo_engine_batch_decode_greedy: tok int64 [nb] (device; in = first token to feed per sequence, out = last produced),
  *     out_tokens int64 [nb, n_steps], logits_ws fp32 [nb, vocab]; every sequence advances n_steps tokens (the caller cuts at <eot>);
- *     one hipGraph replay per step with the nb positions in device memory.  bf16 operands (precision 0) only. */
+ *     one hipGraph replay per step with the nb positions in device memory.  Precision 0 (bf16) or 2 (fp16 operands). */
 int showo_engine_batch_begin(showo_engine* e, int nb, int cap_tokens);
 int showo_engine_batch_prefill(showo_engine* e, int b, const int64_t* ids, const float* embeds, const float* mask, int L,
                                float* logits_last, void* stream);
 int showo_engine_batch_decode_greedy(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws, int use_graph,
                                      void* stream);
+/* showo_engine_batch_decode_greedy with a per-slot draw and a per-slot stop.  Host arrays of nb entries:
+ *   top_k[b]        1 = arg-max (the greedy pick); <= 0 or >= vocab: no filter; else top-k (ties with the k-th value stay)
+ *   temperature[b]  > 0 where top_k[b] != 1
+ *   seed[b], draw0[b]  draw j of slot b in this call = showo_sample_topk(..., seed[b], step = draw0[b] + j)
+ *   exp_noise       NULL, or nb entries each NULL or a device fp32 [*, vocab] table whose row draw0[b] + j replaces the Philox draw
+ *   budget[b]       tokens slot b may still emit in this call (0 = idle from the start); eot: stop id, -1 = none
+ * A slot stops after its budget[b]-th token or after emitting eot; for the rest of the call it is idle: its position stays, its
+ * out_tokens entries are -1, it feeds a zero row (its K/V append rewrites one column beyond its live length, never beyond the cache).
+ * tok int64 [nb] (device): in = the token each decoding slot feeds first, out = its last token.  out_tokens int64 [nb, n_steps]
+ * (device).  produced[b] (host) = tokens slot b emitted; its cache length grows by that much.  Capacity: P0[b] + min(budget[b],
+ * n_steps) <= cap for every slot.
+ * Refill: showo_engine_batch_prefill(e, b, ...) on a running batch replaces the occupant of slot b (new length, new mask, re-zeroed
+ * tail columns); the other slots' caches and positions are untouched, so a scheduler can refill a stopped slot between calls. */
+int showo_engine_batch_decode_sample(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws, const int* top_k,
+                                     const float* temperature, const uint64_t* seed, const int* draw0, const float* const* exp_noise,
+                                     const int* budget, int64_t eot, int* produced, int use_graph, void* stream);
 /* Next-token draw of the AR decode (modeling_showo.py:220-228): x = logits / temperature; values below the top_k-th largest
  * are dropped (top_k <= 0 or >= V: none); token = multinomial(softmax(x), 1) computed as argmax_i p_i / E_i, E ~ Exp(1):
  * E = exp_noise[step * V + i] when exp_noise != NULL (parity tests inject the reference's draws), else Philox(seed; step, i). */

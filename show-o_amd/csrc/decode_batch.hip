@@ -16,7 +16,9 @@
 // The whole step replays as a hipGraph with the NB positions in device memory.
 #include "engine.h"
 #include "decode_common.h"
+#include "sample_row.h"
 #include <cstdlib>
+#include <string>
 
 using namespace showo;
 
@@ -321,27 +323,11 @@ __global__ __launch_bounds__(1024) void greedy_seam_rows_kernel(const float* __r
                                                                 const int* __restrict__ base, const float* __restrict__ table,
                                                                 float* __restrict__ x, int H, const int32_t* __restrict__ last_iv,
                                                                 const int* __restrict__ L0, int32_t* __restrict__ iv) {
-    __shared__ float sv[16];
-    __shared__ int si[16];
+    __shared__ RowPickSmem sm;
     __shared__ int s_tok;
-    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const float* row = logits + (int64_t)b * V;
-    float best = -INFINITY;
-    int bi = 0x7fffffff;
-    for (int i = tid; i < V; i += 1024) {
-        const float v = row[i];
-        if (v > best || (v == best && i < bi)) { best = v; bi = i; }
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ob = __shfl_xor(best, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-    }
-    if (lane == 0) { sv[wave] = best; si[wave] = bi; }
-    __syncthreads();
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int bi = argmax_row_1024(logits + (int64_t)b * V, V, sm);
     if (tid == 0) {
-        for (int w = 1; w < 16; ++w)
-            if (sv[w] > best || (sv[w] == best && si[w] < bi)) { best = sv[w]; bi = si[w]; }
         s_tok = bi;
         tok[b] = bi;
         const int P = pos[b];
@@ -358,6 +344,86 @@ __global__ __launch_bounds__(1024) void greedy_seam_rows_kernel(const float* __r
     }
     const float* src = table + (int64_t)id * H;
     for (int i = tid; i < H; i += 1024) xr[i] = src[i];
+}
+
+// Per-slot state of showo_engine_batch_decode_sample: set by the host before the steps are captured, advanced by the sampled seam.
+struct SlotDraw {
+    const float* noise;  // NULL or [*, V] Exp(1) rows: row d replaces the Philox draw d
+    uint64_t seed;
+    float temperature;
+    int top_k;
+    int draw0;     // draw index of the slot's first token in this call
+    int budget;    // tokens the slot may emit in this call
+    int produced;  // tokens emitted so far in this call
+    int step;      // seam launches so far in this call (the column of out_tokens)
+    int active;    // 0: stopped (budget spent or <eot> emitted) or idle from the start
+};
+
+// Row of slot b for its next step: the embedding of its token while it decodes; zeros once it is idle (a fixed, finite row, so the
+// idle slot's residual row stays bounded while the other slots keep decoding).
+__device__ __forceinline__ void slot_embed_row(int64_t id, bool active, const float* __restrict__ table, float* __restrict__ xr, int H, int V,
+                                               int tid, int nthr) {
+    if (!active) {
+        for (int i = tid; i < H; i += nthr) xr[i] = 0.f;
+    } else if (id < 0 || id >= V) {
+        for (int i = tid; i < H; i += nthr) xr[i] = __builtin_nanf("");
+    } else {
+        const float* src = table + id * H;
+        for (int i = tid; i < H; i += nthr) xr[i] = src[i];
+    }
+}
+__global__ __launch_bounds__(256) void slot_embed_kernel(const int64_t* __restrict__ tok, const SlotDraw* __restrict__ sd,
+                                                         const float* __restrict__ table, float* __restrict__ x, int H, int V) {
+    const int b = blockIdx.x;
+    slot_embed_row(tok[b], sd[b].active != 0, table, x + (int64_t)b * H, H, V, threadIdx.x, 256);
+}
+
+// Token boundary of the batched sampled loop, one block per slot.  A decoding slot picks its token -- the arg-max for top_k == 1 (the
+// greedy seam's pick), else sample_topk_row with its own top_k / temperature / seed / draw index (the batch-1 sampler's draw) -- and
+// stores it, then either advances (position + 1, next mask row, next embedding row) or, after its last budgeted token or <eot>, goes
+// idle.  An idle slot writes -1 into its output row, keeps its position (at most lim - 1, so its K/V append never leaves the cache and
+// the rotary tables) and feeds the zero row.
+__global__ __launch_bounds__(1024) void sample_seam_rows_kernel(const float* __restrict__ logits, int V, int64_t eot, int64_t* __restrict__ tok,
+                                                                int64_t* __restrict__ out_tokens, int n_steps, int* __restrict__ pos, int lim,
+                                                                SlotDraw* __restrict__ sd, const float* __restrict__ table, float* __restrict__ x,
+                                                                int H, const int32_t* __restrict__ last_iv, const int* __restrict__ L0,
+                                                                int32_t* __restrict__ iv) {
+    __shared__ RowPickSmem sm;
+    __shared__ int s_tok, s_go;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    SlotDraw* s = sd + b;
+    const int active = s->active, top_k = s->top_k, d = s->draw0 + s->produced;  // block-uniform
+    int pick = -1;
+    if (active) {
+        const float* row = logits + (int64_t)b * V;
+        if (top_k == 1) pick = argmax_row_1024(row, V, sm);
+        else pick = sample_topk_row(row, V, top_k, s->temperature, s->noise ? s->noise + (int64_t)d * V : nullptr, s->seed, d, sm);
+    }
+    __syncthreads();  // every thread has read *s
+    if (tid == 0) {
+        const int j = s->step;
+        int64_t* out = out_tokens + (int64_t)b * n_steps;
+        const int P = pos[b];
+        int go = 0;
+        if (active) {
+            tok[b] = pick;
+            if (j < n_steps) out[j] = pick;
+            const int np = s->produced + 1;
+            s->produced = np;
+            go = !(np >= s->budget || pick == eot);
+            if (!go) s->active = 0;
+            const int Pn = go ? P + 1 : min(P + 1, lim - 1);
+            pos[b] = Pn;
+            next_iv(last_iv + 4 * b, L0[b], Pn, iv + 4 * b);
+        } else if (j < n_steps) {
+            out[j] = -1;
+        }
+        s->step = j + 1;
+        s_tok = pick;
+        s_go = go;
+    }
+    __syncthreads();
+    slot_embed_row(s_tok, s_go != 0, table, x + (int64_t)b * H, H, V, tid, 1024);
 }
 
 template <int NB>
@@ -476,6 +542,7 @@ struct showo_engine::BatchDecode {
     int *pos_dev = nullptr, *L0_dev = nullptr, *base_dev = nullptr;
     int32_t *last_iv_dev = nullptr, *iv_dev = nullptr;
     float* y2 = nullptr;  // [nb, H] fc2 + b2 of the current layer (co-scheduled form)
+    SlotDraw* slots_dev = nullptr;  // [MAXB] per-slot draw / stop state of showo_engine_batch_decode_sample
     int precision = 0;    // the precision the caches were prefilled under (element type of K / V^T)
 };
 
@@ -544,86 +611,82 @@ extern "C" int showo_engine_batch_prefill(showo_engine* e, int b, const int64_t*
     return 0;
 }
 
-// tok int64 [nb] (device): in = the token each sequence feeds first (e.g. the arg-max of its prefill logits), out = the last tokens
-// produced; out_tokens int64 [nb, n_steps] (device); logits_ws fp32 [nb, vocab] (device).  Every sequence advances n_steps tokens
-// (the caller cuts each row at its <eot>, like the chunked batch-1 loop of Showo.mmu_generate).
-extern "C" int showo_engine_batch_decode_greedy(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws,
-                                                int use_graph, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    if (!e || !e->bd || e->bd->nb == 0) return set_error_msg(1, "batch_decode_greedy: showo_engine_batch_begin + _batch_prefill first");
+namespace {
+// Preconditions shared by the batched decode entries (precision, weight images, per-slot prefill, two-interval mask rows).
+int batch_decode_checks(showo_engine* e, const char* what) {
     auto* d = e->bd;
-    const int nb = d->nb, H = e->H, F = e->F, nH = e->nH, V = e->V;
-    if (!tok || !out_tokens || !logits_ws || n_steps < 1) return set_error_msg(1, "batch_decode_greedy: bad arguments");
-    if (e->precision == 1) return set_error_msg(1, "batch_decode_greedy: precision 0 (bf16 operands) or 2 (fp16 operands)");
+    auto fail = [&](int code, const char* msg) { return set_error_msg(code, (std::string(what) + ": " + msg).c_str()); };
+    if (e->precision == 1) return fail(1, "precision 0 (bf16 operands) or 2 (fp16 operands)");
     const int op = e->precision == 2 ? SHOWO_OP_F16 : SHOWO_OP_BF16;
-    if ((op == SHOWO_OP_F16) != e->img_f16) return set_error_msg(4, "batch_decode_greedy: the weight images hold the other 16-bit type: upload the weights again");
-    if (d->precision != e->precision) return set_error_msg(1, "batch_decode_greedy: the caches were prefilled under another precision: prefill again");
-    if (op && (!e->wlm_lo || !e->lo_loaded.count("showo.lm_head.weight"))) return set_error_msg(4, "batch_decode_greedy (precision 2): the lm_head's low half is missing: upload the weights again");
-    int lk_max = 0;
-    int P0[MAXB];
-    for (int b = 0; b < nb; ++b) {
-        if (d->cache_len[b] <= 0) return set_error_msg(1, "batch_decode_greedy: a sequence has no prefill");
-        P0[b] = d->cache_len[b];
-        if (P0[b] + n_steps > d->cap || P0[b] + n_steps > e->cfg.max_pos) return set_error_msg(5, "batch_decode_greedy: cache full");
+    if ((op == SHOWO_OP_F16) != e->img_f16) return fail(4, "the weight images hold the other 16-bit type: upload the weights again");
+    if (d->precision != e->precision) return fail(1, "the caches were prefilled under another precision: prefill again");
+    if (op && (!e->wlm_lo || !e->lo_loaded.count("showo.lm_head.weight")))
+        return fail(4, "(precision 2) the lm_head's low half is missing: upload the weights again");
+    for (int b = 0; b < d->nb; ++b) {
+        if (d->cache_len[b] <= 0) return fail(1, "a sequence has no prefill");
         const int *v = d->last_iv[b], L0 = d->prompt_len[b];
         if (!((v[1] == L0 && v[0] < v[1]) || (v[3] == L0 && v[2] < v[3]) || !(v[2] < v[3]) || !(v[0] < v[1])))
-            return set_error_msg(6, "batch_decode_greedy: mask row needs more than two intervals");
-        lk_max = lk_max > P0[b] + n_steps ? lk_max : P0[b] + n_steps;
+            return fail(6, "mask row needs more than two intervals");
     }
-    SHOWO_CHECK_HIP(hipMemcpyAsync(d->pos_dev, P0, sizeof(int) * nb, hipMemcpyHostToDevice, s));
-    SHOWO_CHECK_HIP(hipMemcpyAsync(d->base_dev, P0, sizeof(int) * nb, hipMemcpyHostToDevice, s));
-    SHOWO_CHECK_HIP(hipMemcpyAsync(d->L0_dev, d->prompt_len, sizeof(int) * nb, hipMemcpyHostToDevice, s));
-    SHOWO_CHECK_HIP(hipMemcpyAsync(d->last_iv_dev, d->last_iv, sizeof(int32_t) * 4 * nb, hipMemcpyHostToDevice, s));
-    SHOWO_CHECK_HIP(hipStreamSynchronize(s));  // P0 is a host temporary of this call
-    TRY(showo_embed_f32(tok, e->embed, e->x, nb, H, V, s));
-    batch_iv_kernel<<<1, 64, 0, s>>>(d->last_iv_dev, d->L0_dev, d->pos_dev, d->iv_dev, nb);
-    SHOWO_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// One token step of the batch up to its logits: nb rows through the layers against their caches, final LayerNorm + lm_head.
+// co: the co-scheduled layer (2..4 sequences at Phi-1.5's shape), else three plain launches per layer.
+int batch_step_layers(showo_engine* e, int op, bool co, int lk_max, float* logits_ws, hipStream_t s) {
+    auto* d = e->bd;
+    const int nb = d->nb, H = e->H, F = e->F, nH = e->nH, V = e->V;
     const int64_t per_seq = (int64_t)nH * d->cap * 64, lstride = (int64_t)nb * per_seq;
-    // co-scheduled layer (fc2 streams next to the latency-bound attention blocks): Phi-1.5's shape, 2..4 sequences (the fc2 role
-    // keeps nb x 8192 bf16 activations in LDS); SHOWO_DECODE_BATCH_CO=0 / other shapes: three plain launches per layer
+    const int co_blocks = showo::decode_tuning().batch_co_blocks;  // 128 role blocks + 32 nb attention blocks = one block per CU at nb = 4
+    for (int li = 0; li < e->nL; ++li) {
+        showo::Layer& l = e->layers[li];
+        LnGemvBArgs a{e->x, l.ln_w, l.ln_b, e->cfg.ln_eps, H, l.wqkv, l.bqkv, e->qkv, nullptr, 3 * H, 3 * H, l.w1, l.b1, e->ffn, F, F};
+        TRY(ln_gemvB(nb, a, s, op));
+        OutGemvBArgs o{e->x, l.wd, e->attn, l.bd, H, H, l.w2, e->ffn, l.b2, F, F, H, d->y2};
+        if (co) {
+            // [ attention of the nb x heads (sequence, head) pairs || fc2 of all nb sequences -> y2 ] -> dense + both residual adds
+            // (Phi's block is parallel-residual, models/phi.py:806-835: fc2 does not depend on the attention; decode.hip's batch-1 layer
+            // co-schedules the same way)
+            showo::DecodePrefetch pf;
+            showo::decode_prefetch_plan(e, li, &pf);
+            TRY(showo::attn_decode_co_batch(e->qkv, l.qln_w, l.qln_b, l.kln_w, l.kln_b, e->cosT, e->sinT, d->k + li * lstride,
+                                            d->vt + li * lstride, d->iv_dev, e->attn, nb, nH, e->cfg.rotary_dim, e->cfg.ln_eps,
+                                            d->pos_dev, lk_max, d->cap, d->cap, o, co_blocks, s, &pf, op));
+            TRY(out_dense_y2B(nb, o, s, op));
+        } else {
+            TRY(showo::attn_decode_fused_batch(e->qkv, l.qln_w, l.qln_b, l.kln_w, l.kln_b, e->cosT, e->sinT, d->k + li * lstride,
+                                               d->vt + li * lstride, d->iv_dev, e->attn, nb, nH, e->cfg.rotary_dim, e->cfg.ln_eps,
+                                               d->pos_dev, lk_max, d->cap, d->cap, s, op));
+            TRY(out_gemvB(nb, o, s, op));
+        }
+    }
+    if (op) {  // precision 2: the lm_head is the split-bf16 product (its images stay bf16 (hi, lo) at that precision)
+        TRY(showo::decode_split_head(e->x, e->fln_w, e->fln_b, e->cfg.ln_eps, H, e->wlm, e->wlm_lo, e->blm, logits_ws, V, V, nb, s));
+    } else {
+        LnGemvBArgs h{e->x, e->fln_w, e->fln_b, e->cfg.ln_eps, H, e->wlm, e->blm, nullptr, logits_ws, V, V, nullptr, nullptr, nullptr, 0, 0};
+        TRY(ln_gemvB(nb, h, s));
+    }
+    return 0;
+}
+
+// co-scheduled layer (fc2 streams next to the latency-bound attention blocks): Phi-1.5's shape, 2..4 sequences (the fc2 role keeps
+// nb x 8192 bf16 activations in LDS); SHOWO_DECODE_BATCH_CO=0 / other shapes: three plain launches per layer
+int batch_use_co(showo_engine* e, bool* co) {
     static int co_on = -1;
     if (co_on < 0) {
         const char* env = getenv("SHOWO_DECODE_BATCH_CO");
         co_on = env ? (atoi(env) != 0) : 1;
     }
-    const int co_blocks = showo::decode_tuning().batch_co_blocks;  // 128 role blocks + 32 nb attention blocks = one block per CU at nb = 4
-    const bool co = co_on && F == 8192 && H <= 2048 && nb >= 2 && nb <= 4 && (size_t)nb * F * 2 <= 128 * 1024;
-    if (co && !d->y2) TRY(e->alloc(&d->y2, (int64_t)MAXB * H));
-    auto one = [&]() -> int {
-        for (int li = 0; li < e->nL; ++li) {
-            showo::Layer& l = e->layers[li];
-            LnGemvBArgs a{e->x, l.ln_w, l.ln_b, e->cfg.ln_eps, H, l.wqkv, l.bqkv, e->qkv, nullptr, 3 * H, 3 * H, l.w1, l.b1, e->ffn, F, F};
-            TRY(ln_gemvB(nb, a, s, op));
-            OutGemvBArgs o{e->x, l.wd, e->attn, l.bd, H, H, l.w2, e->ffn, l.b2, F, F, H, d->y2};
-            if (co) {
-                // [ attention of the nb x heads (sequence, head) pairs || fc2 of all nb sequences -> y2 ] -> dense + both residual adds
-                // (Phi's block is parallel-residual, models/phi.py:806-835: fc2 does not depend on the attention; decode.hip's batch-1 layer
-                // co-schedules the same way)
-                showo::DecodePrefetch pf;
-                showo::decode_prefetch_plan(e, li, &pf);
-                TRY(showo::attn_decode_co_batch(e->qkv, l.qln_w, l.qln_b, l.kln_w, l.kln_b, e->cosT, e->sinT, d->k + li * lstride,
-                                                d->vt + li * lstride, d->iv_dev, e->attn, nb, nH, e->cfg.rotary_dim, e->cfg.ln_eps,
-                                                d->pos_dev, lk_max, d->cap, d->cap, o, co_blocks, s, &pf, op));
-                TRY(out_dense_y2B(nb, o, s, op));
-            } else {
-                TRY(showo::attn_decode_fused_batch(e->qkv, l.qln_w, l.qln_b, l.kln_w, l.kln_b, e->cosT, e->sinT, d->k + li * lstride,
-                                                   d->vt + li * lstride, d->iv_dev, e->attn, nb, nH, e->cfg.rotary_dim, e->cfg.ln_eps,
-                                                   d->pos_dev, lk_max, d->cap, d->cap, s, op));
-                TRY(out_gemvB(nb, o, s, op));
-            }
-        }
-        if (op) {  // precision 2: the lm_head is the split-bf16 product (its images stay bf16 (hi, lo) at that precision)
-            TRY(showo::decode_split_head(e->x, e->fln_w, e->fln_b, e->cfg.ln_eps, H, e->wlm, e->wlm_lo, e->blm, logits_ws, V, V, nb, s));
-        } else {
-            LnGemvBArgs h{e->x, e->fln_w, e->fln_b, e->cfg.ln_eps, H, e->wlm, e->blm, nullptr, logits_ws, V, V, nullptr, nullptr, nullptr, 0, 0};
-            TRY(ln_gemvB(nb, h, s));
-        }
-        greedy_seam_rows_kernel<<<dim3(nb), dim3(1024), 0, s>>>(logits_ws, V, tok, out_tokens, n_steps, d->pos_dev, d->base_dev, e->embed, e->x,
-                                                               H, d->last_iv_dev, d->L0_dev, d->iv_dev);
-        SHOWO_CHECK_HIP(hipGetLastError());
-        return 0;
-    };
-    int rc = one();  // eager first step (kernel attributes)
+    const int nb = e->bd->nb;
+    *co = co_on && e->F == 8192 && e->H <= 2048 && nb >= 2 && nb <= 4 && (size_t)nb * e->F * 2 <= 128 * 1024;
+    if (*co && !e->bd->y2) TRY(e->alloc(&e->bd->y2, (int64_t)MAXB * e->H));
+    return 0;
+}
+
+// n_steps runs of one(): the first eagerly (kernel attributes), the rest as replays of one captured step (use_graph) or eagerly
+template <class Step>
+int run_batch_steps(Step&& one, int n_steps, int use_graph, hipStream_t s) {
+    int rc = one();
     hipGraph_t g = nullptr;
     hipGraphExec_t ge = nullptr;
     const bool graph = use_graph && n_steps > 1 && !showo::g_prof_on_query();
@@ -649,7 +712,115 @@ extern "C" int showo_engine_batch_decode_greedy(showo_engine* e, int64_t* tok, i
     }
     if (ge) { hipStreamSynchronize(s); hipGraphExecDestroy(ge); }
     if (g) hipGraphDestroy(g);
-    if (rc) return rc;
+    return rc;
+}
+}  // namespace
+
+// tok int64 [nb] (device): in = the token each sequence feeds first (e.g. the arg-max of its prefill logits), out = the last tokens
+// produced; out_tokens int64 [nb, n_steps] (device); logits_ws fp32 [nb, vocab] (device).  Every sequence advances n_steps tokens
+// (the caller cuts each row at its <eot>, like the chunked batch-1 loop of Showo.mmu_generate).
+extern "C" int showo_engine_batch_decode_greedy(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws,
+                                                int use_graph, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!e || !e->bd || e->bd->nb == 0) return set_error_msg(1, "batch_decode_greedy: showo_engine_batch_begin + _batch_prefill first");
+    auto* d = e->bd;
+    const int nb = d->nb, H = e->H, V = e->V;
+    if (!tok || !out_tokens || !logits_ws || n_steps < 1) return set_error_msg(1, "batch_decode_greedy: bad arguments");
+    TRY(batch_decode_checks(e, "batch_decode_greedy"));
+    const int op = e->precision == 2 ? SHOWO_OP_F16 : SHOWO_OP_BF16;
+    int lk_max = 0;
+    int P0[MAXB];
+    for (int b = 0; b < nb; ++b) {
+        P0[b] = d->cache_len[b];
+        if (P0[b] + n_steps > d->cap || P0[b] + n_steps > e->cfg.max_pos) return set_error_msg(5, "batch_decode_greedy: cache full");
+        lk_max = lk_max > P0[b] + n_steps ? lk_max : P0[b] + n_steps;
+    }
+    SHOWO_CHECK_HIP(hipMemcpyAsync(d->pos_dev, P0, sizeof(int) * nb, hipMemcpyHostToDevice, s));
+    SHOWO_CHECK_HIP(hipMemcpyAsync(d->base_dev, P0, sizeof(int) * nb, hipMemcpyHostToDevice, s));
+    SHOWO_CHECK_HIP(hipMemcpyAsync(d->L0_dev, d->prompt_len, sizeof(int) * nb, hipMemcpyHostToDevice, s));
+    SHOWO_CHECK_HIP(hipMemcpyAsync(d->last_iv_dev, d->last_iv, sizeof(int32_t) * 4 * nb, hipMemcpyHostToDevice, s));
+    SHOWO_CHECK_HIP(hipStreamSynchronize(s));  // P0 is a host temporary of this call
+    TRY(showo_embed_f32(tok, e->embed, e->x, nb, H, V, s));
+    batch_iv_kernel<<<1, 64, 0, s>>>(d->last_iv_dev, d->L0_dev, d->pos_dev, d->iv_dev, nb);
+    SHOWO_CHECK_HIP(hipGetLastError());
+    bool co = false;
+    TRY(batch_use_co(e, &co));
+    auto one = [&]() -> int {
+        TRY(batch_step_layers(e, op, co, lk_max, logits_ws, s));
+        greedy_seam_rows_kernel<<<dim3(nb), dim3(1024), 0, s>>>(logits_ws, V, tok, out_tokens, n_steps, d->pos_dev, d->base_dev, e->embed, e->x,
+                                                               H, d->last_iv_dev, d->L0_dev, d->iv_dev);
+        SHOWO_CHECK_HIP(hipGetLastError());
+        return 0;
+    };
+    TRY(run_batch_steps(one, n_steps, use_graph, s));
     for (int b = 0; b < nb; ++b) d->cache_len[b] = P0[b] + n_steps;
+    return 0;
+}
+
+// The sampled form with a per-slot stop (include/showo_hip.h): slot b draws with its own top_k / temperature / seed / draw index and
+// emits at most budget[b] tokens, stopping early after `eot`; a stopped or idle slot keeps decoding a fixed row in place so that the
+// captured step stays the same for every slot.  Its cache length advances by what it produced.
+extern "C" int showo_engine_batch_decode_sample(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws,
+                                                const int* top_k, const float* temperature, const uint64_t* seed, const int* draw0,
+                                                const float* const* exp_noise, const int* budget, int64_t eot, int* produced,
+                                                int use_graph, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!e || !e->bd || e->bd->nb == 0) return set_error_msg(1, "batch_decode_sample: showo_engine_batch_begin + _batch_prefill first");
+    auto* d = e->bd;
+    const int nb = d->nb, H = e->H, V = e->V;
+    if (!tok || !out_tokens || !logits_ws || n_steps < 1 || !top_k || !temperature || !seed || !draw0 || !budget || !produced)
+        return set_error_msg(1, "batch_decode_sample: bad arguments");
+    TRY(batch_decode_checks(e, "batch_decode_sample"));
+    const int op = e->precision == 2 ? SHOWO_OP_F16 : SHOWO_OP_BF16;
+    // positions stay below lim: the cache capacity and the rotary tables (max_position_embeddings)
+    const int lim = d->cap < e->cfg.max_pos ? d->cap : e->cfg.max_pos;
+    int lk_max = 0;
+    int P0[MAXB], pos0[MAXB];
+    SlotDraw sd[MAXB];
+    for (int b = 0; b < nb; ++b) {
+        if (budget[b] < 0 || draw0[b] < 0) return set_error_msg(1, "batch_decode_sample: budget and draw0 must be >= 0");
+        if (budget[b] > 0 && top_k[b] != 1 && !(temperature[b] > 0.f)) return set_error_msg(1, "batch_decode_sample: temperature must be > 0");
+        P0[b] = d->cache_len[b];
+        const int emit = budget[b] < n_steps ? budget[b] : n_steps;  // what the slot can still emit in this call
+        if (P0[b] + emit > lim) return set_error_msg(5, "batch_decode_sample: cache full");
+        pos0[b] = P0[b] < lim - 1 ? P0[b] : lim - 1;
+        // highest position + 1 the slot reaches: P0 + emit while it decodes, one more once it idles after its stop (below lim)
+        const int reach = P0[b] + emit + 1 < lim ? P0[b] + emit + 1 : lim;
+        lk_max = lk_max > reach ? lk_max : reach;
+        sd[b].noise = exp_noise ? exp_noise[b] : nullptr;
+        sd[b].seed = seed[b];
+        sd[b].temperature = temperature[b];
+        sd[b].top_k = top_k[b];
+        sd[b].draw0 = draw0[b];
+        sd[b].budget = budget[b];
+        sd[b].produced = 0;
+        sd[b].step = 0;
+        sd[b].active = budget[b] > 0;
+    }
+    if (!d->slots_dev) TRY(e->alloc(&d->slots_dev, MAXB));
+    SHOWO_CHECK_HIP(hipMemcpyAsync(d->pos_dev, pos0, sizeof(int) * nb, hipMemcpyHostToDevice, s));
+    SHOWO_CHECK_HIP(hipMemcpyAsync(d->L0_dev, d->prompt_len, sizeof(int) * nb, hipMemcpyHostToDevice, s));
+    SHOWO_CHECK_HIP(hipMemcpyAsync(d->last_iv_dev, d->last_iv, sizeof(int32_t) * 4 * nb, hipMemcpyHostToDevice, s));
+    SHOWO_CHECK_HIP(hipMemcpyAsync(d->slots_dev, sd, sizeof(SlotDraw) * nb, hipMemcpyHostToDevice, s));
+    SHOWO_CHECK_HIP(hipStreamSynchronize(s));  // pos0 / sd are host temporaries of this call
+    slot_embed_kernel<<<dim3(nb), dim3(256), 0, s>>>(tok, d->slots_dev, e->embed, e->x, H, V);
+    batch_iv_kernel<<<1, 64, 0, s>>>(d->last_iv_dev, d->L0_dev, d->pos_dev, d->iv_dev, nb);
+    SHOWO_CHECK_HIP(hipGetLastError());
+    bool co = false;
+    TRY(batch_use_co(e, &co));
+    auto one = [&]() -> int {
+        TRY(batch_step_layers(e, op, co, lk_max, logits_ws, s));
+        sample_seam_rows_kernel<<<dim3(nb), dim3(1024), 0, s>>>(logits_ws, V, eot, tok, out_tokens, n_steps, d->pos_dev, lim, d->slots_dev,
+                                                               e->embed, e->x, H, d->last_iv_dev, d->L0_dev, d->iv_dev);
+        SHOWO_CHECK_HIP(hipGetLastError());
+        return 0;
+    };
+    TRY(run_batch_steps(one, n_steps, use_graph, s));
+    SHOWO_CHECK_HIP(hipMemcpyAsync(sd, d->slots_dev, sizeof(SlotDraw) * nb, hipMemcpyDeviceToHost, s));
+    SHOWO_CHECK_HIP(hipStreamSynchronize(s));
+    for (int b = 0; b < nb; ++b) {
+        produced[b] = sd[b].produced;
+        d->cache_len[b] = P0[b] + sd[b].produced;
+    }
     return 0;
 }

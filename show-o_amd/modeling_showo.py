@@ -833,22 +833,194 @@ class Showo(PretrainedMixin, nn.Module):
         return result
 
 
+# Slot scheduler of mmu_generate_batch (n >= 2 sequences at precision 0 / 2 beyond the all-greedy 2..8 case).  Slot count for more
+# than _MMU_BATCH_MAX sequences: 5..8 slots run the plain three-launch batched layer, 2..4 the co-scheduled one (decode_batch.hip).
+# tools/mmu_batch_bench.py at the cfg4 shape: 8 slots lead 4 by 2.5-3.4 % on top-k sampled batches of 16 / 32 and trail by 1.3-1.5 % on
+# greedy ones ("Sampled batches and slot refill").
+_MMU_BATCH_MAX = 8
+_MMU_BATCH_SLOTS = 8
+_MMU_BATCH_CHUNK = 16
+
+
+def _mmu_batch_slots(n):
+    return n if n <= _MMU_BATCH_MAX else _MMU_BATCH_SLOTS
+
+
+def _mmu_batch_seeds(top_ks, generator):
+    """the Philox seed of every sampled sequence, drawn as n sequential mmu_generate calls draw them: one draw per sequence with
+    top_k != 1, in sequence order, none for greedy ones (None)"""
+    seeds = []
+    for k in top_ks:
+        if k == 1:
+            seeds.append(None)
+        elif generator is not None:
+            seeds.append(int(torch.randint(0, 2 ** 62, (1,), generator=generator, device=generator.device).item()))
+        else:
+            seeds.append(int(torch.randint(0, 2 ** 62, (1,)).item()))
+    return seeds
+
+
+def _mmu_batch_schedule(eng, n, slots, max_new_tokens, eot_token, chunk=_MMU_BATCH_CHUNK):
+    """Serve requests 0..n-1 on `slots` decode slots; returns their token lists in input order.
+
+    `eng` is the engine side: `prefill(slot, r)` puts request r into a free slot and returns its first token (drawn from the prefill
+    logits); `decode(m, budget, draw0)` runs m steps of every slot -- slot s emits at most budget[s] tokens (0: idle) with draw indices
+    draw0[s], draw0[s] + 1, ..., stopping early after <eot> -- and returns (rows, produced): the tokens of each slot and how many it
+    emitted.  Free slots are refilled in slot order with the pending requests in input order, at chunk boundaries."""
+    results = [None] * n
+    pending = list(range(n))[::-1]
+    occupant = [None] * slots
+    remaining = [0] * slots
+    while True:
+        for s in range(slots):
+            while occupant[s] is None and pending:
+                r = pending.pop()
+                first = eng.prefill(s, r)
+                results[r] = [first][:max_new_tokens]
+                if not ((eot_token is not None and first == eot_token) or max_new_tokens <= 1):
+                    occupant[s], remaining[s] = r, max_new_tokens - 1
+        live = [s for s in range(slots) if occupant[s] is not None]
+        if not live:
+            return results
+        m = min(chunk, max(remaining[s] for s in live))
+        budget = [min(remaining[s], m) if occupant[s] is not None else 0 for s in range(slots)]
+        draw0 = [max_new_tokens - remaining[s] if occupant[s] is not None else 0 for s in range(slots)]
+        rows, produced = eng.decode(m, budget, draw0)
+        for s in live:
+            toks = list(rows[s][:produced[s]])
+            results[occupant[s]].extend(toks)
+            remaining[s] -= produced[s]
+            if remaining[s] <= 0 or (eot_token is not None and toks and toks[-1] == eot_token):
+                occupant[s] = None
+
+
+class _MmuSlotEngine:
+    """engine side of _mmu_batch_schedule: `slots` KV caches of showo_engine_batch_*, one request per slot"""
+
+    def __init__(self, model, eng, idx, input_embeddings, masks, lens, slots, temps, top_ks, seeds, noises, eot_token, dev):
+        self.model, self.eng, self.idx, self.emb, self.masks, self.lens = model, eng, idx, input_embeddings, masks, lens
+        self.slots, self.temps, self.top_ks, self.seeds, self.noises = slots, temps, top_ks, seeds, noises
+        self.eot = -1 if eot_token is None else int(eot_token)
+        self.dev = dev
+        V = model.vocab_size
+        self.logits = torch.empty((slots, V), dtype=torch.float32, device=dev)
+        self.tok = torch.empty((slots,), dtype=torch.int64, device=dev)
+        self.occ = [None] * slots
+        self.use_graph = int(getattr(model, "decode_graph", 1))
+        if getattr(model, "_graph_stream", None) is None:
+            model._graph_stream = torch.cuda.Stream()
+
+    def prefill(self, s, r):
+        from .prompting_utils import IntervalMask
+        m, eng, L = self.model, self.eng, self.lens[r]
+        ids = emb = None
+        if self.idx is not None:
+            ids = self.idx[r].to(torch.int64).contiguous()
+        else:
+            emb = self.emb[r].detach().float().contiguous()
+        am = self.masks[r]
+        mask = m._use_mask(eng, am) if isinstance(am, IntervalMask) else (
+            None if am is None else am.detach().float().reshape(1, 1, L, L).contiguous())
+        try:
+            _lib.call("showo_engine_batch_prefill", eng, s, _lib.ptr(ids), _lib.ptr(emb), _lib.ptr(mask), L, _lib.ptr(self.logits[s]),
+                      _lib.stream())
+        finally:
+            _lib.call("showo_engine_use_intervals", eng, None, None)
+        k = self.top_ks[r]
+        if k == 1:
+            _lib.call("showo_argmax_f32", _lib.ptr(self.logits[s]), m.vocab_size, _lib.ptr(self.tok[s:s + 1]), _lib.stream())
+        else:
+            _lib.call("showo_sample_topk", _lib.ptr(self.logits[s]), m.vocab_size, 0 if k is None else int(k), float(self.temps[r]),
+                      _lib.ptr(self.noises[r]), self.seeds[r], 0, _lib.ptr(self.tok[s:s + 1]), _lib.stream())
+        self.occ[s] = r
+        return int(self.tok[s].item())
+
+    def decode(self, m, budget, draw0):
+        import ctypes as C
+        S = self.slots
+        occ = [r if budget[s] > 0 else None for s, r in enumerate(self.occ)]
+        k = [1 if r is None else (0 if self.top_ks[r] is None else int(self.top_ks[r])) for r in occ]
+        temp = [1.0 if r is None else float(self.temps[r]) for r in occ]
+        seed = [0 if r is None or self.seeds[r] is None else self.seeds[r] for r in occ]
+        noise = [None if r is None or self.noises[r] is None else _lib.ptr(self.noises[r]) for r in occ]
+        a_k, a_t, a_s = (C.c_int * S)(*k), (C.c_float * S)(*temp), (C.c_uint64 * S)(*seed)
+        a_d, a_n, a_b, prod = (C.c_int * S)(*draw0), (C.c_void_p * S)(*noise), (C.c_int * S)(*budget), (C.c_int * S)()
+        out = torch.empty((S, m), dtype=torch.int64, device=self.dev)
+        cur = torch.cuda.current_stream()
+        gs = self.model._graph_stream
+        gs.wait_stream(cur)
+        with torch.cuda.stream(gs):
+            _lib.call("showo_engine_batch_decode_sample", self.eng, _lib.ptr(self.tok), m, _lib.ptr(out), _lib.ptr(self.logits),
+                      *(C.cast(a, C.c_void_p) for a in (a_k, a_t, a_s, a_d, a_n, a_b)), self.eot, C.cast(prod, C.c_void_p),
+                      self.use_graph, _lib.stream())
+        cur.wait_stream(gs)
+        return out.tolist(), list(prod)
+
+
 @torch.no_grad()
 def mmu_generate_batch(self, idx=None, input_embeddings=None, attention_mask=None, max_new_tokens=100, temperature=1.0, top_k=None,
-                       eot_token=None):
+                       eot_token=None, generator=None, _exp_noise=None):
     """n independent `mmu_generate` calls served together (BASELINE cfg4: "batch=4 images"; the reference's mmu_generate is batch-1 and
     inference_mmu.py:87-177 walks the images one by one).  `idx` / `input_embeddings` / `attention_mask` are LISTS (one entry per
     sequence, each what a single `mmu_generate` call takes: [1, L_b] ids or [1, L_b, H] embeddings, its own mask or IntervalMask);
-    returns a list of n token lists -- exactly what n separate calls return.  Greedy (`top_k=1`, the reference caller's setting,
-    inference_mmu.py:81) at precision 0 or 2 runs on the batched engine path (csrc/decode_batch.hip: n KV caches, ONE weight stream per
-    token step, every sequence bit-identical to its batch-1 run); anything else falls back to n sequential calls."""
+    `temperature` / `top_k` are scalars or lists of n values, `_exp_noise` None or a list of n entries (None or [max_new_tokens, vocab]).
+
+    Returns a list of n token lists: result[b] is what `mmu_generate(<sequence b>, attention_mask=masks[b], max_new_tokens,
+    temperature[b], top_k[b], eot_token, generator=generator, _exp_noise=_exp_noise[b])` returns when those calls are made in order
+    b = 0, 1, ..., n-1 (the same seeds are drawn from `generator`, or torch's global generator, in the same order).  At precision 0 and 2
+    every n >= 2 runs on the batched engine path (csrc/decode_batch.hip: one weight stream per token step for all slots, every sequence
+    bit-identical to its batch-1 run): all-greedy batches of 2..8 on showo_engine_batch_decode_greedy, anything else on up to 8 slots
+    of showo_engine_batch_decode_sample that are refilled as sequences finish.  Precision 1 and n < 2 make the sequential calls."""
     seqs = idx if idx is not None else input_embeddings
     n = len(seqs)
     masks = attention_mask if isinstance(attention_mask, (list, tuple)) else [attention_mask] * n
-    if top_k != 1 or int(getattr(self, "_precision", 0)) == 1 or n > 8 or n < 2:
-        return [self.mmu_generate(idx=None if idx is None else idx[b], input_embeddings=None if input_embeddings is None else input_embeddings[b],
-                                  attention_mask=masks[b], max_new_tokens=max_new_tokens, temperature=temperature, top_k=top_k,
-                                  eot_token=eot_token) for b in range(n)]
+    temps = list(temperature) if isinstance(temperature, (list, tuple)) else [temperature] * n
+    top_ks = list(top_k) if isinstance(top_k, (list, tuple)) else [top_k] * n
+    noises = list(_exp_noise) if _exp_noise is not None else [None] * n
+    if not (len(masks) == len(temps) == len(top_ks) == len(noises) == n):
+        raise ValueError("attention_mask / temperature / top_k / _exp_noise lists need one entry per sequence")
+
+    def single(b):
+        return self.mmu_generate(idx=None if idx is None else idx[b], input_embeddings=None if input_embeddings is None else input_embeddings[b],
+                                 attention_mask=masks[b], max_new_tokens=max_new_tokens, temperature=temps[b], top_k=top_ks[b],
+                                 eot_token=eot_token, generator=generator, _exp_noise=noises[b])
+
+    if int(getattr(self, "_precision", 0)) == 1 or n < 2:
+        return [single(b) for b in range(n)]
+    if n <= _MMU_BATCH_MAX and all(k == 1 for k in top_ks):
+        return self._mmu_generate_batch_greedy(idx, input_embeddings, masks, max_new_tokens, eot_token, single)
+    for b in range(n):
+        if seqs[b].shape[0] != 1:
+            raise ValueError("every sequence of mmu_generate_batch is one batch-1 mmu_generate call (reference modeling_showo.py:204,229)")
+        if top_ks[b] != 1 and not temps[b] > 0:
+            raise ValueError("temperature must be > 0")
+        if top_ks[b] != 1 and noises[b] is not None and tuple(noises[b].shape) != (max_new_tokens, self.vocab_size):
+            raise ValueError("_exp_noise must be [max_new_tokens, vocab_size]")
+    eng = self.engine()
+    dev = seqs[0].device
+    lens = [int(t.shape[1]) for t in seqs]
+    slots = _mmu_batch_slots(n)
+    try:
+        _lib.call("showo_engine_batch_begin", eng, slots, max(lens) + max_new_tokens + 1)
+    except RuntimeError:
+        # the batch's common capacity (longest prompt + max_new_tokens) does not fit the engine (max_position_embeddings, the single-block
+        # decode attention): n sequential calls fail only if a sequence actually reaches the limit before <eot> (ADVICE r5)
+        return [single(b) for b in range(n)]
+    seeds = _mmu_batch_seeds(top_ks, generator)
+    noises = [None if (k == 1 or z is None) else z.detach().float().contiguous().to(dev) for k, z in zip(top_ks, noises)]
+    se = _MmuSlotEngine(self, eng, idx, input_embeddings, masks, lens, slots, temps, top_ks, seeds, noises, eot_token, dev)
+    out = _mmu_batch_schedule(se, n, slots, max_new_tokens, eot_token)
+    return [[torch.tensor(t, device=dev) for t in r] for r in out]
+
+
+Showo.mmu_generate_batch = mmu_generate_batch
+
+
+@torch.no_grad()
+def _mmu_generate_batch_greedy(self, idx, input_embeddings, masks, max_new_tokens, eot_token, single):
+    """all-greedy batch of 2..8 sequences: one slot per sequence on showo_engine_batch_decode_greedy (the cfg4 bench leg)"""
+    seqs = idx if idx is not None else input_embeddings
+    n = len(seqs)
     from .prompting_utils import IntervalMask
     eng = self.engine()
     dev = seqs[0].device
@@ -858,9 +1030,7 @@ def mmu_generate_batch(self, idx=None, input_embeddings=None, attention_mask=Non
     except RuntimeError:
         # the batch's common capacity (longest prompt + max_new_tokens) does not fit the engine (max_position_embeddings, the single-block
         # decode attention): n sequential calls fail only if a sequence actually reaches the limit before <eot>
-        return [self.mmu_generate(idx=None if idx is None else idx[b], input_embeddings=None if input_embeddings is None else input_embeddings[b],
-                                  attention_mask=masks[b], max_new_tokens=max_new_tokens, temperature=temperature, top_k=top_k,
-                                  eot_token=eot_token) for b in range(n)]
+        return [single(b) for b in range(n)]
     logits = torch.empty((n, self.vocab_size), dtype=torch.float32, device=dev)
     tok = torch.empty((n,), dtype=torch.int64, device=dev)
     for b in range(n):
@@ -908,7 +1078,9 @@ def mmu_generate_batch(self, idx=None, input_embeddings=None, attention_mask=Non
     return [r[:max_new_tokens] for r in results]
 
 
-Showo.mmu_generate_batch = mmu_generate_batch
+
+
+Showo._mmu_generate_batch_greedy = _mmu_generate_batch_greedy
 
 
 def _dense_mask_of(attention_mask, L, device):

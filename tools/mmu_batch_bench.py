@@ -1,0 +1,106 @@
+"""Whole-call throughput of Showo.mmu_generate_batch vs n sequential mmu_generate calls at the BASELINE cfg4 shape.
+
+Inputs are built like bench_configs.py's mmu leg: full-size seeded weights (w_clip_vit), 631-embedding prompts (mm_projector of 576
+synthetic CLIP features spliced between 30 system / 25 question token embeddings), 100 new tokens, eot_token=None.  Every figure is
+tokens / s of a whole call, device-synchronised, after one warm-up call of the same shape; the batched call's tokens are checked
+against the sequential calls' (same generator seed).
+
+  python tools/mmu_batch_bench.py              # the JSON below (n = 4, 16, 32; greedy and top_k=5 / temperature=0.7)
+  python tools/mmu_batch_bench.py --profile    # one batched greedy and one batched sampled n = 4 call, for a kernel trace
+                                               # (rocprofv3 --kernel-trace --stats -- python tools/mmu_batch_bench.py --profile)
+
+The slot count for n > 8 is set through modeling_showo._MMU_BATCH_SLOTS for this run only."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+NEW = 100
+SAMPLED = dict(top_k=5, temperature=0.7)
+GREEDY = dict(top_k=1)
+
+
+def build(n_prompts):
+    import showo_amd
+    from showo_amd import synthetic
+    from showo_amd.prompting_utils import create_attention_mask_for_mmu_vit
+    torch.manual_seed(0)
+    model = synthetic.random_init_showo(max_batch=1, max_seq=768, w_clip_vit=True).eval()
+    tab = model.showo.model.embed_tokens.weight
+    embs, masks = [], []
+    for b in range(n_prompts):
+        gg = torch.Generator(device="cuda").manual_seed(100 + b)
+        feats = torch.randn(1, 576, 1024, device="cuda", generator=gg)
+        ids = torch.randint(0, 50256, (1, 55), device="cuda", generator=gg)
+        with torch.no_grad():
+            img = model.mm_projector(feats)
+            txt = tab[ids]
+            embs.append(torch.cat([txt[:, :30], img, txt[:, 30:]], dim=1).contiguous())
+        masks.append(create_attention_mask_for_mmu_vit(embs[-1], system_prompt_len=28)[0])
+    assert embs[0].shape[1] == 631
+    return showo_amd, model, embs, masks
+
+
+def timed(fn):
+    fn()  # warm-up call of the same shape
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    out = fn()
+    torch.cuda.synchronize()
+    return time.perf_counter() - t0, [[int(t) for t in r] for r in out]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--profile", action="store_true")
+    a = ap.parse_args()
+    pkg, model, embs, masks = build(4 if a.profile else 32)
+    M = pkg.modeling_showo
+    gen = lambda: torch.Generator(device="cuda").manual_seed(7)  # noqa: E731
+
+    def batched(n, kw):
+        return lambda: model.mmu_generate_batch(input_embeddings=embs[:n], attention_mask=masks[:n], max_new_tokens=NEW, generator=gen(), **kw)
+
+    def sequential(n, kw):
+        def run():
+            g = gen()
+            return [model.mmu_generate(input_embeddings=embs[b], attention_mask=masks[b], max_new_tokens=NEW, generator=g, **kw)
+                    for b in range(n)]
+        return run
+
+    if a.profile:
+        for kw in (GREEDY, SAMPLED):
+            batched(4, kw)()
+        torch.cuda.synchronize()
+        print(json.dumps({"profiled": "mmu_generate_batch n=4 greedy, then n=4 top_k=5 temperature=0.7"}))
+        return
+    res = {"shape": "cfg4: 631-embedding w_clip_vit prompts, 100 new tokens each, full-size seeded weights", "unit": "tokens/s (whole call)"}
+    for n in (4, 16, 32):
+        for name, kw in (("greedy", GREEDY), ("sampled_topk5_t0.7", SAMPLED)):
+            row = {}
+            ts, want = timed(sequential(n, kw))
+            row["sequential"] = n * NEW / ts
+            slot_choices = [None] if n <= 8 else [4, 8]
+            for slots in slot_choices:
+                keep = M._MMU_BATCH_SLOTS
+                if slots is not None:
+                    M._MMU_BATCH_SLOTS = slots
+                try:
+                    tb, got = timed(batched(n, kw))
+                finally:
+                    M._MMU_BATCH_SLOTS = keep
+                assert got == want, (n, name, slots)
+                row["batched" if slots is None else f"batched_{slots}_slots"] = n * NEW / tb
+            res[f"n{n}_{name}"] = row
+            print(f"n={n} {name}: {row}", file=sys.stderr, flush=True)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
