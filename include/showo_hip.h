@@ -620,8 +620,25 @@ int showo_vq_get_code(showo_vq* v, const float* pixels, int B, int H, int W, int
 typedef struct showo_trainer showo_trainer;
 int showo_train_create(showo_engine* e, int max_batch, int max_seq, showo_trainer** out);
 void showo_train_destroy(showo_trainer* t);
-/* call after showo_engine_load changed weights (optimizer step): the transposed images are rebuilt lazily */
+/* The transposed images of the dgrad GEMMs follow the engine's per-tensor version stamps (showo_engine_load and the fused AdamW
+ * stamp every write): the next forward rebuilds the images of the tensors that changed, and only those.  This call marks every
+ * image stale regardless. */
 int showo_train_invalidate_weights(showo_trainer* t);
+/* Trainable set (reference: torch AdamW built over the `requires_grad` parameters only, training/train.py:210-223).  key = a
+ * reference state-dict key; every tensor starts trainable.  A frozen tensor gets no weight-gradient launch, no optimizer update
+ * (showo_train_adamw_step) and no image rebuild; a launch whose only consumer is frozen does not run (a backward phase with nothing
+ * trainable at or below it launches nothing).  Zero contract: after a backward every frozen tensor's gradient slot reads as zeros
+ * (cleared once, when it froze), so showo_grad_clip_norm over the flat buffer is the norm over the trainable tensors.  With every
+ * tensor trainable the launch sequence and every bit are those of the full backward.
+ * Bias coupling: the dense / fc2 bias gradients of block i are column sums written by the LayerNorm backward of block i + 1 (of
+ * the final LayerNorm for the top block); that write happens whenever block i's biases train. */
+int showo_train_set_trainable(showo_trainer* t, const char* key, int on);
+/* whether d(loss)/d(input embeddings) of a showo_train_forward_embeds is wanted (default 1; 0: showo_train_input_grad refuses and
+ * the backward stops at the lowest block that trains) */
+int showo_train_set_input_grad(showo_trainer* t, int on);
+/* launch counters since the last reset (tests): out6 = {weight-gradient GEMMs, data-gradient GEMMs, block phases that ran,
+ * embedding-phase launches, transposed weight images rebuilt, fused block images rebuilt by the engine}; reset != 0 zeroes them */
+int showo_train_counters(showo_trainer* t, int64_t* out6, int reset);
 /* Training with visibility intervals built on the device (showo_mask_predict_next / showo_mask_mmu; reference
  * training/train.py:522-577 builds and concatenates dense [B,1,L,L] masks instead): the next showo_train_forward call with
  * mask == NULL uses iv int32 [B,L,4] for the forward and the backward; iv == NULL restores the causal default.
@@ -672,8 +689,8 @@ int showo_train_losses(showo_trainer* t, float* out3, void* stream);
  * saved activations are still those of its own forward; -1 for a NULL handle */
 int64_t showo_train_generation(showo_trainer* t);
 /* optimizer (torch.optim.AdamW with the reference's two parameter groups, training/train.py:205-231): register the fp32
- * master tensor and the two moment buffers of a state-dict key once, then one call per step updates every parameter from
- * the gradients of the last backward and refreshes the engine's bf16 weight images. */
+ * master tensor and the two moment buffers of a state-dict key once, then one call per step updates every trainable bound
+ * parameter from the gradients of the last backward and refreshes its engine weight image; frozen ones are left untouched. */
 int showo_train_bind_param(showo_trainer* t, const char* key, float* param, float* exp_avg, float* exp_avg_sq, int64_t n);
 int showo_train_adamw_step(showo_trainer* t, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                            void* stream);

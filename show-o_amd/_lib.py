@@ -60,6 +60,9 @@ _PROTOS = {
     "showo_gelu_bf16": [c_p, c_p, c_i64, c_p],
     "showo_train_create": [c_p, c_i, c_i, c_p],
     "showo_train_invalidate_weights": [c_p],
+    "showo_train_set_trainable": [c_p, C.c_char_p, c_i],
+    "showo_train_set_input_grad": [c_p, c_i],
+    "showo_train_counters": [c_p, c_p, c_i],
     "showo_trainer_use_intervals": [c_p, c_p, c_p],
     "showo_train_forward": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p],
     "showo_train_forward_embeds": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p],

@@ -61,8 +61,6 @@ def resume_from_checkpoint(model, output_dir, trainer=None):
         from safetensors.torch import load_file
         sd = load_file(os.path.join(wdir, "pytorch_model.safetensors"))
     model.load_state_dict(sd, strict=True)
-    if hasattr(model, "_weights_changed"):
-        model._weights_changed = True
     opt = os.path.join(path, "optimizer.bin")
     if trainer is not None and os.path.isfile(opt):
         trainer.load_state_dict(torch.load(opt, map_location="cpu", weights_only=False))

@@ -23,6 +23,10 @@ struct Layer {
     // accuracy mode on the production kernels: K-concatenated, tiled split images (precise_sync in engine.hip)
     //   wq1x3 rows [w_hi | w_hi | w_lo] of [Wqkv ; W1]  ([3H + F, 3H]);  wd2x3 rows [Wd_hi | W2_hi | Wd_hi | W2_hi | Wd_lo | W2_lo] ([H, 3 (H + F)])
     bf16_t *wq1x3 = nullptr, *wd2x3 = nullptr;
+    // image versions (showo::engine_version): wqkv (any of q / k / v), wd, w1, w2, bd, b2 -- stamped from showo_engine::clock whenever the
+    // tensor is written; fused_at = the clock when this block's wd2 / bd2 / wq1t images were last built (0: never)
+    uint64_t ver[6] = {0, 0, 0, 0, 0, 0};
+    uint64_t fused_at = 0;
 };
 }  // namespace showo
 
@@ -76,6 +80,10 @@ int precise_gelu_split(const float* f, bf16_t* hi, bf16_t* lo, int64_t n, hipStr
 void engine_batch_free(showo_engine* e);  // decode_batch.hip
 extern int g_decode_impl;  // 0 = fused decode layer (default), 1 = the seven-launch path (showo_decode_set_impl)
 extern bool g_prof_on_query();
+// version stamp of a state-dict tensor that derived weight images are built from (nullptr: none is) -- engine.hip
+uint64_t* engine_version(showo_engine* e, const char* key);
+void engine_bump_all(showo_engine* e);  // every image stale (a blanket write: showo_engine_weights_touched, precision switch)
+bool engine_fused_stale(const showo_engine* e);
 }  // namespace showo
 
 using showo::bf16_t;
@@ -89,7 +97,11 @@ struct showo_engine {
     std::vector<void*> allocs;
     std::set<std::string> loaded;
     int expected = 0;
-    bool fused_valid = false;  // wd2 / bd2 / wq1t images match the weights
+    // per-tensor image validity: every write of a weight that some derived image is made from stamps the tensor's version with ++clock
+    // (showo_engine_load, the trainer's fused AdamW); fused_sync rebuilds the blocks whose stamps are newer than their images
+    uint64_t clock = 0;
+    uint64_t ver_wlm = 0;        // lm_head.weight (the trainer's transposed image)
+    int64_t fused_rebuilt = 0;   // blocks whose fused images were rebuilt (showo_train_counters)
     bool fused_tiled = false;  // layout of wd2 (and use of wq1t): tiled (default) or row-major (SHOWO_W_TILED=0)
     bf16_t* wtmp = nullptr;    // staging of one layer's [Wd | W2] rows while its tiled image is built
     // weights

@@ -15,6 +15,7 @@
 //   K-contiguous, exactly what the MFMA GEMM's operand loader wants); biases / LayerNorm params fp32.
 #include "engine.h"
 #include "decode_common.h"
+#include <algorithm>
 #include <cstdio>
 #include <vector>
 #include <cstring>
@@ -245,7 +246,9 @@ extern "C" int showo_engine_load(showo_engine* e, const char* key, const float* 
     }
     if (rc == -1) return set_error_msg(3, "engine_load: unknown state-dict key");
     if (rc == 0) e->loaded.insert(k);
-    e->fused_valid = false;  // the fused weight images (and with them a cached t2i graph's preconditions) are rebuilt on the next call
+    // the images made from this tensor (the fused block images -- and with them a cached t2i graph's preconditions -- and the
+    // trainer's transposed images) are rebuilt by their next user
+    if (uint64_t* v = showo::engine_version(e, key)) *v = ++e->clock;
     e->px3_valid = false;
     e->head3_valid = false;
     return rc;
@@ -295,12 +298,40 @@ extern "C" int showo_engine_slot(showo_engine* e, const char* key, int64_t n, ui
 // the caller rewrote weight images through showo_engine_slot pointers: same bookkeeping as showo_engine_load
 extern "C" int showo_engine_weights_touched(showo_engine* e) {
     if (!e) return set_error_msg(1, "engine: null handle");
-    e->fused_valid = false;
+    showo::engine_bump_all(e);
     e->px3_valid = false;
     e->head3_valid = false;
     e->lo_loaded.clear();  // the hi images were rewritten without their low halves: accuracy mode needs a re-upload
     e->img_f16 = false;    // the trainer writes bf16 images: a precision-2 engine needs a re-upload too (run_layers checks)
     return 0;
+}
+
+uint64_t* showo::engine_version(showo_engine* e, const char* key) {
+    if (!strcmp(key, "showo.lm_head.weight")) return &e->ver_wlm;
+    int li = -1;
+    char sub[128];
+    if (sscanf(key, "showo.model.layers.%d.%127s", &li, sub) != 2 || li < 0 || li >= e->nL) return nullptr;
+    showo::Layer& l = e->layers[li];
+    const char* names[6] = {nullptr, "self_attn.dense.weight", "mlp.fc1.weight", "mlp.fc2.weight", "self_attn.dense.bias", "mlp.fc2.bias"};
+    if (!strcmp(sub, "self_attn.q_proj.weight") || !strcmp(sub, "self_attn.k_proj.weight") || !strcmp(sub, "self_attn.v_proj.weight")) return &l.ver[0];
+    for (int j = 1; j < 6; ++j)
+        if (!strcmp(sub, names[j])) return &l.ver[j];
+    return nullptr;
+}
+
+void showo::engine_bump_all(showo_engine* e) {
+    const uint64_t v = ++e->clock;
+    for (auto& l : e->layers)
+        for (uint64_t& x : l.ver) x = v;
+    e->ver_wlm = v;
+}
+
+static bool block_stale(const showo::Layer& l) { return l.fused_at == 0 || *std::max_element(l.ver, l.ver + 6) > l.fused_at; }
+
+bool showo::engine_fused_stale(const showo_engine* e) {
+    for (auto& l : e->layers)
+        if (block_stale(l)) return true;
+    return false;
 }
 
 namespace {
@@ -320,15 +351,16 @@ static bool w_tiled_enabled() {
     return v != 0;
 }
 
-// Weight images of the two fused projections, rebuilt after any weight load:
+// Weight images of the two fused projections, rebuilt for every block whose wqkv / wd / w1 / w2 / bd / b2 changed since they were built:
 //   wd2  = [Wd | W2] ([H, H + F], K-concatenated) for showo_gemm_kcat_bf16, bd2 = bd + b2;
 //   wq1t = tiled copy of [Wqkv ; W1] (showo_gemm_tile_weight) -- with SHOWO_W_TILED (default) wd2 is stored tiled as well
 static int fused_sync(showo_engine* e, hipStream_t s) {
-    if (e->fused_valid) return 0;
+    if (!showo::engine_fused_stale(e)) return 0;
     const int H = e->H, F = e->F;
     const bool tiled = w_tiled_enabled();
     if (tiled && !e->wtmp) TRY(e->alloc(&e->wtmp, (int64_t)H * (H + F)));
     for (auto& l : e->layers) {
+        if (!block_stale(l)) continue;
         bf16_t* cat = tiled ? e->wtmp : l.wd2;
         SHOWO_CHECK_HIP(hipMemcpy2DAsync(cat, (size_t)(H + F) * 2, l.wd, (size_t)H * 2, (size_t)H * 2, H, hipMemcpyDeviceToDevice, s));
         SHOWO_CHECK_HIP(hipMemcpy2DAsync(cat + H, (size_t)(H + F) * 2, l.w2, (size_t)F * 2, (size_t)F * 2, H, hipMemcpyDeviceToDevice, s));
@@ -338,10 +370,11 @@ static int fused_sync(showo_engine* e, hipStream_t s) {
             TRY(showo_gemm_tile_weight(l.wqkv, H, 3 * H + F, H, l.wq1t, s));
         }
         add2_f32_kernel<<<dim3((H + 255) / 256), dim3(256), 0, s>>>(l.bd, l.b2, l.bd2, H);
+        l.fused_at = std::max<uint64_t>(e->clock, 1);
+        ++e->fused_rebuilt;
     }
     SHOWO_CHECK_HIP(hipGetLastError());
     e->fused_tiled = tiled;
-    e->fused_valid = true;
     return 0;
 }
 
@@ -498,7 +531,7 @@ extern "C" int showo_engine_set_precision(showo_engine* e, int precision) {
             if (gemm_w) it = e->loaded.erase(it); else ++it;
         }
         e->lo_loaded.clear();
-        e->fused_valid = false; e->px3_valid = false; e->head3_valid = false;
+        showo::engine_bump_all(e); e->px3_valid = false; e->head3_valid = false;
     }
     if (precision == 1 && !e->p_hlo) {  // low halves of every GEMM weight + fp32 workspaces, allocated on first use
         const int64_t H = e->H, F = e->F, V = e->V, T = e->maxT;
@@ -759,7 +792,7 @@ static int run_layers(showo_engine* e, int B, int L, int pos0, const KVDest& kv,
     if (fused) {
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         hipStreamIsCapturing(s, &cs);
-        if (!e->fused_valid && cs != hipStreamCaptureStatusNone) return set_error_msg(7, "engine: fused weight images must be built before a stream capture");
+        if (showo::engine_fused_stale(e) && cs != hipStreamCaptureStatusNone) return set_error_msg(7, "engine: fused weight images must be built before a stream capture");
         TRY(fused_sync(e, s));
         for (int li = 0; li < e->nL; ++li) {
             showo::Layer& l = e->layers[li];

@@ -15,6 +15,7 @@
 #include <cstring>
 #include <algorithm>
 #include <map>
+#include <set>
 
 using namespace showo;
 
@@ -36,8 +37,15 @@ struct LayerT {
     float *gwqkv = nullptr, *gbqkv = nullptr, *gwd = nullptr, *gbd = nullptr, *gw1 = nullptr, *gb1 = nullptr, *gw2 = nullptr, *gb2 = nullptr;
     float *gln = nullptr;   // [2,H] (weight, bias)
     float* gqk = nullptr;   // [4,64] (q_ln w, b, k_ln w, b)
+    uint64_t tv[4] = {0, 0, 0, 0};  // engine versions (Layer::ver) the transposed images wqkvT, wdT, w1T, w2T were made from
 };
 struct Grad { float* p; int64_t n; };
+// which of a block's gradients the backward writes (showo_train_set_trainable): a group flag is on when any of its tensors trains
+struct LayerPlan {
+    bool wqkv = true, bqkv = true, wd = true, bd = true, w1 = true, b1 = true, w2 = true, b2 = true, ln = true, qk = true;
+    bool any = true;
+    std::vector<Grad> clear;  // frozen members of a group that one launch writes whole (q/k/v, LayerNorm pairs): cleared after it
+};
 struct Bound { std::string key; float *p, *m, *v; int64_t n; bool decay; };
 
 // SHOWO_TRAIN_TN (default 1): weight gradients by showo_gemm_tn_bf16 on the token-major tensors the backward already holds (dY, and the
@@ -63,6 +71,7 @@ struct showo_trainer {
     int64_t* adam_start_of = nullptr;
     int adam_chunks = 0;
     bool adam_dirty = true;
+    std::vector<std::pair<std::string, uint64_t*>> adam_keys;  // tensors the table updates + their engine version stamps
     // head
     float *logits = nullptr, *gembed = nullptr, *gfln = nullptr, *gwlm = nullptr, *gblm = nullptr;
     bf16_t *dlogits = nullptr, *bigT = nullptr;  // bigT: [max(Vp, F, 3H), Tp] transposed image of the dY side (SHOWO_TRAIN_TN=0 only)
@@ -80,7 +89,18 @@ struct showo_trainer {
     uint64_t generation = 0;  // training forwards started (showo_train_generation)
     bool has_mask = false;
     bool from_embeds = false;  // last forward started from caller-provided embeddings: d(loss)/d(embeddings) = dy
-    bool weights_synced = false;
+    uint64_t tv_wlm = 0;  // engine version of lm_head.weight that wlmT was made from
+    // trainable set (showo_train_set_trainable): state-dict keys whose gradients are not wanted; their slots read as zeros
+    std::set<std::string> frozen, pending_zero;
+    bool want_input = true;  // d(loss)/d(input embeddings) is wanted (showo_train_set_input_grad)
+    bool plan_dirty = true;
+    std::vector<LayerPlan> plan;
+    std::vector<char> any_below;  // any_below[i]: some block j < i trains
+    bool p_emb = true, p_fln = true, p_wlm = true, p_blm = true;
+    std::vector<Grad> fln_clear;
+    bool gembed_dirty = false;  // gembed holds a scatter of an earlier backward (the next one that does not scatter clears it)
+    float *sc_ln = nullptr, *sc_b = nullptr, *sc_b1 = nullptr, *sc_qk = nullptr;  // side outputs of fused launches for frozen tensors
+    int64_t cnt[5] = {0, 0, 0, 0, 0};  // showo_train_counters
     // loss weights announced before the forward (showo_train_set_loss_weights): the forward's cross-entropy pass then writes the
     // logit gradients as well, and a backward with the same labels / split / weights skips its own pass over the 2.6 GB of logits
     bool lw_set = false;
@@ -209,6 +229,7 @@ extern "C" int showo_train_create(showo_engine* e, int max_batch, int max_seq, s
     rc |= t->alloc(&t->lnpart, (int64_t)showo_ln_bwd_blocks((int)T) * 3 * H);
     rc |= t->alloc(&t->qkpart, (int64_t)showo_qkln_rope_bwd_blocks((int)T, (int)nH) * 256);
     rc |= t->alloc(&t->rowloss, 2 * T);
+    rc |= t->alloc(&t->sc_ln, 2 * H); rc |= t->alloc(&t->sc_b, H); rc |= t->alloc(&t->sc_b1, F); rc |= t->alloc(&t->sc_qk, 256);
     rc |= t->alloc((char**)&t->ce_rows, 12 * T);
     rc |= t->alloc(&t->counts, 4);
     rc |= t->alloc(&t->order_ws, 2 * T);
@@ -228,25 +249,119 @@ extern "C" void showo_train_destroy(showo_trainer* t) {
 
 extern "C" int showo_train_invalidate_weights(showo_trainer* t) {
     if (!t) return set_error_msg(1, "train: null handle");
-    t->weights_synced = false;
+    for (auto& l : t->L) std::fill(l.tv, l.tv + 4, 0);
+    t->tv_wlm = 0;
     return 0;
 }
 
-// transposed bf16 weight images for the dgrad GEMMs (call after the engine's weights changed)
+// transposed bf16 weight images for the dgrad GEMMs: rebuilt for the tensors whose engine image changed since they were made
+// (engine versions, Layer::ver: showo_engine_load and the fused AdamW stamp every write)
 static int sync_weights(showo_trainer* t, hipStream_t s) {
-    if (t->weights_synced) return 0;
     showo_engine* e = t->e;
     const int H = e->H, F = e->F, V = e->V;
     for (int i = 0; i < e->nL; ++i) {
         Layer& w = e->layers[i];
         LayerT& l = t->L[i];
-        TRY(showo_transpose_bf16(w.wqkv, H, l.wqkvT, 3 * H, H, 3 * H, 0, nullptr, nullptr, 0, s));  // [3H,H] -> [H,3H]
-        TRY(showo_transpose_bf16(w.wd, H, l.wdT, H, H, H, 0, nullptr, nullptr, 0, s));
-        TRY(showo_transpose_bf16(w.w1, H, l.w1T, F, H, F, 0, nullptr, nullptr, 0, s));                // [F,H] -> [H,F]
-        TRY(showo_transpose_bf16(w.w2, F, l.w2T, H, F, H, 0, nullptr, nullptr, 0, s));                // [H,F] -> [F,H]
+        const bool st[4] = {l.tv[0] < w.ver[0], l.tv[1] < w.ver[1], l.tv[2] < w.ver[2], l.tv[3] < w.ver[3]};
+        if (st[0]) TRY(showo_transpose_bf16(w.wqkv, H, l.wqkvT, 3 * H, H, 3 * H, 0, nullptr, nullptr, 0, s));  // [3H,H] -> [H,3H]
+        if (st[1]) TRY(showo_transpose_bf16(w.wd, H, l.wdT, H, H, H, 0, nullptr, nullptr, 0, s));
+        if (st[2]) TRY(showo_transpose_bf16(w.w1, H, l.w1T, F, H, F, 0, nullptr, nullptr, 0, s));                // [F,H] -> [H,F]
+        if (st[3]) TRY(showo_transpose_bf16(w.w2, F, l.w2T, H, F, H, 0, nullptr, nullptr, 0, s));                // [H,F] -> [F,H]
+        for (int k = 0; k < 4; ++k)
+            if (st[k]) { l.tv[k] = w.ver[k]; ++t->cnt[4]; }
     }
-    TRY(showo_transpose_bf16(e->wlm, H, t->wlmT, V, H, t->Vp, 0, nullptr, nullptr, 0, s));            // [V,H] -> [H,Vp]
-    t->weights_synced = true;
+    if (t->tv_wlm < e->ver_wlm) {
+        TRY(showo_transpose_bf16(e->wlm, H, t->wlmT, V, H, t->Vp, 0, nullptr, nullptr, 0, s));        // [V,H] -> [H,Vp]
+        t->tv_wlm = e->ver_wlm;
+        ++t->cnt[4];
+    }
+    return 0;
+}
+
+// ---- trainable set
+// (Re)derive the per-block plan from the frozen keys, and clear the gradient slots of tensors frozen since the last call: a frozen
+// tensor's slot is zeroed ONCE and never written again, so the flat buffer's norm is the norm over the trainable tensors.
+static int plan_sync(showo_trainer* t, hipStream_t s) {
+    for (const std::string& k : t->pending_zero) {
+        const Grad& g = t->grads[k];
+        SHOWO_CHECK_HIP(hipMemsetAsync(g.p, 0, (size_t)g.n * sizeof(float), s));
+        if (k == "showo.model.embed_tokens.weight") t->gembed_dirty = false;
+    }
+    t->pending_zero.clear();
+    if (!t->plan_dirty) return 0;
+    const int nL = t->e->nL;
+    auto on = [&](const std::string& k) { return t->frozen.count(k) == 0; };
+    // group flag = any member trains; members that do not are cleared after the group's launch (LayerPlan::clear)
+    auto group = [&](const std::vector<std::string>& keys, std::vector<Grad>& clear) {
+        bool any = false;
+        for (auto& k : keys) any = any || on(k);
+        if (any)
+            for (auto& k : keys)
+                if (!on(k)) clear.push_back(t->grads[k]);
+        return any;
+    };
+    t->plan.assign(nL, LayerPlan());
+    t->any_below.assign(nL + 1, 0);
+    for (int i = 0; i < nL; ++i) {
+        LayerPlan& p = t->plan[i];
+        const std::string pre = "showo.model.layers." + std::to_string(i) + ".";
+        const std::string a = pre + "self_attn.";
+        p.wqkv = group({a + "q_proj.weight", a + "k_proj.weight", a + "v_proj.weight"}, p.clear);
+        p.bqkv = group({a + "q_proj.bias", a + "k_proj.bias", a + "v_proj.bias"}, p.clear);
+        p.ln = group({pre + "input_layernorm.weight", pre + "input_layernorm.bias"}, p.clear);
+        p.qk = group({a + "q_layernorm.weight", a + "q_layernorm.bias", a + "k_layernorm.weight", a + "k_layernorm.bias"}, p.clear);
+        p.wd = on(a + "dense.weight"); p.bd = on(a + "dense.bias");
+        p.w1 = on(pre + "mlp.fc1.weight"); p.b1 = on(pre + "mlp.fc1.bias");
+        p.w2 = on(pre + "mlp.fc2.weight"); p.b2 = on(pre + "mlp.fc2.bias");
+        p.any = p.wqkv || p.bqkv || p.ln || p.qk || p.wd || p.bd || p.w1 || p.b1 || p.w2 || p.b2;
+        t->any_below[i + 1] = t->any_below[i] || p.any;
+    }
+    t->fln_clear.clear();
+    t->p_fln = group({"showo.model.final_layernorm.weight", "showo.model.final_layernorm.bias"}, t->fln_clear);
+    t->p_wlm = on("showo.lm_head.weight");
+    t->p_blm = on("showo.lm_head.bias");
+    t->p_emb = on("showo.model.embed_tokens.weight");
+    t->plan_dirty = false;
+    return 0;
+}
+
+// d(loss)/d(input of block i) is consumed below it: by a lower block, the embedding table (ids flow) or the caller (embeddings flow)
+static bool below_needs(const showo_trainer* t, int i) {
+    return (t->from_embeds ? t->want_input : t->p_emb) || t->any_below[i];
+}
+
+// where the column sums of block i's residual-stream gradient (= the dense and fc2 bias gradients) go: fc2's slot, else dense's, else nowhere
+static float* b2_dst(showo_trainer* t, int i) {
+    const LayerPlan& p = t->plan[i];
+    return p.b2 ? t->L[i].gb2 : p.bd ? t->L[i].gbd : nullptr;
+}
+
+extern "C" int showo_train_set_trainable(showo_trainer* t, const char* key, int on) {
+    if (!t || !key) return set_error_msg(1, "train_set_trainable: null argument");
+    std::string k(key);
+    if (!t->grads.count(k)) return set_error_msg(3, "train_set_trainable: unknown state-dict key");
+    const bool was = t->frozen.count(k) == 0;
+    if (was == (on != 0)) return 0;
+    if (on) { t->frozen.erase(k); t->pending_zero.erase(k); }
+    else { t->frozen.insert(k); t->pending_zero.insert(k); }
+    t->plan_dirty = true;
+    t->adam_dirty = true;
+    return 0;
+}
+
+extern "C" int showo_train_set_input_grad(showo_trainer* t, int on) {
+    if (!t) return set_error_msg(1, "train_set_input_grad: null handle");
+    t->want_input = on != 0;
+    return 0;
+}
+
+extern "C" int showo_train_counters(showo_trainer* t, int64_t* out6, int reset) {
+    if (!t) return set_error_msg(1, "train_counters: null handle");
+    if (out6) {
+        for (int k = 0; k < 5; ++k) out6[k] = t->cnt[k];
+        out6[5] = t->e->fused_rebuilt;
+    }
+    if (reset) { std::fill(t->cnt, t->cnt + 5, 0); t->e->fused_rebuilt = 0; }
     return 0;
 }
 
@@ -281,6 +396,7 @@ static int train_forward_impl(showo_trainer* t, const int64_t* ids, const float*
         return set_error_msg(4, "train: the engine's weight images hold fp16 (precision 2); training runs on bf16 images -- "
                                 "showo_engine_set_precision(e, 0) and upload the weights again");
     TRY(sync_weights(t, s));
+    TRY(plan_sync(t, s));
     const int H = e->H, F = e->F, V = e->V, nH = e->nH, T = B * L;
     const int Lp = ((L + 63) / 64) * 64;
     if (ids) {
@@ -383,6 +499,7 @@ extern "C" int showo_train_forward_embeds(showo_trainer* t, const float* embeds,
 extern "C" int showo_train_input_grad(showo_trainer* t, float* out, int64_t n, void* stream) {
     if (!t || !out || !t->have_fwd) return set_error_msg(1, "train_input_grad: run forward + backward first");
     if (n != (int64_t)t->B * t->Lq * t->e->H) return set_error_msg(1, "train_input_grad: size mismatch");
+    if (!t->want_input) return set_error_msg(1, "train_input_grad: not requested (showo_train_set_input_grad)");
     SHOWO_CHECK_HIP(hipMemcpyAsync(out, t->dy, (size_t)n * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return 0;
 }
@@ -398,23 +515,34 @@ extern "C" int showo_train_input_grad(showo_trainer* t, float* out, int64_t n, v
     const int32_t* iv = t->has_mask ? e->iv : nullptr;                                                                \
     (void)F; (void)V; (void)nH; (void)Vp; (void)Tp; (void)Lp; (void)iv; (void)s;
 
-// the head phase after d(logits) is in t->dlogits: lm_head weight / bias gradients, d(final LayerNorm), dy of the top block
+// the head phase after d(logits) is in t->dlogits: lm_head weight / bias gradients, d(final LayerNorm), dy of the top block.
+// Frozen lm_head tensors get no launch; the dgrad GEMM and the final-LayerNorm backward run only when something below consumes them.
 static int backward_head_from_dlogits(showo_trainer* t, void* stream) {
     BW_PROLOGUE
+    TRY(plan_sync(t, s));
     if (train_tn()) {
-        TRY(showo_colsum_bf16(t->dlogits, Vp, T, Vp, t->colpart, t->gblm, 0, s));                                        // lm_head bias grad
-        TRY(showo_gemm_tn_bf16(t->dlogits, Vp, e->hf, H, t->gwlm, H, V, H, T, 0, 1, s));                                    // dWlm [V,H]
+        if (t->p_blm) TRY(showo_colsum_bf16(t->dlogits, Vp, T, Vp, t->colpart, t->gblm, 0, s));                         // lm_head bias grad
+        if (t->p_wlm) { TRY(showo_gemm_tn_bf16(t->dlogits, Vp, e->hf, H, t->gwlm, H, V, H, T, 0, 1, s)); ++t->cnt[0]; }   // dWlm [V,H]
     } else {
-    TRY(showo_transpose_bf16(t->dlogits, Vp, t->bigT, T, Vp, Tp, 0, t->colpart, t->gblm, 0, s));  // dlogits^T + lm_head bias grad
+    if (t->p_wlm || t->p_blm)  // dlogits^T + lm_head bias grad
+        TRY(showo_transpose_bf16(t->dlogits, Vp, t->bigT, T, Vp, Tp, 0, t->colpart, t->p_blm ? t->gblm : nullptr, 0, s));
+    if (t->p_wlm) {
     TRY(showo_transpose_bf16(e->hf, H, t->xT, T, H, Tp, 0, nullptr, nullptr, 0, s));
     TRY(showo_gemm_bf16(t->bigT, Tp, t->xT, Tp, nullptr, 0, t->gwlm, H, nullptr, 0, V, H, Tp, SHOWO_EPI_F32, s));      // dWlm [V,H]
+    ++t->cnt[0];
     }
+    }
+    if (!t->p_fln && !below_needs(t, e->nL)) return 0;  // nothing below the head trains (linear probe): no dgrad, no LayerNorm backward
     TRY(showo_gemm_bf16(t->dlogits, Vp, t->wlmT, Vp, nullptr, 0, t->dh, H, nullptr, 0, T, H, Vp, SHOWO_EPI_F32, s));   // d hf
+    ++t->cnt[1];
     SHOWO_CHECK_HIP(hipMemsetAsync(t->dy, 0, (size_t)T * H * sizeof(float), s));
+    float* gfln = t->p_fln ? t->gfln : t->sc_ln;
     if (train_tn() && e->nL > 0) {  // + column sums of dy16 = the dense / fc2 bias gradients of the top block
-        TRY(showo_ln_bwd_colsum(e->x, e->fln_w, t->dh, t->dy, t->dy, t->dy16, t->lnpart, t->gfln, t->L[e->nL - 1].gb2, T, H, e->cfg.ln_eps, s));
+        float* cb = b2_dst(t, e->nL - 1);
+        TRY(showo_ln_bwd_colsum(e->x, e->fln_w, t->dh, t->dy, t->dy, t->dy16, t->lnpart, gfln, cb ? cb : t->sc_b, T, H, e->cfg.ln_eps, s));
     } else
-    TRY(showo_ln_bwd(e->x, e->fln_w, t->dh, t->dy, t->dy, t->dy16, t->lnpart, t->gfln, T, H, e->cfg.ln_eps, s));
+    TRY(showo_ln_bwd(e->x, e->fln_w, t->dh, t->dy, t->dy, t->dy16, t->lnpart, gfln, T, H, e->cfg.ln_eps, s));
+    for (const Grad& g : t->fln_clear) SHOWO_CHECK_HIP(hipMemsetAsync(g.p, 0, (size_t)g.n * sizeof(float), s));
     return 0;
 }
 
@@ -448,65 +576,126 @@ extern "C" int showo_train_backward_head_dev(showo_trainer* t, const int64_t* la
 // driven from the host checks that the saved activations still belong to its own forward
 extern "C" int64_t showo_train_generation(showo_trainer* t) { return t ? (int64_t)t->generation : -1; }
 
+// Block i's phase.  Frozen tensors get no weight-gradient launch; the fused launches that also carry a parameter gradient as a side
+// output (dgelu_colsum, qkln_rope_bwd, ln_bwd_colsum) keep running for their data gradients with that output pointed at scratch, so
+// the data-gradient chain is the same bits whatever trains.  A chain runs only if something consumes it: d a -> d f for W1 / b1 or
+// dh, d o -> attention -> d qkv for Wqkv / bqkv / q,k-LN or dh, and dh + the LayerNorm backward only when this block's LayerNorm or
+// anything below trains (the lowest phase anything needs stops there).  Nothing at or below the block trains: no launch at all.
 extern "C" int showo_train_backward_layer(showo_trainer* t, int i, void* stream) {
     BW_PROLOGUE
     if (i < 0 || i >= e->nL) return set_error_msg(1, "train_backward_layer: bad layer index");
+    TRY(plan_sync(t, s));
+    const LayerPlan& p = t->plan[i];
+    const bool below = below_needs(t, i);
+    if (!p.any && !below) return 0;
+    ++t->cnt[2];
+    const bool need_dh = below || p.ln;
+    const bool mlp = p.w1 || p.b1 || need_dh;
+    const bool attn = p.wqkv || p.bqkv || p.qk || need_dh;
     {
         Layer& w = e->layers[i];
         LayerT& l = t->L[i];
+        float* gb1 = p.b1 ? l.gb1 : t->sc_b1;
+        float* gqk = p.qk ? l.gqk : t->sc_qk;
         if (train_tn() && l.a) {
             // weight gradients straight from the token-major tensors: dW = dY^T X by showo_gemm_tn_bf16, db = column sums of dY
-            // db2 = dbd = column sums of dy16: written into l.gb2 by the LayerNorm backward that produced dy16 (showo_ln_bwd_colsum)
-            SHOWO_CHECK_HIP(hipMemcpyAsync(l.gbd, l.gb2, (size_t)H * sizeof(float), hipMemcpyDeviceToDevice, s));
-            TRY(showo_gemm_tn_bf16(t->dy16, H, l.a, F, l.gw2, F, H, F, T, 0, 1, s));                                               // dW2 [H,F]
-            TRY(showo_gemm_tn_bf16(t->dy16, H, l.attn, H, l.gwd, H, H, H, T, 0, 1, s));                                            // dWd [H,H]
+            // db2 = dbd = column sums of dy16: written into l.gb2 (l.gbd when fc2.bias is frozen) by the LayerNorm backward that
+            // produced dy16 (showo_ln_bwd_colsum)
+            if (p.bd && p.b2) SHOWO_CHECK_HIP(hipMemcpyAsync(l.gbd, l.gb2, (size_t)H * sizeof(float), hipMemcpyDeviceToDevice, s));
+            if (p.w2) { TRY(showo_gemm_tn_bf16(t->dy16, H, l.a, F, l.gw2, F, H, F, T, 0, 1, s)); ++t->cnt[0]; }                // dW2 [H,F]
+            if (p.wd) { TRY(showo_gemm_tn_bf16(t->dy16, H, l.attn, H, l.gwd, H, H, H, T, 0, 1, s)); ++t->cnt[0]; }             // dWd [H,H]
+            if (mlp) {
             TRY(showo_gemm_bf16(t->dy16, H, l.w2T, H, nullptr, 0, t->dff, F, nullptr, 0, T, F, H, SHOWO_EPI_BF16, s));          // d a
-            TRY(showo_dgelu_colsum_bf16(t->dff, l.f, t->dff, F, T, F, t->colpart, l.gb1, s));                                   // d f, db1
-            TRY(showo_gemm_tn_bf16(t->dff, F, l.h, H, l.gw1, H, F, H, T, 0, 1, s));                                                // dW1 [F,H]
+            ++t->cnt[1];
+            TRY(showo_dgelu_colsum_bf16(t->dff, l.f, t->dff, F, T, F, t->colpart, gb1, s));                                    // d f, db1
+            if (p.w1) { TRY(showo_gemm_tn_bf16(t->dff, F, l.h, H, l.gw1, H, F, H, T, 0, 1, s)); ++t->cnt[0]; }                 // dW1 [F,H]
+            if (need_dh) {
             TRY(showo_gemm_bf16(t->dff, F, l.w1T, F, nullptr, 0, t->dh, H, nullptr, 0, T, H, F, SHOWO_EPI_F32, s));             // dh (mlp)
+            ++t->cnt[1];
+            }
+            }
             // attention
+            if (attn) {
             TRY(showo_gemm_bf16(t->dy16, H, l.wdT, H, nullptr, 0, t->d_o, H, nullptr, 0, T, H, H, SHOWO_EPI_BF16, s));          // d o
+            ++t->cnt[1];
             TRY(showo_head_transpose(l.Q, t->QT, B, nH, L, Lp, (int64_t)nH * L * 64, (int64_t)L * 64, 64, s));
             TRY(showo_head_transpose(l.K, t->KT, B, nH, L, Lp, (int64_t)nH * L * 64, (int64_t)L * 64, 64, s));
             TRY(showo_attn_bwd(l.Q, l.K, t->QT, t->KT, l.qkv + 2 * H, 3 * H, l.attn, t->d_o, H, t->dOT, l.lse, t->D, iv, nullptr, t->dqk, 2 * H,
                                t->dqk + H, 2 * H, t->dqkv + 2 * H, 3 * H, B, nH, L, Lp, s));
-            TRY(showo_qkln_rope_bwd(t->dqk, t->dqk + H, 2 * H, l.qkv, w.qln_w, w.kln_w, e->cosT, e->sinT, t->dqkv, t->qkpart, l.gqk, T, L,
+            TRY(showo_qkln_rope_bwd(t->dqk, t->dqk + H, 2 * H, l.qkv, w.qln_w, w.kln_w, e->cosT, e->sinT, t->dqkv, t->qkpart, gqk, T, L,
                                     nH, e->cfg.rotary_dim, e->cfg.ln_eps, s));
-            TRY(showo_colsum_bf16(t->dqkv, 3 * H, T, 3 * H, t->colpart, l.gbqkv, 0, s));                                        // dbqkv
-            TRY(showo_gemm_tn_bf16(t->dqkv, 3 * H, l.h, H, l.gwqkv, H, 3 * H, H, T, 0, 1, s));                                     // dWqkv [3H,H]
+            if (p.bqkv) TRY(showo_colsum_bf16(t->dqkv, 3 * H, T, 3 * H, t->colpart, l.gbqkv, 0, s));                            // dbqkv
+            if (p.wqkv) { TRY(showo_gemm_tn_bf16(t->dqkv, 3 * H, l.h, H, l.gwqkv, H, 3 * H, H, T, 0, 1, s)); ++t->cnt[0]; }     // dWqkv [3H,H]
+            if (need_dh) {
             TRY(showo_gemm_bf16(t->dqkv, 3 * H, l.wqkvT, 3 * H, nullptr, 0, t->dh, H, t->dh, H, T, H, 3 * H, SHOWO_EPI_RESID_F32, s));  // dh += attn part
+            ++t->cnt[1];
+            }
+            }
         } else {
         // dy^T (+ bias grads of fc2 and dense: both are column sums of dy)
-        TRY(showo_transpose_bf16(t->dy16, H, t->bigT, T, H, Tp, 0, t->colpart, l.gb2, 0, s));
-        SHOWO_CHECK_HIP(hipMemcpyAsync(l.gbd, l.gb2, (size_t)H * sizeof(float), hipMemcpyDeviceToDevice, s));
+        float* cb2 = b2_dst(t, i);
+        if (p.w2 || p.wd || cb2) TRY(showo_transpose_bf16(t->dy16, H, t->bigT, T, H, Tp, 0, t->colpart, cb2, 0, s));
+        if (p.bd && p.b2) SHOWO_CHECK_HIP(hipMemcpyAsync(l.gbd, l.gb2, (size_t)H * sizeof(float), hipMemcpyDeviceToDevice, s));
         // MLP
+        if (p.w2) {
         TRY(showo_transpose_bf16(l.f, F, t->xT, T, F, Tp, 1, nullptr, nullptr, 0, s));                                      // gelu(f)^T
         TRY(showo_gemm_bf16(t->bigT, Tp, t->xT, Tp, nullptr, 0, l.gw2, F, nullptr, 0, H, F, Tp, SHOWO_EPI_F32, s));         // dW2 [H,F]
+        ++t->cnt[0];
+        }
+        if (p.wd) {
         TRY(showo_transpose_bf16(l.attn, H, t->xT, T, H, Tp, 0, nullptr, nullptr, 0, s));                                   // attn^T
         TRY(showo_gemm_bf16(t->bigT, Tp, t->xT, Tp, nullptr, 0, l.gwd, H, nullptr, 0, H, H, Tp, SHOWO_EPI_F32, s));         // dWd [H,H]
+        ++t->cnt[0];
+        }
+        bool hT = false;  // xT holds h^T (the operand of dW1 and dWqkv)
+        if (mlp) {
         TRY(showo_gemm_bf16(t->dy16, H, l.w2T, H, nullptr, 0, t->dff, F, nullptr, 0, T, F, H, SHOWO_EPI_BF16, s));          // d a
+        ++t->cnt[1];
         TRY(showo_dgelu_bf16(t->dff, l.f, t->dff, (int64_t)T * F, s));                                                      // d f
-        TRY(showo_transpose_bf16(t->dff, F, t->bigT, T, F, Tp, 0, t->colpart, l.gb1, 0, s));                                // df^T, db1
-        TRY(showo_transpose_bf16(l.h, H, t->xT, T, H, Tp, 0, nullptr, nullptr, 0, s));                                      // h^T
+        if (p.w1 || p.b1) TRY(showo_transpose_bf16(t->dff, F, t->bigT, T, F, Tp, 0, t->colpart, p.b1 ? l.gb1 : nullptr, 0, s));  // df^T, db1
+        if (p.w1 || p.wqkv) { TRY(showo_transpose_bf16(l.h, H, t->xT, T, H, Tp, 0, nullptr, nullptr, 0, s)); hT = true; }    // h^T
+        if (p.w1) {
         TRY(showo_gemm_bf16(t->bigT, Tp, t->xT, Tp, nullptr, 0, l.gw1, H, nullptr, 0, F, H, Tp, SHOWO_EPI_F32, s));         // dW1 [F,H]
+        ++t->cnt[0];
+        }
+        if (need_dh) {
         TRY(showo_gemm_bf16(t->dff, F, l.w1T, F, nullptr, 0, t->dh, H, nullptr, 0, T, H, F, SHOWO_EPI_F32, s));             // dh (mlp)
+        ++t->cnt[1];
+        }
+        }
         // attention
+        if (attn) {
         TRY(showo_gemm_bf16(t->dy16, H, l.wdT, H, nullptr, 0, t->d_o, H, nullptr, 0, T, H, H, SHOWO_EPI_BF16, s));          // d o
+        ++t->cnt[1];
         TRY(showo_head_transpose(l.Q, t->QT, B, nH, L, Lp, (int64_t)nH * L * 64, (int64_t)L * 64, 64, s));
         TRY(showo_head_transpose(l.K, t->KT, B, nH, L, Lp, (int64_t)nH * L * 64, (int64_t)L * 64, 64, s));
         TRY(showo_attn_bwd(l.Q, l.K, t->QT, t->KT, l.qkv + 2 * H, 3 * H, l.attn, t->d_o, H, t->dOT, l.lse, t->D, iv, nullptr, t->dqk, 2 * H,
                            t->dqk + H, 2 * H, t->dqkv + 2 * H, 3 * H, B, nH, L, Lp, s));
-        TRY(showo_qkln_rope_bwd(t->dqk, t->dqk + H, 2 * H, l.qkv, w.qln_w, w.kln_w, e->cosT, e->sinT, t->dqkv, t->qkpart, l.gqk, T, L,
+        TRY(showo_qkln_rope_bwd(t->dqk, t->dqk + H, 2 * H, l.qkv, w.qln_w, w.kln_w, e->cosT, e->sinT, t->dqkv, t->qkpart, gqk, T, L,
                                 nH, e->cfg.rotary_dim, e->cfg.ln_eps, s));
-        TRY(showo_transpose_bf16(t->dqkv, 3 * H, t->bigT, T, 3 * H, Tp, 0, t->colpart, l.gbqkv, 0, s));                     // dqkv^T, dbqkv
+        if (p.wqkv || p.bqkv)                                                                                                // dqkv^T, dbqkv
+            TRY(showo_transpose_bf16(t->dqkv, 3 * H, t->bigT, T, 3 * H, Tp, 0, t->colpart, p.bqkv ? l.gbqkv : nullptr, 0, s));
+        if (p.wqkv) {
+        if (!hT) TRY(showo_transpose_bf16(l.h, H, t->xT, T, H, Tp, 0, nullptr, nullptr, 0, s));
         TRY(showo_gemm_bf16(t->bigT, Tp, t->xT, Tp, nullptr, 0, l.gwqkv, H, nullptr, 0, 3 * H, H, Tp, SHOWO_EPI_F32, s));   // dWqkv (xT = h^T)
-        TRY(showo_gemm_bf16(t->dqkv, 3 * H, l.wqkvT, 3 * H, nullptr, 0, t->dh, H, t->dh, H, T, H, 3 * H, SHOWO_EPI_RESID_F32, s));  // dh += attn part
+        ++t->cnt[0];
         }
-        // LayerNorm + residual
+        if (need_dh) {
+        TRY(showo_gemm_bf16(t->dqkv, 3 * H, l.wqkvT, 3 * H, nullptr, 0, t->dh, H, t->dh, H, T, H, 3 * H, SHOWO_EPI_RESID_F32, s));  // dh += attn part
+        ++t->cnt[1];
+        }
+        }
+        }
+        // LayerNorm + residual (+ the column sums of dy16 = the dense / fc2 bias gradients of block i - 1, wherever that block trains)
+        if (need_dh) {
+        float* gln = p.ln ? l.gln : t->sc_ln;
         if (train_tn() && i > 0 && t->L[i - 1].a) {
-            TRY(showo_ln_bwd_colsum(l.x, w.ln_w, t->dh, t->dy, t->dy, t->dy16, t->lnpart, l.gln, t->L[i - 1].gb2, T, H, e->cfg.ln_eps, s));
+            float* cb = b2_dst(t, i - 1);
+            TRY(showo_ln_bwd_colsum(l.x, w.ln_w, t->dh, t->dy, t->dy, t->dy16, t->lnpart, gln, cb ? cb : t->sc_b, T, H, e->cfg.ln_eps, s));
         } else
-        TRY(showo_ln_bwd(l.x, w.ln_w, t->dh, t->dy, t->dy, t->dy16, t->lnpart, l.gln, T, H, e->cfg.ln_eps, s));
+        TRY(showo_ln_bwd(l.x, w.ln_w, t->dh, t->dy, t->dy, t->dy16, t->lnpart, gln, T, H, e->cfg.ln_eps, s));
+        }
+        for (const Grad& g : p.clear) SHOWO_CHECK_HIP(hipMemsetAsync(g.p, 0, (size_t)g.n * sizeof(float), s));
         }
     return 0;
 }
@@ -524,10 +713,19 @@ extern "C" int showo_train_set_loss_weights(showo_trainer* t, float w_t2i, float
 
 extern "C" int showo_train_backward_embed(showo_trainer* t, void* stream) {
     BW_PROLOGUE
-    // ---- embedding
+    // ---- embedding: a frozen table gets no launch (its slot was zeroed when it froze); a forward from caller-provided embeddings did
+    // not read the table, its caller owns d/d(embeddings) (showo_train_input_grad) and the table's gradient is zero -- cleared once
+    // after a scatter of an earlier backward, not on every step
+    TRY(plan_sync(t, s));
+    if (!t->p_emb) return 0;
+    if (t->from_embeds && !t->gembed_dirty) return 0;
     SHOWO_CHECK_HIP(hipMemsetAsync(t->gembed, 0, (size_t)V * H * sizeof(float), s));
-    if (t->from_embeds) return 0;  // the table was not read by this forward; its caller owns d/d(embeddings) (showo_train_input_grad)
+    ++t->cnt[3];
+    t->gembed_dirty = false;
+    if (t->from_embeds) return 0;
     TRY(showo_embed_bwd(t->ids, t->dy, t->gembed, t->order_ws, T, H, V, s));
+    ++t->cnt[3];
+    t->gembed_dirty = true;
     return 0;
 }
 
@@ -590,8 +788,9 @@ extern "C" int showo_train_bind_param(showo_trainer* t, const char* key, float* 
     return 0;
 }
 
-// torch.optim.AdamW.step() over every bound parameter with the gradients of the last backward, followed by the refresh of
-// the engine's bf16 weight images (the transposed images are rebuilt lazily by the next forward)
+// torch.optim.AdamW.step() over every bound parameter that trains (showo_train_set_trainable) with the gradients of the last backward,
+// followed by the refresh of the engine's bf16 weight images of those parameters: their version stamps make the next user rebuild
+// exactly the derived images (transposed dgrad images, fused block images) that depend on them
 extern "C" int showo_train_adamw_step(showo_trainer* t, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                                       void* stream) {
     if (!t) return set_error_msg(1, "train_adamw_step: null handle");
@@ -605,7 +804,10 @@ extern "C" int showo_train_adamw_step(showo_trainer* t, float lr, float beta1, f
             std::vector<showo::AdamSeg> segs;
             std::vector<int> seg_of;
             std::vector<int64_t> start_of;
+            t->adam_keys.clear();
             for (auto& b : t->bound) {
+                if (t->frozen.count(b.key)) continue;
+                t->adam_keys.push_back({b.key, showo::engine_version(t->e, b.key.c_str())});
                 showo::AdamSeg sg{b.p, b.m, b.v, t->grads[b.key].p, nullptr, nullptr, b.n, b.decay ? 1 : 0};
                 uint16_t* d16 = nullptr;
                 TRY(showo_engine_slot(t->e, b.key.c_str(), b.n, &d16, &sg.dst32));
@@ -613,6 +815,7 @@ extern "C" int showo_train_adamw_step(showo_trainer* t, float lr, float beta1, f
                 for (int64_t st = 0; st < b.n; st += showo::ADAM_CHUNK) { seg_of.push_back((int)segs.size()); start_of.push_back(st); }
                 segs.push_back(sg);
             }
+            if (segs.empty()) return set_error_msg(1, "train_adamw_step: every bound parameter is frozen");
             hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
             hipStreamIsCapturing(s, &cs);
             if (cs != hipStreamCaptureStatusNone) return set_error_msg(7, "train_adamw_step: the segment table must be built outside a stream capture");
@@ -627,15 +830,22 @@ extern "C" int showo_train_adamw_step(showo_trainer* t, float lr, float beta1, f
             t->adam_dirty = false;
         }
         TRY(showo::adamw_multi_launch(t->adam_segs, t->adam_seg_of, t->adam_start_of, t->adam_chunks, lr, beta1, beta2, eps, weight_decay, step, s));
-        TRY(showo_engine_weights_touched(t->e));
-        t->weights_synced = false;
+        // the bookkeeping of showo_engine_weights_touched, for the rewritten tensors only
+        showo_engine* e = t->e;
+        for (auto& kv : t->adam_keys) {
+            if (kv.second) *kv.second = ++e->clock;
+            e->lo_loaded.erase(kv.first);  // the hi images were rewritten without their low halves: accuracy mode needs a re-upload
+        }
+        e->px3_valid = false;
+        e->head3_valid = false;
+        e->img_f16 = false;  // the trainer writes bf16 images: a precision-2 engine needs a re-upload too (run_layers checks)
         return 0;
     }
     for (auto& b : t->bound) {
+        if (t->frozen.count(b.key)) continue;
         const Grad& g = t->grads[b.key];
         TRY(showo_adamw(b.p, g.p, b.m, b.v, b.n, lr, beta1, beta2, eps, b.decay ? weight_decay : 0.f, step, stream));
         TRY(showo_engine_load(t->e, b.key.c_str(), b.p, b.n, stream));
     }
-    t->weights_synced = false;
     return 0;
 }

@@ -123,13 +123,17 @@ class _TrainRun:
             raise RuntimeError(f"Showo backward ({node}): another training forward ran on this model after the one this loss comes from, "
                                "so its saved activations are gone; call backward() before the next labelled forward")
 
-    def hand_out(self, bucket):
-        """ONE device copy of gradient bucket `bucket` into a fresh tensor, returned as views shaped like its parameters (in the order of
-        _train_param_groups): autograd / DDP may keep them, the next backward overwrites only the trainer's own buffer"""
+    def hand_out(self, bucket, needs):
+        """the gradients of bucket `bucket` that autograd asks for (`needs`, one flag per parameter in the order of _train_param_groups;
+        None for the others) in fresh tensors: ONE device copy of the whole bucket when every parameter needs its gradient, else one
+        copy per needed tensor.  Autograd / DDP may keep them, the next backward overwrites only the trainer's own buffer."""
         n, src, parts = self.layout[bucket]
-        buf = torch.empty(n, dtype=torch.float32, device=src.device)
-        buf.copy_(src)
-        return [buf[o:o + k].view(shape) for o, k, shape in parts]
+        needs = list(needs)
+        if all(needs):
+            buf = torch.empty(n, dtype=torch.float32, device=src.device)
+            buf.copy_(src)
+            return [buf[o:o + k].view(shape) for o, k, shape in parts]
+        return [src[o:o + k].clone().view(shape) if need else None for (o, k, shape), need in zip(parts, needs)]
 
 
 def _train_param_groups(model):
@@ -142,6 +146,22 @@ def _train_param_groups(model):
     groups.append([("showo.model.final_layernorm." + n, p) for n, p in ph.model.final_layernorm.named_parameters()] +
                   [("showo.lm_head." + n, p) for n, p in ph.lm_head.named_parameters()])
     return groups
+
+
+def sync_trainable(model, tr, flags, input_grad):
+    """hand the trainable set {state-dict key: trains} and the input-gradient flag to the native trainer (showo_train_set_trainable /
+    showo_train_set_input_grad): only what differs from what that trainer handle was last told"""
+    st = model.__dict__.get("_trainable_state")
+    if st is None or st[0] is not tr:
+        st = (tr, {}, True)  # a new trainer: everything trainable, input gradient on
+    known, inp = st[1], st[2]
+    for k, on in flags.items():
+        if known.get(k, True) != bool(on):
+            _lib.call("showo_train_set_trainable", tr, k.encode(), int(bool(on)))
+            known[k] = bool(on)
+    if inp != bool(input_grad):
+        _lib.call("showo_train_set_input_grad", tr, int(bool(input_grad)))
+    model.__dict__["_trainable_state"] = (tr, known, bool(input_grad))
 
 
 def _grad_layout(model, tr, groups, device):
@@ -187,10 +207,10 @@ class _EmbedNode(torch.autograd.Function):
         run = ctx.run
         run.check("embedding")
         _lib.call("showo_train_backward_embed", run.tr, _lib.stream())
-        (g_w,) = run.hand_out(0)
+        (g_w,) = run.hand_out(0, ctx.needs_input_grad[2:3])
         g_emb = None
         if run.emb_shape is not None and ctx.needs_input_grad[1]:
-            g_emb = torch.empty(run.emb_shape[0], dtype=torch.float32, device=g_w.device)
+            g_emb = torch.empty(run.emb_shape[0], dtype=torch.float32, device=run.lab.device)
             _lib.call("showo_train_input_grad", run.tr, _lib.ptr(g_emb), g_emb.numel(), _lib.stream())
             g_emb = g_emb.to(run.emb_shape[1])
         return None, g_emb, g_w
@@ -210,8 +230,7 @@ class _BlockNode(torch.autograd.Function):
         run = ctx.run
         run.check(f"block {ctx.i}")
         _lib.call("showo_train_backward_layer", run.tr, ctx.i, _lib.stream())
-        grads = run.hand_out(1 + ctx.i)
-        return (None, None, g_tok.new_empty(0)) + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[3:]))
+        return (None, None, g_tok.new_empty(0)) + tuple(run.hand_out(1 + ctx.i, ctx.needs_input_grad[3:]))
 
 
 class _HeadNode(torch.autograd.Function):
@@ -229,6 +248,8 @@ class _HeadNode(torch.autograd.Function):
         if attention_mask is not None and tuple(attention_mask.shape) != (B, 1, L, L):
             raise ValueError(f"Attention mask should be of size {(B, 1, L, L)}, but is {tuple(attention_mask.shape)}")
         from .training import train_mask
+        # the trainable set of this forward's backward: requires_grad of every parameter, and of the input embeddings
+        sync_trainable(model, tr, {k: p.requires_grad for g in run.groups for k, p in g}, run.emb_grad)
         mask = train_mask(tr, attention_mask)  # dense fp32 mask, or an IntervalMask registered with the trainer
         logits = torch.empty((B, L, model.vocab_size), dtype=torch.float32, device=lab.device)
         losses = torch.empty(3, dtype=torch.float32, device=lab.device)
@@ -262,9 +283,7 @@ class _HeadNode(torch.autograd.Function):
                           for g in (g_t2i, g_lm, g_mmu)])  # the loss weights stay on the device (training/train.py:600)
         b_t2i, b_lm, b_mmu, msl = run.meta
         _lib.call("showo_train_backward_head_dev", run.tr, _lib.ptr(run.lab), b_t2i, b_lm, b_mmu, msl, _lib.ptr(g3), _lib.stream())
-        grads = run.hand_out(len(run.groups) - 1)
-        return ((None,) * 8 + (torch.empty(0, device=dev),)
-                + tuple(g if need else None for g, need in zip(grads, ctx.needs_input_grad[9:])))
+        return ((None,) * 8 + (torch.empty(0, device=dev),) + tuple(run.hand_out(len(run.groups) - 1, ctx.needs_input_grad[9:])))
 
 
 def _train_forward(model, input_ids, input_embeddings, attention_mask, labels, b_t2i, b_lm, b_mmu, max_seq_length):
@@ -276,6 +295,7 @@ def _train_forward(model, input_ids, input_embeddings, attention_mask, labels, b
     run.groups = _train_param_groups(model)
     run.emb = None if input_embeddings is None else input_embeddings.detach()
     run.emb_shape = None if input_embeddings is None else (tuple(input_embeddings.shape), input_embeddings.dtype)
+    run.emb_grad = input_embeddings is not None and input_embeddings.requires_grad
     (embed_w,) = [p for _, p in run.groups[0]]
     tok = _EmbedNode.apply(run, input_embeddings, embed_w)
     for i, group in enumerate(run.groups[1:-1]):
@@ -418,7 +438,6 @@ class Showo(PretrainedMixin, nn.Module):
         self._engine_key = None
         self._engine_versions = None
         self._trainer = None
-        self._weights_changed = True
         self.max_batch = int(kwargs.get("max_batch", 32))
         self.max_seq = int(kwargs.get("max_seq", 1280))
         self._precision = 0
@@ -532,7 +551,6 @@ class Showo(PretrainedMixin, nn.Module):
         (data_ptr, tensor._version); updates made through `.data` (p.data.copy_(), DeepSpeed ZeRO flat-buffer updates, EMA swaps)
         do not bump the version counter, so an optimizer of that kind must call this after `optimizer.step()`."""
         self._engine_versions = {} if self._engine is not None else None
-        self._weights_changed = True
         if getattr(self, "mm_projector", None) is not None:
             self.mm_projector.mark_weights_dirty()
 
@@ -577,10 +595,8 @@ class Showo(PretrainedMixin, nn.Module):
             h = C.c_void_p()
             _lib.check(_lib.load().showo_train_create(eng, self.max_batch, self.max_seq, C.byref(h)), "showo_train_create")
             self._trainer = h
-            self._weights_changed = True
-        if self._weights_changed:
-            _lib.call("showo_train_invalidate_weights", self._trainer)
-            self._weights_changed = False
+        # no invalidation here: every upload engine() makes stamps the tensor's version, and the trainer rebuilds the images of the
+        # tensors that changed (include/showo_hip.h showo_train_invalidate_weights)
         return self._trainer
 
     def __del__(self):
@@ -638,7 +654,6 @@ class Showo(PretrainedMixin, nn.Module):
         for k, v in self._engine_params():
             ver = (v.data_ptr(), v._version)
             if self._engine_versions.get(k) != ver:
-                self._weights_changed = True
                 src = v.detach()
                 if src.dtype != torch.float32 or not src.is_contiguous():
                     src = src.float().contiguous()

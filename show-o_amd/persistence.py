@@ -193,6 +193,4 @@ class PretrainedMixin:
             raise KeyError(f"checkpoint {d} lacks {len(missing)} keys, e.g. {missing[:5]}")
         if torch_dtype is not None:
             model = model.to(torch_dtype)
-        if hasattr(model, "_weights_changed"):
-            model._weights_changed = True
         return model.eval()

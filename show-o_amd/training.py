@@ -156,6 +156,13 @@ class Trainer:
         self.max_grad_norm = max_grad_norm
         self.step_count = 0
         self.params = [("showo." + n, p) for n, p in model.showo.named_parameters()]
+        # the trainable set is read once, as the reference builds its optimizer once over the `requires_grad` parameters
+        # (training/train.py:210-223): frozen tensors get no gradient, no exchange of a wholly frozen bucket and no update
+        self.trainable = {n: bool(p.requires_grad) for n, p in self.params}
+        if not any(self.trainable.values()):
+            raise ValueError("Trainer: no parameter of model.showo requires grad; nothing to train")
+        from .modeling_showo import _train_param_groups
+        self._bucket_trains = [any(self.trainable[k] for k, _ in g) for g in _train_param_groups(model)]
         self.m = {n: torch.zeros_like(p) for n, p in self.params}
         self.v = {n: torch.zeros_like(p) for n, p in self.params}
         self._wire, self._force_exchange = wire, force_exchange
@@ -293,9 +300,14 @@ class Trainer:
         # manual edits); the native AdamW below updates them through raw pointers and refreshes the engine images itself
         self.tr = self.model.trainer()
         cur = [("showo." + n, p) for n, p in self.model.showo.named_parameters()]  # assign=True loads replace the Parameter objects
+        if any(bool(p.requires_grad) != self.trainable.get(n) for n, p in cur):
+            raise RuntimeError("Trainer: requires_grad of model.showo's parameters changed after the Trainer was built; build a new "
+                               "Trainer for the new trainable set")
         if self._binding_key(cur) != self._bound:  # new native trainer, or a parameter's storage moved: rebuild every raw-pointer binding
             self.params = cur
             self._bind()
+        from .modeling_showo import sync_trainable
+        sync_trainable(self.model, self.tr, self.trainable, False)  # only what the native trainer was not told yet
         m, tr, s = self.model, self.tr, _lib.stream
         B, L = input_ids.shape
         ids = input_ids.to(torch.int64).contiguous()
@@ -321,15 +333,21 @@ class Trainer:
             # the announcement is per step: a later forward with labels outside Trainer.step (the module's autograd path, an eval loop)
             # must not write the T x Vp d(logits) tensor (1.3 GB at the stage-1 batch) for a backward that never comes
             _lib.call("showo_train_set_loss_weights", tr, 0.0, 0.0, 0.0, 0)
-        if ex is not None:
+        # frozen tensors: a wholly frozen bucket is not exchanged (a partly frozen one goes on the wire with its zeros), and the
+        # backward stops at the lowest phase anything needs
+        bt = self._bucket_trains
+        lo = 0 if bt[0] else next((i for i in range(nL) if bt[1 + i]), nL)
+        if ex is not None and bt[nL + 1]:
             ex.launch(nL + 1)
-        for i in range(nL - 1, -1, -1):
+        for i in range(nL - 1, lo - 1, -1):
             _lib.call("showo_train_backward_layer", tr, i, s())
-            if ex is not None:
+            if ex is not None and bt[i + 1]:
                 ex.launch(i + 1)  # the collective of block i overlaps the backward of block i - 1
-        _lib.call("showo_train_backward_embed", tr, s())
+        if bt[0]:
+            _lib.call("showo_train_backward_embed", tr, s())
+            if ex is not None:
+                ex.launch(0)
         if ex is not None:
-            ex.launch(0)
             ex.finish()
         if self.max_grad_norm is not None:
             self.clip_grad_norm_(self.max_grad_norm)
