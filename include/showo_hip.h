@@ -160,6 +160,14 @@ int showo_copy_b128(const void* src, void* dst, int64_t nbytes, void* stream);
 int showo_cast_f32_bf16(const float* src, uint16_t* dst, int64_t n, void* stream);
 /* fp32 -> 16-bit cast of either operand type (round to nearest even; SHOWO_OP_F16 saturates at +-65504) */
 int showo_cast_f32_op16(const float* src, uint16_t* dst, int64_t n, int op, void* stream);
+/* Per-row symmetric int8 weight format (the weight images of showo_engine_set_precision(e, 3)).  w fp32 [N, K] row-major, per row n:
+ *   amax = max_k |w[n,k]|;  scale[n] = amax / 127.0f (IEEE);  q[n,k] = clamp(rint(w[n,k] / scale[n]), -127, 127) (IEEE division,
+ *   round half to even; -128 is never produced);  amax < 2^-100 (an all-zero row included): scale[n] = 1, q[n,:] = 0.
+ * q int8 [N, K] row-major, scale fp32 [N].  A row that holds NaN or inf is refused (error return; q / scale are then undefined).
+ * Synchronises the stream (the refusal is decided on the device). */
+int showo_quantize_rows_i8(const float* w, int64_t N, int64_t K, int8_t* q, float* scale, void* stream);
+/* w[n,k] = (float)q[n,k] * scale[n] (one rounding) */
+int showo_dequantize_rows_i8(const int8_t* q, const float* scale, int64_t N, int64_t K, float* w, void* stream);
 /* number of elements of a 16-bit image whose magnitude is >= 65504 or NaN when read as IEEE half: the range check of precision 2
  * (a saturated convert leaves exactly 65504).  count: device int64, ACCUMULATED into (zero it first). */
 int showo_count_f16_saturated(const uint16_t* x, int64_t n, int64_t* count, void* stream);
@@ -292,7 +300,9 @@ int showo_attn_set_impl(int impl);
 /* AR decode step (one new token against the KV cache): 0 = fused layer, three launches (LN + qkv/fc1 GEMV; prep +
  * single-query attention with the fc2 GEMV co-scheduled on the CUs the 32 attention blocks leave idle (F = 8192 only);
  * dense GEMV + both residual adds; default), 1 = the general seven-launch layer, 2 = the fused layer as a plain chain
- * (fc2 in the third launch).  All three give the same bits; 1 and 2 exist so that tests and profiles can compare them. */
+ * (fc2 in the third launch).  All three give the same bits; 1 and 2 exist so that tests and profiles can compare them.
+ * Under precision 3 (int8 decode) 0 and 2 stream the int8 images and agree bit for bit; 1 has no int8 form and runs on the bf16
+ * image of the dequantised weights, so it gives the bits of 0 / 2 for power-of-two row scales only. */
 int showo_decode_set_impl(int impl);
 /* Infinity-Cache prefetch role of the co-scheduled decode launches (batch 1 and batched): `blocks` extra blocks of every layer's
  * attention launch read, by LDS-DMA, weights the NEXT launches will stream -- this layer's dense matrix when dense != 0, then
@@ -501,7 +511,21 @@ int showo_engine_set_collect(showo_engine* e, float* buf);
  * tests/test_modules_gpu.py).  KV-cached decode steps run on the general (seven-launch) layer; the batched decode refuses.
  * Switching between precision 2 and 0 / 1 un-loads the GEMM weights (their images change element type): showo_engine_missing() is
  * then > 0 until the host has uploaded them again.  Training keeps bf16 images (showo_train_* refuse a precision-2 engine). */
+/* precision 3: int8 decode.  bf16 operands everywhere, as in precision 0, on a QUANTISED model: showo_engine_load of a GEMM weight
+ * (q/k/v_proj, dense, fc1, fc2 of every block, lm_head) quantises the fp32 source per output row (showo_quantize_rows_i8) and keeps two
+ * images: int8 + scale, which the fused decode step (showo_decode_set_impl 0 / 2) streams at one byte per weight, and the bf16 image of
+ * the dequantised values bf16(q * scale) for everything on the MFMA GEMMs (prefill, forward, forward_rows, t2i_generate, the
+ * seven-launch decode layer).  Decode arithmetic per output column: the int8 weights converted exactly to bf16, the dot2 chain, lane
+ * split and wave reduction of the bf16 kernels, then ONE fp32 multiply by scale[n] in front of the unchanged epilogue -- bit-identical
+ * to the bf16 kernels on q * scale whenever the scales are powers of two.  Biases, LayerNorm parameters, embeddings: fp32, unchanged.
+ * This mode trades accuracy for speed (the only one that does).  Costs 1 byte per GEMM weight on top of the bf16 images.  Switching to
+ * or from 3 un-loads the GEMM weights like precision 2 does.  Refused unless hidden <= 2048, ffn <= 8192, both multiples of 16; a
+ * decode step against a KV cache too long for the fused layer (capacity > 14 488 tokens) is refused as well, never served from the
+ * bf16 image.  The batched decode (showo_engine_batch_*) streams the int8 images too: every sequence keeps its batch-1 bits. */
 int showo_engine_set_precision(showo_engine* e, int precision);
+/* precision 3 only: load a caller-quantised GEMM weight (same keys as showo_engine_load; q int8 [N, K] row-major with |q| <= 127,
+ * scale fp32 [N] positive and finite, both on the device) into both images.  Synchronises the stream (the inputs are validated). */
+int showo_engine_load_q8(showo_engine* e, const char* key, const int8_t* q, const float* scale, int64_t N, int64_t K, void* stream);
 int showo_engine_get_precision(const showo_engine* e);
 /* precision 2 range check: while count != NULL (device int64, zero it first) every forward adds the number of fp16 activation
  * elements (LayerNorm output, q|k|v or Q, attention output, gelu(fc1)) that left a convert saturated (|x| = 65504) or non-finite.

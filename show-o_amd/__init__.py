@@ -19,3 +19,4 @@ from . import image_utils  # noqa: F401
 from .image_utils import image_transform  # noqa: F401
 from . import synthetic  # noqa: F401
 from . import checkpointing  # noqa: F401
+from . import quantization  # noqa: F401

@@ -94,6 +94,9 @@ _PROTOS = {
     # 16-bit operand type as an argument (SHOWO_OP_BF16 = 0 | SHOWO_OP_F16 = 1, second to last): the `_bf16` entry points are op = 0
     "showo_cast_f32_op16": [c_p, c_p, c_i64, c_i, c_p],
     "showo_count_f16_saturated": [c_p, c_i64, c_p, c_p],
+    # per-row int8 weight format of precision 3 (csrc/quant.hip)
+    "showo_quantize_rows_i8": [c_p, c_i64, c_i64, c_p, c_p, c_p],
+    "showo_dequantize_rows_i8": [c_p, c_p, c_i64, c_i64, c_p, c_p],
     "showo_layernorm_f32_op16": [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_f, c_i, c_p],
     "showo_gemm_op16": [c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p],
     "showo_gemm_qkv_fc1_op16": [c_p, c_i, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i,
@@ -132,6 +135,7 @@ _PROTOS = {
     "showo_argmax_f32": [c_p, c_i, c_p, c_p],
     "showo_engine_create": [c_p, C.POINTER(c_p)],
     "showo_engine_load": [c_p, C.c_char_p, c_p, c_i64, c_p],
+    "showo_engine_load_q8": [c_p, C.c_char_p, c_p, c_p, c_i64, c_i64, c_p],
     "showo_engine_slot": [c_p, c_p, c_i64, c_p, c_p],
     "showo_engine_weights_touched": [c_p],
     "showo_engine_missing": [c_p],

@@ -844,13 +844,13 @@ __global__ __launch_bounds__(1024) void attn_decode_kernel(AttnArgs a, DecPrep f
 // remaining blocks stream the fc2 weights (33.5 MB at Phi-1.5's shape) and write y2 = fc2(gelu(fc1)) + b2, which does not depend on
 // the attention (Phi's block is parallel-residual, models/phi.py:806-835).  No synchronisation between the roles: the following
 // out_gemv2_kernel<1, 2> launch adds dense(attn) and y2 into the residual row.  One launch instead of a stream fork / join.
-template <bool F16 = false>
+template <bool F16 = false, bool Q8 = false>  // Q8: the fc2 role streams the int8 image of W2 (precision 3); the attention role is unchanged
 __global__ __launch_bounds__(1024) void attn_decode_co_kernel(AttnArgs a, DecPrep f, showo::OutGemvArgs g, showo::DecodePrefetch pf) {
     if ((int)blockIdx.x >= a.nH) {
         extern __shared__ float sp[];
         const int nrole = gridDim.x - a.nH - pf.blocks;
         if ((int)blockIdx.x >= a.nH + nrole) showo::prefetch_role(pf, blockIdx.x - a.nH - nrole, pf.blocks, sp);
-        else showo::fc2_columns_role<4, F16>(g, blockIdx.x - a.nH, nrole, 16, reinterpret_cast<bf16_t*>(sp));
+        else showo::fc2_columns_role<4, F16, Q8>(g, blockIdx.x - a.nH, nrole, 16, reinterpret_cast<bf16_t*>(sp));
         return;
     }
     attn_decode_body<true, F16>(a, f, blockIdx.x, 0);
@@ -858,14 +858,14 @@ __global__ __launch_bounds__(1024) void attn_decode_co_kernel(AttnArgs a, DecPre
 
 // Batched form of the co-scheduled launch (decode_batch.hip): blocks [0, nH * B) = the (sequence, head) attention blocks, the rest
 // stream the fc2 weights ONCE for all NB sequences (fc2_columns_roleB: the NB activation rows as bf16 in LDS).
-template <int NB, bool F16 = false>
+template <int NB, bool F16 = false, bool Q8 = false>
 __global__ __launch_bounds__(1024) void attn_decode_coB_kernel(AttnArgs a, DecPrep f, showo::OutGemvBArgs g, showo::DecodePrefetch pf) {
     const int nab = a.nH * a.B;
     if ((int)blockIdx.x >= nab) {
         extern __shared__ float sp[];
         const int nrole = gridDim.x - nab - pf.blocks;
         if ((int)blockIdx.x >= nab + nrole) showo::prefetch_role(pf, blockIdx.x - nab - nrole, pf.blocks, sp);
-        else showo::fc2_columns_roleB<4, NB, F16>(g, blockIdx.x - nab, nrole, 16, reinterpret_cast<bf16_t*>(sp));
+        else showo::fc2_columns_roleB<4, NB, F16, Q8>(g, blockIdx.x - nab, nrole, 16, reinterpret_cast<bf16_t*>(sp));
         return;
     }
     attn_decode_body<true, F16>(a, f, blockIdx.x % a.nH, blockIdx.x / a.nH);
@@ -1056,17 +1056,20 @@ int attn_decode_co_batch(const bf16_t* qkv, const float* qw, const float* qb, co
     const size_t smem_f = (size_t)B * fc2.K1 * sizeof(bf16_t);
     const size_t smem = smem_a > smem_f ? smem_a : smem_f;
     const dim3 grid(nH * B + co_blocks + pf.blocks);
-    static bool attr[20] = {};
+    const bool q8 = fc2.s1 != nullptr;  // the fc2 role streams the int8 image of W2 (precision 3)
+    if (q8 && op) return set_error_msg(1, "batched decode attention: int8 fc2 weights take bf16 activations");
+    static bool attr[30] = {};
     auto launch = [&](auto kfn) -> int {
-        if (!attr[B + (op ? 10 : 0)]) {
+        if (!attr[B + (op ? 10 : 0) + (q8 ? 20 : 0)]) {
             hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, 144 * 1024);
             if (e != hipSuccess) return set_error_hip(e, "hipFuncSetAttribute(attn_decode_coB)", __FILE__, __LINE__);
-            attr[B + (op ? 10 : 0)] = true;
+            attr[B + (op ? 10 : 0) + (q8 ? 20 : 0)] = true;
         }
         kfn<<<grid, dim3(1024), smem, s>>>(a, f, fc2, pf);
         return 0;
     };
-    const int rc = op ? (B == 2 ? launch(attn_decode_coB_kernel<2, true>) : B == 3 ? launch(attn_decode_coB_kernel<3, true>) : launch(attn_decode_coB_kernel<4, true>))
+    const int rc = q8 ? (B == 2 ? launch(attn_decode_coB_kernel<2, false, true>) : B == 3 ? launch(attn_decode_coB_kernel<3, false, true>) : launch(attn_decode_coB_kernel<4, false, true>))
+                 : op ? (B == 2 ? launch(attn_decode_coB_kernel<2, true>) : B == 3 ? launch(attn_decode_coB_kernel<3, true>) : launch(attn_decode_coB_kernel<4, true>))
                       : (B == 2 ? launch(attn_decode_coB_kernel<2>) : B == 3 ? launch(attn_decode_coB_kernel<3>) : launch(attn_decode_coB_kernel<4>));
     if (rc) return rc;
     SHOWO_CHECK_HIP(hipGetLastError());
@@ -1075,7 +1078,7 @@ int attn_decode_co_batch(const bf16_t* qkv, const float* qw, const float* qb, co
 int attn_decode_fused(const bf16_t* qkv, const float* qw, const float* qb, const float* kw, const float* kb, const float* cosT,
                       const float* sinT, bf16_t* K, bf16_t* Vt, const int32_t* iv, bf16_t* O, int nH, int rot, float eps, int pos,
                       int Lcap, int Lp, hipStream_t s, const bf16_t* W2, const bf16_t* ffn, const float* b2, int F, int Hout, float* y2,
-                      int co_blocks, const DecodePrefetch* pfp, int op) {
+                      int co_blocks, const DecodePrefetch* pfp, int op, const float* s2) {
     if ((Lp % 64) || Lp <= pos || Lcap <= pos) return set_error_msg(1, "decode attention: bad Lp/Lcap");
     DecodePrefetch pf{};
     if (pfp && W2) pf = *pfp;
@@ -1089,9 +1092,11 @@ int attn_decode_fused(const bf16_t* qkv, const float* qw, const float* qb, const
     if (smem > 60000) return set_error_msg(5, "decode attention: cache longer than the single-block kernel supports");
     if (W2) {  // co-scheduled fc2 role (see attn_decode_co_kernel): needs K1 = 4 x 2048
         if (F != 8192 || !y2 || !ffn || !b2) return set_error_msg(1, "decode attention: co-scheduled fc2 needs F = 8192 and y2");
-        showo::OutGemvArgs g{nullptr, nullptr, nullptr, nullptr, 0, W2, ffn, b2, F, Hout, y2};
+        if (s2 && op) return set_error_msg(1, "decode attention: int8 fc2 weights take bf16 activations");
+        showo::OutGemvArgs g{nullptr, nullptr, nullptr, nullptr, 0, W2, ffn, b2, F, Hout, y2, nullptr, s2};
         const size_t smem2 = smem > (size_t)F * sizeof(bf16_t) ? smem : (size_t)F * sizeof(bf16_t);
-        if (op) attn_decode_co_kernel<true><<<dim3(nH + co_blocks + pf.blocks, 1), dim3(1024), smem2, s>>>(a, f, g, pf);
+        if (s2) attn_decode_co_kernel<false, true><<<dim3(nH + co_blocks + pf.blocks, 1), dim3(1024), smem2, s>>>(a, f, g, pf);
+        else if (op) attn_decode_co_kernel<true><<<dim3(nH + co_blocks + pf.blocks, 1), dim3(1024), smem2, s>>>(a, f, g, pf);
         else attn_decode_co_kernel<false><<<dim3(nH + co_blocks + pf.blocks, 1), dim3(1024), smem2, s>>>(a, f, g, pf);
     } else if (op) {
         attn_decode_kernel<true, true><<<dim3(nH, 1), dim3(1024), smem, s>>>(a, f);

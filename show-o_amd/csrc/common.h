@@ -243,6 +243,12 @@ __device__ inline uint4 ldg_nt16(const void* p) {
     const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
     return make_uint4(v.x, v.y, v.z, v.w);
 }
+// the 8-byte form: a lane's share of a sub-span of the int8 weight images (precision 3)
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+__device__ inline uint2 ldg_nt8(const void* p) {
+    const u32x2 v = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(p));
+    return make_uint2(v.x, v.y);
+}
 
 // direct HBM -> LDS copy, 16 B per lane; the LDS destination is wave-uniform base + lane * 16 (lane-linear image)
 __device__ inline void glds16(const bf16_t* src, bf16_t* lds_dst_wave_base) {

@@ -34,19 +34,22 @@ struct LnGemvArgs {
     const float* b1;
     bf16_t* out1;
     int N1;
+    const float* s0 = nullptr;  // Q8 instances (precision 3): W0 / W1 are int8 row-major, s0 [N0] / s1 [N1] their row scales
+    const float* s1 = nullptr;
 };
 
 // R = weight rows in flight per wave (2; see decode_ln_gemv2 for the measurement of 4); larger matrices (lm_head) loop and refill.
-template <int R, bool F16 = false>
+// Q8: int8 weight rows (8-byte loads, exact conversion to bf16, the same dot2 chain) and acc * scale[n] in front of the epilogue.
+template <int R, bool F16 = false, bool Q8 = false>
 __global__ __launch_bounds__(256) void ln_gemv2_kernel(LnGemvArgs g) {  // H <= 2048: one 4-load group covers a weight row
     extern __shared__ bf16_t sh[];  // normalised row, bf16 like showo_layernorm_f32_bf16's output
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform: weight-row bases in SGPRs
     const int H = g.H, Ntot = g.N0 + g.N1;
     const int stride = gridDim.x * 4;
     int n = blockIdx.x * 4 + wave;
-    auto rowp = [&](int c) { return c < g.N0 ? g.W0 + (int64_t)c * H : g.W1 + (int64_t)(c - g.N0) * H; };
+    auto rowp = [&](int c) { return c < g.N0 ? wrow<Q8>(g.W0, c, H) : wrow<Q8>(g.W1, c - g.N0, H); };
     // the first R weight rows of the wave are in flight before anything else: they do not depend on the LayerNorm
-    uint4 br[R][4];
+    typename WVec<Q8>::type br[R][4];
 #pragma unroll
     for (int r = 0; r < R; ++r)
         if (n + r * stride < Ntot) load4(rowp(n + r * stride), lane * 8, H, br[r]);
@@ -92,11 +95,13 @@ __global__ __launch_bounds__(256) void ln_gemv2_kernel(LnGemvArgs g) {  // H <= 
         acc = wave_sum_swap(acc);
         if (lane == 0) {
             if (c < g.N0) {
-                const float v = acc + g.b0[c];
+                const float a = q8_scale<Q8>(acc, g.s0, c);
+                const float v = a + g.b0[c];
                 if (g.outf) g.outf[c] = v;
                 else g.out0[c] = Op16<F16>::cvt(v);
             } else {
-                g.out1[c - g.N0] = Op16<F16>::cvt(gelu_new_fast(acc + g.b1[c - g.N0]));
+                const float a = q8_scale<Q8>(acc, g.s1, c - g.N0);
+                g.out1[c - g.N0] = Op16<F16>::cvt(gelu_new_fast(a + g.b1[c - g.N0]));
             }
         }
     };
@@ -121,18 +126,19 @@ __global__ __launch_bounds__(256) void ln_gemv2_kernel(LnGemvArgs g) {  // H <= 
 //   MODE 1 (K0 = 0): y2[n] = fc2 + b2            (side stream, next to the attention kernel)
 //   MODE 2 (K1 = 0): x[n] = (x[n] + (dense + bd)) + y2[n]   (after the join)
 // Same lane split, accumulation order and parenthesisation in every mode: the three forms agree bit for bit.
-template <int C, int MODE, bool F16 = false>
+template <int C, int MODE, bool F16 = false, bool Q8 = false>
 __global__ __launch_bounds__(512) void out_gemv2_kernel(OutGemvArgs g) {
     extern __shared__ bf16_t sa[];  // [K0] attention row, [K1] gelu(fc1) row: read once per block instead of once per wave
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform: weight-row bases in SGPRs
     const int stride = gridDim.x * 8;
     const int c0 = (g.K0 + 2047) / 2048;
     int n = blockIdx.x * 8 + wave;
-    auto issue = [&](int col, int t, uint4 (&wv)[4]) {
-        if (t < c0) load4(g.W0 + (int64_t)col * g.K0, t * 2048 + lane * 8, g.K0, wv);
-        else load4(g.W1 + (int64_t)col * g.K1, (t - c0) * 2048 + lane * 8, g.K1, wv);
+    typedef typename WVec<Q8>::type wvec_t;
+    auto issue = [&](int col, int t, wvec_t (&wv)[4]) {
+        if (t < c0) load4(wrow<Q8>(g.W0, col, g.K0), t * 2048 + lane * 8, g.K0, wv);
+        else load4(wrow<Q8>(g.W1, col, g.K1), (t - c0) * 2048 + lane * 8, g.K1, wv);
     };
-    uint4 buf[C][4];
+    wvec_t buf[C][4];
     if (n < g.N) {
 #pragma unroll
         for (int t = 0; t < C; ++t) issue(n, t, buf[t]);
@@ -154,6 +160,8 @@ __global__ __launch_bounds__(512) void out_gemv2_kernel(OutGemvArgs g) {
         acc0 = wave_sum_swap(acc0);
         acc1 = wave_sum_swap(acc1);
         if (lane == 0) {
+            if (MODE != 1) acc0 = q8_scale<Q8>(acc0, g.s0, n);
+            if (MODE != 2) acc1 = q8_scale<Q8>(acc1, g.s1, n);
             if (MODE == 1) {
                 g.y2[n] = acc1 + g.b1[n];
             } else {
@@ -181,13 +189,19 @@ bool decode_fused_shapes_ok(int H, int F) { return (H % 8) == 0 && (F % 8) == 0 
 
 // x -> LN(lnw, lnb) -> { out0 = bf16(W0 h + b0) | outf = fp32(W0 h + b0) } and out1 = bf16(gelu(W1 h + b1))  (N1 may be 0)
 int decode_ln_gemv2(const float* x, const float* lnw, const float* lnb, float eps, int H, const bf16_t* W0, const float* b0,
-                    bf16_t* out0, float* outf, int N0, const bf16_t* W1, const float* b1, bf16_t* out1, int N1, hipStream_t s, int op) {
-    LnGemvArgs g{x, lnw, lnb, eps, H, W0, b0, out0, outf, N0, W1, b1, out1, N1};
+                    bf16_t* out0, float* outf, int N0, const bf16_t* W1, const float* b1, bf16_t* out1, int N1, hipStream_t s, int op,
+                    const float* s0, const float* s1) {
+    LnGemvArgs g{x, lnw, lnb, eps, H, W0, b0, out0, outf, N0, W1, b1, out1, N1, s0, s1};
+    if (s0 && (op || (N1 && !s1) || (H % 16)))
+        return set_error_msg(1, "decode_ln_gemv2: int8 weights take bf16 activations, a scale per matrix and H % 16 == 0");
     // two weight rows in flight per wave (12 rows per block; a wave's third row is requested behind its first FMA).  Four rows -- the whole
     // layer matrix requested at kernel start -- measured SLOWER on cfg4 (0.983-0.992 vs 0.958-0.969 ms per token, round 2: 123 VGPRs halve
     // the resident waves and the single burst queues behind itself); that instance left the library in round 6.
     const dim3 grid(pick_blocks(N0 + N1, 12, showo::decode_tuning().ln_blocks));
-    if (op) ln_gemv2_kernel<2, true><<<grid, dim3(256), (size_t)H * sizeof(bf16_t), s>>>(g);
+    // (int8 instance: four rows in flight per wave -- the bytes in flight of the bf16 instance's two -- measured no faster on cfg4 in a
+    // one-process A/B; that instance is not built)
+    if (s0) ln_gemv2_kernel<2, false, true><<<grid, dim3(256), (size_t)H * sizeof(bf16_t), s>>>(g);
+    else if (op) ln_gemv2_kernel<2, true><<<grid, dim3(256), (size_t)H * sizeof(bf16_t), s>>>(g);
     else ln_gemv2_kernel<2><<<grid, dim3(256), (size_t)H * sizeof(bf16_t), s>>>(g);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return set_error_hip(e, "ln_gemv2 launch", __FILE__, __LINE__);
@@ -196,14 +210,32 @@ int decode_ln_gemv2(const float* x, const float* lnw, const float* lnb, float ep
 
 // x[n] += (W0[n,:] a0 + b0[n]);  x[n] += (W1[n,:] a1 + b1[n])
 int decode_out_gemv2(float* x, const bf16_t* W0, const bf16_t* a0, const float* b0, int K0, const bf16_t* W1, const bf16_t* a1,
-                     const float* b1, int K1, int N, hipStream_t s, int mode, float* y2, int op) {
-    OutGemvArgs g{x, W0, a0, b0, K0, W1, a1, b1, K1, N, y2};
+                     const float* b1, int K1, int N, hipStream_t s, int mode, float* y2, int op, const float* s0, const float* s1) {
+    OutGemvArgs g{x, W0, a0, b0, K0, W1, a1, b1, K1, N, y2, s0, s1};
+    if ((s0 || s1) && (op || (mode != 1 && !s0) || (mode != 2 && !s1) || (K0 % 16) || (K1 % 16)))
+        return set_error_msg(1, "decode_out_gemv2: int8 weights take bf16 activations, a scale per matrix and K % 16 == 0");
     if (mode == 1) g.K0 = 0;
     if (mode == 2) g.K1 = 0;
     if (mode && !y2) return set_error_msg(1, "decode_out_gemv2: y2 required");
     const int C = (g.K0 + 2047) / 2048 + (g.K1 + 2047) / 2048;
     const dim3 grid(pick_blocks(N, 8, showo::decode_tuning().out_blocks));
     const size_t smem = (size_t)(g.K0 + g.K1) * sizeof(bf16_t);
+    if (s0 || s1) {  // int8 weight images (precision 3)
+        if (mode == 1 && C == 4) out_gemv2_kernel<4, 1, false, true><<<grid, dim3(512), smem, s>>>(g);
+        else if (mode == 1 && C >= 1 && C <= 3) out_gemv2_kernel<3, 1, false, true><<<grid, dim3(512), smem, s>>>(g);
+        else if (mode == 2 && C == 1) out_gemv2_kernel<1, 2, false, true><<<grid, dim3(512), smem, s>>>(g);
+        else if (mode != 0) return set_error_msg(1, "decode_out_gemv2: unsupported K0/K1 for the forked layer");
+        else switch (C) {
+            case 2: out_gemv2_kernel<2, 0, false, true><<<grid, dim3(512), smem, s>>>(g); break;
+            case 3: out_gemv2_kernel<3, 0, false, true><<<grid, dim3(512), smem, s>>>(g); break;
+            case 4: out_gemv2_kernel<4, 0, false, true><<<grid, dim3(512), smem, s>>>(g); break;
+            case 5: out_gemv2_kernel<5, 0, false, true><<<grid, dim3(512), smem, s>>>(g); break;
+            default: return set_error_msg(1, "decode_out_gemv2: unsupported K0/K1 (decode_fused_shapes_ok)");
+        }
+        hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return set_error_hip(e, "out_gemv2 launch", __FILE__, __LINE__);
+        return 0;
+    }
     if (op) {  // IEEE-half operands (precision 2): the shapes of the fused layer at Phi-1.5's size
         if (mode == 1 && C == 4) out_gemv2_kernel<4, 1, true><<<grid, dim3(512), smem, s>>>(g);
         else if (mode == 1 && C >= 1 && C <= 3) out_gemv2_kernel<3, 1, true><<<grid, dim3(512), smem, s>>>(g);

@@ -57,6 +57,8 @@ struct LnGemvBArgs {
     bf16_t* out1;
     int N1, ld1;
     const bf16_t* W0lo = nullptr;  // HEAD3 instances (precision 2's lm_head): low halves of W0's rows, same layout
+    const float* s0 = nullptr;     // Q8 instances (precision 3): W0 / W1 are int8 row-major, s0 [N0] / s1 [N1] their row scales
+    const float* s1 = nullptr;
 };
 
 // REG (NB <= 4): after the LayerNorm every lane keeps ITS 32 activation values of each sequence in registers as 16 packed bf16 pairs
@@ -68,17 +70,21 @@ struct LnGemvBArgs {
 // normalised row is kept as a (hi, lo) bf16 pair and the weights come as (hi, lo) bf16 rows (W0, W0lo): acc = hi.hi + lo.hi + hi.lo in
 // ONE chain per sequence -- the split-bf16 product of engine.hip head_rows_precise_fast without its 3 H image (2 x 240 MB instead of
 // 719 MB per token step) and without a separate LayerNorm launch.
-template <int NB, bool REG, bool F16 = false, bool HEAD3 = false>
+// Q8 (precision 3): int8 weight rows, converted exactly to bf16 ONCE per weight for all NB sequences, and tot * scale[n] in front of the
+// epilogue (decode_common.h): per sequence the arithmetic of ln_gemv2_kernel's int8 instance.
+template <int NB, bool REG, bool F16 = false, bool HEAD3 = false, bool Q8 = false>
 __global__ __launch_bounds__(256, 2) void ln_gemvB_kernel(LnGemvBArgs g) {  // H <= 2048; 2 weight rows in flight per wave (4: measured slower)
     static_assert(!(HEAD3 && (REG || F16)), "the split head keeps its activations in LDS and multiplies bf16 halves");
+    static_assert(!(Q8 && (F16 || HEAD3)), "int8 weights multiply bf16 activations");
     constexpr int R = 2;
     extern __shared__ bf16_t sh[];  // [NB][H] normalised rows (16-bit, like showo_layernorm_f32_op16's output); HEAD3: [NB][2 H] = hi | lo
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform: row bases live in SGPRs
     const int H = g.H, Ntot = g.N0 + g.N1;
     const int stride = gridDim.x * 4;
     int n = blockIdx.x * 4 + wave;
-    auto rowp = [&](int c) { return c < g.N0 ? g.W0 + (int64_t)c * H : g.W1 + (int64_t)(c - g.N0) * H; };
-    uint4 br[R][4], bl[HEAD3 ? R : 1][4];
+    auto rowp = [&](int c) { return c < g.N0 ? wrow<Q8>(g.W0, c, H) : wrow<Q8>(g.W1, c - g.N0, H); };
+    typename WVec<Q8>::type br[R][4];
+    uint4 bl[HEAD3 ? R : 1][4];
 #pragma unroll
     for (int r = 0; r < R; ++r)
         if (n + r * stride < Ntot) {
@@ -166,11 +172,13 @@ __global__ __launch_bounds__(256, 2) void ln_gemvB_kernel(LnGemvBArgs g) {  // H
                     const int b = lane >> 4;
                     if ((lane & 15) == 0 && b < NB) {
                         if (c < g.N0) {
-                            const float v = tot + g.b0[c];
+                            const float a = q8_scale<Q8>(tot, g.s0, c);
+                            const float v = a + g.b0[c];
                             if (g.outf) g.outf[(int64_t)b * g.ld0 + c] = v;
                             else g.out0[(int64_t)b * g.ld0 + c] = Op16<F16>::cvt(v);
                         } else {
-                            g.out1[(int64_t)b * g.ld1 + (c - g.N0)] = Op16<F16>::cvt(gelu_new_fast(tot + g.b1[c - g.N0]));
+                            const float a = q8_scale<Q8>(tot, g.s1, c - g.N0);
+                            g.out1[(int64_t)b * g.ld1 + (c - g.N0)] = Op16<F16>::cvt(gelu_new_fast(a + g.b1[c - g.N0]));
                         }
                     }
                 } else {
@@ -181,14 +189,18 @@ __global__ __launch_bounds__(256, 2) void ln_gemvB_kernel(LnGemvBArgs g) {  // H
                             const float bias = g.b0[c];
 #pragma unroll
                             for (int b = 0; b < NB; ++b) {
-                                const float v = acc[b] + bias;
+                                const float a = q8_scale<Q8>(acc[b], g.s0, c);
+                                const float v = a + bias;
                                 if (g.outf) g.outf[(int64_t)b * g.ld0 + c] = v;
                                 else g.out0[(int64_t)b * g.ld0 + c] = Op16<F16>::cvt(v);
                             }
                         } else {
                             const float bias = g.b1[c - g.N0];
 #pragma unroll
-                            for (int b = 0; b < NB; ++b) g.out1[(int64_t)b * g.ld1 + (c - g.N0)] = Op16<F16>::cvt(gelu_new_fast(acc[b] + bias));
+                            for (int b = 0; b < NB; ++b) {
+                                const float a = q8_scale<Q8>(acc[b], g.s1, c - g.N0);
+                                g.out1[(int64_t)b * g.ld1 + (c - g.N0)] = Op16<F16>::cvt(gelu_new_fast(a + bias));
+                            }
                         }
                     }
                 }
@@ -199,7 +211,7 @@ __global__ __launch_bounds__(256, 2) void ln_gemvB_kernel(LnGemvBArgs g) {  // H
 }
 
 // C = 2048-element chunks per output column (dense chunks first, then fc2 chunks), all in flight per wave (out_gemv2_kernel<C, 0>)
-template <int C, int NB, bool F16 = false>
+template <int C, int NB, bool F16 = false, bool Q8 = false>
 __global__ __launch_bounds__(512) void out_gemvB_kernel(OutGemvBArgs g) {
     extern __shared__ bf16_t sa[];  // [NB][K0 + K1]
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform: row bases live in SGPRs
@@ -207,11 +219,12 @@ __global__ __launch_bounds__(512) void out_gemvB_kernel(OutGemvBArgs g) {
     const int c0 = (g.K0 + 2047) / 2048;
     const int KK = g.K0 + g.K1;
     int n = blockIdx.x * 8 + wave;
-    auto issue = [&](int col, int t, uint4 (&wv)[4]) {
-        if (t < c0) load4(g.W0 + (int64_t)col * g.K0, t * 2048 + lane * 8, g.K0, wv);
-        else load4(g.W1 + (int64_t)col * g.K1, (t - c0) * 2048 + lane * 8, g.K1, wv);
+    typedef typename WVec<Q8>::type wvec_t;
+    auto issue = [&](int col, int t, wvec_t (&wv)[4]) {
+        if (t < c0) load4(wrow<Q8>(g.W0, col, g.K0), t * 2048 + lane * 8, g.K0, wv);
+        else load4(wrow<Q8>(g.W1, col, g.K1), (t - c0) * 2048 + lane * 8, g.K1, wv);
     };
-    uint4 buf[C][4];
+    wvec_t buf[C][4];
     if (n < g.N) {
 #pragma unroll
         for (int t = 0; t < C; ++t) issue(n, t, buf[t]);
@@ -228,10 +241,15 @@ __global__ __launch_bounds__(512) void out_gemvB_kernel(OutGemvBArgs g) {
         for (int b = 0; b < NB; ++b) { acc0[b] = 0.f; acc1[b] = 0.f; }
 #pragma unroll
         for (int t = 0; t < C; ++t) {
+            if constexpr (Q8) {  // fma4 per sequence, u ascending into the same chain; an int8 group is converted once for all NB
+                if (t < c0) fma4_lds<NB>(buf[t], sa, KK, t * 2048 + lane * 8, g.K0, acc0);
+                else fma4_lds<NB>(buf[t], sa + g.K0, KK, (t - c0) * 2048 + lane * 8, g.K1, acc1);
+            } else {
 #pragma unroll
-            for (int b = 0; b < NB; ++b) {
-                if (t < c0) acc0[b] = fma4<F16>(buf[t], sa + b * KK, t * 2048 + lane * 8, g.K0, acc0[b]);
-                else acc1[b] = fma4<F16>(buf[t], sa + b * KK + g.K0, (t - c0) * 2048 + lane * 8, g.K1, acc1[b]);
+                for (int b = 0; b < NB; ++b) {
+                    if (t < c0) acc0[b] = fma4<F16>(buf[t], sa + b * KK, t * 2048 + lane * 8, g.K0, acc0[b]);
+                    else acc1[b] = fma4<F16>(buf[t], sa + b * KK + g.K0, (t - c0) * 2048 + lane * 8, g.K1, acc1[b]);
+                }
             }
             if (nn < g.N) issue(nn, t, buf[t]);
         }
@@ -239,9 +257,10 @@ __global__ __launch_bounds__(512) void out_gemvB_kernel(OutGemvBArgs g) {
             const float t0 = wave_sum_groups<NB>(acc0), t1 = wave_sum_groups<NB>(acc1);
             if ((lane & 15) == 0 && (lane >> 4) < NB) {
                 const int64_t i = (int64_t)(lane >> 4) * g.N + n;
-                float v = t0 + g.b0[n];  // x1 = x + (dense + bd)       (out_gemv2_kernel's order and parenthesisation)
+                const float d0 = q8_scale<Q8>(t0, g.s0, n), d1 = q8_scale<Q8>(t1, g.s1, n);
+                float v = d0 + g.b0[n];  // x1 = x + (dense + bd)       (out_gemv2_kernel's order and parenthesisation)
                 v += g.x[i];
-                float v2 = t1 + g.b1[n];  // x2 = x1 + (fc2 + b2)
+                float v2 = d1 + g.b1[n];  // x2 = x1 + (fc2 + b2)
                 v2 += v;
                 g.x[i] = v2;
             }
@@ -252,9 +271,10 @@ __global__ __launch_bounds__(512) void out_gemvB_kernel(OutGemvBArgs g) {
                 const float bd = g.b0[n], b2 = g.b1[n];
 #pragma unroll
                 for (int b = 0; b < NB; ++b) {
-                    float v = acc0[b] + bd;
+                    const float d0 = q8_scale<Q8>(acc0[b], g.s0, n), d1 = q8_scale<Q8>(acc1[b], g.s1, n);
+                    float v = d0 + bd;
                     v += g.x[(int64_t)b * g.N + n];
-                    float v2 = acc1[b] + b2;
+                    float v2 = d1 + b2;
                     v2 += v;
                     g.x[(int64_t)b * g.N + n] = v2;
                 }
@@ -267,13 +287,13 @@ __global__ __launch_bounds__(512) void out_gemvB_kernel(OutGemvBArgs g) {
 // Third launch of the co-scheduled batched layer: x[b][n] = (x[b][n] + (dense(attn[b]) + bd)) + y2[b][n]  (out_gemv2_kernel<1, 2>'s
 // expression; y2 = fc2 + b2 from the fc2 role of the attention launch).  K0 <= 2048: the lane's 32 attention values per sequence stay
 // in registers.
-template <int NB, bool F16 = false>
+template <int NB, bool F16 = false, bool Q8 = false>
 __global__ __launch_bounds__(512) void out_dense_y2B_kernel(OutGemvBArgs g) {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // wave-uniform: row bases live in SGPRs
     const int stride = gridDim.x * 8;
     int n = blockIdx.x * 8 + wave;
-    uint4 buf[4];
-    if (n < g.N) load4(g.W0 + (int64_t)n * g.K0, lane * 8, g.K0, buf);
+    typename WVec<Q8>::type buf[4];
+    if (n < g.N) load4(wrow<Q8>(g.W0, n, g.K0), lane * 8, g.K0, buf);
     uint32_t act[NB][16];
 #pragma unroll
     for (int b = 0; b < NB; ++b) load_act_pairs(g.a0 + (int64_t)b * g.lda0, lane * 8, g.K0, act[b]);
@@ -288,10 +308,11 @@ __global__ __launch_bounds__(512) void out_dense_y2B_kernel(OutGemvBArgs g) {
 #pragma unroll
         for (int b = 0; b < NB; ++b) acc0[b] = 0.f;
         fma4_regs<NB, F16>(buf, act, lane * 8, g.K0, acc0);
-        if (nn < g.N) load4(g.W0 + (int64_t)nn * g.K0, lane * 8, g.K0, buf);
+        if (nn < g.N) load4(wrow<Q8>(g.W0, nn, g.K0), lane * 8, g.K0, buf);
         const float tot = wave_sum_groups<NB>(acc0);
         if (writer) {
-            float v = tot + bd;
+            const float d0 = q8_scale<Q8>(tot, g.s0, n);
+            float v = d0 + bd;
             v += xv;
             float v2 = yv;
             v2 += v;
@@ -429,7 +450,19 @@ __global__ __launch_bounds__(1024) void sample_seam_rows_kernel(const float* __r
 template <int NB>
 int launch_ln_gemvB(const LnGemvBArgs& g, hipStream_t s, int op, bool head3) {
     const int Ntot = g.N0 + g.N1;
-    if (head3) {  // precision 2's lm_head: (hi, lo) activations in LDS, (hi, lo) bf16 weight rows
+    if (g.s0) {  // int8 weight images (precision 3): the grids of the bf16 instances
+        if (op || head3 || (g.N1 && !g.s1) || (g.H % 16)) return set_error_msg(1, "ln_gemvB: int8 weights take bf16 activations, a scale per matrix and H % 16 == 0");
+        if (NB <= 4) {
+            int blocks = (Ntot + 7) / 8;
+            const int cap = showo::decode_tuning().batch_ln_blocks;
+            if (blocks > cap) blocks = cap;
+            ln_gemvB_kernel<NB, (NB <= 4), false, false, true><<<dim3(blocks), dim3(256), (size_t)NB * g.H * sizeof(bf16_t), s>>>(g);
+        } else {
+            int blocks = (Ntot + 11) / 12;
+            if (blocks > 1280) blocks = 1280;
+            ln_gemvB_kernel<NB, false, false, false, true><<<dim3(blocks), dim3(256), (size_t)NB * g.H * sizeof(bf16_t), s>>>(g);
+        }
+    } else if (head3) {  // precision 2's lm_head: (hi, lo) activations in LDS, (hi, lo) bf16 weight rows
         if (!g.W0lo || !g.outf || g.N1) return set_error_msg(1, "ln_gemvB: the split head writes fp32 logits from (hi, lo) weight rows");
         int blocks = (Ntot + 11) / 12;
         if (blocks > 1280) blocks = 1280;
@@ -462,11 +495,11 @@ int ln_gemvB(int nb, const LnGemvBArgs& g, hipStream_t s, int op = 0, bool head3
     return set_error_msg(1, "batched decode: 1..8 sequences");
 }
 
-template <int C, int NB, bool F16>
+template <int C, int NB, bool F16, bool Q8 = false>
 int launch_out_gemvB(const OutGemvBArgs& g, hipStream_t s) {
     static bool attr_set = false;
     const size_t smem = (size_t)NB * (g.K0 + g.K1) * sizeof(bf16_t);
-    auto kfn = out_gemvB_kernel<C, NB, F16>;
+    auto kfn = out_gemvB_kernel<C, NB, F16, Q8>;
     if (!attr_set && smem > 65536) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return set_error_hip(e, "hipFuncSetAttribute(out_gemvB)", __FILE__, __LINE__);
@@ -481,6 +514,16 @@ int launch_out_gemvB(const OutGemvBArgs& g, hipStream_t s) {
 template <int NB>
 int out_gemvB_c(const OutGemvBArgs& g, hipStream_t s, int op) {
     const int C = (g.K0 + 2047) / 2048 + (g.K1 + 2047) / 2048;
+    if (g.s0 || g.s1) {  // int8 weight images (precision 3)
+        if (op || !g.s0 || !g.s1 || (g.K0 % 16) || (g.K1 % 16)) return set_error_msg(1, "out_gemvB: int8 weights take bf16 activations, both scales and K % 16 == 0");
+        switch (C) {
+            case 2: return launch_out_gemvB<2, NB, false, true>(g, s);
+            case 3: return launch_out_gemvB<3, NB, false, true>(g, s);
+            case 4: return launch_out_gemvB<4, NB, false, true>(g, s);
+            case 5: return launch_out_gemvB<5, NB, false, true>(g, s);
+        }
+        return set_error_msg(1, "batched decode: unsupported K0 / K1 (decode_fused_shapes_ok)");
+    }
     switch (C) {
         case 2: return op ? launch_out_gemvB<2, NB, true>(g, s) : launch_out_gemvB<2, NB, false>(g, s);
         case 3: return op ? launch_out_gemvB<3, NB, true>(g, s) : launch_out_gemvB<3, NB, false>(g, s);
@@ -492,6 +535,16 @@ int out_gemvB_c(const OutGemvBArgs& g, hipStream_t s, int op) {
 int out_dense_y2B(int nb, const OutGemvBArgs& g, hipStream_t s, int op) {
     int blocks = (g.N + 7) / 8;
     if (blocks > showo::decode_tuning().out_blocks) blocks = showo::decode_tuning().out_blocks;
+    if (g.s0) {  // int8 image of the dense matrix (precision 3)
+        if (op || (g.K0 % 16)) return set_error_msg(1, "out_dense_y2B: int8 weights take bf16 activations and K % 16 == 0");
+        switch (nb) {
+            case 2: out_dense_y2B_kernel<2, false, true><<<dim3(blocks), dim3(512), 0, s>>>(g); break;
+            case 3: out_dense_y2B_kernel<3, false, true><<<dim3(blocks), dim3(512), 0, s>>>(g); break;
+            case 4: out_dense_y2B_kernel<4, false, true><<<dim3(blocks), dim3(512), 0, s>>>(g); break;
+            default: return set_error_msg(1, "batched decode: the co-scheduled layer serves 2..4 sequences");
+        }
+        return hipGetLastError() == hipSuccess ? 0 : set_error_msg(7, "out_dense_y2B launch failed");
+    }
     switch (nb * 2 + (op ? 1 : 0)) {
         case 4: out_dense_y2B_kernel<2><<<dim3(blocks), dim3(512), 0, s>>>(g); break;
         case 6: out_dense_y2B_kernel<3><<<dim3(blocks), dim3(512), 0, s>>>(g); break;
@@ -617,6 +670,8 @@ int batch_decode_checks(showo_engine* e, const char* what) {
     auto* d = e->bd;
     auto fail = [&](int code, const char* msg) { return set_error_msg(code, (std::string(what) + ": " + msg).c_str()); };
     if (e->precision == 1) return fail(1, "precision 0 (bf16 operands) or 2 (fp16 operands)");
+    if (e->precision == 3 && (int)e->q8_loaded.size() != e->nL * 6 + 1)
+        return fail(4, "(precision 3) the int8 weight images are missing or stale: upload the weights again");
     const int op = e->precision == 2 ? SHOWO_OP_F16 : SHOWO_OP_BF16;
     if ((op == SHOWO_OP_F16) != e->img_f16) return fail(4, "the weight images hold the other 16-bit type: upload the weights again");
     if (d->precision != e->precision) return fail(1, "the caches were prefilled under another precision: prefill again");
@@ -637,18 +692,24 @@ int batch_step_layers(showo_engine* e, int op, bool co, int lk_max, float* logit
     auto* d = e->bd;
     const int nb = d->nb, H = e->H, F = e->F, nH = e->nH, V = e->V;
     const int64_t per_seq = (int64_t)nH * d->cap * 64, lstride = (int64_t)nb * per_seq;
+    const bool q8 = e->precision == 3;
     const int co_blocks = showo::decode_tuning().batch_co_blocks;  // 128 role blocks + 32 nb attention blocks = one block per CU at nb = 4
     for (int li = 0; li < e->nL; ++li) {
         showo::Layer& l = e->layers[li];
         LnGemvBArgs a{e->x, l.ln_w, l.ln_b, e->cfg.ln_eps, H, l.wqkv, l.bqkv, e->qkv, nullptr, 3 * H, 3 * H, l.w1, l.b1, e->ffn, F, F};
-        TRY(ln_gemvB(nb, a, s, op));
         OutGemvBArgs o{e->x, l.wd, e->attn, l.bd, H, H, l.w2, e->ffn, l.b2, F, F, H, d->y2};
+        if (q8) {  // precision 3: the same launches stream the int8 images (pointers travel as bf16_t*; the scales select the instances)
+            a.W0 = reinterpret_cast<const bf16_t*>(l.qqkv); a.W1 = reinterpret_cast<const bf16_t*>(l.q1); a.s0 = l.sqkv; a.s1 = l.s1;
+            o.W0 = reinterpret_cast<const bf16_t*>(l.qd); o.W1 = reinterpret_cast<const bf16_t*>(l.q2); o.s0 = l.sd; o.s1 = l.s2;
+        }
+        TRY(ln_gemvB(nb, a, s, op));
         if (co) {
             // [ attention of the nb x heads (sequence, head) pairs || fc2 of all nb sequences -> y2 ] -> dense + both residual adds
             // (Phi's block is parallel-residual, models/phi.py:806-835: fc2 does not depend on the attention; decode.hip's batch-1 layer
             // co-schedules the same way)
             showo::DecodePrefetch pf;
             showo::decode_prefetch_plan(e, li, &pf);
+            if (q8) pf = showo::DecodePrefetch{};  // (the plan describes the bf16 images, which these launches never stream)
             TRY(showo::attn_decode_co_batch(e->qkv, l.qln_w, l.qln_b, l.kln_w, l.kln_b, e->cosT, e->sinT, d->k + li * lstride,
                                             d->vt + li * lstride, d->iv_dev, e->attn, nb, nH, e->cfg.rotary_dim, e->cfg.ln_eps,
                                             d->pos_dev, lk_max, d->cap, d->cap, o, co_blocks, s, &pf, op));
@@ -664,6 +725,7 @@ int batch_step_layers(showo_engine* e, int op, bool co, int lk_max, float* logit
         TRY(showo::decode_split_head(e->x, e->fln_w, e->fln_b, e->cfg.ln_eps, H, e->wlm, e->wlm_lo, e->blm, logits_ws, V, V, nb, s));
     } else {
         LnGemvBArgs h{e->x, e->fln_w, e->fln_b, e->cfg.ln_eps, H, e->wlm, e->blm, nullptr, logits_ws, V, V, nullptr, nullptr, nullptr, 0, 0};
+        if (q8) { h.W0 = reinterpret_cast<const bf16_t*>(e->qlm); h.s0 = e->slm; }
         TRY(ln_gemvB(nb, h, s));
     }
     return 0;

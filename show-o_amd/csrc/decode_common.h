@@ -11,6 +11,44 @@ static __device__ __forceinline__ void load4(const bf16_t* row, int k0, int K, u
         wv[u] = k < K ? ldg_nt16(row + k) : make_uint4(0, 0, 0, 0);
     }
 }
+// ---- int8 weight stream (precision 3) -----------------------------------------------------------------------------------------------
+// The int8 image is row-major: a lane keeps its k assignment (k in [8 l, 8 l + 8) + 512 u) and loads 8 bytes per sub-span instead of
+// 16.  WVec<Q8>::type is what one such load returns; wrow<Q8> is the typed base of weight row `col` of a [*, K] matrix whose pointer
+// travels as bf16_t* in the argument structs.
+template <bool Q8> struct WVec { typedef uint4 type; };
+template <> struct WVec<true> { typedef uint2 type; };
+template <bool Q8>
+static __device__ __forceinline__ auto wrow(const bf16_t* W, int64_t col, int K) {
+    if constexpr (Q8) return reinterpret_cast<const int8_t*>(W) + col * K;
+    else return W + col * K;
+}
+static __device__ __forceinline__ void load4(const int8_t* row, int k0, int K, uint2 (&wv)[4]) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int k = k0 + u * 512;
+        wv[u] = k < K ? ldg_nt8(row + k) : make_uint2(0, 0);
+    }
+}
+// 8 int8 weights -> 4 packed bf16 pairs, EXACTLY (|q| <= 127 fits bf16's 8-bit significand: the fp32 image truncates without loss)
+static __device__ __forceinline__ uint32_t q8_pair(uint32_t w, int i) {
+    const float lo = (float)(int)(int8_t)(w >> (8 * i)), hi = (float)(int)(int8_t)(w >> (8 * i + 8));
+    return (__float_as_uint(lo) >> 16) | (__float_as_uint(hi) & 0xffff0000u);
+}
+static __device__ __forceinline__ uint4 q8_to_bf16x8(const uint2& w) {
+    return make_uint4(q8_pair(w.x, 0), q8_pair(w.x, 2), q8_pair(w.y, 0), q8_pair(w.y, 2));
+}
+// the weight scale of output column n in front of the epilogue: ONE fp32 multiply, a statement of its own (never contracted into the
+// bias add), so every kernel form gives the same bits; for a power-of-two scale the result is what the bf16 kernel computes on q * s
+template <bool Q8>
+static __device__ __forceinline__ float q8_scale(float acc, const float* s, int n) {
+    if constexpr (Q8) {
+        const float v = acc * s[n];
+        return v;
+    } else {
+        return acc;
+    }
+}
+
 // acc += sum over the 4 loaded 8-element groups, in gemv_kernel's order (u ascending, pairs ascending: dot8_bf16)
 // F16: the operand type of weights and activations (common.h Op16; precision 2 = IEEE half on v_dot2_f32_f16)
 template <bool F16 = false, class AP>
@@ -20,6 +58,18 @@ static __device__ __forceinline__ float fma4(const uint4 (&wv)[4], AP act, int k
         const int k = k0 + u * 512;
         if (k >= K) break;
         acc = dot8_op<F16>(wv[u], *reinterpret_cast<const uint4*>(act + k), acc);
+    }
+    return acc;
+}
+// the same chain on int8 weights (bf16 activations): the conversion is exact, the dot2 chain is the bf16 one
+template <bool F16 = false, class AP>
+static __device__ __forceinline__ float fma4(const uint2 (&wv)[4], AP act, int k0, int K, float acc) {
+    static_assert(!F16, "int8 weights multiply bf16 activations");
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int k = k0 + u * 512;
+        if (k >= K) break;
+        acc = dot8_op<false>(q8_to_bf16x8(wv[u]), *reinterpret_cast<const uint4*>(act + k), acc);
     }
     return acc;
 }
@@ -36,21 +86,23 @@ struct OutGemvArgs {
     int K1;
     int N;
     float* y2;          // [N] fp32: fc2 + b2 of the forked layer (MODE 1 writes it, MODE 2 adds it)
+    const float* s0 = nullptr;  // Q8 instances: W0 / W1 are int8 [N, K0] / [N, K1], s0 / s1 [N] their row scales
+    const float* s1 = nullptr;
 };
 
 
 // fc2 role of the co-scheduled decode launch (attention.hip, attn_decode_co_kernel): y2[n] = W1[n, :] a1 + b1[n] for the columns of
 // role-block `rb` of `nrb`, `nw` waves per block.  Same lane split, accumulation order and epilogue expression as
 // out_gemv2_kernel<C, 1> (decode.hip), so the result does not depend on which launch computed it.  sa: >= K1 bf16 of LDS.
-template <int C, bool F16 = false>
+template <int C, bool F16 = false, bool Q8 = false>
 static __device__ __forceinline__ void fc2_columns_role(const OutGemvArgs& g, int rb, int nrb, int nw, bf16_t* sa) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int stride = nrb * nw;
     int n = wave * nrb + rb;
-    uint4 buf[C][4];
+    typename WVec<Q8>::type buf[C][4];
     if (n < g.N) {
 #pragma unroll
-        for (int t = 0; t < C; ++t) load4(g.W1 + (int64_t)n * g.K1, t * 2048 + lane * 8, g.K1, buf[t]);
+        for (int t = 0; t < C; ++t) load4(wrow<Q8>(g.W1, n, g.K1), t * 2048 + lane * 8, g.K1, buf[t]);
     }
     for (int i = threadIdx.x * 8; i < g.K1; i += nw * 64 * 8) *reinterpret_cast<uint4*>(sa + i) = *reinterpret_cast<const uint4*>(g.a1 + i);
     __syncthreads();
@@ -60,10 +112,13 @@ static __device__ __forceinline__ void fc2_columns_role(const OutGemvArgs& g, in
 #pragma unroll
         for (int t = 0; t < C; ++t) {
             acc1 = fma4<F16>(buf[t], sa, t * 2048 + lane * 8, g.K1, acc1);
-            if (nn < g.N) load4(g.W1 + (int64_t)nn * g.K1, t * 2048 + lane * 8, g.K1, buf[t]);
+            if (nn < g.N) load4(wrow<Q8>(g.W1, nn, g.K1), t * 2048 + lane * 8, g.K1, buf[t]);
         }
         acc1 = wave_sum_swap(acc1);
-        if (lane == 0) g.y2[n] = acc1 + g.b1[n];
+        if (lane == 0) {
+            const float v1 = q8_scale<Q8>(acc1, g.s1, n);
+            g.y2[n] = v1 + g.b1[n];
+        }
         n = nn;
     }
 }
@@ -108,6 +163,8 @@ struct OutGemvBArgs {
     int K1, lda1;
     int N;
     float* y2;         // [NB, N] fp32: fc2 + b2 per sequence (written by the co-scheduled role, added by out_gemvB_kernel<.., 2>)
+    const float* s0 = nullptr;  // Q8 instances: W0 / W1 are int8 [N, K0] / [N, K1], s0 / s1 [N] their row scales
+    const float* s1 = nullptr;
 };
 
 // wave_sum of up to four accumulators at once, each with wave_sum's own order of additions (partners 32, 16, 8, 4, 2, 1 away: the same
@@ -145,6 +202,21 @@ static __device__ __forceinline__ void fma4_regs(const uint4 (&wv)[4], const uin
             for (int b = 0; b < NB; ++b) acc[b] = Op16<F16>::dot2(w[p], act[b][u * 4 + p], acc[b]);
     }
 }
+// int8 weights: converted once per weight (not per sequence), then the bf16 chain
+template <int NB, bool F16 = false>
+static __device__ __forceinline__ void fma4_regs(const uint2 (&wv)[4], const uint32_t (&act)[NB][16], int k0, int K, float (&acc)[NB]) {
+    static_assert(!F16, "int8 weights multiply bf16 activations");
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        if (k0 + u * 512 >= K) break;
+        const uint4 wb = q8_to_bf16x8(wv[u]);
+        const uint32_t w[4] = {wb.x, wb.y, wb.z, wb.w};
+#pragma unroll
+        for (int p = 0; p < 4; ++p)
+#pragma unroll
+            for (int b = 0; b < NB; ++b) acc[b] = Op16<false>::dot2(w[p], act[b][u * 4 + p], acc[b]);
+    }
+}
 // this lane's 16 pairs of one bf16 activation row (global or LDS), zero beyond K
 template <class AP>
 static __device__ __forceinline__ void load_act_pairs(AP row, int k0, int K, uint32_t (&act)[16]) {
@@ -168,19 +240,32 @@ static __device__ __forceinline__ void fma4_lds(const uint4 (&wv)[4], const bf16
     }
 }
 
+template <int NB, bool F16 = false>
+static __device__ __forceinline__ void fma4_lds(const uint2 (&wv)[4], const bf16_t* sa, int ld, int k0, int K, float (&acc)[NB]) {
+    static_assert(!F16, "int8 weights multiply bf16 activations");
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int k = k0 + u * 512;
+        if (k >= K) break;
+        const uint4 wb = q8_to_bf16x8(wv[u]);
+#pragma unroll
+        for (int b = 0; b < NB; ++b) acc[b] = dot8_op<false>(wb, *reinterpret_cast<const uint4*>(sa + (size_t)b * ld + k), acc[b]);
+    }
+}
+
 // fc2 role of the co-scheduled BATCHED decode launch (attention.hip, attn_decode_coB_kernel): y2[b][n] = W1[n, :] a1[b] + b1[n] for
 // the columns of role-block rb of nrb, nw waves per block.  fc2_columns_role's lane split and accumulation order per sequence (chunks
 // t ascending into ONE accumulator chain, then the wave reduction): the bits of the batch-1 launch.  The NB activation rows live in
 // LDS as bf16 (NB * K1 * 2 bytes: 64 KiB at NB = 4).
-template <int C, int NB, bool F16 = false>
+template <int C, int NB, bool F16 = false, bool Q8 = false>
 static __device__ __forceinline__ void fc2_columns_roleB(const OutGemvBArgs& g, int rb, int nrb, int nw, bf16_t* sa) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int stride = nrb * nw;
     int n = wave * nrb + rb;
-    uint4 buf[C][4];
+    typename WVec<Q8>::type buf[C][4];
     if (n < g.N) {
 #pragma unroll
-        for (int t = 0; t < C; ++t) load4(g.W1 + (int64_t)n * g.K1, t * 2048 + lane * 8, g.K1, buf[t]);
+        for (int t = 0; t < C; ++t) load4(wrow<Q8>(g.W1, n, g.K1), t * 2048 + lane * 8, g.K1, buf[t]);
     }
     for (int b = 0; b < NB; ++b)
         for (int i = threadIdx.x * 8; i < g.K1; i += nw * 64 * 8)
@@ -194,10 +279,13 @@ static __device__ __forceinline__ void fc2_columns_roleB(const OutGemvBArgs& g, 
 #pragma unroll
         for (int t = 0; t < C; ++t) {
             fma4_lds<NB, F16>(buf[t], sa, g.K1, t * 2048 + lane * 8, g.K1, acc1);
-            if (nn < g.N) load4(g.W1 + (int64_t)nn * g.K1, t * 2048 + lane * 8, g.K1, buf[t]);
+            if (nn < g.N) load4(wrow<Q8>(g.W1, nn, g.K1), t * 2048 + lane * 8, g.K1, buf[t]);
         }
         const float tot = wave_sum_groups<NB>(acc1);
-        if ((lane & 15) == 0 && (lane >> 4) < NB) g.y2[(int64_t)(lane >> 4) * g.N + n] = tot + g.b1[n];
+        if ((lane & 15) == 0 && (lane >> 4) < NB) {
+            const float v1 = q8_scale<Q8>(tot, g.s1, n);
+            g.y2[(int64_t)(lane >> 4) * g.N + n] = v1 + g.b1[n];
+        }
         n = nn;
     }
 }

@@ -23,6 +23,10 @@ struct Layer {
     // accuracy mode on the production kernels: K-concatenated, tiled split images (precise_sync in engine.hip)
     //   wq1x3 rows [w_hi | w_hi | w_lo] of [Wqkv ; W1]  ([3H + F, 3H]);  wd2x3 rows [Wd_hi | W2_hi | Wd_hi | W2_hi | Wd_lo | W2_lo] ([H, 3 (H + F)])
     bf16_t *wq1x3 = nullptr, *wd2x3 = nullptr;
+    // int8 decode (showo_engine_set_precision 3): row-major int8 images and fp32 row scales of the four matrices, streamed by the fused
+    // decode step; qqkv / q1 and sqkv / s1 are one allocation each like wqkv / w1.  The bf16 images above then hold bf16(q * scale).
+    int8_t *qqkv = nullptr, *qd = nullptr, *q1 = nullptr, *q2 = nullptr;
+    float *sqkv = nullptr, *sd = nullptr, *s1 = nullptr, *s2 = nullptr;
     // image versions (showo::engine_version): wqkv (any of q / k / v), wd, w1, w2, bd, b2 -- stamped from showo_engine::clock whenever the
     // tensor is written; fused_at = the clock when this block's wd2 / bd2 / wq1t images were last built (0: never)
     uint64_t ver[6] = {0, 0, 0, 0, 0, 0};
@@ -42,15 +46,22 @@ struct DecodePrefetch;
 bool decode_fused_shapes_ok(int H, int F);
 int decode_ln_gemv2(const float* x, const float* lnw, const float* lnb, float eps, int H, const bf16_t* W0, const float* b0,
                     bf16_t* out0, float* outf, int N0, const bf16_t* W1, const float* b1, bf16_t* out1, int N1, hipStream_t s,
-                    int op = 0);  // op: SHOWO_OP_BF16 | SHOWO_OP_F16 -- the element type of weights and 16-bit activations (all decode entry points)
+                    int op = 0,  // op: SHOWO_OP_BF16 | SHOWO_OP_F16 -- the element type of weights and 16-bit activations (all decode entry points)
+                    const float* s0 = nullptr, const float* s1 = nullptr);  // row scales: W0 / W1 are then int8 images (precision 3, op 0)
 int decode_split_head(const float* x, const float* lnw, const float* lnb, float eps, int H, const bf16_t* Whi, const bf16_t* Wlo,
                       const float* bias, float* logits, int N, int ld, int nb, hipStream_t s);  // decode_batch.hip: precision 2's head on a decode step
 int decode_out_gemv2(float* x, const bf16_t* W0, const bf16_t* a0, const float* b0, int K0, const bf16_t* W1, const bf16_t* a1,
-                     const float* b1, int K1, int N, hipStream_t s, int mode = 0, float* y2 = nullptr, int op = 0);
+                     const float* b1, int K1, int N, hipStream_t s, int mode = 0, float* y2 = nullptr, int op = 0,
+                     const float* s0 = nullptr, const float* s1 = nullptr);  // row scales of int8 W0 / W1 (precision 3)
 int attn_decode_fused(const bf16_t* qkv, const float* qw, const float* qb, const float* kw, const float* kb, const float* cosT,
                       const float* sinT, bf16_t* K, bf16_t* Vt, const int32_t* iv, bf16_t* O, int nH, int rot, float eps, int pos,
                       int Lcap, int Lp, hipStream_t s, const bf16_t* W2 = nullptr, const bf16_t* ffn = nullptr, const float* b2 = nullptr,
-                      int F = 0, int Hout = 0, float* y2 = nullptr, int co_blocks = 0, const DecodePrefetch* pf = nullptr, int op = 0);
+                      int F = 0, int Hout = 0, float* y2 = nullptr, int co_blocks = 0, const DecodePrefetch* pf = nullptr, int op = 0,
+                      const float* s2 = nullptr);  // s2: W2 is the int8 image of fc2 and s2 its row scales (precision 3)
+// int8 weight format helpers (quant.hip)
+int q8_dequant_bf16(const int8_t* q, const float* scale, int64_t N, int64_t K, bf16_t* w, hipStream_t s);
+int q8_validate(const int8_t* q, const float* scale, int64_t N, int64_t K, int* bad, hipStream_t s);  // bad: 2 device ints of the caller
+int q8_quantize_rows(const float* w, int64_t N, int64_t K, int8_t* q, float* scale, int* bad, hipStream_t s);
 // Infinity-Cache prefetch role of the co-scheduled decode launches (decode_common.h): what layer li's attention launch reads ahead.
 // next_mb: MB of the next launches' weights ([Wqkv ; W1] of layer li + 1, the lm_head after the last layer), dense: this layer's Wd
 // first, blocks: prefetch blocks per launch (0: off).  Defaults from SHOWO_DECODE_PF_MB / _DENSE / _BLOCKS; showo_decode_set_prefetch.
@@ -174,6 +185,12 @@ struct showo_engine {
     bool head3_valid = false;  // wlm3 = [hi | hi | lo] rows of the lm_head matches wlm / wlm_lo
     int64_t* range_count = nullptr;  // precision 2 range check (showo_engine_set_range_check): device counter of saturated fp16 elements
     std::set<std::string> lo_loaded;
+    // precision 3: int8 image + row scales of the lm_head, and the GEMM weights whose int8 images are current (the loader makes them
+    // next to the bf16 image of the dequantised values; cleared when somebody rewrites the bf16 images behind the loader's back)
+    int8_t* qlm = nullptr;
+    float* slm = nullptr;
+    int* q8_flags = nullptr;  // flag word of the quantiser / validator (one read-back per loaded tensor, no allocation)
+    std::set<std::string> q8_loaded;
     bf16_t* wlm_lo = nullptr;
     bf16_t *p_hlo = nullptr, *p_actlo = nullptr;                            // low halves of h / hf and of attn | gelu(fc1)
     float *p_qkv = nullptr, *p_f = nullptr, *p_Q = nullptr, *p_K = nullptr, *p_V = nullptr, *p_a = nullptr;  // fp32 intermediates

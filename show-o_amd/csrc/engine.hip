@@ -194,9 +194,21 @@ static int copy_f32(float* dst, const float* src, int64_t n, int64_t expect, hip
 }
 // GEMM weight: bf16 image; in accuracy mode also the low half (hi + lo = w to 2^-17; hi is the same RNE rounding either way)
 // Precision 2: the layer weights become IEEE-half images (saturating RNE); the lm_head keeps its (hi, lo) bf16 pair (head_rows_split).
+// Precision 3: the fp32 source is quantised per output row (quant.hip) into the int8 image + scales the decode step streams, and the
+// bf16 image becomes bf16(q * scale): every entry point then runs the same quantised model.
+struct Q8Slot { int8_t* q = nullptr; float* scale = nullptr; int64_t N = 0, K = 0; };
 static int cast_w(showo_engine* e, const std::string& key, bf16_t* dst, bf16_t* dst_lo, const float* src, int64_t n, int64_t expect, hipStream_t s,
-                  bool is_head = false) {
+                  bool is_head = false, Q8Slot q8 = Q8Slot()) {
     if (n != expect) return set_error_msg(2, "engine_load: element count mismatch");
+    if (e->precision == 3) {
+        if (!q8.q || q8.N * q8.K != n) return set_error_msg(4, "engine_load (precision 3): the int8 images are missing (showo_engine_set_precision(e, 3) makes them)");
+        if (!is_head) e->img_f16 = false;
+        e->q8_loaded.erase(key);
+        TRY(showo::q8_quantize_rows(src, q8.N, q8.K, q8.q, q8.scale, e->q8_flags, s));
+        TRY(showo::q8_dequant_bf16(q8.q, q8.scale, q8.N, q8.K, dst, s));
+        e->q8_loaded.insert(key);
+        return 0;
+    }
     if ((e->precision == 1 || (e->precision == 2 && is_head)) && dst_lo) {
         if (!is_head) e->img_f16 = false;  // the hi half is a bf16 image (a precision-2 engine switched to 1 must not keep the fp16 flag)
         int rc = showo_split_f32_bf16(src, dst, dst_lo, n, s);
@@ -207,6 +219,37 @@ static int cast_w(showo_engine* e, const std::string& key, bf16_t* dst, bf16_t* 
     return showo_cast_f32_op16(src, dst, n, (e->precision == 2 && !is_head) ? SHOWO_OP_F16 : SHOWO_OP_BF16, s);
 }
 
+// The seven GEMM weight kinds (q/k/v_proj, dense, fc1, fc2 of a block; lm_head): where their images live.  q8.N / q8.K are always set;
+// q8.q / q8.scale once precision 3 has allocated the int8 images.
+static bool gemm_weight_slot(showo_engine* e, const char* key, bf16_t** dst, bf16_t** dst_lo, Q8Slot* q8, bool* is_head) {
+    const int64_t H = e->H, F = e->F, V = e->V;
+    *is_head = false;
+    if (!strcmp(key, "showo.lm_head.weight")) {
+        *dst = e->wlm; *dst_lo = e->wlm_lo; *is_head = true;
+        *q8 = Q8Slot{e->qlm, e->slm, V, H};
+        return true;
+    }
+    int li = -1;
+    char sub[128];
+    if (sscanf(key, "showo.model.layers.%d.%127s", &li, sub) != 2 || li < 0 || li >= e->nL) return false;
+    showo::Layer& l = e->layers[li];
+    const std::string t(sub);
+    int j = t == "self_attn.q_proj.weight" ? 0 : t == "self_attn.k_proj.weight" ? 1 : t == "self_attn.v_proj.weight" ? 2 : -1;
+    if (j >= 0) {  // three tensors stacked in wqkv; their int8 rows and scales stack the same way
+        *dst = l.wqkv + j * H * H; *dst_lo = l.wqkv_lo ? l.wqkv_lo + j * H * H : nullptr;
+        *q8 = Q8Slot{l.qqkv ? l.qqkv + j * H * H : nullptr, l.sqkv ? l.sqkv + j * H : nullptr, H, H};
+    } else if (t == "self_attn.dense.weight") {
+        *dst = l.wd; *dst_lo = l.wd_lo; *q8 = Q8Slot{l.qd, l.sd, H, H};
+    } else if (t == "mlp.fc1.weight") {
+        *dst = l.w1; *dst_lo = l.w1_lo; *q8 = Q8Slot{l.q1, l.s1, F, H};
+    } else if (t == "mlp.fc2.weight") {
+        *dst = l.w2; *dst_lo = l.w2_lo; *q8 = Q8Slot{l.q2, l.s2, H, F};
+    } else {
+        return false;
+    }
+    return true;
+}
+
 extern "C" int showo_engine_load(showo_engine* e, const char* key, const float* src, int64_t n, void* stream) {
     if (!e || !key || !src) return set_error_msg(1, "engine_load: null argument");
     hipStream_t s = (hipStream_t)stream;
@@ -215,31 +258,28 @@ extern "C" int showo_engine_load(showo_engine* e, const char* key, const float* 
     int rc = -1;
     int li = -1;
     char sub[128];
-    if (k == "showo.model.embed_tokens.weight") rc = copy_f32(e->embed, src, n, V * H, s);
+    bf16_t *gdst = nullptr, *gdst_lo = nullptr;
+    Q8Slot q8;
+    bool is_head = false;
+    if (gemm_weight_slot(e, key, &gdst, &gdst_lo, &q8, &is_head)) rc = cast_w(e, k, gdst, gdst_lo, src, n, q8.N * q8.K, s, is_head, q8);
+    else if (k == "showo.model.embed_tokens.weight") rc = copy_f32(e->embed, src, n, V * H, s);
     else if (k == "showo.model.final_layernorm.weight") rc = copy_f32(e->fln_w, src, n, H, s);
     else if (k == "showo.model.final_layernorm.bias") rc = copy_f32(e->fln_b, src, n, H, s);
-    else if (k == "showo.lm_head.weight") rc = cast_w(e, k, e->wlm, e->wlm_lo, src, n, V * H, s, true);
     else if (k == "showo.lm_head.bias") rc = copy_f32(e->blm, src, n, V, s);
     else if (k == "rope.cos") rc = copy_f32(e->cosT, src, n, (int64_t)e->cfg.max_pos * e->cfg.rotary_dim, s);
     else if (k == "rope.sin") rc = copy_f32(e->sinT, src, n, (int64_t)e->cfg.max_pos * e->cfg.rotary_dim, s);
     else if (sscanf(key, "showo.model.layers.%d.%127s", &li, sub) == 2 && li >= 0 && li < e->nL) {
         showo::Layer& l = e->layers[li];
         std::string t(sub);
-        if (t == "self_attn.q_proj.weight") rc = cast_w(e, k, l.wqkv, l.wqkv_lo, src, n, H * H, s);
-        else if (t == "self_attn.k_proj.weight") rc = cast_w(e, k, l.wqkv + H * H, l.wqkv_lo ? l.wqkv_lo + H * H : nullptr, src, n, H * H, s);
-        else if (t == "self_attn.v_proj.weight") rc = cast_w(e, k, l.wqkv + 2 * H * H, l.wqkv_lo ? l.wqkv_lo + 2 * H * H : nullptr, src, n, H * H, s);
-        else if (t == "self_attn.q_proj.bias") rc = copy_f32(l.bqkv, src, n, H, s);
+        if (t == "self_attn.q_proj.bias") rc = copy_f32(l.bqkv, src, n, H, s);
         else if (t == "self_attn.k_proj.bias") rc = copy_f32(l.bqkv + H, src, n, H, s);
         else if (t == "self_attn.v_proj.bias") rc = copy_f32(l.bqkv + 2 * H, src, n, H, s);
-        else if (t == "self_attn.dense.weight") rc = cast_w(e, k, l.wd, l.wd_lo, src, n, H * H, s);
         else if (t == "self_attn.dense.bias") rc = copy_f32(l.bd, src, n, H, s);
         else if (t == "self_attn.q_layernorm.weight") rc = copy_f32(l.qln_w, src, n, 64, s);
         else if (t == "self_attn.q_layernorm.bias") rc = copy_f32(l.qln_b, src, n, 64, s);
         else if (t == "self_attn.k_layernorm.weight") rc = copy_f32(l.kln_w, src, n, 64, s);
         else if (t == "self_attn.k_layernorm.bias") rc = copy_f32(l.kln_b, src, n, 64, s);
-        else if (t == "mlp.fc1.weight") rc = cast_w(e, k, l.w1, l.w1_lo, src, n, F * H, s);
         else if (t == "mlp.fc1.bias") rc = copy_f32(l.b1, src, n, F, s);
-        else if (t == "mlp.fc2.weight") rc = cast_w(e, k, l.w2, l.w2_lo, src, n, H * F, s);
         else if (t == "mlp.fc2.bias") rc = copy_f32(l.b2, src, n, H, s);
         else if (t == "input_layernorm.weight") rc = copy_f32(l.ln_w, src, n, H, s);
         else if (t == "input_layernorm.bias") rc = copy_f32(l.ln_b, src, n, H, s);
@@ -252,6 +292,30 @@ extern "C" int showo_engine_load(showo_engine* e, const char* key, const float* 
     e->px3_valid = false;
     e->head3_valid = false;
     return rc;
+}
+
+extern "C" int showo_engine_load_q8(showo_engine* e, const char* key, const int8_t* q, const float* scale, int64_t N, int64_t K, void* stream) {
+    if (!e || !key || !q || !scale) return set_error_msg(1, "engine_load_q8: null argument");
+    if (e->precision != 3) return set_error_msg(1, "engine_load_q8: int8 images exist under precision 3 only (showo_engine_set_precision(e, 3) first)");
+    hipStream_t s = (hipStream_t)stream;
+    bf16_t *dst = nullptr, *dst_lo = nullptr;
+    Q8Slot q8;
+    bool is_head = false;
+    if (!gemm_weight_slot(e, key, &dst, &dst_lo, &q8, &is_head)) return set_error_msg(3, "engine_load_q8: not a GEMM weight key");
+    if (N != q8.N || K != q8.K) return set_error_msg(2, "engine_load_q8: shape mismatch");
+    if (!q8.q) return set_error_msg(4, "engine_load_q8: the int8 images are missing");
+    TRY(showo::q8_validate(q, scale, N, K, e->q8_flags, s));
+    e->q8_loaded.erase(key);
+    SHOWO_CHECK_HIP(hipMemcpyAsync(q8.q, q, (size_t)(N * K), hipMemcpyDeviceToDevice, s));
+    SHOWO_CHECK_HIP(hipMemcpyAsync(q8.scale, scale, (size_t)N * sizeof(float), hipMemcpyDeviceToDevice, s));
+    TRY(showo::q8_dequant_bf16(q8.q, q8.scale, N, K, dst, s));
+    if (!is_head) e->img_f16 = false;
+    e->q8_loaded.insert(key);
+    e->loaded.insert(key);
+    if (uint64_t* v = showo::engine_version(e, key)) *v = ++e->clock;  // same bookkeeping as showo_engine_load
+    e->px3_valid = false;
+    e->head3_valid = false;
+    return 0;
 }
 
 // Destination of a state-dict tensor inside the engine, without copying: bf16 weight image OR fp32 vector (exactly one is set).
@@ -303,6 +367,7 @@ extern "C" int showo_engine_weights_touched(showo_engine* e) {
     e->head3_valid = false;
     e->lo_loaded.clear();  // the hi images were rewritten without their low halves: accuracy mode needs a re-upload
     e->img_f16 = false;    // the trainer writes bf16 images: a precision-2 engine needs a re-upload too (run_layers checks)
+    e->q8_loaded.clear();  // ... and the int8 images of precision 3 no longer match them
     return 0;
 }
 
@@ -510,7 +575,31 @@ static bool precise_fast_shape_ok(const showo_engine* e) {
 static bool precise_fast_ok(const showo_engine* e) { return precise_fast_shape_ok(e) && e->p_h3 != nullptr; }
 extern "C" int showo_engine_set_precision(showo_engine* e, int precision) {
     if (!e) return set_error_msg(1, "engine: null handle");
-    if (precision < 0 || precision > 2) return set_error_msg(1, "engine_set_precision: 0 = bf16 operands, 1 = split bf16 (fp32-class), 2 = fp16 operands");
+    if (precision < 0 || precision > 3)
+        return set_error_msg(1, "engine_set_precision: 0 = bf16 operands, 1 = split bf16 (fp32-class), 2 = fp16 operands, 3 = int8 decode weights");
+    if (precision == 3) {
+        // the int8 rows are read by the fused decode step alone: without it the mode would silently be precision 0 on rounded weights
+        if (!showo::decode_fused_shapes_ok(e->H, e->F) || e->H % 16 || e->F % 16)
+            return set_error_msg(1, "engine_set_precision(3): the int8 decode needs hidden <= 2048 and ffn <= 8192, both multiples of 16");
+        if (!e->qlm) {  // int8 images + row scales, allocated on first use: 1 byte per GEMM weight next to the bf16 images
+            const int64_t H = e->H, F = e->F, V = e->V;
+            int rc = 0;
+            for (auto& l : e->layers) {
+                rc |= e->alloc(&l.qqkv, (3 * H + F) * H); rc |= e->alloc(&l.sqkv, 3 * H + F);
+                if (!rc) { l.q1 = l.qqkv + 3 * H * H; l.s1 = l.sqkv + 3 * H; }
+                rc |= e->alloc(&l.qd, H * H); rc |= e->alloc(&l.sd, H);
+                rc |= e->alloc(&l.q2, H * F); rc |= e->alloc(&l.s2, H);
+            }
+            rc |= e->alloc(&e->slm, V);
+            if (!e->q8_flags) rc |= e->alloc(&e->q8_flags, 2);
+            if (!rc) rc |= e->alloc(&e->qlm, V * H);
+            if (rc) {
+                for (auto& l : e->layers) { e->release(&l.qqkv); e->release(&l.sqkv); e->release(&l.qd); e->release(&l.sd); e->release(&l.q2); e->release(&l.s2); l.q1 = nullptr; l.s1 = nullptr; }
+                e->release(&e->slm); e->release(&e->qlm);
+                return rc;
+            }
+        }
+    }
     if (precision == 2 && !e->wlm3) {  // the lm_head of precision 2 is a split-bf16 product: its low half, [hi | hi | lo] image and LayerNorm workspace
         const int64_t H = e->H, V = e->V, T = e->maxT;
         int rc = 0;
@@ -520,9 +609,11 @@ extern "C" int showo_engine_set_precision(showo_engine* e, int precision) {
         if (rc) { e->release(&e->wlm3); return rc; }
         e->head3_valid = false;
     }
-    if ((precision == 2) != (e->precision == 2)) {
-        // the layer weight images change their element type: un-load every GEMM weight so that the host uploads them again
-        // (showo_engine_missing() > 0 until it has); cached t2i graphs are keyed on the precision and simply miss
+    // what the GEMM weight images hold: bf16(w) (precision 0 / 1), fp16(w) (2), bf16 of the int8-dequantised w (3)
+    auto img_class = [](int p) { return p == 2 ? 2 : p == 3 ? 3 : 0; };
+    if (img_class(precision) != img_class(e->precision)) {
+        // the layer weight images change their element type or their values: un-load every GEMM weight so that the host uploads them
+        // again (showo_engine_missing() > 0 until it has); cached t2i graphs are keyed on the precision and simply miss
         for (auto it = e->loaded.begin(); it != e->loaded.end();) {
             const std::string& k = *it;
             const bool gemm_w = k.size() > 7 && k.compare(k.size() - 7, 7, ".weight") == 0 &&
@@ -531,6 +622,7 @@ extern "C" int showo_engine_set_precision(showo_engine* e, int precision) {
             if (gemm_w) it = e->loaded.erase(it); else ++it;
         }
         e->lo_loaded.clear();
+        e->q8_loaded.clear();
         showo::engine_bump_all(e); e->px3_valid = false; e->head3_valid = false;
     }
     if (precision == 1 && !e->p_hlo) {  // low halves of every GEMM weight + fp32 workspaces, allocated on first use
@@ -739,9 +831,18 @@ static int run_layers(showo_engine* e, int B, int L, int pos0, const KVDest& kv,
     if ((op == SHOWO_OP_F16) != e->img_f16)
         return set_error_msg(4, "engine: the weight images hold the other 16-bit type (loaded under another precision, or rewritten by the "
                                 "trainer): upload the weights again");
+    // precision 3: bf16 operands on the images of the dequantised weights; the fused decode step below streams the int8 images instead
+    const bool q8 = e->precision == 3;
+    if (q8 && (int)e->q8_loaded.size() != e->nL * 6 + 1)
+        return set_error_msg(4, "engine (precision 3): the int8 weight images are missing or stale (the weights were loaded before "
+                                "showo_engine_set_precision(e, 3), or rewritten by the trainer): upload the weights again");
     TRY(collect_x(e, 0, T, s));
     const int Lk = pos0 + L;
     const int Lcap = kv.Lcap, Lp = kv.Lp;
+    // a decode step that the fused layer cannot take would be served from the bf16 images at 2 bytes per weight: refused, not silent
+    // (showo_decode_set_impl(1) asks for that layer explicitly; a one-token forward with a dense mask is not a decode step)
+    if (q8 && T == 1 && showo::g_decode_impl == 0 && !dense && (size_t)Lcap * 4 + 2048 > 60000)
+        return set_error_msg(5, "engine (precision 3): the int8 decode step serves KV caches of up to 14 488 tokens");
     // (the fused three-launch decode layer of decode.hip has instances for both operand types since round 6)
     if (T == 1 && showo::g_decode_impl == 0 && !dense && showo::decode_fused_shapes_ok(H, F) && (size_t)Lcap * 4 + 2048 <= 60000) {
         // AR decode step (decode.hip): three launches per layer.  Co-scheduled layer (default): the attention launch carries extra
@@ -766,6 +867,24 @@ static int run_layers(showo_engine* e, int B, int L, int pos0, const KVDest& kv,
             showo::Layer& l = e->layers[li];
             bf16_t* Kd = kv.k + li * kv.k_lstride;
             bf16_t* Vd = kv.vt + li * kv.v_lstride;
+            if (q8) {
+                // the same three launches on the int8 images (pointers travel as bf16_t*; the row scales select the int8 instances).
+                // No prefetch role: it would read ahead in the bf16 images, which these launches never stream.
+                const bf16_t *Wqkv = reinterpret_cast<const bf16_t*>(l.qqkv), *W1 = reinterpret_cast<const bf16_t*>(l.q1),
+                             *Wd = reinterpret_cast<const bf16_t*>(l.qd), *W2 = reinterpret_cast<const bf16_t*>(l.q2);
+                TRY(showo::decode_ln_gemv2(e->x, l.ln_w, l.ln_b, e->cfg.ln_eps, H, Wqkv, l.bqkv, e->qkv, nullptr, 3 * H, W1, l.b1, e->ffn, F, s, 0,
+                                           l.sqkv, l.s1));
+                if (co) {
+                    TRY(showo::attn_decode_fused(e->qkv, l.qln_w, l.qln_b, l.kln_w, l.kln_b, e->cosT, e->sinT, Kd, Vd, iv, e->attn, nH,
+                                                 e->cfg.rotary_dim, e->cfg.ln_eps, pos0, Lcap, Lp, s, W2, e->ffn, l.b2, F, H, e->y2, co_blocks, nullptr, 0, l.s2));
+                    TRY(showo::decode_out_gemv2(e->x, Wd, e->attn, l.bd, H, W2, e->ffn, l.b2, F, H, s, 2, e->y2, 0, l.sd, l.s2));
+                } else {
+                    TRY(showo::attn_decode_fused(e->qkv, l.qln_w, l.qln_b, l.kln_w, l.kln_b, e->cosT, e->sinT, Kd, Vd, iv, e->attn, nH,
+                                                 e->cfg.rotary_dim, e->cfg.ln_eps, pos0, Lcap, Lp, s, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, nullptr, 0));
+                    TRY(showo::decode_out_gemv2(e->x, Wd, e->attn, l.bd, H, W2, e->ffn, l.b2, F, H, s, 0, nullptr, 0, l.sd, l.s2));
+                }
+                continue;
+            }
             if (co) {
                 TRY(showo::decode_ln_gemv2(e->x, l.ln_w, l.ln_b, e->cfg.ln_eps, H, l.wqkv, l.bqkv, e->qkv, nullptr, 3 * H, l.w1, l.b1,
                                            e->ffn, F, s, op));
@@ -881,6 +1000,13 @@ static int head_rows(showo_engine* e, const int32_t* rows, int nrows, int col0, 
                                             e->wlm_lo + (int64_t)col0 * e->H, e->blm + col0, logits, ncols, ncols, 1, s);
         return head_rows_precise_fast(e, rows, nrows, col0, ncols, logits, s);  // (any shape)
     }
+    if (e->precision == 3 && nrows == 1 && !rows && showo::g_decode_impl == 0 && showo::decode_fused_shapes_ok(e->H, e->F)) {
+        // decode step under precision 3: the same launch on the int8 image of the lm_head
+        if (!e->q8_loaded.count("showo.lm_head.weight"))
+            return set_error_msg(4, "engine (precision 3): the int8 image of the lm_head is missing or stale: upload the weights again");
+        return showo::decode_ln_gemv2(e->x, e->fln_w, e->fln_b, e->cfg.ln_eps, e->H, reinterpret_cast<const bf16_t*>(e->qlm + (int64_t)col0 * e->H),
+                                      e->blm + col0, nullptr, logits, ncols, nullptr, nullptr, nullptr, 0, s, 0, e->slm + col0, nullptr);
+    }
     if (nrows == 1 && !rows && showo::g_decode_impl == 0 && showo::decode_fused_shapes_ok(e->H, e->F))  // decode step: LN + lm_head in one launch
         return showo::decode_ln_gemv2(e->x, e->fln_w, e->fln_b, e->cfg.ln_eps, e->H, e->wlm + (int64_t)col0 * e->H, e->blm + col0,
                                       nullptr, logits, ncols, nullptr, nullptr, nullptr, 0, s);
@@ -944,7 +1070,7 @@ extern "C" int showo_engine_t2i_generate(showo_engine* e, int64_t* ids_cond, int
     const int La = L - prefix;
     const int LpC = ((L + 63) / 64) * 64;
     const bool pfast = e->precision == 1 && precise_fast_ok(e);
-    const bool reuse_ok = (e->precision == 0 || e->precision == 2 || pfast) && !(use_graph & 2) && steps > 1 && prefix >= 1 && La >= N + 1 && nseq * La >= 1;
+    const bool reuse_ok = (e->precision == 0 || e->precision == 2 || e->precision == 3 || pfast) && !(use_graph & 2) && steps > 1 && prefix >= 1 && La >= N + 1 && nseq * La >= 1;
     hipStreamCaptureStatus cs0 = hipStreamCaptureStatusNone;
     hipStreamIsCapturing(s, &cs0);
     if (cs0 != hipStreamCaptureStatusNone) return set_error_msg(7, "t2i_generate: the call captures its own graph; do not call it inside a stream capture");
@@ -1023,7 +1149,7 @@ extern "C" int showo_engine_t2i_generate(showo_engine* e, int64_t* ids_cond, int
     const int n_eager = reuse ? 2 : 1;
     // A registered range-check counter forces the eager path: its launches (and the caller's counter pointer) must not be baked into a
     // cached graph that later plain calls replay, and a replayed cached graph would skip them.
-    const bool graph = (use_graph & 1) && steps > n_eager && !showo::g_prof_on_query() && (e->precision == 0 || e->precision == 2 || pfast) &&
+    const bool graph = (use_graph & 1) && steps > n_eager && !showo::g_prof_on_query() && (e->precision == 0 || e->precision == 2 || e->precision == 3 || pfast) &&
                        !(e->range_count && e->precision == 2);
     if (!graph) {
         for (int step = 0; step < steps; ++step) TRY(denoise_step(step, step == 0 || !reuse));

@@ -395,6 +395,9 @@ static int train_forward_impl(showo_trainer* t, const int64_t* ids, const float*
     if (e->img_f16 || e->precision == 2)
         return set_error_msg(4, "train: the engine's weight images hold fp16 (precision 2); training runs on bf16 images -- "
                                 "showo_engine_set_precision(e, 0) and upload the weights again");
+    if (e->precision == 3)
+        return set_error_msg(4, "train: the engine's weight images hold the int8-dequantised weights (precision 3); training runs on the "
+                                "bf16 images of the masters -- showo_engine_set_precision(e, 0) and upload the weights again");
     TRY(sync_weights(t, s));
     TRY(plan_sync(t, s));
     const int H = e->H, F = e->F, V = e->V, nH = e->nH, T = B * L;

@@ -525,9 +525,18 @@ class Showo(PretrainedMixin, nn.Module):
         precision 1: logits within 1e-3 of the reference's fp32 inference (rel_rms ~8e-4 at model scale where bf16 operands give
         7e-3) at the speed of the default path.  Converts saturate at +-65504 (`range_check()` counts saturated activations);
         the KV-cached decode steps run the fp16 instances of the fused three-launch layer and of the batched layer (csrc/decode.hip, decode_batch.hip; the lm_head of a decode step is one fused LayerNorm + (hi, lo) GEMV launch), the
-        mm_projector runs in its fp32-class mode (it is one small MLP).  Switching to / from 2 re-uploads the weight images."""
-        if int(precision) not in (0, 1, 2):
-            raise ValueError("precision must be 0 (bf16 operands), 1 (split-bf16, fp32-class) or 2 (fp16 operands)")
+        mm_projector runs in its fp32-class mode (it is one small MLP).  Switching to / from 2 re-uploads the weight images.
+        3: int8 decode -- the one mode that trades accuracy for speed, so it is opt-in.  Every GEMM weight (q/k/v_proj, dense, fc1,
+        fc2 of the blocks, lm_head) is quantised per output row to int8 with an fp32 scale amax / 127 (`showo_amd.quantization`); the
+        model IS that quantised model on every entry point (prefill, forward, t2i_generate run bf16 operands on bf16(q * scale)), and
+        the KV-cached decode steps of mmu_generate stream the int8 images: half the weight bytes per token (csrc/decode.hip, Q8
+        instances; int8 converts exactly to bf16, one extra fp32 multiply by the row scale per output).  Cost in accuracy: logits
+        rel_rms ~2.6e-2 against the unquantised fp32 model on seeded full-size weights (bf16 operands alone: 5e-3), see README.
+        Cost in memory: + 1 byte per GEMM weight (1.45 GB at model scale) next to the bf16 images.  mmu_generate_batch runs the int8
+        instances of the batched kernels (every sequence bit-identical to its batch-1 run).  Needs hidden <= 2048 and ffn <= 8192, multiples of 16 (the
+        engine refuses other shapes).  Training maps 3 to 0 like 2; switching to / from 3 re-uploads (re-quantises) the weights."""
+        if int(precision) not in (0, 1, 2, 3):
+            raise ValueError("precision must be 0 (bf16 operands), 1 (split-bf16, fp32-class), 2 (fp16 operands) or 3 (int8 decode weights)")
         self._precision = int(precision)
         if self.__dict__.get("_modules", {}).get("mm_projector") is not None:
             self.mm_projector.set_precision(1 if int(precision) else 0)
@@ -620,7 +629,8 @@ class Showo(PretrainedMixin, nn.Module):
 
     def engine(self, for_training=False):
         """Create the HIP engine if needed and (re)upload weights whose version changed.  for_training: the trainer works on bf16
-        weight images, so a model in precision 2 (fp16 images) trains on a precision-0 engine (and re-uploads on the way back)."""
+        weight images, so a model in precision 2 (fp16 images) or 3 (images of the int8-dequantised weights) trains on a precision-0
+        engine (and re-uploads on the way back)."""
         _lib.require_gpu()
         lib = _lib.load()
         dev = self.showo.lm_head.weight.device
@@ -643,14 +653,14 @@ class Showo(PretrainedMixin, nn.Module):
             _lib.call("showo_engine_load", self._engine, b"rope.sin", _lib.ptr(sin), sin.numel(), _lib.stream())
             torch.cuda.current_stream().synchronize()
         want = int(getattr(self, "_precision", 0))
-        if for_training and want == 2:
+        if for_training and want in (2, 3):  # the trainer works on the bf16 images of the fp32 masters
             want = 0
         if lib.showo_engine_get_precision(self._engine) != want:
             _lib.call("showo_engine_set_precision", self._engine, want)
         if want == 1 and not lib.showo_engine_precise_ready(self._engine):
             self._engine_versions = {}  # the low halves of the weights are made by the loader: upload everything again
         if lib.showo_engine_missing(self._engine):
-            self._engine_versions = {}  # first use, or the weight images changed their element type (precision 2 <-> 0 / 1)
+            self._engine_versions = {}  # first use, or the weight images changed their element type / values (precision 2 or 3 <-> others)
         for k, v in self._engine_params():
             ver = (v.data_ptr(), v._version)
             if self._engine_versions.get(k) != ver:
@@ -982,7 +992,7 @@ def mmu_generate_batch(self, idx=None, input_embeddings=None, attention_mask=Non
 
     Returns a list of n token lists: result[b] is what `mmu_generate(<sequence b>, attention_mask=masks[b], max_new_tokens,
     temperature[b], top_k[b], eot_token, generator=generator, _exp_noise=_exp_noise[b])` returns when those calls are made in order
-    b = 0, 1, ..., n-1 (the same seeds are drawn from `generator`, or torch's global generator, in the same order).  At precision 0 and 2
+    b = 0, 1, ..., n-1 (the same seeds are drawn from `generator`, or torch's global generator, in the same order).  At precision 0, 2 and 3
     every n >= 2 runs on the batched engine path (csrc/decode_batch.hip: one weight stream per token step for all slots, every sequence
     bit-identical to its batch-1 run): all-greedy batches of 2..8 on showo_engine_batch_decode_greedy, anything else on up to 8 slots
     of showo_engine_batch_decode_sample that are refilled as sequences finish.  Precision 1 and n < 2 make the sequential calls."""
