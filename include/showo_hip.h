@@ -487,6 +487,13 @@ int showo_engine_missing(const showo_engine* e);
 /* number of times showo_engine_t2i_generate captured a denoise step into a hipGraph on this engine (the instantiated graph is
  * cached: identical calls replay it without capturing again) */
 int showo_engine_t2i_captures(const showo_engine* e);
+/* what step 0 of the last showo_engine_t2i_generate call ran: out[0] sequences (B + 1 of 2 B when the unconditional sequences of a CFG
+ * call were found identical), out[1] leading rows trimmed from every sequence, out[2] rows run (= out[0] * (L - out[1])), out[3] host
+ * time in microseconds spent waiting for that decision.  Without prefix reuse: all sequences, 0, all rows, 0. */
+int showo_engine_t2i_step0(const showo_engine* e, int* out);
+/* test hooks of showo_engine_t2i_generate.  logits0 (device fp32 [(2)B * num_vq_tokens, codebook], or NULL): receives the logit rows of
+ * step 0.  poison_kv != 0: the batch-wide K cache is filled with NaN bit patterns at the start of every call. */
+int showo_engine_t2i_debug(showo_engine* e, float* logits0, int poison_kv);
 /* parity hook: while buf != NULL every forward copies the fp32 residual stream into buf fp32 [layers + 1, B*L, hidden] (slot 0 = the
  * embedded input, slot i = output of transformer block i - 1), so that a test can check each block against the oracle evaluated on
  * the block's own input as the GPU computed it (no error amplification across blocks). */
@@ -554,7 +561,9 @@ int showo_engine_forward_rows(showo_engine* e, const int64_t* ids, const float* 
  * reference; ids_uncond may be NULL (no CFG).  mask fp32 [(2)B,1,L,L].  mask_len_host/temps_host: per-step
  * host constants (floor(N*schedule((k+1)/T)) and the compounding temperature).  use_graph: bit 0 = capture one
  * denoise step into a hipGraph and replay it; bit 1 = do NOT reuse the step-invariant text rows (by default step 0 runs
- * the whole sequence and leaves every layer's K / V^T in a cache, later steps run only the rows from <soi> on).  Optional injected noise (tests): exp_noise [steps,B*N,V],
+ * the whole sequence and leaves every layer's K / V^T in a cache, later steps run only the rows from <soi> on); bit 2 = do NOT reduce
+ * step 0 (by default, with reuse, it skips the leading rows that no later row can see and runs identical unconditional sequences once;
+ * the host waits once, before step 0, for that decision).  Optional injected noise (tests): exp_noise [steps,B*N,V],
  * uniform [steps,B,N].  out sampled int64 [B,N]. */
 int showo_engine_t2i_generate(showo_engine* e, int64_t* ids_cond, int64_t* ids_uncond, const float* mask, int B, int L,
                               int num_vq_tokens, int text_len, int64_t mask_id, int id_offset, int codebook,

@@ -140,6 +140,8 @@ _PROTOS = {
     "showo_engine_weights_touched": [c_p],
     "showo_engine_missing": [c_p],
     "showo_engine_t2i_captures": [c_p],
+    "showo_engine_t2i_step0": [c_p, c_p],
+    "showo_engine_t2i_debug": [c_p, c_p, c_i],
     "showo_engine_set_collect": [c_p, c_p],
     "showo_engine_set_precision": [c_p, c_i],
     "showo_engine_get_precision": [c_p],

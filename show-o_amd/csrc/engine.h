@@ -37,6 +37,7 @@ struct Layer {
 struct showo_engine;
 namespace showo {
 void sampler_set_device_step(const int* step_dev, const float* sched, int steps);
+void gemm_pin_split_m(int M);  // gemm2p.hip (documented in gemm_common.h): split-K count of this thread's GEMM launches taken from M rows; 0 = off
 int sampler_step_inc(int* step_dev, hipStream_t s);
 void attn_set_decode_pos(const int* p, int lk_max = 0);
 int sample_topk_launch(const float* logits, int V, int top_k, float temperature, const float* exp_noise, int64_t noise_stride,
@@ -207,6 +208,9 @@ struct showo_engine {
     BatchDecode* bd = nullptr;
     float* collect = nullptr;  // parity hook (showo_engine_set_collect)
     int t2i_captures = 0;  // how often a denoise step was captured (tests: a second identical call must not capture again)
+    int t2i_step0[4] = {0, 0, 0, 0};  // last t2i_generate call: sequences / rows trimmed / rows run in step 0, host wait in us (showo_engine_t2i_step0)
+    float* t2i_logits0 = nullptr;     // test hooks (showo_engine_t2i_debug): step-0 logits go here; NaN-fill the K cache per call
+    bool t2i_poison = false;
     int* step_dev = nullptr;
     float* sched_dev = nullptr;
     int sched_cap = 0;

@@ -16,6 +16,7 @@
 #include "engine.h"
 #include "decode_common.h"
 #include <algorithm>
+#include <chrono>
 #include <cstdio>
 #include <vector>
 #include <cstring>
@@ -86,6 +87,78 @@ __global__ void prefix_check_kernel(const int32_t* __restrict__ iv, const int32_
     if (v.z < v.w) hi = max(hi, v.w);
     if (hi > prefix) atomicOr(out, 1);
 }
+// ---- t2i reduced step 0: which rows of the full step does the result need?  One block per sequence b.
+//   p_b = the largest p <= prefix such that no row r >= p of the sequence sees a column < p (rows [p_b, L) are closed under "sees"; both
+//         intervals of a row count).  With left padding that is the pad count: text and image rows never see a pad column.
+//   out[2] / out[3] = max over the sequences [0, first] / (first, nseq) of prefix - p_b  (the uniform trim is the smallest p_b)
+//   out[1] |= 1  when an unconditional sequence first+1 .. nseq-1 differs from sequence `first` in an id or an interval row (first > 0:
+//                CFG call), or when the mask is not an interval mask (then also p = 0)
+// (out[0] belongs to prefix_check_kernel; all four ints are zeroed before the two launches.)
+__global__ void step0_plan_kernel(const int64_t* __restrict__ ids, const int32_t* __restrict__ iv, const int32_t* __restrict__ mask_flag,
+                                  int32_t* __restrict__ out, int first, int nseq, int L, int prefix) {
+    __shared__ int s_min[256];
+    __shared__ int s_best;
+    const int b = blockIdx.x, t = threadIdx.x;
+    const int4* row = reinterpret_cast<const int4*>(iv) + (int64_t)b * L;
+    auto lo_of = [&](int r) {  // first column row r sees (INT_MAX: none)
+        const int4 v = row[r];
+        int lo = 0x7fffffff;
+        if (v.x < v.y) lo = min(lo, v.x);
+        if (v.z < v.w) lo = min(lo, v.z);
+        return lo;
+    };
+    const int chunk = (L + 255) / 256, r0 = min(L, t * chunk), r1 = min(L, r0 + chunk);
+    int m = 0x7fffffff;
+    for (int r = r0; r < r1; ++r) m = min(m, lo_of(r));
+    s_min[t] = m;
+    if (t == 0) s_best = 0;
+    __syncthreads();
+    m = 0x7fffffff;  // min over the rows behind this thread's chunk
+    for (int j = t + 1; j < 256; ++j) m = min(m, s_min[j]);
+    for (int r = r1 - 1; r >= r0; --r) {
+        m = min(m, lo_of(r));
+        if (r <= prefix && m >= r) { atomicMax(&s_best, r); break; }
+    }
+    __syncthreads();
+    if (t == 0) {
+        atomicMax(out + (b <= first ? 2 : 3), prefix - s_best);
+        if (b == 0 && mask_flag && *mask_flag) { atomicOr(out + 1, 1); atomicMax(out + 2, prefix); }
+    }
+    if (first > 0 && b > first) {
+        const int64_t *ia = ids + (int64_t)first * L, *ib = ids + (int64_t)b * L;
+        const int4* ra = reinterpret_cast<const int4*>(iv) + (int64_t)first * L;
+        bool diff = false;
+        for (int r = t; r < L; r += 256) {
+            const int4 u = ra[r], v = row[r];
+            diff |= ia[r] != ib[r] || u.x != v.x || u.y != v.y || u.z != v.z || u.w != v.w;
+        }
+        if (diff) atomicOr(out + 1, 1);
+    }
+}
+// interval rows [p, L) of the first nseq sequences with every interval cut to columns >= p.  A no-op for the rows that are closed under
+// "sees" at p; a pad row of a sequence with more than p pads would otherwise read cache rows < p, which the reduced step 0 never writes.
+// Such a row then computes something else than in the full step, but nothing that is used can see it (it lies before its sequence's p_b).
+__global__ void gather_iv_cut_kernel(const int32_t* __restrict__ iv, int32_t* __restrict__ act, int nseq, int L, int p) {
+    const int La = L - p;
+    int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nseq * La) return;
+    int b = i / La, j = i - b * La;
+    int4 v = reinterpret_cast<const int4*>(iv)[(int64_t)b * L + p + j];
+    v.x = max(v.x, p); v.z = max(v.z, p);
+    reinterpret_cast<int4*>(act)[i] = v;
+}
+// Copies `len` units at `off` of every (layer, inner) chunk of one sequence to the same place of the next `ndst` sequences:
+// chunk (li, h) starts at base + li * lstride + h * istride, sequences are seq_stride apart.  T = uint4 wherever the layout allows.
+template <class T>
+__global__ void bcast_seq_kernel(T* __restrict__ base, int64_t lstride, int inner, int64_t istride, int64_t off, int len, int64_t seq_stride,
+                                 int ndst, int64_t total) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int64_t o = i / len, li = o / inner;
+    T* src = base + li * lstride + (o - li * inner) * istride + off + (i - o * len);
+    const T v = *src;
+    for (int d = 1; d <= ndst; ++d) src[d * seq_stride] = v;
+}
 // mask row of the token at position *pos: the last prompt row extended by the columns [L0, pos] (modeling_showo.py:203-217)
 __global__ void decode_iv_kernel(const int32_t* __restrict__ last_iv, int L0, const int* __restrict__ pos, int32_t* __restrict__ iv) {
     if (threadIdx.x != 0) return;
@@ -119,6 +192,25 @@ __global__ void copy_i64_kernel(const int64_t* s, int64_t* d, int n) {
         int _rc = (expr);    \
         if (_rc) return _rc; \
     } while (0)
+
+// bcast_seq_kernel in the widest unit that every stride, offset and length (given in elements of E) is a multiple of
+template <class E>
+static int bcast_seq(E* base, int64_t lstride, int n_layers, int inner, int64_t istride, int64_t off, int64_t len, int64_t seq_stride, int ndst,
+                     hipStream_t s) {
+    if (ndst <= 0 || len <= 0) return 0;
+    constexpr int W = 16 / (int)sizeof(E);
+    const bool wide = !(lstride % W) && !(istride % W) && !(off % W) && !(len % W) && !(seq_stride % W) && !((uintptr_t)base & 15);
+    const int64_t u = wide ? W : 1, total = (int64_t)n_layers * inner * (len / u);
+    if (len / u >= ((int64_t)1 << 31) || (total + 255) / 256 >= ((int64_t)1 << 31)) return set_error_msg(5, "t2i: broadcast too large");
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (wide)
+        bcast_seq_kernel<uint4><<<grid, dim3(256), 0, s>>>(reinterpret_cast<uint4*>(base), lstride / W, inner, istride / W, off / W, (int)(len / W),
+                                                           seq_stride / W, ndst, total);
+    else
+        bcast_seq_kernel<E><<<grid, dim3(256), 0, s>>>(base, lstride, inner, istride, off, (int)len, seq_stride, ndst, total);
+    SHOWO_CHECK_HIP(hipGetLastError());
+    return 0;
+}
 
 extern "C" int showo_engine_create(const showo_engine_config* c, showo_engine** out) {
     if (!c || !out) return set_error_msg(1, "engine_create: null argument");
@@ -183,6 +275,21 @@ extern "C" int showo_engine_set_collect(showo_engine* e, float* buf) {
 }
 
 extern "C" int showo_engine_t2i_captures(const showo_engine* e) { return e ? e->t2i_captures : -1; }
+// what step 0 of the last showo_engine_t2i_generate call ran: sequences, leading rows trimmed, rows (= out[0] * (L - out[1])), and the
+// host time in microseconds spent waiting for that decision
+extern "C" int showo_engine_t2i_step0(const showo_engine* e, int* out) {
+    if (!e || !out) return set_error_msg(1, "engine: null argument");
+    for (int i = 0; i < 4; ++i) out[i] = e->t2i_step0[i];
+    return 0;
+}
+// test hooks of t2i_generate.  logits0 (device, fp32 [nseq * N, codebook], or null): receives the logit rows of step 0.  poison_kv: the
+// batch-wide K cache is filled with NaN bit patterns at the start of every call (rows that no step writes must never reach a result).
+extern "C" int showo_engine_t2i_debug(showo_engine* e, float* logits0, int poison_kv) {
+    if (!e) return set_error_msg(1, "engine: null handle");
+    e->t2i_logits0 = logits0;
+    e->t2i_poison = poison_kv != 0;
+    return 0;
+}
 
 extern "C" int showo_engine_missing(const showo_engine* e) { return e ? e->expected - (int)e->loaded.size() : -1; }
 
@@ -1082,52 +1189,120 @@ extern "C" int showo_engine_t2i_generate(showo_engine* e, int64_t* ids_cond, int
         SHOWO_CHECK_HIP(hipHostMalloc((void**)&e->pfx_host, 64, hipHostMallocDefault));
         SHOWO_CHECK_HIP(hipEventCreateWithFlags(&e->ev_pfx, hipEventDisableTiming));
     }
+    e->t2i_step0[0] = nseq; e->t2i_step0[1] = 0; e->t2i_step0[2] = nseq * L; e->t2i_step0[3] = 0;
     for (int attempt = 0; attempt < 2; ++attempt) {
     const bool reuse = reuse_ok && attempt == 0;
     bool check_pending = false;
+    // ---- reduced step 0 (use_graph bit 2 disables it).  Step 0 only has to leave the prefix K / V^T in the cache and produce the image
+    // rows' logits.  (a) Leading rows that no later row can see (left pads) feed nothing: rows [p0, L) are run, p0 the smallest of the
+    // sequences' own trims (the pad rows that a sequence has beyond p0 run with their intervals cut at p0: nothing that is used sees
+    // them).  (b) In a pure t2i CFG call the unconditional sequences are ONE sequence (empty prompt, all-mask image part): it is run once
+    // and its prefix K / V^T and logit rows are copied to the other B - 1.  Both are decided on the device from the ids and intervals of
+    // THIS call; grid sizes depend on the answer, so the host waits for it here, once, before the first launch of step 0.
+    const bool red = reuse && iv && !(use_graph & 4);
+    int nseq0 = nseq, p0 = 0;
+    bool shared = false;
     build_ids_kernel<<<dim3((B * L + thr - 1) / thr), dim3(thr), 0, s>>>(ids_cond, cfg ? ids_uncond : nullptr, e->ids_all, B, L,
                                                                        text_len + 1);
     init_cur_kernel<<<dim3((B * N + thr - 1) / thr), dim3(thr), 0, s>>>(ids_cond, L, img_start, mask_id, id_offset, e->cur, N, B * N);
     rows_index_kernel<<<dim3((nrows + thr - 1) / thr), dim3(thr), 0, s>>>(e->rows, nseq, L, img_start, N);
     SHOWO_CHECK_HIP(hipGetLastError());
     if (reuse && iv) {
-        SHOWO_CHECK_HIP(hipMemsetAsync(e->pfx_flag, 0, sizeof(int32_t), s));
+        SHOWO_CHECK_HIP(hipMemsetAsync(e->pfx_flag, 0, 4 * sizeof(int32_t), s));
         prefix_check_kernel<<<dim3((nseq * prefix + thr - 1) / thr), dim3(thr), 0, s>>>(iv, flag, e->pfx_flag, nseq, L, prefix);
-        SHOWO_CHECK_HIP(hipMemcpyAsync(e->pfx_host, e->pfx_flag, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        if (red) step0_plan_kernel<<<dim3(nseq), dim3(256), 0, s>>>(e->ids_all, iv, flag, e->pfx_flag, cfg ? B : 0, nseq, L, prefix);
+        SHOWO_CHECK_HIP(hipMemcpyAsync(e->pfx_host, e->pfx_flag, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
         SHOWO_CHECK_HIP(hipEventRecord(e->ev_pfx, s));
         check_pending = true;
     }
+    if (red) {
+        const auto t0 = std::chrono::steady_clock::now();
+        SHOWO_CHECK_HIP(hipEventSynchronize(e->ev_pfx));
+        e->t2i_step0[3] += (int)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+        const volatile int32_t* h = e->pfx_host;
+        if (h[0]) continue;  // the prefix check, read in the same wait: repeat without reuse (and without the optimistic attempt)
+        check_pending = false;
+        shared = cfg && B > 1 && !h[1];
+        const int trim_short = shared ? h[2] : std::max(h[2], h[3]);
+        p0 = std::min(std::max(prefix - trim_short, 0), prefix);
+        nseq0 = shared ? B + 1 : nseq;
+    }
+    const bool reduced = shared || p0 > 0;
+    if (reuse) { e->t2i_step0[0] = nseq0; e->t2i_step0[1] = p0; e->t2i_step0[2] = nseq0 * (L - p0); }
     KVDest kvc = kv_workspace(e, L);
     if (reuse) {
         const int64_t kn = (int64_t)e->nL * nseq * e->nH * L * 64, vn = (int64_t)e->nL * nseq * e->nH * 64 * LpC;
         if (kn > e->tk_cap) { TRY(e->alloc(&e->tk, kn)); e->tk_cap = kn; }
         if (vn > e->tvt_cap) { TRY(e->alloc(&e->tvt, vn)); e->tvt_cap = vn; }
         SHOWO_CHECK_HIP(hipMemsetAsync(e->tvt, 0, (size_t)vn * sizeof(bf16_t), s));  // pad key columns must stay finite
-        if (!e->ids_act) { TRY(e->alloc(&e->ids_act, e->maxT)); TRY(e->alloc(&e->iv_act, e->maxT * 4)); TRY(e->alloc(&e->rows_act, e->maxT)); }
+        // (iv_act / rows_act: the active rows of the later steps, and behind them those of the reduced step 0)
+        if (!e->ids_act) { TRY(e->alloc(&e->ids_act, e->maxT)); TRY(e->alloc(&e->iv_act, e->maxT * 8)); TRY(e->alloc(&e->rows_act, e->maxT * 2)); }
+        if (e->t2i_poison) SHOWO_CHECK_HIP(hipMemsetAsync(e->tk, 0xff, (size_t)kn * sizeof(bf16_t), s));
         if (pfast) {
             if (kn > e->tk_lo_cap) { TRY(e->alloc(&e->tk_lo, kn)); e->tk_lo_cap = kn; }
             if (vn > e->tvt_lo_cap) { TRY(e->alloc(&e->tvt_lo, vn)); e->tvt_lo_cap = vn; }
             SHOWO_CHECK_HIP(hipMemsetAsync(e->tvt_lo, 0, (size_t)vn * sizeof(bf16_t), s));
+            if (e->t2i_poison) SHOWO_CHECK_HIP(hipMemsetAsync(e->tk_lo, 0xff, (size_t)kn * sizeof(bf16_t), s));
         }
         kvc = KVDest{e->tk, e->tvt, (int64_t)nseq * e->nH * L * 64, (int64_t)nseq * e->nH * 64 * LpC, L, LpC, pfast ? e->tk_lo : nullptr,
                      pfast ? e->tvt_lo : nullptr};
         if (iv) gather_iv_kernel<<<dim3((nseq * La + thr - 1) / thr), dim3(thr), 0, s>>>(iv, e->iv_act, nseq, L, prefix);
         rows_index_kernel<<<dim3((nrows + thr - 1) / thr), dim3(thr), 0, s>>>(e->rows_act, nseq, La, img_start - prefix, N);
+        if (reduced) {
+            gather_iv_cut_kernel<<<dim3((nseq0 * (L - p0) + thr - 1) / thr), dim3(thr), 0, s>>>(iv, e->iv_act + e->maxT * 4, nseq0, L, p0);
+            rows_index_kernel<<<dim3((nseq0 * N + thr - 1) / thr), dim3(thr), 0, s>>>(e->rows_act + e->maxT, nseq0, L - p0, img_start - p0, N);
+        }
         SHOWO_CHECK_HIP(hipGetLastError());
     }
+    bool first_step = true;
     // one denoise step (modeling_showo.py:135-179).  step < 0: the step index / schedule constants are read on the device.
     // full: run every row (always in step 0); otherwise only the rows [prefix, L) against the cached prefix keys.
     auto denoise_step = [&](int step, bool full) -> int {
-        if (full) {
+        if (full && reduced) {
+            // rows [p0, L) of the sequences 0 .. nseq0 - 1 through the machinery of the later steps; K / V^T go to their true positions in
+            // the batch-wide cache (cache rows < p0 are never written and never visible: the attention kernel selects masked scores away,
+            // V^T there is zero).  Every GEMM keeps the k-partition of the full-shape launch it replaces (gemm_pin_split_m).
+            const int L0 = L - p0;
+            gather_ids_kernel<<<dim3((nseq0 * L0 + thr - 1) / thr), dim3(thr), 0, s>>>(e->ids_all, e->ids_act, nseq0, L, p0);
+            TRY(showo_embed_f32(e->ids_act, e->embed, e->x, nseq0 * L0, e->H, e->V, s));
+            showo::gemm_pin_split_m(nseq * L);
+            int rc = run_layers(e, nseq0, L0, p0, kvc, e->iv_act + e->maxT * 4, nullptr, nullptr, s);
+            showo::gemm_pin_split_m(nseq * N);
+            if (!rc) rc = head_rows(e, e->rows_act + e->maxT, nseq0 * N, id_offset, codebook, e->row_logits, s);
+            showo::gemm_pin_split_m(0);
+            TRY(rc);
+            if (shared) {
+                // the one unconditional sequence (index B) stands for all B: its prefix K rows [p0, prefix) and V^T columns (widened to
+                // 16-byte units: columns < p0 are zero on both sides, columns >= prefix are rewritten by every later step) of every
+                // layer, and its logit rows
+                const int64_t ks = (int64_t)e->nH * L * 64, vs = (int64_t)e->nH * 64 * LpC;
+                const int c0 = p0 & ~7, c1 = std::min(LpC, (prefix + 7) & ~7);
+                for (int half = 0; half < (pfast ? 2 : 1); ++half) {
+                    TRY(bcast_seq(half ? kvc.k_lo : kvc.k, kvc.k_lstride, e->nL, e->nH, (int64_t)L * 64, B * ks + (int64_t)p0 * 64,
+                                  (int64_t)(prefix - p0) * 64, ks, B - 1, s));
+                    TRY(bcast_seq(half ? kvc.vt_lo : kvc.vt, kvc.v_lstride, e->nL, e->nH * 64, (int64_t)LpC, B * vs + c0, (int64_t)(c1 - c0), vs, B - 1, s));
+                }
+                TRY(bcast_seq(e->row_logits, 0, 1, 1, 0, (int64_t)B * N * codebook, (int64_t)N * codebook, (int64_t)N * codebook, B - 1, s));
+            }
+        } else if (full) {
             TRY(showo_embed_f32(e->ids_all, e->embed, e->x, nseq * L, e->H, e->V, s));
             TRY(run_layers(e, nseq, L, 0, kvc, iv, flag, mask, s));
             TRY(head_rows(e, e->rows, nrows, id_offset, codebook, e->row_logits, s));
         } else {
             gather_ids_kernel<<<dim3((nseq * La + thr - 1) / thr), dim3(thr), 0, s>>>(e->ids_all, e->ids_act, nseq, L, prefix);
             TRY(showo_embed_f32(e->ids_act, e->embed, e->x, nseq * La, e->H, e->V, s));
-            TRY(run_layers(e, nseq, La, prefix, kvc, iv ? e->iv_act : nullptr, nullptr, nullptr, s));
+            // like the reduced step 0, the active-rows launches sum K in the order of the full-shape launches they stand for: with fewer
+            // than 16 sequences the residual GEMM splits K and the count follows M, and the text rows in the cache (step 0) and the path
+            // without reuse were summed in the full shape's order.  (Baked into the captured launches; a no-op where neither shape splits.)
+            showo::gemm_pin_split_m(nseq * L);
+            const int rc = run_layers(e, nseq, La, prefix, kvc, iv ? e->iv_act : nullptr, nullptr, nullptr, s);
+            showo::gemm_pin_split_m(0);
+            TRY(rc);
             TRY(head_rows(e, e->rows_act, nrows, id_offset, codebook, e->row_logits, s));
         }
+        if (first_step && e->t2i_logits0)
+            SHOWO_CHECK_HIP(hipMemcpyAsync(e->t2i_logits0, e->row_logits, (size_t)nrows * codebook * sizeof(float), hipMemcpyDeviceToDevice, s));
+        first_step = false;
         const float* lu = cfg ? e->row_logits + (int64_t)B * N * codebook : nullptr;
         const bool dev = step < 0;  // device-step mode: noise offsets are applied inside the kernels
         TRY(showo_cfg_softmax_sample(e->row_logits, lu, codebook, guidance, e->cur, mask_id,

@@ -206,7 +206,8 @@ int pick_bm(int M, int N, int cus) {
 // g_bm_cache / the split-K workspaces are process-wide: guarded by g_gemm_mu (autograd's backward thread launches GEMMs too).
 std::mutex g_gemm_mu;
 
-std::map<std::tuple<int, int, int, int>, int> g_bm_cache;  // (M, N, K, EPI) -> variant | tile-group width << 16
+std::map<std::tuple<int, int, int, int, int>, int> g_bm_cache;  // (M, N, K, EPI, split-policy M) -> variant | tile-group width << 16
+thread_local int t_split_m_pin = 0;  // gemm_pin_split_m
 int g_gemm_tune = -1;
 
 // one tile variant of (epilogue, operand type) by run-time codes
@@ -220,8 +221,8 @@ int launch2p_bm(const GemmArgs& g, int EPI, hipStream_t s) {
     if (g_gemm_bm == 0) pick_bm(g.M, g.N, cus);  // reads SHOWO_GEMM_BM
     if (g_gemm_bm > 0) return launch_variant(g, EPI, g_gemm_bm, s);
     if (g_gemm_tune < 0) { const char* e = getenv("SHOWO_GEMM_TUNE"); g_gemm_tune = e ? atoi(e) : 1; }
-    const auto key = std::make_tuple(g.M, g.N, g.K, EPI | (F16 ? 0x80 : 0) | (cus << 8));  // the CU budget of the stream is part of the shape: other split counts, other rounds
-    const bool split_shape = splitk_count(g.M, g.N, g.K, cus) >= 2;  // ring variants never split: not candidates (bit-identity, see above)
+    const auto key = std::make_tuple(g.M, g.N, g.K, EPI | (F16 ? 0x80 : 0) | (cus << 8), g.split_m);  // the CU budget of the stream is part of the shape: other split counts, other rounds
+    const bool split_shape = splitk_count(g.split_m ? g.split_m : g.M, g.N, g.K, cus) >= 2;  // ring variants never split: not candidates (bit-identity, see above)
     auto it = g_bm_cache.find(key);
     if (it != g_bm_cache.end()) {
         GemmArgs c = g;
@@ -314,8 +315,11 @@ void gemm_count_launch(bool split) {
     if (split) g_cnt_splitk++;
 }
 
+void gemm_pin_split_m(int M) { t_split_m_pin = M > 0 ? M : 0; }
+
 int gemm2p_dispatch(GemmArgs g, int epilogue, hipStream_t s) {
     std::lock_guard<std::mutex> lock(g_gemm_mu);
+    g.split_m = (t_split_m_pin && t_split_m_pin != g.M) ? t_split_m_pin : 0;
     g_cnt_gemm2p++;
     if (epilogue == EPI_QKV && g.raw && g.pre) g_cnt_qkv_save++;
     g.gn = g_gemm_gn > 0 ? g_gemm_gn : 1;

@@ -321,9 +321,10 @@ int launch2p(const GemmArgs& g0, hipStream_t s) {
     int tilesM = (g.M + BMT - 1) / BMT, tilesN = (g.N + B2 - 1) / B2;
     const int tiles = tilesM * tilesN, nk = g.K / GEMM_BK;
     // split-K: the split count S (hence the k-partition and the fp32 summation order) is a function of (M, N, K) ALONE
-    // (splitk_count below): every split-capable tile variant produces the same bits, whichever one the tuner picks.
+    // (splitk_count below): every split-capable tile variant produces the same bits, whichever one the tuner picks.  M is the
+    // launch's own, or the pinned one of the launch whose rows it computes (GemmArgs::split_m).
     g.splits = 1;
-    const int S = splitk_count(g.M, g.N, g.K, showo_cu_usable((void*)s));
+    const int S = splitk_count(g.split_m ? g.split_m : g.M, g.N, g.K, showo_cu_usable((void*)s));
     if (S >= 2) {
         constexpr int NFS = 4 * (MF0 > MF1 ? MF0 : MF1);
         if (tiles * S > SPLITK_TICKS || !splitk_ws(s, (size_t)tiles * S * NFS * 512 * sizeof(float4), &g.ws, &g.tick))

@@ -54,6 +54,9 @@ struct GemmArgs {
     // 16-bit operand type of A, W and of every 16-bit output (common.h Op16): 0 = bfloat16, 1 = IEEE half (SHOWO_OP_F16).  Host-side
     // selector of the kernel instance; the device code carries it as the template parameter F16.
     int op = 0;
+    // host only: the M that the split-K policy is asked about (0 = this launch's own M).  A launch that computes a subset of the rows of
+    // another launch keeps that launch's k-partition -- the fp32 summation order of every output element -- this way (gemm_pin_split_m).
+    int split_m = 0;
 };
 
 constexpr int EPI_QKV = 4;  // internal epilogue code of showo_gemm_qkv_bf16
@@ -754,6 +757,9 @@ static __device__ __forceinline__ void epilogue_qkv_split(const GemmArgs& g, f32
 
 // production kernel (gemm2p.hip)
 int gemm2p_dispatch(GemmArgs g, int epilogue, hipStream_t s);  // epilogue: SHOWO_EPI_* or EPI_QKV
+// Every launch that THIS THREAD sends through gemm2p_dispatch until the next call takes its split-K count from a problem of M rows
+// instead of its own (0 = off): the t2i engine runs step 0 on fewer rows than the full step it replaces and must sum K in that step's order.
+void gemm_pin_split_m(int M);
 // split-K policy and per-stream workspace of the production family (gemm2p.hip), shared with gemm_tn.hip
 int gemm_splitk_count(int M, int N, int K, int cus);  // cus = showo_cu_usable(stream)
 bool gemm_splitk_ws(hipStream_t s, size_t need, float4** ws, unsigned** tick);

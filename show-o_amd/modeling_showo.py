@@ -747,8 +747,9 @@ class Showo(PretrainedMixin, nn.Module):
         # the denoise steps run as replays of ONE captured hipGraph (cached on the engine across calls) unless use_graph=0 is
         # passed or per-launch event timing is on (the engine then runs the steps eagerly)
         use_graph = int(kwargs.get("use_graph", 1))
-        # bit 0: hipGraph replay of the denoise step; bit 1: recompute the step-invariant text rows every step (A/B switch)
-        flags = (1 if use_graph else 0) | (0 if kwargs.get("reuse_prefix", True) else 2)
+        # bit 0: hipGraph replay of the denoise step; bit 1: recompute the step-invariant text rows every step (A/B switch);
+        # bit 2: run every row of every sequence in step 0 (reduce_step0=False; A/B switch)
+        flags = (1 if use_graph else 0) | (0 if kwargs.get("reuse_prefix", True) else 2) | (0 if kwargs.get("reduce_step0", True) else 4)
 
         def run():
             _lib.call("showo_engine_t2i_generate", eng, _lib.ptr(input_ids), _lib.ptr(unc), _lib.ptr(mask), B, L, N, text_len,
