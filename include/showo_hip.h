@@ -371,6 +371,16 @@ int showo_ln_bwd_blocks(int T);
  * exactly these sums (no second pass over dx16).  part: scratch fp32 [showo_ln_bwd_blocks(T), 3, H]. */
 int showo_ln_bwd_colsum(const float* x, const float* gamma, const float* dh, const float* dy, float* dx32, uint16_t* dx16, float* part,
                         float* dgb, float* dxsum, int T, int H, float eps, void* stream);
+/* Accumulating forms of the parameter-gradient side outputs (gradient accumulation over micro-batches).  Contract of every
+ * showo_*_acc entry point: accumulate == 0 is the plain call; accumulate != 0 gives out = out_old + v where v is, bit for bit, what
+ * the plain call writes for the same inputs -- the old value is added once, to the finished fp32 sum, by the last stage of the
+ * kernel's fixed-order reduction (the way SHOWO_EPI_RESID_F32 / showo_gemm_tn_bf16(accumulate) add theirs).  Data-gradient outputs
+ * (dx32, dx16, dqkv, df) are per micro-batch and always overwritten.  showo_ln_bwd_colsum_acc has one switch per destination. */
+int showo_ln_bwd_acc(const float* x, const float* gamma, const float* dh, const float* dy, float* dx32, uint16_t* dx16, float* part,
+                     float* dgb, int accumulate, int T, int H, float eps, void* stream);
+int showo_ln_bwd_colsum_acc(const float* x, const float* gamma, const float* dh, const float* dy, float* dx32, uint16_t* dx16,
+                            float* part, float* dgb, float* dxsum, int accumulate_dgb, int accumulate_dxsum, int T, int H, float eps,
+                            void* stream);
 /* Backward of q/k LayerNorm(64) + partial rotary + the 1/8 fold (phi.py:661-694): dq, dk bf16 [T, ldg] (w.r.t. the stored Q,
  * K), raw qkv bf16 [T, 3*nH*64] -> dqkv bf16 [T, 3*nH*64] (q and k sections), dparams fp32 [4,64] = (dq_ln_w, dq_ln_b,
  * dk_ln_w, dk_ln_b); part: scratch fp32 [showo_qkln_rope_bwd_blocks(T, nH), 4, 64]. */
@@ -378,6 +388,9 @@ int showo_qkln_rope_bwd(const uint16_t* dq, const uint16_t* dk, int ldg, const u
                         const float* cos_tab, const float* sin_tab, uint16_t* dqkv, float* part, float* dparams, int T, int L,
                         int nH, int rot, float eps, void* stream);
 int showo_qkln_rope_bwd_blocks(int T, int nH);
+int showo_qkln_rope_bwd_acc(const uint16_t* dq, const uint16_t* dk, int ldg, const uint16_t* qkv, const float* qw, const float* kw,
+                            const float* cos_tab, const float* sin_tab, uint16_t* dqkv, float* part, float* dparams, int accumulate,
+                            int T, int L, int nH, int rot, float eps, void* stream);
 /* The three mean cross-entropies of Showo.forward (modeling_showo.py:80-98) and their gradient.
  * logits fp32 [B*L, ldl]; labels int64 [B,L] (-100 = ignore).  losses fp32 [3] = (t2i, lm, mmu);
  * dlogits (optional) bf16 [B*L, ldd] = d(g_t2i*loss_t2i + g_lm*loss_lm + g_mmu*loss_mmu)/dlogits, pad columns zero.
@@ -388,6 +401,10 @@ int showo_ce_loss(const float* logits, int ldl, const int64_t* labels, int B, in
 /* Embedding backward (deterministic): dE[ids[t]] = sum of dx[t] over equal ids, in position order.  dE must be
  * zero-filled by the caller; order_ws: scratch int[2*T]. */
 int showo_embed_bwd(const int64_t* ids, const float* dx, float* dE, int* order_ws, int T, int H, int V, void* stream);
+/* accumulate != 0: dE[ids[t]] += the same position-ordered sums, only in the rows this batch touches (no zero-fill, every other row
+ * is left alone); accumulate == 0 is showo_embed_bwd. */
+int showo_embed_bwd_acc(const int64_t* ids, const float* dx, float* dE, int* order_ws, int accumulate, int T, int H, int V,
+                        void* stream);
 /* torch.optim.AdamW step on fp32 tensors (step counts from 1). */
 int showo_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                 float weight_decay, int step, void* stream);
@@ -405,6 +422,8 @@ int showo_dgelu_bf16(const uint16_t* da, const uint16_t* f, uint16_t* df, int64_
  * showo_colsum_bf16 on df); colpart: fp32 scratch of (ceil(T / 64) + 8) * C floats; df may alias da. */
 int showo_dgelu_colsum_bf16(const uint16_t* da, const uint16_t* f, uint16_t* df, int ld, int T, int C, float* colpart, float* colsum,
                             void* stream);
+int showo_dgelu_colsum_bf16_acc(const uint16_t* da, const uint16_t* f, uint16_t* df, int ld, int T, int C, float* colpart,
+                                float* colsum, int accumulate, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * t2i sampler (reference models/modeling_showo.py:140-179, models/sampling.py:14-36)
@@ -669,6 +688,13 @@ int showo_train_set_trainable(showo_trainer* t, const char* key, int on);
 /* whether d(loss)/d(input embeddings) of a showo_train_forward_embeds is wanted (default 1; 0: showo_train_input_grad refuses and
  * the backward stops at the lowest block that trains) */
 int showo_train_set_input_grad(showo_trainer* t, int on);
+/* Gradient accumulation over micro-batches (reference: accelerator.accumulate, training/train.py:589-631).  While on, every
+ * parameter-gradient write of showo_train_backward[_head[_dev] / _layer / _embed] ADDS into the flat buffer (showo_gemm_tn_bf16 /
+ * showo_colsum_bf16 with accumulate, the showo_*_acc side outputs, SHOWO_EPI_RESID_F32 on the SHOWO_TRAIN_TN=0 path) and the
+ * embedding phase adds its row sums into the rows the micro-batch touches without clearing the table.  A window is: off for its
+ * first micro-batch, on for the rest; the sum differs from the fp64 sum of the per-micro-batch gradients by one fp32 rounding per
+ * added micro-batch.  Frozen slots stay zero and side outputs pointed at scratch stay overwriting.  Default off. */
+int showo_train_set_accumulate(showo_trainer* t, int on);
 /* launch counters since the last reset (tests): out6 = {weight-gradient GEMMs, data-gradient GEMMs, block phases that ran,
  * embedding-phase launches, transposed weight images rebuilt, fused block images rebuilt by the engine}; reset != 0 zeroes them */
 int showo_train_counters(showo_trainer* t, int64_t* out6, int reset);

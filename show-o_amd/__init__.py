@@ -9,7 +9,7 @@ from .sampling import get_mask_chedule, cosine_schedule  # noqa: F401
 from .modeling_showo import Showo, gen_config  # noqa: F401
 from .modeling_magvitv2 import MAGVITv2  # noqa: F401
 from . import _lib  # noqa: F401
-from .training import Trainer  # noqa: F401
+from .training import Trainer, AccumulationWindow  # noqa: F401
 from . import prompting_utils  # noqa: F401
 from . import training_utils  # noqa: F401
 from .prompting_utils import UniversalPrompting  # noqa: F401

@@ -58,6 +58,13 @@ _PROTOS = {
     "showo_dgelu_bf16": [c_p, c_p, c_p, c_i64, c_p],
     "showo_dgelu_colsum_bf16": [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_p],
     "showo_gelu_bf16": [c_p, c_p, c_i64, c_p],
+    # accumulating forms of the parameter-gradient side outputs (gradient accumulation over micro-batches)
+    "showo_ln_bwd_acc": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_p],
+    "showo_ln_bwd_colsum_acc": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_f, c_p],
+    "showo_qkln_rope_bwd_acc": [c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_f, c_p],
+    "showo_embed_bwd_acc": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p],
+    "showo_dgelu_colsum_bf16_acc": [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_p],
+    "showo_train_set_accumulate": [c_p, c_i],
     "showo_train_create": [c_p, c_i, c_i, c_p],
     "showo_train_invalidate_weights": [c_p],
     "showo_train_set_trainable": [c_p, C.c_char_p, c_i],

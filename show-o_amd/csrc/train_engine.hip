@@ -109,6 +109,8 @@ struct showo_trainer {
     float dl_g[3] = {0.f, 0.f, 0.f};
     const int64_t* dl_labels = nullptr;
     int dl_split[4] = {0, 0, 0, 0};
+    // gradient accumulation (showo_train_set_accumulate): every parameter-gradient write of the backward adds into the flat buffer
+    bool accumulate = false;
 
     template <class T>
     int alloc(T** p, int64_t n) {
@@ -355,6 +357,12 @@ extern "C" int showo_train_set_input_grad(showo_trainer* t, int on) {
     return 0;
 }
 
+extern "C" int showo_train_set_accumulate(showo_trainer* t, int on) {
+    if (!t) return set_error_msg(1, "train_set_accumulate: null handle");
+    t->accumulate = on != 0;
+    return 0;
+}
+
 extern "C" int showo_train_counters(showo_trainer* t, int64_t* out6, int reset) {
     if (!t) return set_error_msg(1, "train_counters: null handle");
     if (out6) {
@@ -516,7 +524,15 @@ extern "C" int showo_train_input_grad(showo_trainer* t, float* out, int64_t n, v
     const int H = e->H, F = e->F, V = e->V, nH = e->nH, B = t->B, L = t->Lq, T = B * L, Vp = t->Vp;                    \
     const int Tp = ((T + 63) / 64) * 64, Lp = ((L + 63) / 64) * 64;                                                   \
     const int32_t* iv = t->has_mask ? e->iv : nullptr;                                                                \
-    (void)F; (void)V; (void)nH; (void)Vp; (void)Tp; (void)Lp; (void)iv; (void)s;
+    const int acc = t->accumulate ? 1 : 0; /* parameter-gradient writers add into their slot; scratch side outputs never do */ \
+    (void)F; (void)V; (void)nH; (void)Vp; (void)Tp; (void)Lp; (void)iv; (void)s; (void)acc;
+
+// weight gradient of the SHOWO_TRAIN_TN=0 path: out fp32 [M, N] (+)= (dY^T)[M, Tp] (X^T)[N, Tp]^T on the k-contiguous GEMM; accumulating =
+// the residual epilogue with resid = out (the finished accumulator is added to the old value once)
+static int wgrad_nt(const bf16_t* dyT, const bf16_t* xT, float* out, int ldo, int M, int N, int Tp, int acc, hipStream_t s) {
+    return showo_gemm_bf16(dyT, Tp, xT, Tp, nullptr, 0, out, ldo, acc ? out : nullptr, acc ? ldo : 0, M, N, Tp,
+                           acc ? SHOWO_EPI_RESID_F32 : SHOWO_EPI_F32, s);
+}
 
 // the head phase after d(logits) is in t->dlogits: lm_head weight / bias gradients, d(final LayerNorm), dy of the top block.
 // Frozen lm_head tensors get no launch; the dgrad GEMM and the final-LayerNorm backward run only when something below consumes them.
@@ -524,14 +540,14 @@ static int backward_head_from_dlogits(showo_trainer* t, void* stream) {
     BW_PROLOGUE
     TRY(plan_sync(t, s));
     if (train_tn()) {
-        if (t->p_blm) TRY(showo_colsum_bf16(t->dlogits, Vp, T, Vp, t->colpart, t->gblm, 0, s));                         // lm_head bias grad
-        if (t->p_wlm) { TRY(showo_gemm_tn_bf16(t->dlogits, Vp, e->hf, H, t->gwlm, H, V, H, T, 0, 1, s)); ++t->cnt[0]; }   // dWlm [V,H]
+        if (t->p_blm) TRY(showo_colsum_bf16(t->dlogits, Vp, T, Vp, t->colpart, t->gblm, acc, s));                         // lm_head bias grad
+        if (t->p_wlm) { TRY(showo_gemm_tn_bf16(t->dlogits, Vp, e->hf, H, t->gwlm, H, V, H, T, acc, 1, s)); ++t->cnt[0]; }   // dWlm [V,H]
     } else {
     if (t->p_wlm || t->p_blm)  // dlogits^T + lm_head bias grad
-        TRY(showo_transpose_bf16(t->dlogits, Vp, t->bigT, T, Vp, Tp, 0, t->colpart, t->p_blm ? t->gblm : nullptr, 0, s));
+        TRY(showo_transpose_bf16(t->dlogits, Vp, t->bigT, T, Vp, Tp, 0, t->colpart, t->p_blm ? t->gblm : nullptr, acc, s));
     if (t->p_wlm) {
     TRY(showo_transpose_bf16(e->hf, H, t->xT, T, H, Tp, 0, nullptr, nullptr, 0, s));
-    TRY(showo_gemm_bf16(t->bigT, Tp, t->xT, Tp, nullptr, 0, t->gwlm, H, nullptr, 0, V, H, Tp, SHOWO_EPI_F32, s));      // dWlm [V,H]
+    TRY(wgrad_nt(t->bigT, t->xT, t->gwlm, H, V, H, Tp, acc, s));                                                       // dWlm [V,H]
     ++t->cnt[0];
     }
     }
@@ -542,9 +558,10 @@ static int backward_head_from_dlogits(showo_trainer* t, void* stream) {
     float* gfln = t->p_fln ? t->gfln : t->sc_ln;
     if (train_tn() && e->nL > 0) {  // + column sums of dy16 = the dense / fc2 bias gradients of the top block
         float* cb = b2_dst(t, e->nL - 1);
-        TRY(showo_ln_bwd_colsum(e->x, e->fln_w, t->dh, t->dy, t->dy, t->dy16, t->lnpart, gfln, cb ? cb : t->sc_b, T, H, e->cfg.ln_eps, s));
+        TRY(showo_ln_bwd_colsum_acc(e->x, e->fln_w, t->dh, t->dy, t->dy, t->dy16, t->lnpart, gfln, cb ? cb : t->sc_b, acc && t->p_fln,
+                                    acc && cb, T, H, e->cfg.ln_eps, s));
     } else
-    TRY(showo_ln_bwd(e->x, e->fln_w, t->dh, t->dy, t->dy, t->dy16, t->lnpart, gfln, T, H, e->cfg.ln_eps, s));
+    TRY(showo_ln_bwd_acc(e->x, e->fln_w, t->dh, t->dy, t->dy, t->dy16, t->lnpart, gfln, acc && t->p_fln, T, H, e->cfg.ln_eps, s));
     for (const Grad& g : t->fln_clear) SHOWO_CHECK_HIP(hipMemsetAsync(g.p, 0, (size_t)g.n * sizeof(float), s));
     return 0;
 }
@@ -605,13 +622,13 @@ extern "C" int showo_train_backward_layer(showo_trainer* t, int i, void* stream)
             // db2 = dbd = column sums of dy16: written into l.gb2 (l.gbd when fc2.bias is frozen) by the LayerNorm backward that
             // produced dy16 (showo_ln_bwd_colsum)
             if (p.bd && p.b2) SHOWO_CHECK_HIP(hipMemcpyAsync(l.gbd, l.gb2, (size_t)H * sizeof(float), hipMemcpyDeviceToDevice, s));
-            if (p.w2) { TRY(showo_gemm_tn_bf16(t->dy16, H, l.a, F, l.gw2, F, H, F, T, 0, 1, s)); ++t->cnt[0]; }                // dW2 [H,F]
-            if (p.wd) { TRY(showo_gemm_tn_bf16(t->dy16, H, l.attn, H, l.gwd, H, H, H, T, 0, 1, s)); ++t->cnt[0]; }             // dWd [H,H]
+            if (p.w2) { TRY(showo_gemm_tn_bf16(t->dy16, H, l.a, F, l.gw2, F, H, F, T, acc, 1, s)); ++t->cnt[0]; }                // dW2 [H,F]
+            if (p.wd) { TRY(showo_gemm_tn_bf16(t->dy16, H, l.attn, H, l.gwd, H, H, H, T, acc, 1, s)); ++t->cnt[0]; }             // dWd [H,H]
             if (mlp) {
             TRY(showo_gemm_bf16(t->dy16, H, l.w2T, H, nullptr, 0, t->dff, F, nullptr, 0, T, F, H, SHOWO_EPI_BF16, s));          // d a
             ++t->cnt[1];
-            TRY(showo_dgelu_colsum_bf16(t->dff, l.f, t->dff, F, T, F, t->colpart, gb1, s));                                    // d f, db1
-            if (p.w1) { TRY(showo_gemm_tn_bf16(t->dff, F, l.h, H, l.gw1, H, F, H, T, 0, 1, s)); ++t->cnt[0]; }                 // dW1 [F,H]
+            TRY(showo_dgelu_colsum_bf16_acc(t->dff, l.f, t->dff, F, T, F, t->colpart, gb1, acc && p.b1, s));                   // d f, db1
+            if (p.w1) { TRY(showo_gemm_tn_bf16(t->dff, F, l.h, H, l.gw1, H, F, H, T, acc, 1, s)); ++t->cnt[0]; }                 // dW1 [F,H]
             if (need_dh) {
             TRY(showo_gemm_bf16(t->dff, F, l.w1T, F, nullptr, 0, t->dh, H, nullptr, 0, T, H, F, SHOWO_EPI_F32, s));             // dh (mlp)
             ++t->cnt[1];
@@ -625,10 +642,10 @@ extern "C" int showo_train_backward_layer(showo_trainer* t, int i, void* stream)
             TRY(showo_head_transpose(l.K, t->KT, B, nH, L, Lp, (int64_t)nH * L * 64, (int64_t)L * 64, 64, s));
             TRY(showo_attn_bwd(l.Q, l.K, t->QT, t->KT, l.qkv + 2 * H, 3 * H, l.attn, t->d_o, H, t->dOT, l.lse, t->D, iv, nullptr, t->dqk, 2 * H,
                                t->dqk + H, 2 * H, t->dqkv + 2 * H, 3 * H, B, nH, L, Lp, s));
-            TRY(showo_qkln_rope_bwd(t->dqk, t->dqk + H, 2 * H, l.qkv, w.qln_w, w.kln_w, e->cosT, e->sinT, t->dqkv, t->qkpart, gqk, T, L,
+            TRY(showo_qkln_rope_bwd_acc(t->dqk, t->dqk + H, 2 * H, l.qkv, w.qln_w, w.kln_w, e->cosT, e->sinT, t->dqkv, t->qkpart, gqk, acc && p.qk, T, L,
                                     nH, e->cfg.rotary_dim, e->cfg.ln_eps, s));
-            if (p.bqkv) TRY(showo_colsum_bf16(t->dqkv, 3 * H, T, 3 * H, t->colpart, l.gbqkv, 0, s));                            // dbqkv
-            if (p.wqkv) { TRY(showo_gemm_tn_bf16(t->dqkv, 3 * H, l.h, H, l.gwqkv, H, 3 * H, H, T, 0, 1, s)); ++t->cnt[0]; }     // dWqkv [3H,H]
+            if (p.bqkv) TRY(showo_colsum_bf16(t->dqkv, 3 * H, T, 3 * H, t->colpart, l.gbqkv, acc, s));                            // dbqkv
+            if (p.wqkv) { TRY(showo_gemm_tn_bf16(t->dqkv, 3 * H, l.h, H, l.gwqkv, H, 3 * H, H, T, acc, 1, s)); ++t->cnt[0]; }     // dWqkv [3H,H]
             if (need_dh) {
             TRY(showo_gemm_bf16(t->dqkv, 3 * H, l.wqkvT, 3 * H, nullptr, 0, t->dh, H, t->dh, H, T, H, 3 * H, SHOWO_EPI_RESID_F32, s));  // dh += attn part
             ++t->cnt[1];
@@ -637,17 +654,17 @@ extern "C" int showo_train_backward_layer(showo_trainer* t, int i, void* stream)
         } else {
         // dy^T (+ bias grads of fc2 and dense: both are column sums of dy)
         float* cb2 = b2_dst(t, i);
-        if (p.w2 || p.wd || cb2) TRY(showo_transpose_bf16(t->dy16, H, t->bigT, T, H, Tp, 0, t->colpart, cb2, 0, s));
+        if (p.w2 || p.wd || cb2) TRY(showo_transpose_bf16(t->dy16, H, t->bigT, T, H, Tp, 0, t->colpart, cb2, acc, s));
         if (p.bd && p.b2) SHOWO_CHECK_HIP(hipMemcpyAsync(l.gbd, l.gb2, (size_t)H * sizeof(float), hipMemcpyDeviceToDevice, s));
         // MLP
         if (p.w2) {
         TRY(showo_transpose_bf16(l.f, F, t->xT, T, F, Tp, 1, nullptr, nullptr, 0, s));                                      // gelu(f)^T
-        TRY(showo_gemm_bf16(t->bigT, Tp, t->xT, Tp, nullptr, 0, l.gw2, F, nullptr, 0, H, F, Tp, SHOWO_EPI_F32, s));         // dW2 [H,F]
+        TRY(wgrad_nt(t->bigT, t->xT, l.gw2, F, H, F, Tp, acc, s));                                                          // dW2 [H,F]
         ++t->cnt[0];
         }
         if (p.wd) {
         TRY(showo_transpose_bf16(l.attn, H, t->xT, T, H, Tp, 0, nullptr, nullptr, 0, s));                                   // attn^T
-        TRY(showo_gemm_bf16(t->bigT, Tp, t->xT, Tp, nullptr, 0, l.gwd, H, nullptr, 0, H, H, Tp, SHOWO_EPI_F32, s));         // dWd [H,H]
+        TRY(wgrad_nt(t->bigT, t->xT, l.gwd, H, H, H, Tp, acc, s));                                                          // dWd [H,H]
         ++t->cnt[0];
         }
         bool hT = false;  // xT holds h^T (the operand of dW1 and dWqkv)
@@ -655,10 +672,10 @@ extern "C" int showo_train_backward_layer(showo_trainer* t, int i, void* stream)
         TRY(showo_gemm_bf16(t->dy16, H, l.w2T, H, nullptr, 0, t->dff, F, nullptr, 0, T, F, H, SHOWO_EPI_BF16, s));          // d a
         ++t->cnt[1];
         TRY(showo_dgelu_bf16(t->dff, l.f, t->dff, (int64_t)T * F, s));                                                      // d f
-        if (p.w1 || p.b1) TRY(showo_transpose_bf16(t->dff, F, t->bigT, T, F, Tp, 0, t->colpart, p.b1 ? l.gb1 : nullptr, 0, s));  // df^T, db1
+        if (p.w1 || p.b1) TRY(showo_transpose_bf16(t->dff, F, t->bigT, T, F, Tp, 0, t->colpart, p.b1 ? l.gb1 : nullptr, acc, s));  // df^T, db1
         if (p.w1 || p.wqkv) { TRY(showo_transpose_bf16(l.h, H, t->xT, T, H, Tp, 0, nullptr, nullptr, 0, s)); hT = true; }    // h^T
         if (p.w1) {
-        TRY(showo_gemm_bf16(t->bigT, Tp, t->xT, Tp, nullptr, 0, l.gw1, H, nullptr, 0, F, H, Tp, SHOWO_EPI_F32, s));         // dW1 [F,H]
+        TRY(wgrad_nt(t->bigT, t->xT, l.gw1, H, F, H, Tp, acc, s));                                                          // dW1 [F,H]
         ++t->cnt[0];
         }
         if (need_dh) {
@@ -674,13 +691,13 @@ extern "C" int showo_train_backward_layer(showo_trainer* t, int i, void* stream)
         TRY(showo_head_transpose(l.K, t->KT, B, nH, L, Lp, (int64_t)nH * L * 64, (int64_t)L * 64, 64, s));
         TRY(showo_attn_bwd(l.Q, l.K, t->QT, t->KT, l.qkv + 2 * H, 3 * H, l.attn, t->d_o, H, t->dOT, l.lse, t->D, iv, nullptr, t->dqk, 2 * H,
                            t->dqk + H, 2 * H, t->dqkv + 2 * H, 3 * H, B, nH, L, Lp, s));
-        TRY(showo_qkln_rope_bwd(t->dqk, t->dqk + H, 2 * H, l.qkv, w.qln_w, w.kln_w, e->cosT, e->sinT, t->dqkv, t->qkpart, gqk, T, L,
+        TRY(showo_qkln_rope_bwd_acc(t->dqk, t->dqk + H, 2 * H, l.qkv, w.qln_w, w.kln_w, e->cosT, e->sinT, t->dqkv, t->qkpart, gqk, acc && p.qk, T, L,
                                 nH, e->cfg.rotary_dim, e->cfg.ln_eps, s));
         if (p.wqkv || p.bqkv)                                                                                                // dqkv^T, dbqkv
-            TRY(showo_transpose_bf16(t->dqkv, 3 * H, t->bigT, T, 3 * H, Tp, 0, t->colpart, p.bqkv ? l.gbqkv : nullptr, 0, s));
+            TRY(showo_transpose_bf16(t->dqkv, 3 * H, t->bigT, T, 3 * H, Tp, 0, t->colpart, p.bqkv ? l.gbqkv : nullptr, acc, s));
         if (p.wqkv) {
         if (!hT) TRY(showo_transpose_bf16(l.h, H, t->xT, T, H, Tp, 0, nullptr, nullptr, 0, s));
-        TRY(showo_gemm_bf16(t->bigT, Tp, t->xT, Tp, nullptr, 0, l.gwqkv, H, nullptr, 0, 3 * H, H, Tp, SHOWO_EPI_F32, s));   // dWqkv (xT = h^T)
+        TRY(wgrad_nt(t->bigT, t->xT, l.gwqkv, H, 3 * H, H, Tp, acc, s));                                                    // dWqkv (xT = h^T)
         ++t->cnt[0];
         }
         if (need_dh) {
@@ -694,9 +711,10 @@ extern "C" int showo_train_backward_layer(showo_trainer* t, int i, void* stream)
         float* gln = p.ln ? l.gln : t->sc_ln;
         if (train_tn() && i > 0 && t->L[i - 1].a) {
             float* cb = b2_dst(t, i - 1);
-            TRY(showo_ln_bwd_colsum(l.x, w.ln_w, t->dh, t->dy, t->dy, t->dy16, t->lnpart, gln, cb ? cb : t->sc_b, T, H, e->cfg.ln_eps, s));
+            TRY(showo_ln_bwd_colsum_acc(l.x, w.ln_w, t->dh, t->dy, t->dy, t->dy16, t->lnpart, gln, cb ? cb : t->sc_b, acc && p.ln, acc && cb,
+                                        T, H, e->cfg.ln_eps, s));
         } else
-        TRY(showo_ln_bwd(l.x, w.ln_w, t->dh, t->dy, t->dy, t->dy16, t->lnpart, gln, T, H, e->cfg.ln_eps, s));
+        TRY(showo_ln_bwd_acc(l.x, w.ln_w, t->dh, t->dy, t->dy, t->dy16, t->lnpart, gln, acc && p.ln, T, H, e->cfg.ln_eps, s));
         }
         for (const Grad& g : p.clear) SHOWO_CHECK_HIP(hipMemsetAsync(g.p, 0, (size_t)g.n * sizeof(float), s));
         }
@@ -721,6 +739,15 @@ extern "C" int showo_train_backward_embed(showo_trainer* t, void* stream) {
     // after a scatter of an earlier backward, not on every step
     TRY(plan_sync(t, s));
     if (!t->p_emb) return 0;
+    if (acc) {
+        // accumulating: the table keeps the window's partial sum -- no clear, and the scatter adds its position-ordered row sums into the
+        // rows this micro-batch touches; a micro-batch that started from embeddings contributes nothing to the table
+        if (t->from_embeds) return 0;
+        TRY(showo_embed_bwd_acc(t->ids, t->dy, t->gembed, t->order_ws, 1, T, H, V, s));
+        ++t->cnt[3];
+        t->gembed_dirty = true;
+        return 0;
+    }
     if (t->from_embeds && !t->gembed_dirty) return 0;
     SHOWO_CHECK_HIP(hipMemsetAsync(t->gembed, 0, (size_t)V * H * sizeof(float), s));
     ++t->cnt[3];

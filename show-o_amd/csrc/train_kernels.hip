@@ -97,11 +97,12 @@ __global__ void colsum_combine_kernel(const float* __restrict__ sub8, float* __r
     if (c >= C) return;
     const float s = ((sub8[c] + sub8[(int64_t)C + c]) + (sub8[2 * (int64_t)C + c] + sub8[3 * (int64_t)C + c])) +
                     ((sub8[4 * (int64_t)C + c] + sub8[5 * (int64_t)C + c]) + (sub8[6 * (int64_t)C + c] + sub8[7 * (int64_t)C + c]));
+    // accumulate: bit 0 = out, bit 1 = out2; the old value is added once, to the finished sum
     float* o = c < C1 ? out + c : out2 + (c - C1);
-    *o = accumulate ? *o + s : s;
+    *o = (accumulate & (c < C1 ? 1 : 2)) ? *o + s : s;
 }
 // part: [nblk][C] partials followed by 8*C floats of scratch.  Columns >= C1 go to out2[c - C1] when out2 is given (two destinations
-// from one partial buffer: the LayerNorm backward).  (A one-launch form -- 64 columns per 512-thread block, eight waves over the
+// from one partial buffer: the LayerNorm backward).  accumulate: bit 0 adds into out, bit 1 into out2.  (A one-launch form -- 64 columns per 512-thread block, eight waves over the
 // partial rows -- measured 1.5-3 ms per training step SLOWER than these two launches: C / 64 blocks leave most CUs idle.)
 static inline void colsum_reduce(const float* part, float* out, int nblk, int C, int accumulate, hipStream_t s, float* out2 = nullptr, int C1 = 0) {
     float* sub8 = const_cast<float*>(part) + (int64_t)nblk * C;
@@ -556,6 +557,8 @@ __global__ __launch_bounds__(256) void embed_rank_kernel(const int64_t* __restri
         runstart[rank] = earlier ? 0 : 1;
     }
 }
+// ACC: dE[id] = dE_old[id] + (the position-ordered sum the overwriting form stores); rows of ids that do not occur are not touched
+template <bool ACC>
 __global__ __launch_bounds__(256) void embed_bwd_kernel(const int64_t* __restrict__ ids, const int* __restrict__ order,
                                                         const int* __restrict__ runstart, const float* __restrict__ dx,
                                                         float* __restrict__ dE, int T, int H) {
@@ -577,6 +580,10 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(const int64_t* __restric
         for (; j < end; ++j) {
             const float4 v = *reinterpret_cast<const float4*>(dx + (int64_t)order[j] * H + c);
             s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
+        }
+        if (ACC) {
+            const float4 o = *reinterpret_cast<const float4*>(dE + id * H + c);
+            s.x = o.x + s.x; s.y = o.y + s.y; s.z = o.z + s.z; s.w = o.w + s.w;
         }
         *reinterpret_cast<float4*>(dE + id * H + c) = s;
     }
@@ -767,7 +774,7 @@ extern "C" int showo_transpose_bf16(const uint16_t* x, int ld, uint16_t* xt, int
     if (colsum && !colpart) return set_error_msg(1, "transpose: column sums need the partial buffer [Tp/64, C]");
     hipStream_t s = (hipStream_t)stream;
     transpose_kernel<<<dim3((C + 63) / 64, Tp / 64), dim3(256), 0, s>>>(x, xt, colsum ? colpart : nullptr, T, C, ld, Tp, mode);
-    if (colsum) colsum_reduce(colpart, colsum, Tp / 64, C, accumulate, s);
+    if (colsum) colsum_reduce(colpart, colsum, Tp / 64, C, accumulate != 0, s);
     SHOWO_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -781,13 +788,13 @@ extern "C" int showo_colsum_bf16(const uint16_t* x, int ld, int T, int C, float*
     hipStream_t s = (hipStream_t)stream;
     const int nblk = (T + 31) / 32;
     colsum_bf16_kernel<<<dim3((C + 2047) / 2048, nblk), dim3(256), 0, s>>>(x, colpart, T, C, ld);
-    colsum_reduce(colpart, colsum, nblk, C, accumulate, s);
+    colsum_reduce(colpart, colsum, nblk, C, accumulate != 0, s);
     SHOWO_CHECK_HIP(hipGetLastError());
     return 0;
 }
 
 static int ln_bwd_impl(const float* x, const float* gamma, const float* dh, const float* dy, float* dx32, uint16_t* dx16, float* part,
-                       float* dgb, float* dxsum, int T, int H, float eps, void* stream) {
+                       float* dgb, float* dxsum, int acc_dgb, int acc_dxsum, int T, int H, float eps, void* stream) {
     if (T <= 0) return 0;
     if ((H % 4) || H > 2048) return set_error_msg(1, "ln_bwd: H must be a multiple of 4 and <= 2048");
     if (dxsum && !dx16) return set_error_msg(1, "ln_bwd: the column sums are those of dx16");
@@ -802,31 +809,44 @@ static int ln_bwd_impl(const float* x, const float* gamma, const float* dh, cons
     if (dxsum) {
         // part is [nblk][3][H] (dgamma | dbeta | column sums of dx16): ONE reduce, columns < 2H -> dgb, the rest -> dxsum
         ln_bwd_kernel<true><<<dim3(nblk), dim3(256), (size_t)8 * H * sizeof(float), s>>>(x, gamma, dh, dy, dx32, dx16, part, part + 2 * H, T, H, eps);
-        colsum_reduce(part, dgb, nblk, 3 * H, 0, s, dxsum, 2 * H);
+        colsum_reduce(part, dgb, nblk, 3 * H, (acc_dgb ? 1 : 0) | (acc_dxsum ? 2 : 0), s, dxsum, 2 * H);
     } else {
         // part is [nblk][2][H]: reduce it as a [nblk, 2H] matrix -> dgb = (dgamma[H], dbeta[H])
         ln_bwd_kernel<false><<<dim3(nblk), dim3(256), (size_t)8 * H * sizeof(float), s>>>(x, gamma, dh, dy, dx32, dx16, part, nullptr, T, H, eps);
-        colsum_reduce(part, dgb, nblk, 2 * H, 0, s);
+        colsum_reduce(part, dgb, nblk, 2 * H, acc_dgb ? 1 : 0, s);
     }
     SHOWO_CHECK_HIP(hipGetLastError());
     return 0;
 }
 extern "C" int showo_ln_bwd(const float* x, const float* gamma, const float* dh, const float* dy, float* dx32, uint16_t* dx16,
                             float* part, float* dgb, int T, int H, float eps, void* stream) {
-    return ln_bwd_impl(x, gamma, dh, dy, dx32, dx16, part, dgb, nullptr, T, H, eps, stream);
+    return ln_bwd_impl(x, gamma, dh, dy, dx32, dx16, part, dgb, nullptr, 0, 0, T, H, eps, stream);
+}
+// accumulating form (gradient accumulation over micro-batches): accumulate != 0 -> dgb = dgb_old + v, v = the bits showo_ln_bwd writes,
+// the old value added once by the last stage of the reduction; dx32 / dx16 are per micro-batch and always overwritten
+extern "C" int showo_ln_bwd_acc(const float* x, const float* gamma, const float* dh, const float* dy, float* dx32, uint16_t* dx16,
+                                float* part, float* dgb, int accumulate, int T, int H, float eps, void* stream) {
+    return ln_bwd_impl(x, gamma, dh, dy, dx32, dx16, part, dgb, nullptr, accumulate, 0, T, H, eps, stream);
 }
 // the same, plus dxsum[H] = column sums of dx16 (the bias gradients of the projections that consume dx as their dY); part: scratch
 // fp32 [showo_ln_bwd_blocks(T), 3, H]
 extern "C" int showo_ln_bwd_colsum(const float* x, const float* gamma, const float* dh, const float* dy, float* dx32, uint16_t* dx16,
                                    float* part, float* dgb, float* dxsum, int T, int H, float eps, void* stream) {
     if (!dxsum) return set_error_msg(1, "ln_bwd_colsum: dxsum required");
-    return ln_bwd_impl(x, gamma, dh, dy, dx32, dx16, part, dgb, dxsum, T, H, eps, stream);
+    return ln_bwd_impl(x, gamma, dh, dy, dx32, dx16, part, dgb, dxsum, 0, 0, T, H, eps, stream);
+}
+// accumulating form with one switch per destination (the two can belong to different parameters, one of them frozen and pointed at scratch)
+extern "C" int showo_ln_bwd_colsum_acc(const float* x, const float* gamma, const float* dh, const float* dy, float* dx32, uint16_t* dx16,
+                                       float* part, float* dgb, float* dxsum, int accumulate_dgb, int accumulate_dxsum, int T, int H,
+                                       float eps, void* stream) {
+    if (!dxsum) return set_error_msg(1, "ln_bwd_colsum: dxsum required");
+    return ln_bwd_impl(x, gamma, dh, dy, dx32, dx16, part, dgb, dxsum, accumulate_dgb, accumulate_dxsum, T, H, eps, stream);
 }
 extern "C" int showo_ln_bwd_blocks(int T) { return (T + LNB_ROWS - 1) / LNB_ROWS + 8; }  // + 8 rows of reduction scratch
 
-extern "C" int showo_qkln_rope_bwd(const uint16_t* dq, const uint16_t* dk, int ldg, const uint16_t* qkv, const float* qw,
-                                   const float* kw, const float* cos_tab, const float* sin_tab, uint16_t* dqkv, float* part,
-                                   float* dparams, int T, int L, int nH, int rot, float eps, void* stream) {
+static int qkln_rope_bwd_impl(const uint16_t* dq, const uint16_t* dk, int ldg, const uint16_t* qkv, const float* qw, const float* kw,
+                              const float* cos_tab, const float* sin_tab, uint16_t* dqkv, float* part, float* dparams, int accumulate,
+                              int T, int L, int nH, int rot, float eps, void* stream) {
     if (T <= 0) return 0;
     if (rot != 32) return set_error_msg(1, "qkln_rope_bwd: rotary_dim 32 only");
     if ((ldg % 8) || (((uintptr_t)dq) & 15) || (((uintptr_t)dk) & 15) || (((uintptr_t)qkv) & 15) || (((uintptr_t)dqkv) & 15))
@@ -835,9 +855,20 @@ extern "C" int showo_qkln_rope_bwd(const uint16_t* dq, const uint16_t* dk, int l
     const int64_t rows = (int64_t)T * nH;
     const int nblk = (int)((rows + 4 * QKB_ROWS - 1) / (4 * QKB_ROWS));
     qkln_rope_bwd_kernel<<<dim3(nblk), dim3(256), 0, s>>>(dq, dk, ldg, qkv, qw, kw, cos_tab, sin_tab, dqkv, part, T, L, nH, eps);
-    colsum_reduce(part, dparams, nblk, 256, 0, s);  // (dqw, dqb, dkw, dkb) x 64
+    colsum_reduce(part, dparams, nblk, 256, accumulate != 0, s);  // (dqw, dqb, dkw, dkb) x 64
     SHOWO_CHECK_HIP(hipGetLastError());
     return 0;
+}
+extern "C" int showo_qkln_rope_bwd(const uint16_t* dq, const uint16_t* dk, int ldg, const uint16_t* qkv, const float* qw,
+                                   const float* kw, const float* cos_tab, const float* sin_tab, uint16_t* dqkv, float* part,
+                                   float* dparams, int T, int L, int nH, int rot, float eps, void* stream) {
+    return qkln_rope_bwd_impl(dq, dk, ldg, qkv, qw, kw, cos_tab, sin_tab, dqkv, part, dparams, 0, T, L, nH, rot, eps, stream);
+}
+// accumulating form: accumulate != 0 -> dparams = dparams_old + v (v = the bits showo_qkln_rope_bwd writes); dqkv is always overwritten
+extern "C" int showo_qkln_rope_bwd_acc(const uint16_t* dq, const uint16_t* dk, int ldg, const uint16_t* qkv, const float* qw,
+                                       const float* kw, const float* cos_tab, const float* sin_tab, uint16_t* dqkv, float* part,
+                                       float* dparams, int accumulate, int T, int L, int nH, int rot, float eps, void* stream) {
+    return qkln_rope_bwd_impl(dq, dk, ldg, qkv, qw, kw, cos_tab, sin_tab, dqkv, part, dparams, accumulate, T, L, nH, rot, eps, stream);
 }
 extern "C" int showo_qkln_rope_bwd_blocks(int T, int nH) { return (int)(((int64_t)T * nH + 4 * QKB_ROWS - 1) / (4 * QKB_ROWS)) + 8; }
 
@@ -873,7 +904,7 @@ int showo::ce_loss_dev_weights(const float* logits, int ldl, const int64_t* labe
     return 0;
 }
 
-extern "C" int showo_embed_bwd(const int64_t* ids, const float* dx, float* dE, int* order_ws, int T, int H, int V, void* stream) {
+static int embed_bwd_impl(const int64_t* ids, const float* dx, float* dE, int* order_ws, int accumulate, int T, int H, int V, void* stream) {
     if (T <= 0) return 0;
     if (H % 4) return set_error_msg(1, "embed_bwd: H % 4 == 0 required");
     (void)V;
@@ -881,9 +912,19 @@ extern "C" int showo_embed_bwd(const int64_t* ids, const float* dx, float* dE, i
     int* order = order_ws;
     int* runstart = order_ws + T;
     embed_rank_kernel<<<dim3((T + 63) / 64), dim3(256), 0, s>>>(ids, order, runstart, T);
-    embed_bwd_kernel<<<dim3(T), dim3(256), 0, s>>>(ids, order, runstart, dx, dE, T, H);
+    if (accumulate) embed_bwd_kernel<true><<<dim3(T), dim3(256), 0, s>>>(ids, order, runstart, dx, dE, T, H);
+    else embed_bwd_kernel<false><<<dim3(T), dim3(256), 0, s>>>(ids, order, runstart, dx, dE, T, H);
     SHOWO_CHECK_HIP(hipGetLastError());
     return 0;
+}
+extern "C" int showo_embed_bwd(const int64_t* ids, const float* dx, float* dE, int* order_ws, int T, int H, int V, void* stream) {
+    return embed_bwd_impl(ids, dx, dE, order_ws, 0, T, H, V, stream);
+}
+// accumulating form: accumulate != 0 adds the position-ordered row sums into the rows this batch touches (no zero-fill by the caller,
+// every other row of dE is left alone); accumulate == 0 is showo_embed_bwd
+extern "C" int showo_embed_bwd_acc(const int64_t* ids, const float* dx, float* dE, int* order_ws, int accumulate, int T, int H, int V,
+                                   void* stream) {
+    return embed_bwd_impl(ids, dx, dE, order_ws, accumulate, T, H, V, stream);
 }
 
 extern "C" int showo_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
@@ -984,8 +1025,8 @@ extern "C" int showo_dgelu_bf16(const uint16_t* da, const uint16_t* f, uint16_t*
 
 // showo_dgelu_bf16 on a [T, C] matrix (row stride ld; C % 8 == 0, 16-byte aligned) fused with showo_colsum_bf16 of its result:
 // colsum[c] = sum_t df[t][c] (the fc1 bias gradient).  colpart: fp32 scratch of (ceil(T / 64) + 8) * C floats.  df may alias da.
-extern "C" int showo_dgelu_colsum_bf16(const uint16_t* da, const uint16_t* f, uint16_t* df, int ld, int T, int C, float* colpart,
-                                       float* colsum, void* stream) {
+static int dgelu_colsum_impl(const uint16_t* da, const uint16_t* f, uint16_t* df, int ld, int T, int C, float* colpart, float* colsum,
+                             int accumulate, void* stream) {
     if (T <= 0 || C <= 0) return 0;
     if (!da || !f || !df || !colpart || !colsum) return set_error_msg(1, "dgelu_colsum: null argument");
     if ((C % 8) || (ld % 8) || ((((uintptr_t)da) | ((uintptr_t)f) | ((uintptr_t)df)) & 15))
@@ -993,9 +1034,18 @@ extern "C" int showo_dgelu_colsum_bf16(const uint16_t* da, const uint16_t* f, ui
     hipStream_t s = (hipStream_t)stream;
     const int nblk = (T + 63) / 64;
     dgelu_colsum_kernel<<<dim3((C + 2047) / 2048, nblk), dim3(256), 0, s>>>(da, f, df, colpart, T, C, ld);
-    colsum_reduce(colpart, colsum, nblk, C, 0, s);
+    colsum_reduce(colpart, colsum, nblk, C, accumulate != 0, s);
     SHOWO_CHECK_HIP(hipGetLastError());
     return 0;
+}
+extern "C" int showo_dgelu_colsum_bf16(const uint16_t* da, const uint16_t* f, uint16_t* df, int ld, int T, int C, float* colpart,
+                                       float* colsum, void* stream) {
+    return dgelu_colsum_impl(da, f, df, ld, T, C, colpart, colsum, 0, stream);
+}
+// accumulating form: accumulate != 0 -> colsum = colsum_old + v (v = the bits showo_dgelu_colsum_bf16 writes); df is always overwritten
+extern "C" int showo_dgelu_colsum_bf16_acc(const uint16_t* da, const uint16_t* f, uint16_t* df, int ld, int T, int C, float* colpart,
+                                           float* colsum, int accumulate, void* stream) {
+    return dgelu_colsum_impl(da, f, df, ld, T, C, colpart, colsum, accumulate, stream);
 }
 
 extern "C" int showo_gelu_bf16(const uint16_t* f, uint16_t* a, int64_t n, void* stream) {

@@ -141,10 +141,61 @@ def train_mask(tr, attention_mask):
     return attention_mask.detach().float().contiguous()
 
 
+class AccumulationWindow:
+    """Bookkeeping of gradient accumulation (reference: `accelerator.accumulate(model)` around the step body,
+    training/train.py:589-631, with `training.gradient_accumulation_steps` = k): a window is k consecutive micro-batches that feed
+    ONE optimizer step.  Pure Python, no device state: `position` is the index of the NEXT micro-batch inside its window,
+    `is_first` says that it overwrites the gradient buffer (the others add into it), `closes` that it is followed by the exchange,
+    clipping and the optimizer, and `loss_scale` = 1 / k is what accelerate multiplies every micro-batch loss by -- the window's
+    gradient is the mean of the micro-batch gradients (a mean of per-micro-batch means, not a global token mean)."""
+
+    def __init__(self, steps=1):
+        if int(steps) != steps or int(steps) < 1:
+            raise ValueError("gradient_accumulation_steps must be an integer >= 1")
+        self.steps = int(steps)
+        self.position = 0
+        self.windows_closed = 0
+
+    @property
+    def is_first(self):
+        return self.position == 0
+
+    @property
+    def closes(self):
+        return self.position == self.steps - 1
+
+    @property
+    def is_open(self):
+        """some micro-batch of the current window has run and its optimizer step has not: the gradient buffer holds a partial sum"""
+        return self.position != 0
+
+    @property
+    def loss_scale(self):
+        return 1.0 / self.steps
+
+    def scaled(self, coeffs):
+        """the loss weights of one micro-batch; k = 1 hands the caller's values through untouched"""
+        return tuple(coeffs) if self.steps == 1 else tuple(c / self.steps for c in coeffs)
+
+    def advance(self):
+        """one micro-batch done; returns True when it closed its window"""
+        closed = self.closes
+        self.position = 0 if closed else self.position + 1
+        self.windows_closed += int(closed)
+        return closed
+
+    def reset(self):
+        self.position = 0
+
+
 class Trainer:
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, coeffs=(1.0, 0.1, 1.0), group=None,
-                 wire="bf16", max_grad_norm=None, force_exchange=False, reserve_cus=None):
-        """wire: "bf16" | "fp32" gradient wire of the exchange (GradientExchange).  max_grad_norm: global-norm clipping before the
+                 wire="bf16", max_grad_norm=None, force_exchange=False, reserve_cus=None, gradient_accumulation_steps=1):
+        """gradient_accumulation_steps = k (every training YAML of the reference carries it): one step() call is one micro-batch;
+        the first of a window overwrites the native gradient buffer, the others add into it (the accumulating kernel forms,
+        showo_train_set_accumulate) with loss weights coeffs / k, and only the k-th runs the exchange, clipping, AdamW and the image
+        refresh.  `sync_gradients` (accelerate's name) is True exactly after a call that closed a window.  k = 1 is the plain step.
+        wire: "bf16" | "fp32" gradient wire of the exchange (GradientExchange).  max_grad_norm: global-norm clipping before the
         optimizer (training/train.py:614-615; null in the shipped stage-1 YAMLs).  force_exchange: run the exchange even in a
         process group of one rank (tests: drives the RCCL path on a single GPU).  reserve_cus: while an exchange is active the step's
         kernels run on a stream that keeps this many CUs free for RCCL's channel kernels (showo_stream_create_cu_mask; None = the
@@ -155,6 +206,10 @@ class Trainer:
         self.model, self.lr, self.betas, self.eps, self.wd, self.coeffs, self.group = model, lr, betas, eps, weight_decay, coeffs, group
         self.max_grad_norm = max_grad_norm
         self.step_count = 0
+        self.window = AccumulationWindow(gradient_accumulation_steps)
+        self.sync_gradients = False
+        self.grad_norm = None  # total norm (device scalar) found by the clipping of the last closed window; None without max_grad_norm
+        self._win_sum, self._win_n = None, 0
         self.params = [("showo." + n, p) for n, p in model.showo.named_parameters()]
         # the trainable set is read once, as the reference builds its optimizer once over the `requires_grad` parameters
         # (training/train.py:210-223): frozen tensors get no gradient, no exchange of a wholly frozen bucket and no update
@@ -203,7 +258,11 @@ class Trainer:
     # ---- checkpoint / resume of the optimizer (reference: accelerator.save_state / load_state, training/train.py:851-889, 429-443)
     def state_dict(self):
         """torch.optim.AdamW layout: {'state': {i: {'step', 'exp_avg', 'exp_avg_sq'}}, 'param_groups': [...]} with the parameters
-        numbered in `model.showo.named_parameters()` order, so the file is interchangeable with an AdamW built over that list"""
+        numbered in `model.showo.named_parameters()` order, so the file is interchangeable with an AdamW built over that list.
+        Refused inside an open accumulation window: the partial gradient sum is not part of the file."""
+        if self.window.is_open:
+            raise RuntimeError(f"Trainer.state_dict inside an open accumulation window (micro-batch {self.window.position} of "
+                               f"{self.window.steps}): the partial gradient sum is not saved; checkpoint when sync_gradients is True")
         state = {i: {"step": torch.tensor(float(self.step_count)), "exp_avg": self.m[n].detach().clone(),
                      "exp_avg_sq": self.v[n].detach().clone()} for i, (n, _) in enumerate(self.params)}
         group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.wd,
@@ -212,7 +271,9 @@ class Trainer:
 
     def load_state_dict(self, sd):
         """moments are copied INTO the tensors bound to the native optimizer (showo_train_bind_param); lr / betas / eps / weight
-        decay / step count are taken from the file"""
+        decay / step count are taken from the file.  An open accumulation window is dropped: the next step() starts a new one."""
+        self.window.reset()
+        self.sync_gradients = False
         names = [n for n, _ in self.params]
         if "param_names" in sd and list(sd["param_names"]) != names:
             raise ValueError("optimizer state was saved for a different parameter list")
@@ -236,7 +297,8 @@ class Trainer:
         self.step_count = steps.pop() if steps else 0
 
     def set_lr(self, lr):
-        """learning-rate schedulers (training/train.py:303-310 `get_scheduler`) call this between steps"""
+        """learning-rate schedulers (training/train.py:303-310 `get_scheduler`) call this between steps; inside an accumulation
+        window the value at the closing call is the one the optimizer uses"""
         self.lr = float(lr)
 
     def compute_stream(self):
@@ -263,6 +325,13 @@ class Trainer:
         ex.dist.all_reduce(v, op=ex.dist.ReduceOp.SUM, group=ex.group)
         return v / ex.world
 
+    def window_losses(self):
+        """device tensor [3]: the mean of the three losses over the micro-batches of the window that closed last (of the open window's
+        micro-batches so far while one is open); what the reference logs per optimizer step.  No host synchronisation."""
+        if self._win_sum is None:
+            raise RuntimeError("Trainer.window_losses: no step has run")
+        return self._win_sum if self._win_n == 1 else self._win_sum / self._win_n
+
     def close(self):
         """release the CU-masked compute stream (one HIP stream per Trainer that ran with reserve_cus > 0)"""
         h = getattr(self, "_masked_handle", None)
@@ -281,7 +350,8 @@ class Trainer:
             pass
 
     def step(self, input_ids, attention_mask, labels, batch_size_t2i, batch_size_lm, batch_size_mmu, max_seq_length):
-        """one optimisation step; returns the three losses (fp32 device tensor [3])"""
+        """one micro-batch (with gradient_accumulation_steps = 1: one optimisation step); returns its three losses, unscaled (fp32
+        device tensor [3])"""
         ms = None
         if getattr(self, "exchange", None) is not None and self.reserve_cus > 0:
             ms = self.compute_stream()
@@ -293,6 +363,8 @@ class Trainer:
             out = self._step(input_ids, attention_mask, labels, batch_size_t2i, batch_size_lm, batch_size_mmu, max_seq_length)
         cur.wait_stream(ms)
         out.record_stream(cur)  # allocated on the masked stream's pool, consumed on the caller's stream
+        if self._win_sum is not None:
+            self._win_sum.record_stream(cur)
         return out
 
     def _step(self, input_ids, attention_mask, labels, batch_size_t2i, batch_size_lm, batch_size_mmu, max_seq_length):
@@ -303,7 +375,11 @@ class Trainer:
         if any(bool(p.requires_grad) != self.trainable.get(n) for n, p in cur):
             raise RuntimeError("Trainer: requires_grad of model.showo's parameters changed after the Trainer was built; build a new "
                                "Trainer for the new trainable set")
+        win = self.window
         if self._binding_key(cur) != self._bound:  # new native trainer, or a parameter's storage moved: rebuild every raw-pointer binding
+            if win.is_open:
+                raise RuntimeError("Trainer: the native trainer or a parameter's storage changed inside an open accumulation window; "
+                                   "the partial gradient sum belongs to the old binding")
             self.params = cur
             self._bind()
         from .modeling_showo import sync_trainable
@@ -317,8 +393,44 @@ class Trainer:
         # the weights of the three losses are known up front here (training/train.py:600): the forward's cross-entropy pass also
         # writes d(loss)/d(logits), so the backward does not read the [B*L, V] logits again
         ex = self.exchange
+        # accumulation window: the first micro-batch overwrites the gradient buffer, the others add into it; accelerate's 1 / k on the
+        # micro-batch loss goes down as the loss weights, so the announced d(logits) of the forward's pass is still the one reused
+        w = win.scaled(self.coeffs)
+        closes = win.closes
+        self.sync_gradients = False
+        if not win.is_first:
+            _lib.call("showo_train_set_accumulate", tr, 1)
+        try:
+            self._micro_backward(m, tr, ids, mask, lab, B, L, batch_size_t2i, batch_size_lm, batch_size_mmu, max_seq_length, w, losses,
+                                 ex if closes else None)
+        finally:
+            # per call, like the announcement of the loss weights: the module's autograd path shares this native trainer and overwrites
+            if not win.is_first:
+                _lib.call("showo_train_set_accumulate", tr, 0)
+        if win.steps == 1:
+            self._win_sum, self._win_n = losses, 1
+        elif win.is_first:
+            self._win_sum, self._win_n = losses.clone(), 1
+        else:
+            self._win_sum += losses
+            self._win_n += 1
+        win.advance()
+        if not closes:
+            return losses
+        if ex is not None:
+            ex.finish()
+        self.grad_norm = self.clip_grad_norm_(self.max_grad_norm) if self.max_grad_norm is not None else None
+        self.step_count += 1
+        _lib.call("showo_train_adamw_step", tr, self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self.step_count, _lib.stream())
+        self.sync_gradients = True
+        return losses
+
+    def _micro_backward(self, m, tr, ids, mask, lab, B, L, batch_size_t2i, batch_size_lm, batch_size_mmu, max_seq_length, w, losses, ex):
+        """forward + backward of one micro-batch with loss weights w; ex: the exchange whose bucket collectives are launched as the
+        buckets finish (None: no exchange -- no process group, or a micro-batch that does not close its window)"""
+        s = _lib.stream
         nL = m.arch["num_hidden_layers"]
-        _lib.call("showo_train_set_loss_weights", tr, self.coeffs[0], self.coeffs[1], self.coeffs[2], 1)
+        _lib.call("showo_train_set_loss_weights", tr, w[0], w[1], w[2], 1)
         try:  # ONE scope for the announcement: a forward that raises must withdraw it too (ADVICE r4)
             try:
                 _lib.call("showo_train_forward", tr, _lib.ptr(ids), _lib.ptr(mask), _lib.ptr(lab), B, L, batch_size_t2i, batch_size_lm,
@@ -328,7 +440,7 @@ class Trainer:
             # `lab` is this step's own contiguous copy / view and is not written between the forward above and this call: the d(logits)
             # of the forward's cross-entropy pass is reused only for the SAME forward (every forward invalidates it), pointer, split and weights.
             _lib.call("showo_train_backward_head", tr, _lib.ptr(lab), batch_size_t2i, batch_size_lm, batch_size_mmu, max_seq_length,
-                      self.coeffs[0], self.coeffs[1], self.coeffs[2], s())
+                      w[0], w[1], w[2], s())
         finally:
             # the announcement is per step: a later forward with labels outside Trainer.step (the module's autograd path, an eval loop)
             # must not write the T x Vp d(logits) tensor (1.3 GB at the stage-1 batch) for a backward that never comes
@@ -347,13 +459,6 @@ class Trainer:
             _lib.call("showo_train_backward_embed", tr, s())
             if ex is not None:
                 ex.launch(0)
-        if ex is not None:
-            ex.finish()
-        if self.max_grad_norm is not None:
-            self.clip_grad_norm_(self.max_grad_norm)
-        self.step_count += 1
-        _lib.call("showo_train_adamw_step", tr, self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self.step_count, s())
-        return losses
 
     def clip_grad_norm_(self, max_norm):
         """torch.nn.utils.clip_grad_norm_ over the flat gradient buffer (reference training/train.py:614-615
