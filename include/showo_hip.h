@@ -398,6 +398,17 @@ int showo_qkln_rope_bwd_acc(const uint16_t* dq, const uint16_t* dk, int ldg, con
 int showo_ce_loss(const float* logits, int ldl, const int64_t* labels, int B, int L, int V, int b_t2i, int b_lm, int b_mmu,
                   int max_seq_len, float g_t2i, float g_lm, float g_mmu, void* rows_ws, int* counts, float* rowloss,
                   uint16_t* dlogits, int ldd, float* losses, void* stream);
+/* The row census of showo_ce_loss as an ORDERED compaction (the loss head on the labelled rows only, showo_train_set_loss_rows).
+ * A logits row (b, l) is labelled when it carries a t2i target (b < b_t2i, l > max_seq_len, labels[b, l] != -100) or a next-token
+ * target of the lm / mmu slice (l < L - 1, labels[b, l + 1] != -100; b_mmu == 0 selects the whole batch, the reference's
+ * logits[-0:]); a row can carry both.  Writes rows_ws (the 12-byte table of showo_ce_loss, all B*L rows) and counts int[3] as
+ * showo_ce_loss does, and: row_index int32 [Tc] = the labelled rows in ASCENDING row order, row_slot int32 [B*L] = the compact
+ * index of a row or -1, rows_compact = the table entries of the labelled rows in compact order (12 * B*L bytes), *n_rows = Tc.
+ * Ballot / popcount scan over blocks of rows in two passes, no atomic cursor: two runs give the same bits.
+ * scan_ws: int32 [showo_ce_rows_compact_ws(B * L)] (one int per scan block). */
+int showo_ce_rows_compact(const int64_t* labels, int B, int L, int b_t2i, int b_lm, int b_mmu, int max_seq_len, void* rows_ws,
+                          void* rows_compact, int* counts, int* row_index, int* row_slot, int* n_rows, int* scan_ws, void* stream);
+int showo_ce_rows_compact_ws(int rows);
 /* Embedding backward (deterministic): dE[ids[t]] = sum of dx[t] over equal ids, in position order.  dE must be
  * zero-filled by the caller; order_ws: scratch int[2*T]. */
 int showo_embed_bwd(const int64_t* ids, const float* dx, float* dE, int* order_ws, int T, int H, int V, void* stream);
@@ -695,6 +706,18 @@ int showo_train_set_input_grad(showo_trainer* t, int on);
  * first micro-batch, on for the rest; the sum differs from the fp64 sum of the per-micro-batch gradients by one fp32 rounding per
  * added micro-batch.  Frozen slots stay zero and side outputs pointed at scratch stay overwriting.  Default off. */
 int showo_train_set_accumulate(showo_trainer* t, int on);
+/* Loss head on the labelled rows only.  mode 0 (default): every launch as before.  mode 1: a showo_train_forward[_embeds] WITH labels
+ * runs the census above first, waits on the host once (after the blocks are queued, on an event recorded behind the census) for
+ * Tc, and runs the final LayerNorm (gathered), the lm_head GEMM and the cross-entropy on the Tc labelled rows; the head backward
+ * contracts over those rows and a row-slot LayerNorm backward scatters d(hidden) to the B*L rows (zeros elsewhere).  The [B*L, V]
+ * logits are not materialised: logits_out != NULL is refused (error 1).  Any other mode: error 1.  The backward of such a forward
+ * works from the forward's census: it must be asked for the same batch split, and does not read `labels` again.  Every gradient
+ * below lm_head equals the dense mode's; lm_head.weight / .bias differ in the grouping of their fp32 sums over rows; the losses in
+ * the last bit at most.  No labelled row at all: NaN losses (0 / 0), zero head gradients, no zero-sized launch.  The mode is per
+ * call, like showo_train_set_accumulate: reset it after the step, the module's autograd path shares the trainer. */
+int showo_train_set_loss_rows(showo_trainer* t, int mode);
+/* (rows the head of the last forward ran on, B*L of that forward); rows == total after a mode-0 forward.  No synchronisation. */
+int showo_train_loss_rows(showo_trainer* t, int* rows, int* total);
 /* launch counters since the last reset (tests): out6 = {weight-gradient GEMMs, data-gradient GEMMs, block phases that ran,
  * embedding-phase launches, transposed weight images rebuilt, fused block images rebuilt by the engine}; reset != 0 zeroes them */
 int showo_train_counters(showo_trainer* t, int64_t* out6, int reset);

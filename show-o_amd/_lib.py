@@ -65,6 +65,11 @@ _PROTOS = {
     "showo_embed_bwd_acc": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_p],
     "showo_dgelu_colsum_bf16_acc": [c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p, c_i, c_p],
     "showo_train_set_accumulate": [c_p, c_i],
+    # loss head on the labelled rows only
+    "showo_ce_rows_compact": [c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p],
+    "showo_ce_rows_compact_ws": [c_i],
+    "showo_train_set_loss_rows": [c_p, c_i],
+    "showo_train_loss_rows": [c_p, C.POINTER(c_i), C.POINTER(c_i)],
     "showo_train_create": [c_p, c_i, c_i, c_p],
     "showo_train_invalidate_weights": [c_p],
     "showo_train_set_trainable": [c_p, C.c_char_p, c_i],

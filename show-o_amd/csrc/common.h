@@ -318,4 +318,14 @@ int adamw_multi_launch(const AdamSeg* segs, const int* seg_of, const int64_t* st
 int ce_loss_dev_weights(const float* logits, int ldl, const int64_t* labels, int B, int L, int V, int b_t2i, int b_lm, int b_mmu,
                         int max_seq_len, const float* g3, void* rows_ws, int* counts, float* rowloss, uint16_t* dlogits, int ldd,
                         hipStream_t s);
+// The loss head on the labelled rows only (train_kernels.hip; the census itself is showo_ce_rows_compact).
+// ce_loss_compact: the cross-entropy over R compact rows -- rows_c / counts as the census left them, logits fp32 [R, ldl] and dlogits
+// bf16 [R, ldd] (optional) in compact row order; weights from g3[3] in device memory when g3 != NULL, else the three scalars; losses
+// (optional) finalised from the compact row losses.  R == 0 launches only the finalisation (0 / 0 = NaN, like an empty selection).
+int ce_loss_compact(const float* logits, int ldl, int R, int V, float g_t2i, float g_lm, float g_mmu, const float* g3, const void* rows_c,
+                    const int* counts, float* rowloss, uint16_t* dlogits, int ldd, float* losses, hipStream_t s);
+// ln_bwd_slot: showo_ln_bwd[_colsum]_acc over all T rows of x with dy = 0 and a COMPACT dh: row r reads dh[row_slot[r]], a row with
+// row_slot[r] < 0 reads nothing and gets zeros.  dxsum == NULL: no column sums of dx16.  Same partial layout and reduction order.
+int ln_bwd_slot(const float* x, const float* gamma, const float* dh, const int* row_slot, float* dx32, uint16_t* dx16, float* part,
+                float* dgb, float* dxsum, int accumulate_dgb, int accumulate_dxsum, int T, int H, float eps, hipStream_t s);
 }  // namespace showo

@@ -111,6 +111,16 @@ struct showo_trainer {
     int dl_split[4] = {0, 0, 0, 0};
     // gradient accumulation (showo_train_set_accumulate): every parameter-gradient write of the backward adds into the flat buffer
     bool accumulate = false;
+    // loss head on the labelled rows only (showo_train_set_loss_rows): the census of a forward with labels is an ordered compaction,
+    // its row count comes back through a pinned int (the one host wait of the mode) and the head runs on the compact rows
+    int loss_rows = 0;       // the mode the NEXT forward takes (0 = all rows)
+    bool compact = false;    // the LAST forward ran the compact head: logits / dlogits / hf / dh hold Tc rows in row_index order
+    int Tc = 0;              // its labelled rows
+    int lr_split[4] = {0, 0, 0, 0};  // and its batch split (the backward must be asked for the same one)
+    int *row_index = nullptr, *row_slot = nullptr, *scan_ws = nullptr;
+    void* ce_rows_c = nullptr;
+    int32_t* tc_host = nullptr;
+    hipEvent_t ev_tc = nullptr;
 
     template <class T>
     int alloc(T** p, int64_t n) {
@@ -233,7 +243,9 @@ extern "C" int showo_train_create(showo_engine* e, int max_batch, int max_seq, s
     rc |= t->alloc(&t->rowloss, 2 * T);
     rc |= t->alloc(&t->sc_ln, 2 * H); rc |= t->alloc(&t->sc_b, H); rc |= t->alloc(&t->sc_b1, F); rc |= t->alloc(&t->sc_qk, 256);
     rc |= t->alloc((char**)&t->ce_rows, 12 * T);
-    rc |= t->alloc(&t->counts, 4);
+    rc |= t->alloc(&t->counts, 4);  // the three valid-label counts + the labelled rows of the compact census
+    rc |= t->alloc((char**)&t->ce_rows_c, 12 * T);
+    rc |= t->alloc(&t->row_index, T); rc |= t->alloc(&t->row_slot, T); rc |= t->alloc(&t->scan_ws, showo_ce_rows_compact_ws((int)T));
     rc |= t->alloc(&t->order_ws, 2 * T);
     rc |= t->alloc(&t->losses, 4);
     rc |= t->alloc(&t->ids, T);
@@ -246,6 +258,8 @@ extern "C" void showo_train_destroy(showo_trainer* t) {
     if (!t) return;
     for (void* p : t->allocs) hipFree(p);
     if (t->adam_segs) { hipFree(t->adam_segs); hipFree(t->adam_seg_of); hipFree(t->adam_start_of); }
+    if (t->ev_tc) hipEventDestroy(t->ev_tc);
+    if (t->tc_host) hipHostFree(t->tc_host);
     delete t;
 }
 
@@ -363,6 +377,24 @@ extern "C" int showo_train_set_accumulate(showo_trainer* t, int on) {
     return 0;
 }
 
+// Loss head on the labelled rows only.  mode 1: a forward with labels runs the final LayerNorm, the lm_head GEMM and the cross-entropy
+// on the rows that carry a label (ordered compaction, showo_ce_rows_compact), and the head backward contracts over those rows; the
+// full logits are not materialised.  Per call, like the accumulate switch: the module's autograd path shares this trainer.
+extern "C" int showo_train_set_loss_rows(showo_trainer* t, int mode) {
+    if (!t) return set_error_msg(1, "train_set_loss_rows: null handle");
+    if (mode != 0 && mode != 1) return set_error_msg(1, "train_set_loss_rows: mode must be 0 (all rows) or 1 (labelled rows)");
+    t->loss_rows = mode;
+    return 0;
+}
+// (rows the head of the last forward ran on, rows of its batch): the host ints of the forward's one wait, no synchronisation here
+extern "C" int showo_train_loss_rows(showo_trainer* t, int* rows, int* total) {
+    if (!t || !rows || !total) return set_error_msg(1, "train_loss_rows: null argument");
+    if (!t->have_fwd) return set_error_msg(1, "train_loss_rows: run showo_train_forward first");
+    *total = t->B * t->Lq;
+    *rows = t->compact ? t->Tc : *total;
+    return 0;
+}
+
 extern "C" int showo_train_counters(showo_trainer* t, int64_t* out6, int reset) {
     if (!t) return set_error_msg(1, "train_counters: null handle");
     if (out6) {
@@ -388,6 +420,11 @@ namespace {
 __global__ void poison_losses_kernel(float* __restrict__ losses, const int32_t* __restrict__ flag) {
     if (threadIdx.x < 3 && *flag != 0) losses[threadIdx.x] = __builtin_nanf("");
 }
+// Row count of the compact head's GEMM launches (lm_head forward, dgrad): Tc rounded up to 256, at most T.  The labelled-row count
+// changes with every batch (the t2i masking rate is drawn per step) and the GEMM dispatch times its tile candidates once per distinct
+// (M, N, K): rounding bounds the shapes a run meets by T / 256.  The rows between Tc and the rounded count hold stale operands; a GEMM
+// row depends on its own operand row only, and nothing reads those output rows.
+int compact_gemm_rows(int Tc, int T) { return std::min(T, ((Tc + 255) / 256) * 256); }
 }  // namespace
 
 static int train_forward_impl(showo_trainer* t, const int64_t* ids, const float* embeds, const float* mask, const int64_t* labels,
@@ -398,6 +435,16 @@ static int train_forward_impl(showo_trainer* t, const int64_t* ids, const float*
     ++t->generation;
     showo_engine* e = t->e;
     if (showo_engine_missing(e) != 0) return set_error_msg(4, "train: weights missing");
+    const bool compact = t->loss_rows == 1 && labels != nullptr;
+    if (compact && logits_out)
+        return set_error_msg(1, "train_forward: loss rows = labelled (showo_train_set_loss_rows 1) does not materialise the [B*L, V] logits; "
+                                "pass logits_out = NULL, or set mode 0 for a forward that returns them");
+    if (compact) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        hipStreamIsCapturing(s, &cs);
+        if (cs != hipStreamCaptureStatusNone)
+            return set_error_msg(7, "train_forward: loss rows = labelled waits on the host for the row count; not inside a stream capture");
+    }
     if (B > t->maxB || L > t->maxL || (int64_t)B * L > t->Tmax) return set_error_msg(5, "train: batch exceeds the trainer workspace");
     if ((e->H % 64) || (e->F % 64)) return set_error_msg(1, "train: hidden/ffn must be multiples of 64");
     if (e->img_f16 || e->precision == 2)
@@ -410,6 +457,18 @@ static int train_forward_impl(showo_trainer* t, const int64_t* ids, const float*
     TRY(plan_sync(t, s));
     const int H = e->H, F = e->F, V = e->V, nH = e->nH, T = B * L;
     const int Lp = ((L + 63) / 64) * 64;
+    if (compact) {
+        // the row census first: its count is on its way to the host while the blocks are queued, and the wait below (before the head)
+        // is on this event only -- the stream keeps its queue
+        if (!t->tc_host) {
+            SHOWO_CHECK_HIP(hipHostMalloc((void**)&t->tc_host, 64, hipHostMallocDefault));
+            SHOWO_CHECK_HIP(hipEventCreateWithFlags(&t->ev_tc, hipEventDisableTiming));
+        }
+        TRY(showo_ce_rows_compact(labels, B, L, b_t2i, b_lm, b_mmu, max_seq_len, t->ce_rows, t->ce_rows_c, t->counts, t->row_index, t->row_slot,
+                                  t->counts + 3, t->scan_ws, s));
+        SHOWO_CHECK_HIP(hipMemcpyAsync(t->tc_host, t->counts + 3, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        SHOWO_CHECK_HIP(hipEventRecord(t->ev_tc, s));
+    }
     if (ids) {
         SHOWO_CHECK_HIP(hipMemcpyAsync(t->ids, ids, (size_t)T * 8, hipMemcpyDeviceToDevice, s));
         TRY(showo_embed_f32(ids, e->embed, t->L[0].x, T, H, V, s));  // layer 0's saved input IS the embedding output (no copy)
@@ -470,15 +529,42 @@ static int train_forward_impl(showo_trainer* t, const int64_t* ids, const float*
         }
         TRY(showo_gemm_bf16(ffn, F, w.w2, F, w.b2, 0, xnext, H, e->x, H, T, H, F, SHOWO_EPI_RESID_F32, s));
     }
+    int Tc = 0;
+    if (compact) {
+        SHOWO_CHECK_HIP(hipEventSynchronize(t->ev_tc));
+        Tc = *(volatile int32_t*)t->tc_host;
+        if (Tc < 0 || Tc > T) return set_error_msg(1, "train_forward: the row census returned a count outside [0, B*L]");
+        if (Tc > 0) {
+            // compact row j stands for row row_index[j]: gathered final LayerNorm, lm_head on the k-partition of the T-row launch
+            TRY(showo_layernorm_f32_bf16(e->x, e->fln_w, e->fln_b, e->hf, t->row_index, Tc, H, e->cfg.ln_eps, s));
+            showo::gemm_pin_split_m(T);
+            const int rc = showo_gemm_bf16(e->hf, H, e->wlm, H, e->blm, 0, t->logits, V, nullptr, 0, compact_gemm_rows(Tc, T), V, H, SHOWO_EPI_F32, s);
+            showo::gemm_pin_split_m(0);
+            TRY(rc);
+        }
+    } else {
     TRY(showo_layernorm_f32_bf16(e->x, e->fln_w, e->fln_b, e->hf, nullptr, T, H, e->cfg.ln_eps, s));
     TRY(showo_gemm_bf16(e->hf, H, e->wlm, H, e->blm, 0, t->logits, V, nullptr, 0, T, V, H, SHOWO_EPI_F32, s));
+    }
+    t->compact = compact;
+    t->Tc = Tc;
+    t->lr_split[0] = b_t2i; t->lr_split[1] = b_lm; t->lr_split[2] = b_mmu; t->lr_split[3] = max_seq_len;
     if (logits_out) SHOWO_CHECK_HIP(hipMemcpyAsync(logits_out, t->logits, (size_t)T * V * sizeof(float), hipMemcpyDeviceToDevice, s));
     t->B = B; t->Lq = L;
     t->have_fwd = true;
     t->has_mask = iv != nullptr;
     t->dl_valid = false;
     if (labels) {
-        if (t->lw_set) {  // one pass: losses and d(sum_g w_g loss_g)/d(logits)
+        if (compact) {  // the census ran ahead of the blocks: the cross-entropy of the Tc compact rows (none: only the 0 / 0 finalisation)
+            TRY(showo::ce_loss_compact(t->logits, V, Tc, V, t->lw[0], t->lw[1], t->lw[2], nullptr, t->ce_rows_c, t->counts, t->rowloss,
+                                       t->lw_set ? t->dlogits : nullptr, t->Vp, t->losses, s));
+            if (t->lw_set) {
+                t->dl_valid = true;
+                t->dl_labels = labels;
+                for (int k = 0; k < 3; ++k) t->dl_g[k] = t->lw[k];
+                t->dl_split[0] = b_t2i; t->dl_split[1] = b_lm; t->dl_split[2] = b_mmu; t->dl_split[3] = max_seq_len;
+            }
+        } else if (t->lw_set) {  // one pass: losses and d(sum_g w_g loss_g)/d(logits)
             TRY(showo_ce_loss(t->logits, V, labels, B, L, V, b_t2i, b_lm, b_mmu, max_seq_len, t->lw[0], t->lw[1], t->lw[2], t->ce_rows,
                               t->counts, t->rowloss, t->dlogits, t->Vp, t->losses, s));
             t->dl_valid = true;
@@ -539,23 +625,45 @@ static int wgrad_nt(const bf16_t* dyT, const bf16_t* xT, float* out, int ldo, in
 static int backward_head_from_dlogits(showo_trainer* t, void* stream) {
     BW_PROLOGUE
     TRY(plan_sync(t, s));
-    if (train_tn()) {
-        if (t->p_blm) TRY(showo_colsum_bf16(t->dlogits, Vp, T, Vp, t->colpart, t->gblm, acc, s));                         // lm_head bias grad
-        if (t->p_wlm) { TRY(showo_gemm_tn_bf16(t->dlogits, Vp, e->hf, H, t->gwlm, H, V, H, T, acc, 1, s)); ++t->cnt[0]; }   // dWlm [V,H]
+    // R: the token rows the lm_head gradients contract over -- all of them, or the Tc compact rows of a labelled-rows forward
+    // (dlogits, hf and dh are then compact; the row-slot LayerNorm backward scatters dh back to the T rows)
+    const int R = t->compact ? t->Tc : T;
+    if (R == 0) {  // no labelled row: the head's gradients are zero (accumulating: nothing is added), no zero-sized launch
+        if (!acc && t->p_blm) SHOWO_CHECK_HIP(hipMemsetAsync(t->gblm, 0, (size_t)Vp * sizeof(float), s));
+        if (!acc && t->p_wlm) SHOWO_CHECK_HIP(hipMemsetAsync(t->gwlm, 0, (size_t)V * H * sizeof(float), s));
+    } else if (train_tn()) {
+        if (t->p_blm) TRY(showo_colsum_bf16(t->dlogits, Vp, R, Vp, t->colpart, t->gblm, acc, s));                         // lm_head bias grad
+        if (t->p_wlm) { TRY(showo_gemm_tn_bf16(t->dlogits, Vp, e->hf, H, t->gwlm, H, V, H, R, acc, 1, s)); ++t->cnt[0]; }   // dWlm [V,H]
     } else {
     if (t->p_wlm || t->p_blm)  // dlogits^T + lm_head bias grad
-        TRY(showo_transpose_bf16(t->dlogits, Vp, t->bigT, T, Vp, Tp, 0, t->colpart, t->p_blm ? t->gblm : nullptr, acc, s));
+        TRY(showo_transpose_bf16(t->dlogits, Vp, t->bigT, R, Vp, Tp, 0, t->colpart, t->p_blm ? t->gblm : nullptr, acc, s));
     if (t->p_wlm) {
-    TRY(showo_transpose_bf16(e->hf, H, t->xT, T, H, Tp, 0, nullptr, nullptr, 0, s));
+    TRY(showo_transpose_bf16(e->hf, H, t->xT, R, H, Tp, 0, nullptr, nullptr, 0, s));
     TRY(wgrad_nt(t->bigT, t->xT, t->gwlm, H, V, H, Tp, acc, s));                                                       // dWlm [V,H]
     ++t->cnt[0];
     }
     }
     if (!t->p_fln && !below_needs(t, e->nL)) return 0;  // nothing below the head trains (linear probe): no dgrad, no LayerNorm backward
+    float* gfln = t->p_fln ? t->gfln : t->sc_ln;
+    if (t->compact) {
+        if (R > 0) {  // compact d hf on the k-partition of the T-row launch
+            showo::gemm_pin_split_m(T);
+            const int rc = showo_gemm_bf16(t->dlogits, Vp, t->wlmT, Vp, nullptr, 0, t->dh, H, nullptr, 0, compact_gemm_rows(R, T), H, Vp, SHOWO_EPI_F32, s);
+            showo::gemm_pin_split_m(0);
+            TRY(rc);
+            ++t->cnt[1];
+        }
+        // every row of dy / dy16 is written (zeros for the rows without a label): no clear of dy, and with R == 0 dh is never read
+        float* cb = (train_tn() && e->nL > 0) ? b2_dst(t, e->nL - 1) : nullptr;
+        const bool sums = train_tn() && e->nL > 0;
+        TRY(showo::ln_bwd_slot(e->x, e->fln_w, t->dh, t->row_slot, t->dy, t->dy16, t->lnpart, gfln, sums ? (cb ? cb : t->sc_b) : nullptr,
+                               acc && t->p_fln, acc && cb, T, H, e->cfg.ln_eps, s));
+        for (const Grad& g : t->fln_clear) SHOWO_CHECK_HIP(hipMemsetAsync(g.p, 0, (size_t)g.n * sizeof(float), s));
+        return 0;
+    }
     TRY(showo_gemm_bf16(t->dlogits, Vp, t->wlmT, Vp, nullptr, 0, t->dh, H, nullptr, 0, T, H, Vp, SHOWO_EPI_F32, s));   // d hf
     ++t->cnt[1];
     SHOWO_CHECK_HIP(hipMemsetAsync(t->dy, 0, (size_t)T * H * sizeof(float), s));
-    float* gfln = t->p_fln ? t->gfln : t->sc_ln;
     if (train_tn() && e->nL > 0) {  // + column sums of dy16 = the dense / fc2 bias gradients of the top block
         float* cb = b2_dst(t, e->nL - 1);
         TRY(showo_ln_bwd_colsum_acc(e->x, e->fln_w, t->dh, t->dy, t->dy, t->dy16, t->lnpart, gfln, cb ? cb : t->sc_b, acc && t->p_fln,
@@ -574,6 +682,15 @@ extern "C" int showo_train_backward_head(showo_trainer* t, const int64_t* labels
     const bool have_dl = t->dl_valid && t->dl_labels == labels && t->dl_g[0] == g_t2i && t->dl_g[1] == g_lm && t->dl_g[2] == g_mmu &&
                          t->dl_split[0] == b_t2i && t->dl_split[1] == b_lm && t->dl_split[2] == b_mmu && t->dl_split[3] == max_seq_len;
     t->dl_valid = false;  // dlogits^T below reuses nothing of it, but a second backward must not trust a consumed flag blindly
+    if (t->compact) {
+        // the compact logits are in the order of the forward's census: the backward works from that table and those counts
+        if (t->lr_split[0] != b_t2i || t->lr_split[1] != b_lm || t->lr_split[2] != b_mmu || t->lr_split[3] != max_seq_len)
+            return set_error_msg(1, "train_backward: the labelled-rows forward was made with another batch split");
+        if (!have_dl)
+            TRY(showo::ce_loss_compact(t->logits, V, t->Tc, V, g_t2i, g_lm, g_mmu, nullptr, t->ce_rows_c, t->counts, t->rowloss, t->dlogits, Vp,
+                                       nullptr, s));
+        return backward_head_from_dlogits(t, stream);
+    }
     if (!have_dl)
         TRY(showo_ce_loss(t->logits, V, labels, B, L, V, b_t2i, b_lm, b_mmu, max_seq_len, g_t2i, g_lm, g_mmu, t->ce_rows, t->counts,
                           t->rowloss, t->dlogits, Vp, nullptr, s));
@@ -587,6 +704,12 @@ extern "C" int showo_train_backward_head_dev(showo_trainer* t, const int64_t* la
     BW_PROLOGUE
     if (!labels || !g3) return set_error_msg(1, "train_backward_head_dev: labels and g3 required");
     t->dl_valid = false;
+    if (t->compact) {
+        if (t->lr_split[0] != b_t2i || t->lr_split[1] != b_lm || t->lr_split[2] != b_mmu || t->lr_split[3] != max_seq_len)
+            return set_error_msg(1, "train_backward_head_dev: the labelled-rows forward was made with another batch split");
+        TRY(showo::ce_loss_compact(t->logits, V, t->Tc, V, 0.f, 0.f, 0.f, g3, t->ce_rows_c, t->counts, t->rowloss, t->dlogits, Vp, nullptr, s));
+        return backward_head_from_dlogits(t, stream);
+    }
     TRY(showo::ce_loss_dev_weights(t->logits, V, labels, B, L, V, b_t2i, b_lm, b_mmu, max_seq_len, g3, t->ce_rows, t->counts, t->rowloss,
                                    t->dlogits, Vp, s));
     return backward_head_from_dlogits(t, stream);

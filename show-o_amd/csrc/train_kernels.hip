@@ -148,11 +148,14 @@ __global__ __launch_bounds__(256) void colsum_bf16_kernel(const bf16_t* __restri
 constexpr int LNB_ROWS = 16;  // 702 blocks at the stage-1 batch: two resident blocks on every CU (32 rows left a third of the slots empty)
 // DXS: also the column sums of the ROUNDED dx (dx16) -> part2[blk][H]: dx is the output gradient of the block below, and the bias
 // gradients of its dense and fc2 are exactly these column sums (saves a pass over dx16)
-template <bool DXS>
+// SLOT (the loss head on the labelled rows only): dh is COMPACT -- row r of x pairs with dh row row_slot[r]; a row with
+// row_slot[r] < 0 had no label, its dh would be an exact zero row: it loads nothing, gets zeros in dx32 / dx16 and adds nothing to
+// the column partials (the dense form adds exact zeros there), and dy is taken as zero (the head starts the residual gradient).
+template <bool DXS, bool SLOT = false>
 __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ x, const float* __restrict__ gamma,
                                                      const float* __restrict__ dh, const float* dy, float* dx32,
                                                      bf16_t* __restrict__ dx16, float* __restrict__ part, float* __restrict__ part2, int T,
-                                                     int H, float eps) {
+                                                     int H, float eps, const int* __restrict__ row_slot) {
     extern __shared__ float red[];  // [4][2][H] cross-wave reduction of the column partials
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int nv = (H + 255) / 256;  // float4 groups per lane (H % 4 == 0; lanes past the row end idle)
@@ -165,8 +168,19 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ x
     for (int rr = wave; rr < LNB_ROWS; rr += 4) {
         const int r = r0 + rr;
         if (r >= T) break;
+        const int64_t gsrc = SLOT ? (int64_t)row_slot[r] : (int64_t)r;
+        if (SLOT && gsrc < 0) {
+#pragma unroll
+            for (int i = 0; i < 8; ++i)
+                if (i < nv && (i * 64 + lane) * 4 < H) {
+                    const int c = (i * 64 + lane) * 4;
+                    *reinterpret_cast<float4*>(dx32 + (int64_t)r * H + c) = make_float4(0.f, 0.f, 0.f, 0.f);
+                    if (dx16) *reinterpret_cast<uint2*>(dx16 + (int64_t)r * H + c) = make_uint2(0u, 0u);
+                }
+            continue;
+        }
         const float* xr = x + (int64_t)r * H;
-        const float* gr = dh + (int64_t)r * H;
+        const float* gr = dh + gsrc * H;
         // the three rows this iteration reads (x, dh, dy: 24 KB) are requested up front: one HBM round trip per row instead of three
         float4 xv[8], gv[8], ov[8];
 #pragma unroll
@@ -175,7 +189,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const float* __restrict__ x
                 const int c = (i * 64 + lane) * 4;
                 xv[i] = *reinterpret_cast<const float4*>(xr + c);
                 gv[i] = *reinterpret_cast<const float4*>(gr + c);
-                ov[i] = *reinterpret_cast<const float4*>(dy + (int64_t)r * H + c);
+                ov[i] = SLOT ? make_float4(0.f, 0.f, 0.f, 0.f) : *reinterpret_cast<const float4*>(dy + (int64_t)r * H + c);
             }
         float s = 0.f;
 #pragma unroll
@@ -412,6 +426,74 @@ __global__ void ce_rows_kernel(const int64_t* __restrict__ labels, CeRow* __rest
         }
     }
     rows[r] = o;
+}
+
+// The same census as an ORDERED compaction (the loss head on the labelled rows only): besides the table and the counts,
+//   row_index[j] = the j-th row with bits != 0, ascending;  row_slot[r] = j for those rows, -1 for the others;  rows_c[j] =
+//   rows[row_index[j]];  *n_rows = Tc.
+// The compact order fixes the summation order of the lm_head gradients, so it must be the row order on every run: no atomic cursor.
+// Two passes over blocks of CEC_BLOCK rows: pass 1 classifies (ce_rows_kernel's rule, one row per thread) and leaves the block's
+// number of labelled rows in blocksum[blk] (wave64 ballot + popcount, the four wave totals added in wave order); pass 2 adds the
+// totals of the blocks before its own (integers: exact in any order), then places every labelled row at
+// block offset + totals of the lower waves + popcount of the lower lanes of its own wave's ballot.
+constexpr int CEC_BLOCK = 256;
+__global__ __launch_bounds__(CEC_BLOCK) void ce_rows_count_kernel(const int64_t* __restrict__ labels, CeRow* __restrict__ rows,
+                                                                  int* __restrict__ counts, int* __restrict__ blocksum, int B, int L,
+                                                                  int b_t2i, int b_lm, int b_mmu, int max_seq_len) {
+    __shared__ int wtot[CEC_BLOCK / 64];
+    const int r = blockIdx.x * CEC_BLOCK + threadIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    CeRow o;
+    o.labA = -100; o.labB = -100; o.bits = 0;
+    if (r < B * L) {
+        const int b = r / L, l = r - b * L;
+        if (b < b_t2i && l >= max_seq_len + 1) {
+            const int64_t t = labels[r];
+            if (t != -100) { o.labA = (int)t; o.bits |= 1; atomicAdd(&counts[0], 1); }
+        }
+        if (l < L - 1) {
+            const int64_t t = labels[r + 1];
+            if (t != -100) {
+                const bool in_lm = b >= b_t2i && b < b_t2i + b_lm;
+                const bool in_mmu = b_mmu == 0 ? true : b >= B - b_mmu;  // logits[-0:] selects the whole batch (reference quirk)
+                if (in_lm) { o.bits |= 2; atomicAdd(&counts[1], 1); }
+                if (in_mmu) { o.bits |= 4; atomicAdd(&counts[2], 1); }
+                if (in_lm || in_mmu) o.labB = (int)t;
+            }
+        }
+        rows[r] = o;
+    }
+    const unsigned long long live = __ballot(o.bits != 0);
+    if (lane == 0) wtot[wave] = __popcll(live);
+    __syncthreads();
+    if (threadIdx.x == 0) blocksum[blockIdx.x] = (wtot[0] + wtot[1]) + (wtot[2] + wtot[3]);
+}
+__global__ __launch_bounds__(CEC_BLOCK) void ce_rows_place_kernel(const CeRow* __restrict__ rows, const int* __restrict__ blocksum,
+                                                                  CeRow* __restrict__ rows_c, int* __restrict__ row_index,
+                                                                  int* __restrict__ row_slot, int* __restrict__ n_rows, int R) {
+    __shared__ int wtot[CEC_BLOCK / 64];
+    __shared__ int wpre[CEC_BLOCK / 64];
+    __shared__ int base;
+    const int r = blockIdx.x * CEC_BLOCK + threadIdx.x;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int before = 0;  // labelled rows of the blocks before this one
+    for (int k = threadIdx.x; k < (int)blockIdx.x; k += CEC_BLOCK) before += blocksum[k];
+    for (int off = 32; off > 0; off >>= 1) before += __shfl_xor(before, off);
+    CeRow o;
+    o.labA = -100; o.labB = -100; o.bits = 0;
+    if (r < R) o = rows[r];
+    const unsigned long long live = __ballot(o.bits != 0);
+    if (lane == 0) { wtot[wave] = __popcll(live); wpre[wave] = before; }
+    __syncthreads();
+    if (threadIdx.x == 0) base = (wpre[0] + wpre[1]) + (wpre[2] + wpre[3]);
+    __syncthreads();
+    int slot = base + __popcll(live & ((1ull << lane) - 1ull));
+    for (int w = 0; w < wave; ++w) slot += wtot[w];
+    if (r < R) {
+        if (o.bits != 0) { row_index[slot] = r; rows_c[slot] = o; row_slot[r] = slot; }
+        else row_slot[r] = -1;
+    }
+    if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *n_rows = base + (wtot[0] + wtot[1]) + (wtot[2] + wtot[3]);
 }
 
 // kDevW: the three loss weights come from device memory g3[3] (the autograd path, where they are the incoming gradients of the three
@@ -808,11 +890,34 @@ static int ln_bwd_impl(const float* x, const float* gamma, const float* dh, cons
     }
     if (dxsum) {
         // part is [nblk][3][H] (dgamma | dbeta | column sums of dx16): ONE reduce, columns < 2H -> dgb, the rest -> dxsum
-        ln_bwd_kernel<true><<<dim3(nblk), dim3(256), (size_t)8 * H * sizeof(float), s>>>(x, gamma, dh, dy, dx32, dx16, part, part + 2 * H, T, H, eps);
+        ln_bwd_kernel<true><<<dim3(nblk), dim3(256), (size_t)8 * H * sizeof(float), s>>>(x, gamma, dh, dy, dx32, dx16, part, part + 2 * H, T, H, eps, nullptr);
         colsum_reduce(part, dgb, nblk, 3 * H, (acc_dgb ? 1 : 0) | (acc_dxsum ? 2 : 0), s, dxsum, 2 * H);
     } else {
         // part is [nblk][2][H]: reduce it as a [nblk, 2H] matrix -> dgb = (dgamma[H], dbeta[H])
-        ln_bwd_kernel<false><<<dim3(nblk), dim3(256), (size_t)8 * H * sizeof(float), s>>>(x, gamma, dh, dy, dx32, dx16, part, nullptr, T, H, eps);
+        ln_bwd_kernel<false><<<dim3(nblk), dim3(256), (size_t)8 * H * sizeof(float), s>>>(x, gamma, dh, dy, dx32, dx16, part, nullptr, T, H, eps, nullptr);
+        colsum_reduce(part, dgb, nblk, 2 * H, acc_dgb ? 1 : 0, s);
+    }
+    SHOWO_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+int showo::ln_bwd_slot(const float* x, const float* gamma, const float* dh, const int* row_slot, float* dx32, uint16_t* dx16, float* part,
+                       float* dgb, float* dxsum, int acc_dgb, int acc_dxsum, int T, int H, float eps, hipStream_t s) {
+    if (T <= 0) return 0;
+    if ((H % 4) || H > 2048) return set_error_msg(1, "ln_bwd_slot: H must be a multiple of 4 and <= 2048");
+    if (!row_slot) return set_error_msg(1, "ln_bwd_slot: row_slot required");
+    if (dxsum && !dx16) return set_error_msg(1, "ln_bwd_slot: the column sums are those of dx16");
+    const int nblk = (T + LNB_ROWS - 1) / LNB_ROWS;
+    static bool attr_set = false;
+    if (!attr_set) {
+        SHOWO_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ln_bwd_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
+        SHOWO_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ln_bwd_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 65536));
+        attr_set = true;
+    }
+    if (dxsum) {
+        ln_bwd_kernel<true, true><<<dim3(nblk), dim3(256), (size_t)8 * H * sizeof(float), s>>>(x, gamma, dh, nullptr, dx32, dx16, part, part + 2 * H, T, H, eps, row_slot);
+        colsum_reduce(part, dgb, nblk, 3 * H, (acc_dgb ? 1 : 0) | (acc_dxsum ? 2 : 0), s, dxsum, 2 * H);
+    } else {
+        ln_bwd_kernel<false, true><<<dim3(nblk), dim3(256), (size_t)8 * H * sizeof(float), s>>>(x, gamma, dh, nullptr, dx32, dx16, part, nullptr, T, H, eps, row_slot);
         colsum_reduce(part, dgb, nblk, 2 * H, acc_dgb ? 1 : 0, s);
     }
     SHOWO_CHECK_HIP(hipGetLastError());
@@ -900,6 +1005,40 @@ int showo::ce_loss_dev_weights(const float* logits, int ldl, const int64_t* labe
     SHOWO_CHECK_HIP(hipMemsetAsync(counts, 0, 3 * sizeof(int), s));
     ce_rows_kernel<<<dim3((R + 255) / 256), dim3(256), 0, s>>>(labels, rows, counts, B, L, b_t2i, b_lm, b_mmu, max_seq_len);
     ce_kernel<true><<<dim3(R), dim3(256), 0, s>>>(logits, ldl, rows, counts, 0.f, 0.f, 0.f, g3, dlogits, ldd, rowloss, V);
+    SHOWO_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// The census of showo_ce_loss as an ordered compaction (header).  scan_ws: int[showo_ce_rows_compact_ws(B * L)].
+extern "C" int showo_ce_rows_compact(const int64_t* labels, int B, int L, int b_t2i, int b_lm, int b_mmu, int max_seq_len, void* rows_ws,
+                                     void* rows_compact, int* counts, int* row_index, int* row_slot, int* n_rows, int* scan_ws,
+                                     void* stream) {
+    if (B <= 0 || L <= 0) return set_error_msg(1, "ce_rows_compact: empty batch");
+    if (!labels || !rows_ws || !rows_compact || !counts || !row_index || !row_slot || !n_rows || !scan_ws)
+        return set_error_msg(1, "ce_rows_compact: null argument");
+    if ((int64_t)B * L > (int64_t)0x7fffffff - CEC_BLOCK) return set_error_msg(1, "ce_rows_compact: B * L exceeds 32-bit row indices");
+    hipStream_t s = (hipStream_t)stream;
+    const int R = B * L, nblk = (R + CEC_BLOCK - 1) / CEC_BLOCK;
+    CeRow* rows = reinterpret_cast<CeRow*>(rows_ws);
+    SHOWO_CHECK_HIP(hipMemsetAsync(counts, 0, 3 * sizeof(int), s));
+    ce_rows_count_kernel<<<dim3(nblk), dim3(CEC_BLOCK), 0, s>>>(labels, rows, counts, scan_ws, B, L, b_t2i, b_lm, b_mmu, max_seq_len);
+    ce_rows_place_kernel<<<dim3(nblk), dim3(CEC_BLOCK), 0, s>>>(rows, scan_ws, reinterpret_cast<CeRow*>(rows_compact), row_index, row_slot,
+                                                                n_rows, R);
+    SHOWO_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+extern "C" int showo_ce_rows_compact_ws(int rows) { return rows > 0 ? (rows + CEC_BLOCK - 1) / CEC_BLOCK : 1; }
+
+int showo::ce_loss_compact(const float* logits, int ldl, int R, int V, float g_t2i, float g_lm, float g_mmu, const float* g3,
+                           const void* rows_c, const int* counts, float* rowloss, uint16_t* dlogits, int ldd, float* losses,
+                           hipStream_t s) {
+    if (dlogits && ((ldd % 8) || ldd < V)) return set_error_msg(1, "ce_loss_compact: ldd must be a multiple of 8 and >= V");
+    const CeRow* rows = reinterpret_cast<const CeRow*>(rows_c);
+    if (R > 0) {
+        if (g3) ce_kernel<true><<<dim3(R), dim3(256), 0, s>>>(logits, ldl, rows, counts, 0.f, 0.f, 0.f, g3, dlogits, ldd, rowloss, V);
+        else ce_kernel<false><<<dim3(R), dim3(256), 0, s>>>(logits, ldl, rows, counts, g_t2i, g_lm, g_mmu, nullptr, dlogits, ldd, rowloss, V);
+    }
+    if (losses) ce_finalize_kernel<<<dim3(1), dim3(256), 0, s>>>(rowloss, rows, counts, losses, R);
     SHOWO_CHECK_HIP(hipGetLastError());
     return 0;
 }

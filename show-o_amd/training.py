@@ -188,9 +188,21 @@ class AccumulationWindow:
         self.position = 0
 
 
+LOSS_ROWS = ("all", "labelled")
+
+
+def loss_rows_mode(loss_rows):
+    """`Trainer(loss_rows=...)` -> the mode of showo_train_set_loss_rows: "all" = 0 (the head runs on every token row),
+    "labelled" = 1 (on the rows that carry a label).  Anything else is a ValueError (no device is touched)."""
+    if not isinstance(loss_rows, str) or loss_rows not in LOSS_ROWS:
+        raise ValueError(f"loss_rows must be one of {LOSS_ROWS}, got {loss_rows!r}")
+    return LOSS_ROWS.index(loss_rows)
+
+
 class Trainer:
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, coeffs=(1.0, 0.1, 1.0), group=None,
-                 wire="bf16", max_grad_norm=None, force_exchange=False, reserve_cus=None, gradient_accumulation_steps=1):
+                 wire="bf16", max_grad_norm=None, force_exchange=False, reserve_cus=None, gradient_accumulation_steps=1,
+                 loss_rows="all"):
         """gradient_accumulation_steps = k (every training YAML of the reference carries it): one step() call is one micro-batch;
         the first of a window overwrites the native gradient buffer, the others add into it (the accumulating kernel forms,
         showo_train_set_accumulate) with loss weights coeffs / k, and only the k-th runs the exchange, clipping, AdamW and the image
@@ -199,8 +211,14 @@ class Trainer:
         optimizer (training/train.py:614-615; null in the shipped stage-1 YAMLs).  force_exchange: run the exchange even in a
         process group of one rank (tests: drives the RCCL path on a single GPU).  reserve_cus: while an exchange is active the step's
         kernels run on a stream that keeps this many CUs free for RCCL's channel kernels (showo_stream_create_cu_mask; None = the
-        SHOWO_RESERVE_CUS environment variable, default 0 = no mask: profiles/r4_exchange_contention.txt)."""
+        SHOWO_RESERVE_CUS environment variable, default 0 = no mask: profiles/r4_exchange_contention.txt).
+        loss_rows: "all" (default) runs the loss head -- final LayerNorm, lm_head, cross-entropy and their backward -- on every token
+        row; "labelled" on the rows that enter a loss (masked image tokens of the t2i rows, text rows of the lm rows, answer tokens of
+        the mmu rows: training_utils.labelled_rows).  Same gradients below lm_head, lm_head's own differ in the grouping of their fp32
+        row sums; the forward waits once on the host for the row count (DESIGN.md "Loss head on labelled rows")."""
         import os
+        self._loss_rows_mode = loss_rows_mode(loss_rows)  # before anything touches the device
+        self.loss_rows = loss_rows
         self.reserve_cus = int(os.environ.get("SHOWO_RESERVE_CUS", "0")) if reserve_cus is None else int(reserve_cus)
         self._masked_stream = None
         self.model, self.lr, self.betas, self.eps, self.wd, self.coeffs, self.group = model, lr, betas, eps, weight_decay, coeffs, group
@@ -325,6 +343,18 @@ class Trainer:
         ex.dist.all_reduce(v, op=ex.dist.ReduceOp.SUM, group=ex.group)
         return v / ex.world
 
+    def set_loss_rows(self, loss_rows):
+        """switch the loss head between "all" and "labelled" rows for the following step() calls (same validation as the constructor)"""
+        self._loss_rows_mode = loss_rows_mode(loss_rows)
+        self.loss_rows = loss_rows
+
+    @property
+    def loss_rows_count(self):
+        """(rows the loss head of the last step ran on, token rows of its batch); host ints the forward already holds"""
+        rows, total = C.c_int(), C.c_int()
+        _lib.check(_lib.load().showo_train_loss_rows(self.tr, C.byref(rows), C.byref(total)), "showo_train_loss_rows")
+        return rows.value, total.value
+
     def window_losses(self):
         """device tensor [3]: the mean of the three losses over the micro-batches of the window that closed last (of the open window's
         micro-batches so far while one is open); what the reference logs per optimizer step.  No host synchronisation."""
@@ -400,13 +430,18 @@ class Trainer:
         self.sync_gradients = False
         if not win.is_first:
             _lib.call("showo_train_set_accumulate", tr, 1)
+        if self._loss_rows_mode:
+            _lib.call("showo_train_set_loss_rows", tr, self._loss_rows_mode)
         try:
             self._micro_backward(m, tr, ids, mask, lab, B, L, batch_size_t2i, batch_size_lm, batch_size_mmu, max_seq_length, w, losses,
                                  ex if closes else None)
         finally:
             # per call, like the announcement of the loss weights: the module's autograd path shares this native trainer and overwrites
+            # (and must return the full logits: it never runs the head on the labelled rows only)
             if not win.is_first:
                 _lib.call("showo_train_set_accumulate", tr, 0)
+            if self._loss_rows_mode:
+                _lib.call("showo_train_set_loss_rows", tr, 0)
         if win.steps == 1:
             self._win_sum, self._win_n = losses, 1
         elif win.is_first:

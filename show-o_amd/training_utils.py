@@ -107,3 +107,26 @@ def build_training_batch(uni_prompting, config, mask_id, mask_schedule, image_to
     flag = iv_t2i.flag | iv_lm.flag  # "needs more than two runs" of either predict-next block (mmu rows never do)
     mask = _pu.IntervalMask(torch.cat([iv_t2i.iv, iv_lm.iv, iv_mmu.iv], dim=0), flag)
     return input_ids, labels, mask, mask_prob, (ids_t2i.shape[0], ids_lm.shape[0], ids_mmu.shape[0])
+
+
+def labelled_rows(labels, batch_size_t2i, batch_size_lm, batch_size_mmu, max_seq_length):
+    """The logits rows that enter one of the three losses of `Showo.forward` (reference models/modeling_showo.py:83-98), as
+    ascending int64 indices into the flattened [B * L] rows.  Plain torch, works on CPU tensors: the stated rule of the row census
+    that `Trainer(loss_rows="labelled")` runs on the device (showo_ce_rows_compact).
+
+    Row (b, l) is labelled when
+      * b < batch_size_t2i, l > max_seq_length and labels[b, l] != -100         (loss_t2i: logits[:b_t2i, max_seq_length + 1:]), or
+      * l < L - 1, labels[b, l + 1] != -100 and b is an lm row                    (loss_lm: logits[b_t2i:b_t2i + b_lm, :-1]), or
+      * l < L - 1, labels[b, l + 1] != -100 and b is one of the last batch_size_mmu rows (loss_mmu: logits[-b_mmu:, :-1]);
+        batch_size_mmu == 0 selects the WHOLE batch there (`logits[-0:]`), as the reference's slicing does."""
+    B, L = labels.shape
+    valid = labels != -100
+    b = torch.arange(B, device=labels.device)[:, None]
+    l = torch.arange(L, device=labels.device)[None, :]
+    t2i = (b < batch_size_t2i) & (l >= max_seq_length + 1) & valid
+    nxt = torch.zeros_like(valid)
+    nxt[:, :-1] = valid[:, 1:]
+    in_lm = (b >= batch_size_t2i) & (b < batch_size_t2i + batch_size_lm)
+    in_mmu = torch.ones_like(in_lm) if batch_size_mmu == 0 else (b >= B - batch_size_mmu)
+    live = t2i | (nxt & (in_lm | in_mmu))
+    return torch.nonzero(live.reshape(-1)).reshape(-1).to(torch.int64)
