@@ -7,6 +7,12 @@ Checkpoints / tokenizer are optional local directories; without them random-init
 synthetic decimal-id tokenizer are used (same kernels, meaningless text).
 
     python examples/mmu_demo.py --max-new-tokens 32
+    python examples/mmu_demo.py --questions "What is in the image? *** What colour is it?"              # one prefill of the image prefix,
+    python examples/mmu_demo.py --questions "What is in the image? *** What colour is it?" --follow-up  # every question appended to it
+
+`--questions` takes the reference's ` *** ` separator (inference_mmu.py:86) and answers all of them from ONE `Showo.mmu_session`: the
+607-row prefix (<|mmu|>, system prompt, <|soi|>, image, <|eoi|>) is prefilled once; each question is appended to its KV cache and the
+session rewinds to the prefix for the next one.  `--follow-up` keeps the conversation instead: question 2 sees question 1 and its answer.
 """
 import argparse
 import os
@@ -33,6 +39,8 @@ def main():
     ap.add_argument("--tokenizer", default=None)
     ap.add_argument("--image", default=None, help="image file (needs --clip with its preprocessor_config.json); default: noise")
     ap.add_argument("--question", default=None)
+    ap.add_argument("--questions", default=None, help="several questions separated by ' *** ', answered from one mmu_session")
+    ap.add_argument("--follow-up", action="store_true", help="with --questions: ask each question in the same conversation (no rewind)")
     ap.add_argument("--max-new-tokens", type=int, default=100)
     ap.add_argument("--top-k", type=int, default=1)
     ap.add_argument("--temperature", type=float, default=1.0)
@@ -73,6 +81,20 @@ def main():
         txt = model.showo.model.embed_tokens(ids)
         cut = 2 + len(sys_ids)                                               # after <|mmu|>, the system prompt and <|soi|>
         emb = torch.cat([txt[:, :cut], img_emb, txt[:, cut:]], dim=1)
+        if a.questions:                                                      # one prefill of the prefix, no full-prompt call at all
+            prefix = emb[:, :cut + img_emb.shape[1] + 1].contiguous()             # ... up to and including <|eoi|>
+            sess = model.mmu_session(input_embeddings=prefix, attention_mask=intervals_for_mmu_vit(prefix, system_prompt_len=len(sys_ids)))
+            start = sess.mark()
+            for q in [q.strip() for q in a.questions.split(" *** ")]:
+                q_emb = model.showo.model.embed_tokens(torch.tensor([tok([q])["input_ids"][0]], device="cuda"))
+                ans = [int(t) for t in sess.generate(input_embeddings=q_emb, max_new_tokens=a.max_new_tokens, top_k=a.top_k,
+                                                     temperature=a.temperature, eot_token=tok.eos_token_id)]
+                print(f"[{sess.length} rows in the cache] {q!r} -> {len(ans)} tokens:", ans[:24], "..." if len(ans) > 24 else "")
+                if a.tokenizer:
+                    print(tok.decode(ans, skip_special_tokens=True))
+                if not a.follow_up:
+                    sess.rewind(start)
+            return
         mask = intervals_for_mmu_vit(emb, system_prompt_len=len(sys_ids))     # per-row intervals, no [1,1,L,L] tensor
         toks = model.mmu_generate(input_embeddings=emb, attention_mask=mask, max_new_tokens=a.max_new_tokens, top_k=a.top_k,
                                   temperature=a.temperature, eot_token=tok.eos_token_id)

@@ -644,6 +644,51 @@ int showo_engine_batch_decode_greedy(showo_engine* e, int64_t* tok, int n_steps,
 int showo_engine_batch_decode_sample(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws, const int* top_k,
                                      const float* temperature, const uint64_t* seed, const int* draw0, const float* const* exp_noise,
                                      const int* budget, int64_t eot, int* produced, int use_graph, void* stream);
+/* mmu sessions: continue a KV cache with more prompt rows, and fork it to the slots of a decode batch ("mmu sessions").
+ * For the mmu mask families every row at or beyond the end of the image sees what the last prefix row sees plus the columns up to
+ * itself, so K / V^T of the prefix do not depend on what follows it and an appended row is, mask-wise, a decode row.
+ *
+ * showo_mask_append_rows: iv int32 [Ln, 4] (device), row j = the decode rule applied to position P + j: the run of last_iv (HOST, the
+ * last prefill row's intervals) that ends at L0 is extended to P + j + 1, or an empty run becomes [L0, P + j + 1).  Error 6 when both
+ * runs are non-empty and neither ends at L0 (showo_engine_decode_step's refusal), 1 when iv is not 16-byte aligned (a row is one
+ * 16-byte store).  One launch.
+ * showo_kv_fork: bit copy of K rows [0, P) of every (layer, head) ([heads, cap, 64] per layer, layer stride k_lstride elements) and of
+ * V^T columns [0, P) of every (layer, head, dim) row ([heads, 64, cap] per layer) from a cache of capacity cap_src into one of capacity
+ * cap_dst (multiples of 64, >= P; pointers 16-byte aligned, layer strides multiples of 8), and zeroes V^T columns [P, 64 ceil(P / 64))
+ * of the destination.  Nothing else is written: K rows >= P and V^T columns beyond that tile keep their contents.  Two launches of
+ * 16-byte loads and stores (HBM-bound: 4 P 64 nL nH bytes read and as many written). */
+int showo_mask_append_rows(const int32_t* last_iv, int L0, int P, int Ln, int32_t* iv, void* stream);
+int showo_kv_fork(const uint16_t* k_src, const uint16_t* vt_src, int cap_src, int64_t k_lstride_src, int64_t v_lstride_src,
+                  uint16_t* k_dst, uint16_t* vt_dst, int cap_dst, int64_t k_lstride_dst, int64_t v_lstride_dst, int nL, int nH, int P,
+                  void* stream);
+/* showo_engine_prefill_append: Ln more prompt rows (ids or embeds, exactly one non-NULL) at positions P .. P + Ln - 1, P = the cache
+ * length, with the intervals of showo_mask_append_rows; their K / V^T join the decode cache, logits_last fp32 [vocab] = the logits of
+ * row P + Ln - 1, the cache length becomes P + Ln.  prompt_len and the last prefill row's intervals stay those of showo_engine_prefill
+ * (decode steps and further appends keep extending the same run).  Every precision showo_engine_prefill serves; the cache must have
+ * been prefilled under the current one.  Ln == 1 runs showo_engine_decode_step's layer and head launches (same bits) behind the
+ * tail-zeroing launch every append makes when P + Ln is no multiple of 64.  Errors: 1 without a
+ * prefill, 5 when P + Ln + 1 exceeds the cache capacity or max_position_embeddings, or Ln the workspace rows (max_batch * max_seq).
+ * showo_engine_cache_rewind: forget the rows >= len (prompt_len <= len <= cache length) and re-zero the V^T columns
+ * [len, 64 ceil(old length / 64)).  Invariant kept by prefill, append, rewind and fork: V^T columns [cache length, 64 ceil(cache
+ * length / 64)) of the cache they wrote are zero, so the attention's last key tile never multiplies P = 0 with a stale NaN.
+ * showo_engine_cache_state: any out pointer may be NULL; epoch = showo_engine_prefill calls on this engine so far (a host object
+ * that continues the cache can tell that another prompt replaced it).
+ * showo_engine_cache_ptrs / showo_engine_batch_slot_ptrs (test hooks): device pointers and layer strides (elements) of the decode
+ * cache / of slot b of the running batch, and the slot's capacity. */
+int showo_engine_prefill_append(showo_engine* e, const int64_t* ids, const float* embeds, int Ln, float* logits_last, void* stream);
+int showo_engine_cache_rewind(showo_engine* e, int len, void* stream);
+int showo_engine_cache_state(const showo_engine* e, int* cache_len, int* prompt_len, int* cap, int64_t* epoch);
+int showo_engine_cache_ptrs(showo_engine* e, uint16_t** k, uint16_t** vt, int64_t* k_lstride, int64_t* v_lstride);
+int showo_engine_batch_slot_ptrs(showo_engine* e, int b, uint16_t** k, uint16_t** vt, int64_t* k_lstride, int64_t* v_lstride, int* cap);
+/* showo_engine_batch_fork: showo_kv_fork of the decode cache [0, cache length) into slot b of the running batch; the slot takes the
+ * engine's cache length, prompt_len and last prefill row.  Like showo_engine_batch_prefill on a running batch it replaces the
+ * occupant and leaves the other slots alone.  Refused: cache length + 1 > the batch's capacity (5), precision 1 (1), a cache prefilled
+ * under another precision than the current one (1).
+ * showo_engine_batch_prefill_append: showo_engine_prefill_append on slot b (the same code with the slot as destination: the same
+ * prefix and rows give the same bits in the engine's cache and in a forked slot). */
+int showo_engine_batch_fork(showo_engine* e, int b, void* stream);
+int showo_engine_batch_prefill_append(showo_engine* e, int b, const int64_t* ids, const float* embeds, int Ln, float* logits_last,
+                                      void* stream);
 /* Next-token draw of the AR decode (modeling_showo.py:220-228): x = logits / temperature; values below the top_k-th largest
  * are dropped (top_k <= 0 or >= V: none); token = multinomial(softmax(x), 1) computed as argmax_i p_i / E_i, E ~ Exp(1):
  * E = exp_noise[step * V + i] when exp_noise != NULL (parity tests inject the reference's draws), else Philox(seed; step, i). */

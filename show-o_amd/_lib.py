@@ -172,6 +172,16 @@ _PROTOS = {
     "showo_engine_batch_prefill": [c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_p],
     "showo_engine_batch_decode_greedy": [c_p, c_p, c_i, c_p, c_p, c_i, c_p],
     "showo_engine_batch_decode_sample": [c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_i, c_p],
+    # mmu sessions: append prompt rows to a KV cache, fork it to the slots of a decode batch
+    "showo_mask_append_rows": [c_p, c_i, c_i, c_i, c_p, c_p],
+    "showo_kv_fork": [c_p, c_p, c_i, c_i64, c_i64, c_p, c_p, c_i, c_i64, c_i64, c_i, c_i, c_i, c_p],
+    "showo_engine_prefill_append": [c_p, c_p, c_p, c_i, c_p, c_p],
+    "showo_engine_cache_rewind": [c_p, c_i, c_p],
+    "showo_engine_cache_state": [c_p, C.POINTER(c_i), C.POINTER(c_i), C.POINTER(c_i), C.POINTER(c_i64)],
+    "showo_engine_cache_ptrs": [c_p, C.POINTER(c_p), C.POINTER(c_p), C.POINTER(c_i64), C.POINTER(c_i64)],
+    "showo_engine_batch_slot_ptrs": [c_p, c_i, C.POINTER(c_p), C.POINTER(c_p), C.POINTER(c_i64), C.POINTER(c_i64), C.POINTER(c_i)],
+    "showo_engine_batch_fork": [c_p, c_i, c_p],
+    "showo_engine_batch_prefill_append": [c_p, c_i, c_p, c_p, c_i, c_p, c_p],
     "showo_clip_create": [c_p, c_p],
     "showo_clip_load": [c_p, C.c_char_p, c_p, c_i64, c_p],
     "showo_clip_missing": [c_p],

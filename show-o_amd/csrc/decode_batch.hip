@@ -322,15 +322,6 @@ __global__ __launch_bounds__(512) void out_dense_y2B_kernel(OutGemvBArgs g) {
     }
 }
 
-// mask row of the token at position P: the last prompt row extended by the columns [L0, P] (modeling_showo.py:203-217)
-__device__ __forceinline__ void next_iv(const int32_t* last_iv, int L0, int P, int32_t* iv) {
-    int a = last_iv[0], b = last_iv[1], c = last_iv[2], d = last_iv[3];
-    if (b == L0 && a < b) b = P + 1;
-    else if (d == L0 && c < d) d = P + 1;
-    else if (!(c < d)) { c = L0; d = P + 1; }
-    else if (!(a < b)) { a = L0; b = P + 1; }
-    iv[0] = a; iv[1] = b; iv[2] = c; iv[3] = d;
-}
 __global__ void batch_iv_kernel(const int32_t* __restrict__ last_iv, const int* __restrict__ L0, const int* __restrict__ pos, int32_t* __restrict__ iv,
                                 int nb) {
     const int b = threadIdx.x;
@@ -661,6 +652,62 @@ extern "C" int showo_engine_batch_prefill(showo_engine* e, int b, const int64_t*
     d->prompt_len[b] = L;
     d->cache_len[b] = L;
     d->precision = e->precision;
+    return 0;
+}
+
+// ---- mmu sessions: a slot that starts as a copy of the engine's decode cache, and more prompt rows onto a slot ---------------------
+namespace showo {
+int engine_append_into(showo_engine* e, const int64_t* ids, const float* embeds, int Ln, int P, const int* last_iv, int L0, bf16_t* k,
+                       bf16_t* vt, int64_t k_lstride, int64_t v_lstride, int cap, float* logits_last, hipStream_t s, bf16_t* k_lo,
+                       bf16_t* vt_lo);
+}
+
+extern "C" int showo_engine_batch_slot_ptrs(showo_engine* e, int b, uint16_t** k, uint16_t** vt, int64_t* k_lstride, int64_t* v_lstride,
+                                            int* cap) {
+    if (!e || !e->bd || e->bd->nb == 0) return set_error_msg(1, "batch_slot_ptrs: showo_engine_batch_begin first");
+    auto* d = e->bd;
+    if (b < 0 || b >= d->nb) return set_error_msg(1, "batch_slot_ptrs: bad sequence index");
+    const int64_t per_seq = (int64_t)e->nH * d->cap * 64, lstride = (int64_t)d->nb * per_seq;
+    if (k) *k = d->k + b * per_seq;
+    if (vt) *vt = d->vt + b * per_seq;
+    if (k_lstride) *k_lstride = lstride;
+    if (v_lstride) *v_lstride = lstride;
+    if (cap) *cap = d->cap;
+    return 0;
+}
+
+extern "C" int showo_engine_batch_fork(showo_engine* e, int b, void* stream) {
+    if (!e || !e->bd || e->bd->nb == 0) return set_error_msg(1, "batch_fork: showo_engine_batch_begin first");
+    auto* d = e->bd;
+    if (b < 0 || b >= d->nb) return set_error_msg(1, "batch_fork: bad sequence index");
+    if (e->cache_len <= 0) return set_error_msg(1, "batch_fork: prefill first");
+    if (e->precision == 1) return set_error_msg(1, "batch_fork: the batched decode runs at precision 0, 2 or 3");
+    if (e->cache_precision != e->precision) return set_error_msg(1, "batch_fork: the KV cache was prefilled under another precision: prefill again");
+    if (e->cache_len + 1 > d->cap) return set_error_msg(5, "batch_fork: the cache exceeds the batch's cache capacity");
+    const int64_t per_seq = (int64_t)e->nH * d->cap * 64, lstride = (int64_t)d->nb * per_seq;
+    const int64_t src_lstride = (int64_t)e->nH * e->cache_cap * 64;
+    TRY(showo_kv_fork(e->kcache, e->vtcache, e->cache_cap, src_lstride, src_lstride, d->k + b * per_seq, d->vt + b * per_seq, d->cap, lstride,
+                      lstride, e->nL, e->nH, e->cache_len, stream));
+    d->prompt_len[b] = e->prompt_len;
+    d->cache_len[b] = e->cache_len;
+    for (int i = 0; i < 4; ++i) d->last_iv[b][i] = e->last_iv[i];
+    d->precision = e->precision;
+    return 0;
+}
+
+extern "C" int showo_engine_batch_prefill_append(showo_engine* e, int b, const int64_t* ids, const float* embeds, int Ln, float* logits_last,
+                                                 void* stream) {
+    if (!e || !e->bd || e->bd->nb == 0) return set_error_msg(1, "batch_prefill_append: showo_engine_batch_begin first");
+    auto* d = e->bd;
+    if (b < 0 || b >= d->nb) return set_error_msg(1, "batch_prefill_append: bad sequence index");
+    if (d->cache_len[b] <= 0) return set_error_msg(1, "batch_prefill_append: the slot has no prefill (showo_engine_batch_prefill / _batch_fork first)");
+    if (e->precision == 1) return set_error_msg(1, "batch_prefill_append: the batched decode runs at precision 0, 2 or 3");
+    if (d->precision != e->precision) return set_error_msg(1, "batch_prefill_append: the caches were prefilled under another precision: prefill again");
+    const int64_t per_seq = (int64_t)e->nH * d->cap * 64, lstride = (int64_t)d->nb * per_seq;
+    const int P = d->cache_len[b];
+    TRY(showo::engine_append_into(e, ids, embeds, Ln, P, d->last_iv[b], d->prompt_len[b], d->k + b * per_seq, d->vt + b * per_seq, lstride,
+                                  lstride, d->cap, logits_last, (hipStream_t)stream, nullptr, nullptr));
+    d->cache_len[b] = P + Ln;
     return 0;
 }
 

@@ -4,6 +4,16 @@
 
 namespace showo {
 
+// mask row of the token at position P (the batched decode seams, showo_mask_append_rows): the last prompt row extended by the columns [L0, P] (modeling_showo.py:203-217)
+static __device__ __forceinline__ void next_iv(const int32_t* last_iv, int L0, int P, int32_t* iv) {
+    int a = last_iv[0], b = last_iv[1], c = last_iv[2], d = last_iv[3];
+    if (b == L0 && a < b) b = P + 1;
+    else if (d == L0 && c < d) d = P + 1;
+    else if (!(c < d)) { c = L0; d = P + 1; }
+    else if (!(a < b)) { a = L0; b = P + 1; }
+    iv[0] = a; iv[1] = b; iv[2] = c; iv[3] = d;
+}
+
 static __device__ __forceinline__ void load4(const bf16_t* row, int k0, int K, uint4 (&wv)[4]) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) {

@@ -1499,6 +1499,7 @@ extern "C" int showo_engine_prefill(showo_engine* e, const int64_t* ids, const f
     TRY(ensure_cache(e, L + 1));
     if (e->precision == 1) TRY(ensure_cache_lo(e));
     const KVDest kv = kv_decode_cache(e);
+    ++e->cache_epoch;  // from here on the cache belongs to this prompt (also when the call fails half way)
     TRY(showo::engine_prefill_into(e, ids, embeds, mask, L, kv.k, kv.vt, kv.k_lstride, kv.v_lstride, kv.Lcap, e->last_iv, logits_last, s,
                                    kv.k_lo, kv.vt_lo));
     e->prompt_len = L;
@@ -1537,6 +1538,95 @@ extern "C" int showo_engine_decode_step(showo_engine* e, const int64_t* id, cons
     TRY(run_layers(e, 1, 1, P, kv_decode_cache(e), e->iv1, e->flag, nullptr, s));
     e->cache_len = P + 1;
     return head_rows(e, nullptr, 1, 0, e->V, logits_last, s);
+}
+
+// ---- mmu sessions: more prompt rows onto a cache (include/showo_hip.h; DESIGN.md, "mmu sessions") -------------------------------------
+static int zero_vt_tail(showo_engine* e, bf16_t* vt, bf16_t* vt_lo, int64_t v_lstride, int cap, int c0, int c1, hipStream_t s) {
+    if (c1 > cap) c1 = cap;
+    if (c1 <= c0) return 0;
+    zero_vt_cols_kernel<<<dim3(e->nH * 64, e->nL), 64, 0, s>>>(vt, v_lstride, cap, c0, c1);
+    if (vt_lo) zero_vt_cols_kernel<<<dim3(e->nH * 64, e->nL), 64, 0, s>>>(vt_lo, v_lstride, cap, c0, c1);
+    SHOWO_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+// Ln rows of ONE sequence at positions P .. P + Ln - 1 of a per-layer K / V^T destination that holds the rows below P (the engine's
+// decode cache, or a slot of a decode batch): every row attends as a decode row (last prefill row + causal), K / V^T of the new rows
+// land behind the old ones, logits_last = the logits of the last new row.  Ln == 1 is the decode step's layer and head launches behind the tail zeroing.
+namespace showo {
+int engine_append_into(showo_engine* e, const int64_t* ids, const float* embeds, int Ln, int P, const int* last_iv, int L0, bf16_t* k,
+                       bf16_t* vt, int64_t k_lstride, int64_t v_lstride, int cap, float* logits_last, hipStream_t s, bf16_t* k_lo,
+                       bf16_t* vt_lo) {
+    if (showo_engine_missing(e) != 0) return set_error_msg(4, "engine: weights missing (showo_engine_missing() != 0)");
+    if (Ln < 1 || !logits_last) return set_error_msg(1, "prefill_append: needs Ln >= 1 and a logits buffer");
+    if (Ln > e->maxT) return set_error_msg(5, "engine: batch/sequence exceeds the configured workspace");
+    if (P + Ln + 1 > cap || P + Ln + 1 > e->cfg.max_pos) return set_error_msg(5, "prefill_append: cache full");
+    int32_t lv[4] = {last_iv[0], last_iv[1], last_iv[2], last_iv[3]};
+    if (!((lv[1] == L0 && lv[0] < lv[1]) || (lv[3] == L0 && lv[2] < lv[3]) || !(lv[2] < lv[3]) || !(lv[0] < lv[1])))
+        return set_error_msg(6, "prefill_append: mask row needs more than two intervals");
+    TRY(embed_in(e, ids, embeds, Ln, s));
+    // the attention of the new rows reads whole 64-key tiles: the V^T columns behind the last new row meet P = 0 and must be finite
+    // (decode steps leave them as they found them, engine_prefill_into's comment says what may be there)
+    TRY(zero_vt_tail(e, vt, vt_lo, v_lstride, cap, P + Ln, ((P + Ln + 63) / 64) * 64, s));
+    const KVDest kv{k, vt, k_lstride, v_lstride, cap, cap, k_lo, vt_lo};
+    SHOWO_CHECK_HIP(hipMemsetAsync(e->flag, 0, 4, s));
+    if (Ln == 1) {  // showo_engine_decode_step
+        int a = lv[0], b = lv[1], c = lv[2], d = lv[3];
+        if (b == L0 && a < b) b = P + 1;
+        else if (d == L0 && c < d) d = P + 1;
+        else if (!(c < d)) { c = L0; d = P + 1; }
+        else { a = L0; b = P + 1; }
+        set_iv_kernel<<<1, 64, 0, s>>>(e->iv1, a, b, c, d);
+        TRY(run_layers(e, 1, 1, P, kv, e->iv1, e->flag, nullptr, s));
+        return head_rows(e, nullptr, 1, 0, e->V, logits_last, s);
+    }
+    TRY(showo_mask_append_rows(lv, L0, P, Ln, e->iv, s));
+    TRY(run_layers(e, 1, Ln, P, kv, e->iv, e->flag, nullptr, s));
+    set_iv_kernel<<<1, 64, 0, s>>>(e->rows, Ln - 1, 0, 0, 0);  // rows[0] = Ln - 1
+    return head_rows(e, e->rows, 1, 0, e->V, logits_last, s);
+}
+}  // namespace showo
+
+extern "C" int showo_engine_prefill_append(showo_engine* e, const int64_t* ids, const float* embeds, int Ln, float* logits_last,
+                                           void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!e || e->cache_len <= 0) return set_error_msg(1, "prefill_append: prefill first");
+    TRY(check_cache_precision(e));
+    if (e->precision == 1) TRY(ensure_cache_lo(e));
+    const KVDest kv = kv_decode_cache(e);
+    const int P = e->cache_len;
+    TRY(showo::engine_append_into(e, ids, embeds, Ln, P, e->last_iv, e->prompt_len, kv.k, kv.vt, kv.k_lstride, kv.v_lstride, kv.Lcap,
+                                  logits_last, s, kv.k_lo, kv.vt_lo));
+    e->cache_len = P + Ln;
+    return 0;
+}
+
+extern "C" int showo_engine_cache_rewind(showo_engine* e, int len, void* stream) {
+    if (!e || e->cache_len <= 0) return set_error_msg(1, "cache_rewind: prefill first");
+    if (len < e->prompt_len || len > e->cache_len) return set_error_msg(1, "cache_rewind: prompt_len <= len <= cache length required");
+    const KVDest kv = kv_decode_cache(e);
+    TRY(zero_vt_tail(e, kv.vt, kv.vt_lo, kv.v_lstride, kv.Lcap, len, ((e->cache_len + 63) / 64) * 64, (hipStream_t)stream));
+    e->cache_len = len;
+    return 0;
+}
+
+extern "C" int showo_engine_cache_state(const showo_engine* e, int* cache_len, int* prompt_len, int* cap, int64_t* epoch) {
+    if (!e) return set_error_msg(1, "engine: null handle");
+    if (cache_len) *cache_len = e->cache_len;
+    if (prompt_len) *prompt_len = e->prompt_len;
+    if (cap) *cap = e->cache_cap;
+    if (epoch) *epoch = e->cache_epoch;
+    return 0;
+}
+
+extern "C" int showo_engine_cache_ptrs(showo_engine* e, uint16_t** k, uint16_t** vt, int64_t* k_lstride, int64_t* v_lstride) {
+    if (!e || !e->kcache) return set_error_msg(1, "cache_ptrs: no decode cache yet (prefill first)");
+    const KVDest kv = kv_decode_cache(e);
+    if (k) *k = kv.k;
+    if (vt) *vt = kv.vt;
+    if (k_lstride) *k_lstride = kv.k_lstride;
+    if (v_lstride) *v_lstride = kv.v_lstride;
+    return 0;
 }
 
 // Visibility intervals built on the device (showo_mask_predict_next / _mmu / _mmu_vit) instead of a dense mask: the next

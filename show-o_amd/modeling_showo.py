@@ -937,6 +937,11 @@ class _MmuSlotEngine:
             model._graph_stream = torch.cuda.Stream()
 
     def prefill(self, s, r):
+        self.fill(s, r)
+        return self.first(s, r)
+
+    def fill(self, s, r):
+        """request r into slot s: its K / V^T in the slot's cache, its last row's logits in self.logits[s]"""
         from .prompting_utils import IntervalMask
         m, eng, L = self.model, self.eng, self.lens[r]
         ids = emb = None
@@ -952,6 +957,10 @@ class _MmuSlotEngine:
                       _lib.stream())
         finally:
             _lib.call("showo_engine_use_intervals", eng, None, None)
+
+    def first(self, s, r):
+        """request r's first token, drawn from self.logits[s]"""
+        m = self.model
         k = self.top_ks[r]
         if k == 1:
             _lib.call("showo_argmax_f32", _lib.ptr(self.logits[s]), m.vocab_size, _lib.ptr(self.tok[s:s + 1]), _lib.stream())
@@ -1107,6 +1116,384 @@ def _mmu_generate_batch_greedy(self, idx, input_embeddings, masks, max_new_token
 
 
 Showo._mmu_generate_batch_greedy = _mmu_generate_batch_greedy
+
+
+# ---- mmu sessions: one prefill of the question-invariant prefix, questions appended to its KV cache ("mmu sessions") -------
+class _SessionSlotEngine(_MmuSlotEngine):
+    """engine side of _mmu_batch_schedule for MmuSession.generate_batch: a slot is filled by a fork of the session's cache plus an
+    append of the request's rows instead of a prefill of a whole prompt"""
+
+    def __init__(self, model, eng, rows, lens, slots, temps, top_ks, seeds, noises, eot_token, dev):
+        super().__init__(model, eng, None, None, None, lens, slots, temps, top_ks, seeds, noises, eot_token, dev)
+        self.rows = rows
+
+    def fill(self, s, r):
+        ids, emb = self.rows[r]
+        _lib.call("showo_engine_batch_fork", self.eng, s, _lib.stream())
+        _lib.call("showo_engine_batch_prefill_append", self.eng, s, _lib.ptr(ids), _lib.ptr(emb), self.lens[r], _lib.ptr(self.logits[s]),
+                  _lib.stream())
+
+
+class _SessionEngine:
+    """engine side of MmuSession: the model's decode cache behind showo_engine_prefill / _prefill_append / _cache_rewind / _batch_fork
+    and the device loops of mmu_generate / mmu_generate_batch.  (Tests drive MmuSession with a stand-in of this class.)"""
+
+    def __init__(self, model):
+        self.model = model
+        self.eng = model.engine()
+        # the batched decode serves precision 0, 2 and 3 (showo_engine_batch_fork refuses 1): a precision-1 session answers
+        # generate_batch with the sequential calls, as mmu_generate_batch does
+        self.batched = int(getattr(model, "_precision", 0)) != 1
+        self.dev = model.showo.lm_head.weight.device
+        self.logits = torch.empty((model.vocab_size,), dtype=torch.float32, device=self.dev)
+        self.logits0 = None
+        self.tok = torch.empty((1,), dtype=torch.int64, device=self.dev)
+        if getattr(model, "_graph_stream", None) is None:
+            model._graph_stream = torch.cuda.Stream()
+
+    def state(self):
+        """(cache length, prompt length, capacity, epoch) of the engine's decode cache"""
+        import ctypes as C
+        n, p, cap, ep = C.c_int(), C.c_int(), C.c_int(), C.c_int64()
+        _lib.call("showo_engine_cache_state", self.eng, C.byref(n), C.byref(p), C.byref(cap), C.byref(ep))
+        return n.value, p.value, cap.value, ep.value
+
+    def stamp(self):
+        """what must not change under a live session: the engine, its weights and precision, and the prompt in its decode cache.
+        None once the model dropped the engine this session was opened on (configure_workspace): `self.eng` is then a destroyed
+        handle and nothing may be asked of it, so the handle OBJECT is compared first (a later engine may reuse the address)."""
+        m = self.model
+        if m._engine is not self.eng:
+            return None
+        m.engine()
+        return (self.state()[3], int(getattr(m, "_precision", 0)), dict(m._engine_versions))
+
+    def cached_rows(self):
+        """rows the engine itself counts in its decode cache (MmuSession holds its own `length` against it)"""
+        return self.state()[0]
+
+    def prefill(self, idx, input_embeddings, attention_mask):
+        from .prompting_utils import IntervalMask
+        m, eng = self.model, self.eng
+        ids = None if idx is None else idx.to(torch.int64).contiguous()
+        emb = None if input_embeddings is None else input_embeddings.detach().float().contiguous()
+        L = (ids if ids is not None else emb).shape[1]
+        if isinstance(attention_mask, IntervalMask):
+            mask = m._use_mask(eng, attention_mask)
+        else:
+            mask = None if attention_mask is None else attention_mask.detach().float().reshape(1, 1, L, L).contiguous()
+        try:
+            _lib.call("showo_engine_prefill", eng, _lib.ptr(ids), _lib.ptr(emb), _lib.ptr(mask), L, _lib.ptr(self.logits), _lib.stream())
+        finally:
+            _lib.call("showo_engine_use_intervals", eng, None, None)
+        self.logits0 = self.logits.clone()
+        return L
+
+    def embed(self, token):
+        return self.model.showo.model.embed_tokens.weight.detach()[int(token)].float().reshape(1, 1, -1)
+
+    def use_prefix_logits(self):
+        self.logits.copy_(self.logits0)
+
+    def append(self, ids, emb, Ln):
+        _lib.call("showo_engine_prefill_append", self.eng, _lib.ptr(ids), _lib.ptr(emb), Ln, _lib.ptr(self.logits), _lib.stream())
+
+    def rewind(self, length):
+        _lib.call("showo_engine_cache_rewind", self.eng, int(length), _lib.stream())
+
+    def settle(self, length, toks):
+        """after run(): the cache keeps the rows below `length` and the fed tokens toks[:-1] (a chunk of the device loop may have run
+        past an <eot>)"""
+        self.rewind(length + len(toks) - 1)
+
+    def run(self, max_new_tokens, greedy, k, temperature, noise, seed, eot_token):
+        """Showo.mmu_generate behind its prefill: the first token from the current logits, the rest from the device loop in chunks"""
+        m, eng, logits, tok = self.model, self.eng, self.logits, self.tok
+        if greedy:
+            _lib.call("showo_argmax_f32", _lib.ptr(logits), m.vocab_size, _lib.ptr(tok), _lib.stream())
+        else:
+            _lib.call("showo_sample_topk", _lib.ptr(logits), m.vocab_size, k, float(temperature), _lib.ptr(noise), seed, 0, _lib.ptr(tok),
+                      _lib.stream())
+        result = [int(tok.item())]
+        if (eot_token is not None and result[0] == eot_token) or max_new_tokens <= 1:
+            return result
+        use_graph, chunk = int(getattr(m, "decode_graph", 1)), 16
+        cur = torch.cuda.current_stream()
+        remaining = max_new_tokens - 1
+        while remaining > 0:
+            n = min(chunk, remaining)
+            outc = torch.empty((n,), dtype=torch.int64, device=self.dev)
+            m._graph_stream.wait_stream(cur)
+            with torch.cuda.stream(m._graph_stream):
+                if greedy:
+                    _lib.call("showo_engine_decode_greedy", eng, _lib.ptr(tok), n, _lib.ptr(outc), _lib.ptr(logits), use_graph, _lib.stream())
+                else:
+                    _lib.call("showo_engine_decode_sample", eng, _lib.ptr(tok), n, _lib.ptr(outc), _lib.ptr(logits), k, float(temperature),
+                              _lib.ptr(noise), seed, max_new_tokens - remaining, use_graph, _lib.stream())
+            cur.wait_stream(m._graph_stream)
+            for t in outc.tolist():
+                result.append(t)
+                if eot_token is not None and t == eot_token:
+                    return result
+            remaining -= n
+        return result
+
+    def run_batch(self, length, rows, lens, max_new_tokens, temps, top_ks, seeds, noises, eot_token):
+        """n continuations of the cache [0, length) on the slots of a decode batch; None when the batch does not fit the engine"""
+        n = len(rows)
+        slots = _mmu_batch_slots(n)
+        try:
+            _lib.call("showo_engine_batch_begin", self.eng, slots, length + max(lens) + max_new_tokens + 1)
+        except RuntimeError:
+            return None
+        se = _SessionSlotEngine(self.model, self.eng, rows, lens, slots, temps, top_ks, seeds, noises, eot_token, self.dev)
+        return _mmu_batch_schedule(se, n, slots, max_new_tokens, eot_token)
+
+
+class _SessionRecompute:
+    """engine side of MmuSession in accuracy mode without the production-kernel form (tiny test shapes): no KV cache, the session
+    keeps the embeddings and the dense mask and every generate runs the reference's own algorithm on them (_mmu_generate_recompute)"""
+    batched = False
+
+    def __init__(self, model):
+        self.model = model
+        self.dev = model.showo.lm_head.weight.device
+        self.emb = self.mask = None
+
+    def stamp(self):
+        return ()
+
+    def cached_rows(self):
+        return self.emb.shape[1]
+
+    def embed(self, token):
+        return self.model.showo.model.embed_tokens.weight.detach()[int(token)].float().reshape(1, 1, -1)
+
+    def prefill(self, idx, input_embeddings, attention_mask):
+        if input_embeddings is not None:
+            self.emb = input_embeddings.detach().float().contiguous()
+        else:
+            self.emb = self.model.showo.model.embed_tokens.weight.detach().float()[idx.to(torch.int64)].contiguous()
+        L = self.emb.shape[1]
+        self.mask = _dense_mask_of(attention_mask, L, self.dev)
+        return L
+
+    def use_prefix_logits(self):
+        pass
+
+    def append(self, ids, emb, Ln):
+        if emb is None:
+            emb = self.model.showo.model.embed_tokens.weight.detach().float()[ids]
+        L = self.emb.shape[1]
+        neg = float(torch.finfo(torch.float32).min)
+        grown = torch.full((1, 1, L + Ln, L + Ln), neg, dtype=torch.float32, device=self.dev)
+        grown[0, 0, :L, :L] = self.mask[0, 0]
+        grown[0, 0, L:, :L] = self.mask[0, 0, L - 1]  # every new row: the last row + causal among the new ones
+        grown[0, 0, L:, L:].masked_fill_(torch.ones((Ln, Ln), dtype=torch.bool, device=self.dev).tril(), 0.0)
+        self.emb, self.mask = torch.cat([self.emb, emb.reshape(1, Ln, -1)], dim=1).contiguous(), grown
+
+    def rewind(self, length):
+        self.emb, self.mask = self.emb[:, :length].contiguous(), self.mask[:, :, :length, :length].contiguous()
+
+    def settle(self, length, toks):
+        if len(toks) > 1:
+            self.append(torch.tensor([toks[:-1]], dtype=torch.int64, device=self.dev), None, len(toks) - 1)
+
+    def run(self, max_new_tokens, greedy, k, temperature, noise, seed, eot_token):
+        out = self.model._mmu_generate_recompute(None, self.emb, self.mask, max_new_tokens, temperature, 1 if greedy else k, eot_token,
+                                                 greedy, None if greedy else (k, seed, noise))
+        return [int(t) for t in out]
+
+
+class MmuSession:
+    """A conversation about one prefix (`Showo.mmu_session`): the prefix is prefilled once, every `generate` appends its rows to the
+    KV cache and decodes, `mark` / `rewind` go back to an earlier state, `generate_batch` answers n questions about the current state
+    together.  `length`: rows in the cache; `prefix_length`: rows of the prefill (the floor of `rewind`)."""
+
+    def __init__(self, model, idx=None, input_embeddings=None, attention_mask=None, _engine=None):
+        if (idx is None) == (input_embeddings is None):
+            raise ValueError("exactly one of idx / input_embeddings must be given")
+        if (idx if idx is not None else input_embeddings).shape[0] != 1:
+            raise ValueError("an mmu session has batch-1 semantics, like mmu_generate (reference modeling_showo.py:204,229)")
+        self.model = model
+        if _engine is not None:
+            self._be = _engine
+        elif int(getattr(model, "_precision", 0)) == 1 and (getattr(model, "precise_recompute", False) or
+                                                            not _lib.load().showo_engine_precise_fast(model.engine())):
+            self._be = _SessionRecompute(model)
+        else:
+            self._be = _SessionEngine(model)
+        self.prefix_length = self.length = int(self._be.prefill(idx, input_embeddings, attention_mask))
+        self._pending = None  # the last token handed out: not in the cache yet, fed in front of the next rows
+        self._stamp = self._be.stamp()
+
+    def _check(self):
+        stamp = self._be.stamp()
+        if stamp is None or stamp != self._stamp:
+            raise RuntimeError("this mmu session is stale: the engine's decode cache, weights or precision changed since it was opened "
+                               "(mmu_generate, a newer mmu_session, set_precision, configure_workspace or a weight update); open a new "
+                               "session")
+        if self._be.cached_rows() != self.length:
+            raise RuntimeError(f"this mmu session is out of step with its cache ({self._be.cached_rows()} rows cached, {self.length} "
+                               "expected: an earlier call failed midway and could not be undone); open a new session")
+
+    def mark(self):
+        """the current state (rows in the cache, pending token) for a later `rewind`"""
+        return (self.length, self._pending)
+
+    def rewind(self, mark):
+        """back to a state `mark()` returned earlier in THIS session (its length is between the prefix length and the current one)"""
+        length, pending = mark
+        if not self.prefix_length <= int(length) <= self.length:
+            raise ValueError(f"rewind: length {length} outside [{self.prefix_length}, {self.length}]")
+        if pending is None and int(length) != self.prefix_length:
+            raise ValueError("rewind: a state behind the prefix needs its pending token (pass what mark() returned)")
+        self._check()
+        self._be.rewind(int(length))
+        self.length, self._pending = int(length), pending
+
+    def _rows(self, idx, input_embeddings):
+        """the caller's [1, Ln] ids or [1, Ln, H] embeddings with the pending token in front: (ids, emb, Ln), all None / 0 for no rows"""
+        if idx is not None and input_embeddings is not None:
+            raise ValueError("at most one of idx / input_embeddings")
+        dev, p = self._be.dev, self._pending
+        if input_embeddings is not None:
+            if input_embeddings.shape[0] != 1:
+                raise ValueError("an mmu session has batch-1 semantics")
+            emb = input_embeddings.detach().float().to(dev)
+            if p is not None:
+                emb = torch.cat([self._be.embed(p).to(dev), emb], dim=1)
+            return None, emb.contiguous(), int(emb.shape[1])
+        ids = None if idx is None else idx.to(torch.int64).to(dev).reshape(1, -1)
+        if p is not None:
+            head = torch.tensor([[int(p)]], dtype=torch.int64, device=dev)
+            ids = head if ids is None else torch.cat([head, ids], dim=1)
+        if ids is None or ids.shape[1] == 0:
+            return None, None, 0
+        return ids.contiguous(), None, int(ids.shape[1])
+
+    def _draw_args(self, max_new_tokens, temperature, top_k, generator, noise):
+        """(greedy, k, noise, seed) exactly as mmu_generate derives them (one seed draw per sampled call)"""
+        if max_new_tokens < 1:
+            raise ValueError("max_new_tokens must be >= 1")
+        if top_k == 1:
+            return True, 1, None, 0
+        if not temperature > 0:
+            raise ValueError("temperature must be > 0")
+        if generator is not None:
+            seed = int(torch.randint(0, 2 ** 62, (1,), generator=generator, device=generator.device).item())
+        else:
+            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        if noise is not None:
+            noise = noise.detach().float().contiguous()
+            if tuple(noise.shape) != (max_new_tokens, self.model.vocab_size):
+                raise ValueError("_exp_noise must be [max_new_tokens, vocab_size]")
+        return False, 0 if top_k is None else int(top_k), noise, seed
+
+    @torch.no_grad()
+    def generate(self, idx=None, input_embeddings=None, max_new_tokens=100, temperature=1.0, top_k=None, eot_token=None, generator=None,
+                 _exp_noise=None):
+        """Append the rows (ids [1, Ln] or embeddings [1, Ln, H]; none: continue where the last call stopped), then decode like
+        `mmu_generate`: same return type, `eot_token` cut, greedy pick for top_k == 1 and sampled draws.  Afterwards the cache holds the
+        prefix, the rows and the answer up to its last token but one; the last token is pending and is fed first by the next call."""
+        self._check()
+        ids, emb, Ln = self._rows(idx, input_embeddings)
+        if Ln == 0 and self.length != self.prefix_length:
+            raise ValueError("generate: no rows and no pending token to continue from")
+        greedy, k, noise, seed = self._draw_args(max_new_tokens, temperature, top_k, generator, _exp_noise)
+        start = self.length
+        try:
+            if Ln:
+                self._be.append(ids, emb, Ln)
+                self.length += Ln
+            else:
+                self._be.use_prefix_logits()
+            toks = self._be.run(max_new_tokens, greedy, k, temperature, noise, seed, eot_token)
+            self._be.settle(self.length, toks)
+        except BaseException:
+            # a call that fails midway (a full cache inside the decode loop) leaves the session where it was: the rows it wrote are
+            # dropped; if even that fails, _check finds the cache out of step on the next call
+            self.length = start
+            if self._be.cached_rows() != start:
+                self._be.rewind(start)
+            raise
+        self.length += len(toks) - 1
+        self._pending = toks[-1]
+        return [torch.tensor(t, device=self._be.dev) for t in toks]
+
+    @torch.no_grad()
+    def generate_batch(self, idx=None, input_embeddings=None, max_new_tokens=100, temperature=1.0, top_k=None, eot_token=None,
+                       generator=None, _exp_noise=None):
+        """n continuations of the CURRENT state: `idx` / `input_embeddings` is a list of n row blocks ([1, Ln_i] ids or [1, Ln_i, H]
+        embeddings), `temperature` / `top_k` scalars or lists, `_exp_noise` None or a list.  result[i] is what `generate(<block i>)`
+        followed by a rewind returns when those calls are made in order (same seeds from `generator`); the session is left unchanged.
+        n >= 2 at precision 0, 2, 3 runs on the slots of a decode batch, each slot a fork of this cache."""
+        self._check()
+        seqs = idx if idx is not None else input_embeddings
+        n = len(seqs)
+        temps = list(temperature) if isinstance(temperature, (list, tuple)) else [temperature] * n
+        top_ks = list(top_k) if isinstance(top_k, (list, tuple)) else [top_k] * n
+        noises = list(_exp_noise) if _exp_noise is not None else [None] * n
+        if not (len(temps) == len(top_ks) == len(noises) == n):
+            raise ValueError("temperature / top_k / _exp_noise lists need one entry per sequence")
+
+        def single(b):
+            mark = self.mark()
+            try:
+                return self.generate(idx=None if idx is None else idx[b], input_embeddings=None if input_embeddings is None else input_embeddings[b],
+                                     max_new_tokens=max_new_tokens, temperature=temps[b], top_k=top_ks[b], eot_token=eot_token,
+                                     generator=generator, _exp_noise=noises[b])
+            finally:
+                self.rewind(mark)
+
+        if n < 2 or not self._be.batched:
+            return [single(b) for b in range(n)]
+        if max_new_tokens < 1:
+            raise ValueError("max_new_tokens must be >= 1")
+        rows, lens = [], []
+        for b in range(n):
+            ids, emb, Ln = self._rows(idx[b] if idx is not None else None, input_embeddings[b] if input_embeddings is not None else None)
+            if Ln == 0:
+                raise ValueError("generate_batch: every sequence needs rows (or the session a pending token)")
+            if top_ks[b] != 1 and not temps[b] > 0:
+                raise ValueError("temperature must be > 0")
+            if top_ks[b] != 1 and noises[b] is not None and tuple(noises[b].shape) != (max_new_tokens, self.model.vocab_size):
+                raise ValueError("_exp_noise must be [max_new_tokens, vocab_size]")
+            rows.append((ids, emb))
+            lens.append(Ln)
+        gen_state = None if generator is None else generator.get_state()
+        seeds = _mmu_batch_seeds(top_ks, generator)
+        dev = self._be.dev
+        noises = [None if (k == 1 or z is None) else z.detach().float().contiguous().to(dev) for k, z in zip(top_ks, noises)]
+        out = self._be.run_batch(self.length, rows, lens, max_new_tokens, temps, top_ks, seeds, noises, eot_token)
+        if out is None:  # the batch's common capacity does not fit the engine: the sequential calls, drawing the same seeds again
+            if gen_state is not None:
+                generator.set_state(gen_state)
+            return [single(b) for b in range(n)]
+        return [[torch.tensor(t, device=dev) for t in r] for r in out]
+
+
+def mmu_session(self, idx=None, input_embeddings=None, attention_mask=None):
+    """Open an `MmuSession`: prefill `idx` [1, L] or `input_embeddings` [1, L, H] under `attention_mask` (dense or IntervalMask) ONCE and
+    keep its KV cache for any number of questions -- the question loop of the reference's inference_mmu.py:99-176 prefills the whole
+    prompt (631 rows with the CLIP tower, 607 of them question-invariant) per question.
+
+        sess = model.mmu_session(input_embeddings=prefix, attention_mask=prefix_mask)
+        a1 = sess.generate(input_embeddings=q1, max_new_tokens=100, top_k=1, eot_token=eot)   # rows appended, then decoded
+        a2 = sess.generate(idx=q2_ids, ...)                       # follow-up: the cache holds prefix, q1 and a1
+        sess.rewind(mark)                                          # ... or back to `mark = sess.mark()` and ask something else
+        outs = sess.generate_batch(input_embeddings=[q1, q2, q3], ...)   # n questions about the current state, decoded together
+
+    Prefix + appended rows equal the full prompt (in exact arithmetic; on the GPU to the bf16 gates, since a 24-row and a 631-row
+    GEMM round differently) exactly when `prompting_utils.mmu_prefix_is_exact(full_mask, P)` holds for the full prompt's mask at
+    the split P: no prefix row sees a later column and every later row sees what row P - 1 sees plus the columns up to itself.  Both
+    mmu mask families satisfy it at every split behind <|eoi|>.  Appended rows attend as decode rows (last prefill row + causal).
+    The engine owns ONE decode cache: `mmu_generate`, another `mmu_session`, `set_precision` or a weight update make this session
+    stale, and its next call raises RuntimeError."""
+    return MmuSession(self, idx, input_embeddings, attention_mask)
+
+
+Showo.mmu_session = mmu_session
 
 
 def _dense_mask_of(attention_mask, L, device):

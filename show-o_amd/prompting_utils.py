@@ -91,6 +91,23 @@ def intervals_for_mmu_vit(sequence, system_prompt_len=0):
     return IntervalMask(_mmu_vit(sequence, system_prompt_len, False)[0], None)
 
 
+def mmu_prefix_is_exact(attention_mask, P):
+    """True when a prompt with this mask ([1,1,L,L] or [L,L]; additive with 0 = visible, or bool with True = visible) can be split
+    at row P into a prefix that is prefilled alone and rows that `Showo.mmu_session` appends, with the same result in exact
+    arithmetic: no row below P sees a column >= P (K / V^T of the prefix do not depend on what follows), and every row r >= P sees
+    exactly the columns row P - 1 sees plus [P, r] (it is a decode row: last prefix row + causal).  Pure torch, any device."""
+    m = attention_mask
+    vis = (m if m.dtype == torch.bool else m == 0).reshape(m.shape[-2], m.shape[-1])
+    L = vis.shape[0]
+    if vis.shape[1] != L or not 1 <= int(P) < L:
+        return False
+    P = int(P)
+    if bool(vis[:P, P:].any()):
+        return False
+    tail = torch.ones((L - P, L - P), dtype=torch.bool, device=vis.device).tril()
+    return bool(torch.equal(vis[P:, :P], vis[P - 1:P, :P].expand(L - P, P))) and bool(torch.equal(vis[P:, P:], tail))
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # Sequence layout of every task (reference training/prompting_utils.py:17-464 `UniversalPrompting`).
 #
