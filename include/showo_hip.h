@@ -416,6 +416,22 @@ int showo_embed_bwd(const int64_t* ids, const float* dx, float* dE, int* order_w
  * is left alone); accumulate == 0 is showo_embed_bwd. */
 int showo_embed_bwd_acc(const int64_t* ids, const float* dx, float* dE, int* order_ws, int accumulate, int T, int H, int V,
                         void* stream);
+/* Spliced image rows (the w_clip_vit training flow, training/train_w_clip_vit.py:530-589: the projector's rows are concatenated
+ * between the embedded text ids).  Layout: ids int64 [B,L] at full length; the LAST n sequences (0 <= n <= B) each hold P placeholder
+ * columns [start[j], start[j] + P) whose ids are never read; start int32 [n] on the device with 0 <= start[j], start[j] + P <= L
+ * (the caller's contract: the kernels clamp, so a bad start reads and writes nothing outside its tensors, but the results are then
+ * undefined); rows fp32 [n*P, H] = the projector's output.  H % 4 == 0, 16-byte aligned tensors.  No atomics, no host wait.
+ * showo_embed_splice_f32: x fp32 [B*L, H] = rows[j*P + k] at placeholder position (B-n+j, start[j]+k), table[ids] elsewhere -- the
+ * bits of showo_embed_f32, NaN rows for out-of-range ids included; n == 0 is showo_embed_f32.
+ * showo_gather_splice_rows_f32: out fp32 [n*P, H] = the placeholder rows of dx fp32 [B*L, H] in row order.
+ * showo_embed_bwd_splice: showo_embed_bwd_acc that leaves the placeholder positions out of the ranking and of the sums: bit-equal to
+ * showo_embed_bwd[_acc] on the batch with the placeholder tokens removed (ids and dx rows compacted in position order); table rows
+ * no live id names are not written; order_ws: scratch int[2*B*L]; live ids must be in [0, V). */
+int showo_embed_splice_f32(const int64_t* ids, const float* table, const float* rows, const int32_t* start, float* x, int B, int L,
+                           int n, int P, int H, int V, void* stream);
+int showo_gather_splice_rows_f32(const float* dx, const int32_t* start, float* out, int B, int L, int n, int P, int H, void* stream);
+int showo_embed_bwd_splice(const int64_t* ids, const float* dx, float* dE, int* order_ws, const int32_t* start, int accumulate, int B,
+                           int L, int n, int P, int H, int V, void* stream);
 /* torch.optim.AdamW step on fp32 tensors (step counts from 1). */
 int showo_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                 float weight_decay, int step, void* stream);
@@ -785,6 +801,17 @@ int showo_train_forward(showo_trainer* t, const int64_t* ids, const float* mask,
 int showo_train_forward_embeds(showo_trainer* t, const float* embeds, const float* mask, const int64_t* labels, int B, int L,
                                int b_t2i, int b_lm, int b_mmu, int max_seq_len, float* logits_out, float* losses_out, void* stream);
 int showo_train_input_grad(showo_trainer* t, float* out, int64_t n, void* stream);
+/* showo_train_forward with the projector's rows spliced into layer 0's input (showo_embed_splice_f32 is its first launch; layout
+ * above): the native form of the w_clip_vit step.  ids and start are saved for the backward.  Works with the interval masks, the
+ * announced loss weights, the loss-rows mode and the accumulate switch exactly as showo_train_forward does.  Backward: block 0
+ * produces its data gradient when the embedding table trains or showo_train_set_input_grad is on (the projector trains -- also
+ * with the table and every block frozen); showo_train_image_grad then returns the n*P placeholder rows of it, compacted in row
+ * order (fp32 [n*P, H], n_elems = n*P*H), after showo_train_backward_layer(t, 0, ...); showo_train_backward_embed runs the
+ * leave-out scatter (showo_embed_bwd_splice). */
+int showo_train_forward_spliced(showo_trainer* t, const int64_t* ids, const float* rows, const int32_t* start, int n, int P,
+                                const float* mask, const int64_t* labels, int B, int L, int b_t2i, int b_lm, int b_mmu,
+                                int max_seq_len, float* logits_out, float* losses_out, void* stream);
+int showo_train_image_grad(showo_trainer* t, float* out, int64_t n_elems, void* stream);
 /* gradients of g_t2i*loss_t2i + g_lm*loss_lm + g_mmu*loss_mmu of the last forward w.r.t. every parameter */
 int showo_train_backward(showo_trainer* t, const int64_t* labels, int b_t2i, int b_lm, int b_mmu, int max_seq_len, float g_t2i,
                          float g_lm, float g_mmu, void* stream);
@@ -826,6 +853,10 @@ int showo_train_adamw_step(showo_trainer* t, float lr, float beta1, float beta2,
  * device memory: out2 (device, 2 floats) = {total norm, coefficient}; ws = showo_grad_clip_ws_doubles() doubles of scratch. */
 int showo_grad_clip_norm(float* g, int64_t n, float max_norm, double* ws, float* out2, void* stream);
 int showo_grad_clip_ws_doubles(void);
+/* the same over TWO ranges with ONE global norm (the Show-o flat buffer and the projector's gradients: the reference clips
+ * model.parameters(), training/train_w_clip_vit.py): partials of range 0 then range 1, summed in index order; both ranges are scaled
+ * by the one coefficient.  ws = 2 * showo_grad_clip_ws_doubles() doubles.  n1 == 0 (g1 may be NULL) is showo_grad_clip_norm's norm. */
+int showo_grad_clip_norm2(float* g0, int64_t n0, float* g1, int64_t n1, float max_norm, double* ws, float* out2, void* stream);
 int showo_gelu_bf16(const uint16_t* f, uint16_t* a, int64_t n, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
@@ -870,6 +901,11 @@ int showo_projector_precise_ready(const showo_projector* p);  /* as showo_clip_p
  * gb1 [out], dx fp32 [T,in] (optional).  Autograd of nn.Sequential(Linear, GELU(), Linear) (training/train_w_clip_vit.py trains it). */
 int showo_projector_backward(showo_projector* p, const float* dout, int T, float* dx, float* gw0, float* gb0, float* gw1, float* gb1,
                              void* stream);
+/* accumulating form (gradient accumulation over micro-batches, the contract of showo_train_set_accumulate): accumulate != 0 adds the
+ * finished sums into gw0 / gb0 / gw1 / gb1 (one fp32 rounding per added micro-batch); accumulate == 0 is showo_projector_backward.
+ * Any of the four may be NULL (a frozen tensor): its gradient is neither computed nor written. */
+int showo_projector_backward_acc(showo_projector* p, const float* dout, int T, float* dx, float* gw0, float* gb0, float* gw1,
+                                 float* gb1, int accumulate, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Image pre / post-processing on the device.

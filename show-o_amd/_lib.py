@@ -70,6 +70,14 @@ _PROTOS = {
     "showo_ce_rows_compact_ws": [c_i],
     "showo_train_set_loss_rows": [c_p, c_i],
     "showo_train_loss_rows": [c_p, C.POINTER(c_i), C.POINTER(c_i)],
+    # spliced image rows: the native w_clip_vit training step
+    "showo_embed_splice_f32": [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p],
+    "showo_gather_splice_rows_f32": [c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p],
+    "showo_embed_bwd_splice": [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p],
+    "showo_train_forward_spliced": [c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p, c_p],
+    "showo_train_image_grad": [c_p, c_p, c_i64, c_p],
+    "showo_projector_backward_acc": [c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_p],
+    "showo_grad_clip_norm2": [c_p, c_i64, c_p, c_i64, c_f, c_p, c_p, c_p],
     "showo_train_create": [c_p, c_i, c_i, c_p],
     "showo_train_invalidate_weights": [c_p],
     "showo_train_set_trainable": [c_p, C.c_char_p, c_i],

@@ -517,10 +517,12 @@ __global__ void dgelu_erf_kernel(const bf16_t* __restrict__ da, const float* __r
 // Backward of the LAST showo_projector_forward (same x, T): given dout fp32 [T,out] it writes the parameter gradients
 // gw0 fp32 [out,in], gb0 [out], gw1 [out,out], gb1 [out] and (optional) dx fp32 [T,in].  Same machinery as the trainer
 // (train_engine.hip): everything on the NT GEMM with transposed bf16 images, bias gradients as fixed-order column sums.
-extern "C" int showo_projector_backward(showo_projector* p, const float* dout, int T, float* dx, float* gw0, float* gb0,
-                                        float* gw1, float* gb1, void* stream) {
+// acc != 0 (gradient accumulation): the bias column sums add into their slot in the reduction's last stage and the weight-gradient
+// GEMMs take the residual epilogue with resid = out -- the finished fp32 accumulator is added to the old value once.
+static int projector_backward_impl(showo_projector* p, const float* dout, int T, float* dx, float* gw0, float* gb0, float* gw1,
+                                   float* gb1, int acc, void* stream) {
     hipStream_t s = (hipStream_t)stream;
-    if (!p || !dout || !gw0 || !gb0 || !gw1 || !gb1) return set_error_msg(1, "projector_backward: null argument");
+    if (!p || !dout) return set_error_msg(1, "projector_backward: null argument");
     if (T <= 0 || T != p->last_T) return set_error_msg(1, "projector_backward: run showo_projector_forward on the same rows first");
     const int I = p->in_dim, D = p->out_dim;
     const int Tp = ((T + 63) / 64) * 64, Tm = ((p->max_rows + 63) / 64) * 64;
@@ -540,16 +542,33 @@ extern "C" int showo_projector_backward(showo_projector* p, const float* dout, i
     }
     TRY(showo_cast_f32_bf16(dout, p->dout16, (int64_t)T * D, s));
     // second Linear: gb1 = colsum(dout), gw1 = dout^T act, d_act = dout W1
-    TRY(showo_transpose_bf16(p->dout16, D, p->tA, T, D, Tp, 0, p->colpart, gb1, 0, s));
-    TRY(showo_transpose_bf16(p->act, D, p->tB, T, D, Tp, 0, nullptr, nullptr, 0, s));
-    TRY(showo_gemm_bf16(p->tA, Tp, p->tB, Tp, nullptr, 0, gw1, D, nullptr, 0, D, D, Tp, SHOWO_EPI_F32, s));
+    // (a NULL gradient -- a frozen tensor of the accumulating form -- is not computed; the chain below it runs only if something needs it)
+    if (gw1 || gb1) TRY(showo_transpose_bf16(p->dout16, D, p->tA, T, D, Tp, 0, p->colpart, gb1, acc, s));
+    if (gw1) {
+        TRY(showo_transpose_bf16(p->act, D, p->tB, T, D, Tp, 0, nullptr, nullptr, 0, s));
+        TRY(showo_gemm_bf16(p->tA, Tp, p->tB, Tp, nullptr, 0, gw1, D, acc ? gw1 : nullptr, acc ? D : 0, D, D, Tp,
+                            acc ? SHOWO_EPI_RESID_F32 : SHOWO_EPI_F32, s));
+    }
+    if (!gw0 && !gb0 && !dx) return 0;
     TRY(showo_gemm_bf16(p->dout16, D, p->w1T, D, nullptr, 0, p->dact16, D, nullptr, 0, T, D, D, SHOWO_EPI_BF16, s));
     dgelu_erf_kernel<<<dim3(1024), dim3(256), 0, s>>>(p->dact16, p->f, p->df16, (int64_t)T * D);
     // first Linear: gb0 = colsum(df), gw0 = df^T x, dx = df W0
-    TRY(showo_transpose_bf16(p->df16, D, p->tA, T, D, Tp, 0, p->colpart, gb0, 0, s));
-    TRY(showo_transpose_bf16(p->xb, I, p->tB, T, I, Tp, 0, nullptr, nullptr, 0, s));
-    TRY(showo_gemm_bf16(p->tA, Tp, p->tB, Tp, nullptr, 0, gw0, I, nullptr, 0, D, I, Tp, SHOWO_EPI_F32, s));
+    if (gw0 || gb0) TRY(showo_transpose_bf16(p->df16, D, p->tA, T, D, Tp, 0, p->colpart, gb0, acc, s));
+    if (gw0) {
+        TRY(showo_transpose_bf16(p->xb, I, p->tB, T, I, Tp, 0, nullptr, nullptr, 0, s));
+        TRY(showo_gemm_bf16(p->tA, Tp, p->tB, Tp, nullptr, 0, gw0, I, acc ? gw0 : nullptr, acc ? I : 0, D, I, Tp,
+                            acc ? SHOWO_EPI_RESID_F32 : SHOWO_EPI_F32, s));
+    }
     if (dx) TRY(showo_gemm_bf16(p->df16, D, p->w0T, D, nullptr, 0, dx, I, nullptr, 0, T, I, D, SHOWO_EPI_F32, s));
     SHOWO_CHECK_HIP(hipGetLastError());
     return 0;
+}
+extern "C" int showo_projector_backward(showo_projector* p, const float* dout, int T, float* dx, float* gw0, float* gb0,
+                                        float* gw1, float* gb1, void* stream) {
+    if (!gw0 || !gb0 || !gw1 || !gb1) return set_error_msg(1, "projector_backward: null argument");
+    return projector_backward_impl(p, dout, T, dx, gw0, gb0, gw1, gb1, 0, stream);
+}
+extern "C" int showo_projector_backward_acc(showo_projector* p, const float* dout, int T, float* dx, float* gw0, float* gb0,
+                                            float* gw1, float* gb1, int accumulate, void* stream) {
+    return projector_backward_impl(p, dout, T, dx, gw0, gb0, gw1, gb1, accumulate ? 1 : 0, stream);
 }

@@ -89,6 +89,11 @@ struct showo_trainer {
     uint64_t generation = 0;  // training forwards started (showo_train_generation)
     bool has_mask = false;
     bool from_embeds = false;  // last forward started from caller-provided embeddings: d(loss)/d(embeddings) = dy
+    // last forward spliced the projector's rows into layer 0's input (showo_train_forward_spliced): the last sp_n sequences hold sp_P
+    // placeholder columns from start[j]; the table scatter leaves them out and showo_train_image_grad compacts their rows of dy
+    bool spliced = false;
+    int sp_n = 0, sp_P = 0;
+    int32_t* start = nullptr;
     uint64_t tv_wlm = 0;  // engine version of lm_head.weight that wlmT was made from
     // trainable set (showo_train_set_trainable): state-dict keys whose gradients are not wanted; their slots read as zeros
     std::set<std::string> frozen, pending_zero;
@@ -249,6 +254,9 @@ extern "C" int showo_train_create(showo_engine* e, int max_batch, int max_seq, s
     rc |= t->alloc(&t->order_ws, 2 * T);
     rc |= t->alloc(&t->losses, 4);
     rc |= t->alloc(&t->ids, T);
+    rc |= t->alloc(&t->start, max_batch);
+    // the ranking of the leave-out scatter fills order_ws for the live tokens only: whatever else a launch could read is a row index
+    if (!rc && hipMemset(t->order_ws, 0, (size_t)2 * T * sizeof(int)) != hipSuccess) rc = set_error_msg(7, "train_create: hipMemset failed");
     if (rc) { showo_train_destroy(t); return rc; }
     *out = t;
     return 0;
@@ -343,6 +351,7 @@ static int plan_sync(showo_trainer* t, hipStream_t s) {
 
 // d(loss)/d(input of block i) is consumed below it: by a lower block, the embedding table (ids flow) or the caller (embeddings flow)
 static bool below_needs(const showo_trainer* t, int i) {
+    if (t->spliced && t->want_input && t->sp_n * t->sp_P > 0) return true;  // the projector consumes the placeholder rows of dy
     return (t->from_embeds ? t->want_input : t->p_emb) || t->any_below[i];
 }
 
@@ -427,11 +436,17 @@ __global__ void poison_losses_kernel(float* __restrict__ losses, const int32_t* 
 int compact_gemm_rows(int Tc, int T) { return std::min(T, ((Tc + 255) / 256) * 256); }
 }  // namespace
 
+// the spliced rows of a forward (showo_train_forward_spliced); rows == nullptr: a plain ids / embeds forward
+struct Splice { const float* rows = nullptr; const int32_t* start = nullptr; int n = 0, P = 0; };
+
 static int train_forward_impl(showo_trainer* t, const int64_t* ids, const float* embeds, const float* mask, const int64_t* labels,
                               int B, int L, int b_t2i, int b_lm, int b_mmu, int max_seq_len, float* logits_out, float* losses_out,
-                              void* stream) {
+                              void* stream, const Splice* sp = nullptr) {
     hipStream_t s = (hipStream_t)stream;
     if (!t || ((ids == nullptr) == (embeds == nullptr))) return set_error_msg(1, "train_forward: exactly one of ids / embeds");
+    // a refused spliced call leaves the trainer as the last forward left it: checked before anything is counted or queued
+    if (sp && (!ids || sp->n < 0 || sp->n > B || sp->P < 0 || sp->P > L || (sp->n * sp->P > 0 && (!sp->rows || !sp->start))))
+        return set_error_msg(1, "train_forward_spliced: need ids, 0 <= n <= B, 0 <= P <= L, and rows + start when n * P > 0");
     ++t->generation;
     showo_engine* e = t->e;
     if (showo_engine_missing(e) != 0) return set_error_msg(4, "train: weights missing");
@@ -469,13 +484,21 @@ static int train_forward_impl(showo_trainer* t, const int64_t* ids, const float*
         SHOWO_CHECK_HIP(hipMemcpyAsync(t->tc_host, t->counts + 3, sizeof(int32_t), hipMemcpyDeviceToHost, s));
         SHOWO_CHECK_HIP(hipEventRecord(t->ev_tc, s));
     }
-    if (ids) {
+    if (sp) {  // table rows and the projector's rows in one launch; ids and start stay for the backward
+        TRY(showo_embed_splice_f32(ids, e->embed, sp->rows, sp->start, t->L[0].x, B, L, sp->n, sp->P, H, V, s));
+        SHOWO_CHECK_HIP(hipMemcpyAsync(t->ids, ids, (size_t)T * 8, hipMemcpyDeviceToDevice, s));
+        if (sp->n * sp->P > 0)
+            SHOWO_CHECK_HIP(hipMemcpyAsync(t->start, sp->start, (size_t)sp->n * sizeof(int32_t), hipMemcpyDeviceToDevice, s));
+    } else if (ids) {
         SHOWO_CHECK_HIP(hipMemcpyAsync(t->ids, ids, (size_t)T * 8, hipMemcpyDeviceToDevice, s));
         TRY(showo_embed_f32(ids, e->embed, t->L[0].x, T, H, V, s));  // layer 0's saved input IS the embedding output (no copy)
     } else {  // inputs_embeds path (modeling_showo.py:77-78, phi.py:1005-1006): the residual stream starts from the caller's rows
         SHOWO_CHECK_HIP(hipMemcpyAsync(t->L[0].x, embeds, (size_t)T * H * sizeof(float), hipMemcpyDeviceToDevice, s));
     }
     t->from_embeds = ids == nullptr;
+    t->spliced = sp != nullptr;
+    t->sp_n = sp ? sp->n : 0;
+    t->sp_P = sp ? sp->P : 0;
     const int32_t *iv = nullptr, *flag = nullptr;
     if (mask) {
         TRY(showo_mask_compress(mask, e->iv, e->flag, B, L, L, s));
@@ -591,6 +614,24 @@ extern "C" int showo_train_forward_embeds(showo_trainer* t, const float* embeds,
                                           int L, int b_t2i, int b_lm, int b_mmu, int max_seq_len, float* logits_out,
                                           float* losses_out, void* stream) {
     return train_forward_impl(t, nullptr, embeds, mask, labels, B, L, b_t2i, b_lm, b_mmu, max_seq_len, logits_out, losses_out, stream);
+}
+// showo_train_forward with the projector's rows [n*P, H] spliced into layer 0's input (header: layout); the argument list of
+// showo_train_forward itself is unchanged
+extern "C" int showo_train_forward_spliced(showo_trainer* t, const int64_t* ids, const float* rows, const int32_t* start, int n, int P,
+                                           const float* mask, const int64_t* labels, int B, int L, int b_t2i, int b_lm, int b_mmu,
+                                           int max_seq_len, float* logits_out, float* losses_out, void* stream) {
+    Splice sp;
+    sp.rows = rows; sp.start = start; sp.n = n; sp.P = P;
+    return train_forward_impl(t, ids, nullptr, mask, labels, B, L, b_t2i, b_lm, b_mmu, max_seq_len, logits_out, losses_out, stream, &sp);
+}
+// the placeholder rows of d(weighted loss)/d(layer 0's input), compacted in row order: fp32 [n*P, H] = d/d(projector output)
+extern "C" int showo_train_image_grad(showo_trainer* t, float* out, int64_t n_elems, void* stream) {
+    if (!t || !t->have_fwd || !t->spliced) return set_error_msg(1, "train_image_grad: run showo_train_forward_spliced + the backward first");
+    if (!t->want_input) return set_error_msg(1, "train_image_grad: not requested (showo_train_set_input_grad)");
+    if (n_elems != (int64_t)t->sp_n * t->sp_P * t->e->H) return set_error_msg(1, "train_image_grad: size mismatch");
+    if (n_elems == 0) return 0;
+    if (!out) return set_error_msg(1, "train_image_grad: null output");
+    return showo_gather_splice_rows_f32(t->dy, t->start, out, t->B, t->Lq, t->sp_n, t->sp_P, t->e->H, stream);
 }
 // d(weighted loss) / d(input embeddings) fp32 [B*L, H] of the last backward (the residual-stream gradient at block 0's input)
 extern "C" int showo_train_input_grad(showo_trainer* t, float* out, int64_t n, void* stream) {
@@ -866,7 +907,11 @@ extern "C" int showo_train_backward_embed(showo_trainer* t, void* stream) {
         // accumulating: the table keeps the window's partial sum -- no clear, and the scatter adds its position-ordered row sums into the
         // rows this micro-batch touches; a micro-batch that started from embeddings contributes nothing to the table
         if (t->from_embeds) return 0;
-        TRY(showo_embed_bwd_acc(t->ids, t->dy, t->gembed, t->order_ws, 1, T, H, V, s));
+        if (t->spliced) {
+            TRY(showo_embed_bwd_splice(t->ids, t->dy, t->gembed, t->order_ws, t->start, 1, B, L, t->sp_n, t->sp_P, H, V, s));
+        } else {
+            TRY(showo_embed_bwd_acc(t->ids, t->dy, t->gembed, t->order_ws, 1, T, H, V, s));
+        }
         ++t->cnt[3];
         t->gembed_dirty = true;
         return 0;
@@ -876,7 +921,11 @@ extern "C" int showo_train_backward_embed(showo_trainer* t, void* stream) {
     ++t->cnt[3];
     t->gembed_dirty = false;
     if (t->from_embeds) return 0;
-    TRY(showo_embed_bwd(t->ids, t->dy, t->gembed, t->order_ws, T, H, V, s));
+    if (t->spliced) {
+        TRY(showo_embed_bwd_splice(t->ids, t->dy, t->gembed, t->order_ws, t->start, 0, B, L, t->sp_n, t->sp_P, H, V, s));
+    } else {
+        TRY(showo_embed_bwd(t->ids, t->dy, t->gembed, t->order_ws, T, H, V, s));
+    }
     ++t->cnt[3];
     t->gembed_dirty = true;
     return 0;

@@ -672,6 +672,111 @@ __global__ __launch_bounds__(256) void embed_bwd_kernel(const int64_t* __restric
 }
 
 // ------------------------------------------------------------------------------------------------
+// Spliced image rows (w_clip_vit training step): the last n sequences of a [B, L] batch hold P placeholder columns [start[j],
+// start[j] + P) that carry the projector's rows instead of table rows.  The clamped run [ds, de) below never leaves [0, L), so a
+// start outside the contract indexes nothing outside the tensors.
+// ------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void splice_run(const int32_t* __restrict__ start, int j, int P, int L, int& ds, int& de) {
+    const int s0 = start[j];
+    ds = min(max(s0, 0), L);
+    de = min(max(s0 + P, ds), L);
+}
+// layer 0's input: one wave per token row, float4 copies (embed_kernel of basic.hip with the placeholder rows taken from `rows`)
+__global__ __launch_bounds__(256) void embed_splice_kernel(const int64_t* __restrict__ ids, const float* __restrict__ table,
+                                                           const float* __restrict__ rows, const int32_t* __restrict__ start,
+                                                           float* __restrict__ x, int B, int L, int n, int P, int H, int V) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int t = blockIdx.x * 4 + wave;
+    if (t >= B * L) return;
+    const int b = t / L, col = t - b * L, j = b - (B - n);
+    float* xr = x + (int64_t)t * H;
+    const float* src = nullptr;
+    if (j >= 0) {
+        int ds, de;
+        splice_run(start, j, P, L, ds, de);
+        if (col >= ds && col < de) src = rows + ((int64_t)j * P + (col - ds)) * H;  // col - ds < P: inside rows [n*P, H]
+    }
+    if (!src) {
+        const int64_t id = ids[t];
+        if (id < 0 || id >= V) {
+            for (int i = lane; i < H; i += 64) xr[i] = __builtin_nanf("");
+            return;
+        }
+        src = table + id * H;
+    }
+    for (int i = lane * 4; i < H; i += 256) *reinterpret_cast<float4*>(xr + i) = *reinterpret_cast<const float4*>(src + i);  // H % 4 == 0
+}
+// out[j*P + k] = dx[(B-n+j)*L + ds + k] over the run [ds, de) of splice_run (ds = start[j], de = ds + P inside the contract): one wave
+// per row; a row beyond a clamped run, which the splice gave no position, reads zeros
+__global__ __launch_bounds__(256) void gather_splice_kernel(const float* __restrict__ dx, const int32_t* __restrict__ start,
+                                                            float* __restrict__ out, int B, int L, int n, int P, int H) {
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + wave;
+    if (r >= n * P) return;
+    const int j = r / P, k = r - j * P;
+    int ds, de;
+    splice_run(start, j, P, L, ds, de);
+    const int col = ds + k;
+    float* o = out + (int64_t)r * H;
+    if (col >= de) {
+        for (int i = lane * 4; i < H; i += 256) *reinterpret_cast<float4*>(o + i) = make_float4(0.f, 0.f, 0.f, 0.f);
+        return;
+    }
+    const float* src = dx + ((int64_t)(B - n + j) * L + col) * H;
+    for (int i = lane * 4; i < H; i += 256) *reinterpret_cast<float4*>(o + i) = *reinterpret_cast<const float4*>(src + i);
+}
+// embed_rank_kernel over the live positions only: a placeholder position is neither ranked nor scanned (its id is never loaded), so
+// order[0 .. M) lists the M live tokens by (id, position) exactly as embed_rank_kernel ranks the compacted token list.  Each wave
+// walks its quarter of the positions sequence by sequence, as the (at most two) live segments around the sequence's placeholder run.
+__global__ __launch_bounds__(256) void embed_rank_splice_kernel(const int64_t* __restrict__ ids, const int32_t* __restrict__ start,
+                                                                int* __restrict__ order, int* __restrict__ runstart, int B, int L,
+                                                                int n, int P) {
+    __shared__ int srank[4][64], searlier[4][64];
+    const int T = B * L;
+    const int lane = threadIdx.x & 63, part = threadIdx.x >> 6;
+    const int t = blockIdx.x * 64 + lane;
+    bool live = t < T;
+    if (live) {
+        const int b = t / L, j = b - (B - n);
+        if (j >= 0) {
+            int ds, de;
+            splice_run(start, j, P, L, ds, de);
+            const int col = t - b * L;
+            live = col < ds || col >= de;
+        }
+    }
+    const int64_t id = live ? ids[t] : 0;
+    const int per = (T + 3) / 4, u0 = part * per, u1 = min(T, u0 + per);
+    int rank = 0, earlier = 0;
+    if (u0 < u1) {
+        for (int b = u0 / L; b <= (u1 - 1) / L; ++b) {
+            const int base = b * L, j = b - (B - n);
+            int ds = L, de = L;  // no placeholder run: one live segment [0, L)
+            if (j >= 0) splice_run(start, j, P, L, ds, de);
+            const int seg[2][2] = {{base, base + ds}, {base + de, base + L}};
+            for (int k = 0; k < 2; ++k) {
+                const int a = max(seg[k][0], u0), z = min(seg[k][1], u1);
+                for (int u = a; u < z; ++u) {
+                    const int64_t o = ids[u];
+                    const int eq_before = (o == id) & (u < t);
+                    rank += (o < id) | eq_before;
+                    earlier |= eq_before;
+                }
+            }
+        }
+    }
+    srank[part][lane] = rank;
+    searlier[part][lane] = earlier;
+    __syncthreads();
+    if (part == 0 && live) {
+        rank = (srank[0][lane] + srank[1][lane]) + (srank[2][lane] + srank[3][lane]);  // < the live count <= T
+        earlier = searlier[0][lane] | searlier[1][lane] | searlier[2][lane] | searlier[3][lane];
+        order[rank] = t;
+        runstart[rank] = earlier ? 0 : 1;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // AdamW (torch.optim.AdamW semantics: decoupled decay, bias-corrected moments) on fp32 master weights.
 // ------------------------------------------------------------------------------------------------
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
@@ -745,10 +850,11 @@ __global__ __launch_bounds__(256) void sumsq_part_kernel(const float* __restrict
     }
     if (threadIdx.x == 0) part[blockIdx.x] = sh[0];
 }
-__global__ __launch_bounds__(256) void clip_coef_kernel(const double* __restrict__ part, float max_norm, float* __restrict__ out2) {
+__global__ __launch_bounds__(256) void clip_coef_kernel(const double* __restrict__ part, float max_norm, float* __restrict__ out2,
+                                                        int nparts) {
     __shared__ double sh[256];
     double a = 0.0;
-    for (int i = threadIdx.x; i < CLIP_PARTS; i += 256) a += part[i];
+    for (int i = threadIdx.x; i < nparts; i += 256) a += part[i];
     sh[threadIdx.x] = a;
     __syncthreads();
     for (int o = 128; o > 0; o >>= 1) {
@@ -1066,6 +1172,51 @@ extern "C" int showo_embed_bwd_acc(const int64_t* ids, const float* dx, float* d
     return embed_bwd_impl(ids, dx, dE, order_ws, accumulate, T, H, V, stream);
 }
 
+// ---- spliced image rows (header: layout and contracts)
+static int splice_args(int B, int L, int n, int P, int H, const void* start) {
+    if (B <= 0 || L <= 0 || n < 0 || n > B || P < 0 || P > L || H <= 0 || (H % 4) || (int64_t)B * L > 0x7fffffff || (n > 0 && P > 0 && !start))
+        return set_error_msg(1, "spliced rows: need B, L > 0, 0 <= n <= B, 0 <= P <= L, H % 4 == 0, B * L < 2^31 and start when n * P > 0");
+    return 0;
+}
+extern "C" int showo_embed_splice_f32(const int64_t* ids, const float* table, const float* rows, const int32_t* start, float* x, int B,
+                                      int L, int n, int P, int H, int V, void* stream) {
+    if (int rc = splice_args(B, L, n, P, H, start)) return rc;
+    if (!ids || !table || !x || (n > 0 && P > 0 && !rows)) return set_error_msg(1, "embed_splice: null argument");
+    if ((((uintptr_t)table) | ((uintptr_t)x) | ((uintptr_t)rows)) & 15) return set_error_msg(1, "embed_splice: 16-byte aligned tensors required");
+    if (P == 0) n = 0;
+    embed_splice_kernel<<<dim3((B * L + 3) / 4), dim3(256), 0, (hipStream_t)stream>>>(ids, table, rows, start, x, B, L, n, P, H, V);
+    SHOWO_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+extern "C" int showo_gather_splice_rows_f32(const float* dx, const int32_t* start, float* out, int B, int L, int n, int P, int H,
+                                            void* stream) {
+    if (int rc = splice_args(B, L, n, P, H, start)) return rc;
+    if (n * P == 0) return 0;
+    if (!dx || !out) return set_error_msg(1, "gather_splice_rows: null argument");
+    if ((((uintptr_t)dx) | ((uintptr_t)out)) & 15) return set_error_msg(1, "gather_splice_rows: 16-byte aligned tensors required");
+    gather_splice_kernel<<<dim3((n * P + 3) / 4), dim3(256), 0, (hipStream_t)stream>>>(dx, start, out, B, L, n, P, H);
+    SHOWO_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+extern "C" int showo_embed_bwd_splice(const int64_t* ids, const float* dx, float* dE, int* order_ws, const int32_t* start, int accumulate,
+                                      int B, int L, int n, int P, int H, int V, void* stream) {
+    if (int rc = splice_args(B, L, n, P, H, start)) return rc;
+    if (!ids || !dx || !dE || !order_ws) return set_error_msg(1, "embed_bwd_splice: null argument");
+    if ((((uintptr_t)dx) | ((uintptr_t)dE)) & 15) return set_error_msg(1, "embed_bwd_splice: 16-byte aligned tensors required");
+    (void)V;
+    if (P == 0) n = 0;
+    const int T = B * L, M = T - n * P;  // the live tokens: what the ranking fills of order / runstart and what the sums run over
+    if (M <= 0) return 0;
+    hipStream_t s = (hipStream_t)stream;
+    int* order = order_ws;
+    int* runstart = order_ws + T;
+    embed_rank_splice_kernel<<<dim3((T + 63) / 64), dim3(256), 0, s>>>(ids, start, order, runstart, B, L, n, P);
+    if (accumulate) embed_bwd_kernel<true><<<dim3(M), dim3(256), 0, s>>>(ids, order, runstart, dx, dE, M, H);
+    else embed_bwd_kernel<false><<<dim3(M), dim3(256), 0, s>>>(ids, order, runstart, dx, dE, M, H);
+    SHOWO_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
 extern "C" int showo_adamw(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps,
                            float weight_decay, int step, void* stream) {
     if (n <= 0) return 0;
@@ -1204,7 +1355,7 @@ extern "C" int showo_grad_clip_norm(float* g, int64_t n, float max_norm, double*
     if (!g || !ws || !out2 || n <= 0 || (((uintptr_t)g) & 15)) return showo::set_error_msg(1, "grad_clip_norm: bad argument (g 16-byte aligned)");
     hipStream_t s = (hipStream_t)stream;
     sumsq_part_kernel<<<dim3(CLIP_PARTS), dim3(256), 0, s>>>(g, n, ws);
-    clip_coef_kernel<<<dim3(1), dim3(256), 0, s>>>(ws, max_norm, out2);
+    clip_coef_kernel<<<dim3(1), dim3(256), 0, s>>>(ws, max_norm, out2, CLIP_PARTS);
     int64_t blocks = (n / 4 + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     if (blocks < 1) blocks = 1;
@@ -1214,3 +1365,25 @@ extern "C" int showo_grad_clip_norm(float* g, int64_t n, float max_norm, double*
     return 0;
 }
 extern "C" int showo_grad_clip_ws_doubles(void) { return CLIP_PARTS; }
+// ONE global norm over two ranges (header): partials of g0 in ws[0, CLIP_PARTS), of g1 behind them, summed in index order
+extern "C" int showo_grad_clip_norm2(float* g0, int64_t n0, float* g1, int64_t n1, float max_norm, double* ws, float* out2, void* stream) {
+    if (!g0 || !ws || !out2 || n0 <= 0 || n1 < 0 || (n1 > 0 && !g1) || (((uintptr_t)g0) & 15) || (((uintptr_t)g1) & 15))
+        return showo::set_error_msg(1, "grad_clip_norm2: bad argument (g0, g1 16-byte aligned)");
+    hipStream_t s = (hipStream_t)stream;
+    sumsq_part_kernel<<<dim3(CLIP_PARTS), dim3(256), 0, s>>>(g0, n0, ws);
+    if (n1 > 0) sumsq_part_kernel<<<dim3(CLIP_PARTS), dim3(256), 0, s>>>(g1, n1, ws + CLIP_PARTS);
+    else SHOWO_CHECK_HIP(hipMemsetAsync(ws + CLIP_PARTS, 0, CLIP_PARTS * sizeof(double), s));
+    clip_coef_kernel<<<dim3(1), dim3(256), 0, s>>>(ws, max_norm, out2, 2 * CLIP_PARTS);
+    float* g[2] = {g0, g1};
+    const int64_t n[2] = {n0, n1};
+    for (int k = 0; k < 2; ++k) {
+        if (n[k] <= 0) continue;
+        int64_t blocks = (n[k] / 4 + 255) / 256;
+        if (blocks > 4096) blocks = 4096;
+        if (blocks < 1) blocks = 1;
+        scale_by_dev_kernel<<<dim3((unsigned)blocks), dim3(256), 0, s>>>(g[k], n[k], out2 + 1);
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return showo::set_error_hip(e, "grad_clip_norm2 launch", __FILE__, __LINE__);
+    return 0;
+}

@@ -14,6 +14,7 @@ import torch
 from . import _lib
 
 NO_DECAY = ("bias", "layer_norm.weight", "mlm_ln.weight", "embeddings.weight")  # reference training/train.py:211
+PROJECTOR_KEYS = ("mm_projector.0.weight", "mm_projector.0.bias", "mm_projector.2.weight", "mm_projector.2.bias")
 
 
 class _DevView:
@@ -202,7 +203,7 @@ def loss_rows_mode(loss_rows):
 class Trainer:
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, coeffs=(1.0, 0.1, 1.0), group=None,
                  wire="bf16", max_grad_norm=None, force_exchange=False, reserve_cus=None, gradient_accumulation_steps=1,
-                 loss_rows="all"):
+                 loss_rows="all", projector=False):
         """gradient_accumulation_steps = k (every training YAML of the reference carries it): one step() call is one micro-batch;
         the first of a window overwrites the native gradient buffer, the others add into it (the accumulating kernel forms,
         showo_train_set_accumulate) with loss weights coeffs / k, and only the k-th runs the exchange, clipping, AdamW and the image
@@ -215,7 +216,13 @@ class Trainer:
         loss_rows: "all" (default) runs the loss head -- final LayerNorm, lm_head, cross-entropy and their backward -- on every token
         row; "labelled" on the rows that enter a loss (masked image tokens of the t2i rows, text rows of the lm rows, answer tokens of
         the mmu rows: training_utils.labelled_rows).  Same gradients below lm_head, lm_head's own differ in the grouping of their fp32
-        row sums; the forward waits once on the host for the row count (DESIGN.md "Loss head on labelled rows")."""
+        row sums; the forward waits once on the host for the row count (DESIGN.md "Loss head on labelled rows").
+        projector: False (default) trains model.showo alone, whatever else the model holds.  True (the w_clip_vit model, reference
+        training/train_w_clip_vit.py): the `requires_grad` parameters of model.mm_projector join the trainable set -- their four
+        gradients are one more exchange bucket, clipping takes ONE norm over the Show-o and projector gradients, the native AdamW
+        updates them (no decay for names containing "bias"), checkpoints carry their moments after the showo.* entries -- and
+        step_clip_vit() runs the micro-batch with the projector's rows spliced in (DESIGN.md "CLIP-ViT training step").  A model
+        whose showo is wholly frozen (LLaVA-pretrain) is accepted when the projector trains."""
         import os
         self._loss_rows_mode = loss_rows_mode(loss_rows)  # before anything touches the device
         self.loss_rows = loss_rows
@@ -232,19 +239,43 @@ class Trainer:
         # the trainable set is read once, as the reference builds its optimizer once over the `requires_grad` parameters
         # (training/train.py:210-223): frozen tensors get no gradient, no exchange of a wholly frozen bucket and no update
         self.trainable = {n: bool(p.requires_grad) for n, p in self.params}
-        if not any(self.trainable.values()):
-            raise ValueError("Trainer: no parameter of model.showo requires grad; nothing to train")
+        self.projector = bool(projector)
+        self.pparams, self.ptrainable = [], {}
+        if self.projector:
+            mm = getattr(model, "mm_projector", None)
+            if mm is None:
+                raise ValueError("Trainer(projector=True): the model has no mm_projector (build it with w_clip_vit=True)")
+            self.pparams = [("mm_projector." + n, p) for n, p in mm.named_parameters()]
+            if tuple(n for n, _ in self.pparams) != PROJECTOR_KEYS:
+                raise ValueError(f"Trainer(projector=True): mm_projector's parameters are {[n for n, _ in self.pparams]}, expected {PROJECTOR_KEYS}")
+            self.ptrainable = {n: bool(p.requires_grad) for n, p in self.pparams}
+        self._ptrains = any(self.ptrainable.values())
+        self._showo_trains = any(self.trainable.values())
+        if not self._showo_trains and not self._ptrains:
+            raise ValueError("Trainer: no parameter of model.showo requires grad; nothing to train" if not self.projector else
+                             "Trainer: no parameter of model.showo or model.mm_projector requires grad; nothing to train")
         from .modeling_showo import _train_param_groups
         self._bucket_trains = [any(self.trainable[k] for k, _ in g) for g in _train_param_groups(model)]
-        self.m = {n: torch.zeros_like(p) for n, p in self.params}
-        self.v = {n: torch.zeros_like(p) for n, p in self.params}
+        self._pbucket = None  # index of the projector's bucket (set by _bind when a projector parameter trains)
+        self.m = {n: torch.zeros_like(p) for n, p in self.params + self.pparams}
+        self.v = {n: torch.zeros_like(p) for n, p in self.params + self.pparams}
+        # the projector's four gradients: one flat fp32 buffer of 256-byte aligned slots = the exchange bucket behind the head's
+        self._pgrad, self._pviews = None, {}
+        if self._ptrains:
+            offs, cur = [], 0
+            for _, p in self.pparams:
+                offs.append(cur)
+                cur += (p.numel() + 63) // 64 * 64
+            self._pgrad = torch.zeros(cur, dtype=torch.float32, device=self.pparams[0][1].device)
+            self._pviews = {n: self._pgrad[o:o + p.numel()].view(p.shape) for o, (n, p) in zip(offs, self.pparams)}
         self._wire, self._force_exchange = wire, force_exchange
         self._bound = None
         self._bind()
 
-    def _binding_key(self, params=None):
+    def _binding_key(self, params=None, pparams=None):
         params = self.params if params is None else params
-        return (self.tr.value if hasattr(self.tr, "value") else int(self.tr),) + tuple(p.data_ptr() for _, p in params)
+        pparams = self.pparams if pparams is None else pparams
+        return (self.tr.value if hasattr(self.tr, "value") else int(self.tr),) + tuple(p.data_ptr() for _, p in params + pparams)
 
     def _bind(self):
         """(Re)create everything that holds raw pointers into the native trainer or the parameters: the gradient-bucket views, the
@@ -253,7 +284,7 @@ class Trainer:
         .to(), ...): a stale handle would have no parameters bound and the native AdamW would write through dangling pointers."""
         self.tr = self.model.trainer()
         dev = self.params[0][1].device
-        for n, p in self.params:
+        for n, p in self.params + self.pparams:
             if self.m[n].device != p.device or self.m[n].shape != p.shape:
                 self.m[n] = torch.zeros_like(p)
                 self.v[n] = torch.zeros_like(p)
@@ -267,6 +298,12 @@ class Trainer:
             if not p.is_contiguous() or p.dtype != torch.float32:
                 raise ValueError(f"{n}: the native optimizer updates contiguous fp32 master parameters in place")
             _lib.call("showo_train_bind_param", self.tr, n.encode(), p.data_ptr(), self.m[n].data_ptr(), self.v[n].data_ptr(), p.numel())
+        for n, p in self.pparams:
+            if not p.is_contiguous() or p.dtype != torch.float32:
+                raise ValueError(f"{n}: the native optimizer updates contiguous fp32 master parameters in place")
+        if self._ptrains:  # the projector's gradients: one more bucket, behind the head's
+            self._pbucket = len(self.buckets)
+            self.buckets.append(self._pgrad)
         import torch.distributed as dist
         group = self.group
         active = dist.is_available() and dist.is_initialized() and (dist.get_world_size(group) > 1 or self._force_exchange)
@@ -277,24 +314,26 @@ class Trainer:
     def state_dict(self):
         """torch.optim.AdamW layout: {'state': {i: {'step', 'exp_avg', 'exp_avg_sq'}}, 'param_groups': [...]} with the parameters
         numbered in `model.showo.named_parameters()` order, so the file is interchangeable with an AdamW built over that list.
+        A projector=True trainer appends mm_projector.0.weight, .0.bias, .2.weight, .2.bias (the `model.named_parameters()` order).
         Refused inside an open accumulation window: the partial gradient sum is not part of the file."""
         if self.window.is_open:
             raise RuntimeError(f"Trainer.state_dict inside an open accumulation window (micro-batch {self.window.position} of "
                                f"{self.window.steps}): the partial gradient sum is not saved; checkpoint when sync_gradients is True")
         state = {i: {"step": torch.tensor(float(self.step_count)), "exp_avg": self.m[n].detach().clone(),
-                     "exp_avg_sq": self.v[n].detach().clone()} for i, (n, _) in enumerate(self.params)}
+                     "exp_avg_sq": self.v[n].detach().clone()} for i, (n, _) in enumerate(self.params + self.pparams)}
         group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.wd,
-                 "params": list(range(len(self.params)))}
-        return {"state": state, "param_groups": [group], "param_names": [n for n, _ in self.params]}
+                 "params": list(range(len(self.params) + len(self.pparams)))}
+        return {"state": state, "param_groups": [group], "param_names": [n for n, _ in self.params + self.pparams]}
 
     def load_state_dict(self, sd):
         """moments are copied INTO the tensors bound to the native optimizer (showo_train_bind_param); lr / betas / eps / weight
         decay / step count are taken from the file.  An open accumulation window is dropped: the next step() starts a new one."""
         self.window.reset()
         self.sync_gradients = False
-        names = [n for n, _ in self.params]
+        names = [n for n, _ in self.params + self.pparams]
         if "param_names" in sd and list(sd["param_names"]) != names:
-            raise ValueError("optimizer state was saved for a different parameter list")
+            raise ValueError("optimizer state was saved for a different parameter list" +
+                             (" (a file without mm_projector entries does not resume a projector=True trainer)" if self.projector else ""))
         if len(sd["state"]) not in (0, len(names)):
             raise ValueError(f"optimizer state has {len(sd['state'])} entries, the model has {len(names)} parameters")
         steps = set()
@@ -382,22 +421,52 @@ class Trainer:
     def step(self, input_ids, attention_mask, labels, batch_size_t2i, batch_size_lm, batch_size_mmu, max_seq_length):
         """one micro-batch (with gradient_accumulation_steps = 1: one optimisation step); returns its three losses, unscaled (fp32
         device tensor [3])"""
+        return self._on_compute_stream(input_ids, attention_mask, labels, batch_size_t2i, batch_size_lm, batch_size_mmu, max_seq_length)
+
+    def step_clip_vit(self, input_ids, image_features, image_start, attention_mask, labels, batch_size_t2i, batch_size_lm, batch_size_mmu,
+                      max_seq_length):
+        """one micro-batch of the w_clip_vit model (reference training/train_w_clip_vit.py:598-639) on the native path; needs
+        Trainer(projector=True).  input_ids / labels [B, L] at full length: the last n = image_features.shape[0] sequences hold P
+        placeholder columns from image_start (an int, or n ints) whose ids are never read and whose labels are the ignore id
+        (training_utils.splice_image_columns builds both).  image_features [n, P, in_dim]: the frozen tower's output, no gradient.
+        Order of the call: projector forward on bf16 operands (whatever inference precision the module is set to, restored afterwards)
+        -> spliced forward -> head -> blocks -> image-gradient gather -> projector backward -> projector bucket -> embedding phase.
+        Window, loss_rows, reserve_cus, max_grad_norm and sync_gradients behave as in step().  Returns the three unscaled losses."""
+        if not self.projector:
+            raise RuntimeError("Trainer.step_clip_vit needs Trainer(model, projector=True)")
+        B, L = input_ids.shape
+        if image_features.dim() != 3 or image_features.shape[2] != self.model.mm_projector._dims[0]:
+            raise ValueError(f"image_features should be [n, P, {self.model.mm_projector._dims[0]}], got {tuple(image_features.shape)}")
+        n, P = int(image_features.shape[0]), int(image_features.shape[1])
+        from .training_utils import image_starts
+        starts = image_starts(image_start, n)
+        if n > B or any(v < 0 or v + P > L for v in starts):
+            raise ValueError(f"step_clip_vit: {n} image sequences of {P} rows from columns {starts} do not fit a [{B}, {L}] batch")
+        return self._on_compute_stream(input_ids, attention_mask, labels, batch_size_t2i, batch_size_lm, batch_size_mmu, max_seq_length,
+                                       image=(image_features, starts))
+
+    def projector_grads(self):
+        """{state-dict key: gradient} of the four projector tensors: views of the projector's bucket (tests, logging); a frozen
+        tensor's reads zero.  Empty when no projector parameter trains."""
+        return dict(self._pviews)
+
+    def _on_compute_stream(self, *args, **kw):
         ms = None
         if getattr(self, "exchange", None) is not None and self.reserve_cus > 0:
             ms = self.compute_stream()
         if ms is None:
-            return self._step(input_ids, attention_mask, labels, batch_size_t2i, batch_size_lm, batch_size_mmu, max_seq_length)
+            return self._step(*args, **kw)
         cur = torch.cuda.current_stream()
         ms.wait_stream(cur)
         with torch.cuda.stream(ms):
-            out = self._step(input_ids, attention_mask, labels, batch_size_t2i, batch_size_lm, batch_size_mmu, max_seq_length)
+            out = self._step(*args, **kw)
         cur.wait_stream(ms)
         out.record_stream(cur)  # allocated on the masked stream's pool, consumed on the caller's stream
         if self._win_sum is not None:
             self._win_sum.record_stream(cur)
         return out
 
-    def _step(self, input_ids, attention_mask, labels, batch_size_t2i, batch_size_lm, batch_size_mmu, max_seq_length):
+    def _step(self, input_ids, attention_mask, labels, batch_size_t2i, batch_size_lm, batch_size_mmu, max_seq_length, image=None):
         # model.trainer() re-uploads parameters whose (data_ptr, version) changed since the last call (load_state_dict, resume,
         # manual edits); the native AdamW below updates them through raw pointers and refreshes the engine images itself
         self.tr = self.model.trainer()
@@ -405,15 +474,20 @@ class Trainer:
         if any(bool(p.requires_grad) != self.trainable.get(n) for n, p in cur):
             raise RuntimeError("Trainer: requires_grad of model.showo's parameters changed after the Trainer was built; build a new "
                                "Trainer for the new trainable set")
+        pcur = [("mm_projector." + n, p) for n, p in self.model.mm_projector.named_parameters()] if self.projector else []
+        if any(bool(p.requires_grad) != self.ptrainable.get(n) for n, p in pcur):
+            raise RuntimeError("Trainer: requires_grad of model.mm_projector's parameters changed after the Trainer was built; build a "
+                               "new Trainer for the new trainable set")
         win = self.window
-        if self._binding_key(cur) != self._bound:  # new native trainer, or a parameter's storage moved: rebuild every raw-pointer binding
+        if self._binding_key(cur, pcur) != self._bound:  # new native trainer, or a parameter's storage moved: rebuild every raw-pointer binding
             if win.is_open:
                 raise RuntimeError("Trainer: the native trainer or a parameter's storage changed inside an open accumulation window; "
                                    "the partial gradient sum belongs to the old binding")
-            self.params = cur
+            self.params, self.pparams = cur, pcur
             self._bind()
         from .modeling_showo import sync_trainable
-        sync_trainable(self.model, self.tr, self.trainable, False)  # only what the native trainer was not told yet
+        # only what the native trainer was not told yet; block 0 hands its data gradient down when the projector consumes it
+        sync_trainable(self.model, self.tr, self.trainable, image is not None and self._ptrains)
         m, tr, s = self.model, self.tr, _lib.stream
         B, L = input_ids.shape
         ids = input_ids.to(torch.int64).contiguous()
@@ -434,7 +508,7 @@ class Trainer:
             _lib.call("showo_train_set_loss_rows", tr, self._loss_rows_mode)
         try:
             self._micro_backward(m, tr, ids, mask, lab, B, L, batch_size_t2i, batch_size_lm, batch_size_mmu, max_seq_length, w, losses,
-                                 ex if closes else None)
+                                 ex if closes else None, image)
         finally:
             # per call, like the announcement of the loss weights: the module's autograd path shares this native trainer and overwrites
             # (and must return the full logits: it never runs the head on the labelled rows only)
@@ -456,20 +530,86 @@ class Trainer:
             ex.finish()
         self.grad_norm = self.clip_grad_norm_(self.max_grad_norm) if self.max_grad_norm is not None else None
         self.step_count += 1
-        _lib.call("showo_train_adamw_step", tr, self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self.step_count, _lib.stream())
+        if self._showo_trains:
+            _lib.call("showo_train_adamw_step", tr, self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self.step_count, _lib.stream())
+        if self._ptrains:
+            self._projector_adamw()
         self.sync_gradients = True
         return losses
 
-    def _micro_backward(self, m, tr, ids, mask, lab, B, L, batch_size_t2i, batch_size_lm, batch_size_mmu, max_seq_length, w, losses, ex):
+    def _projector_adamw(self):
+        """torch.optim.AdamW on the projector's trainable tensors (reference training/train_w_clip_vit.py:226-239: names containing
+        `bias` take no decay), then their bf16 images go to the HIP projector from the updated masters -- what mark_weights_dirty()
+        would make the next forward do, without its host wait"""
+        mm = self.model.mm_projector
+        for n, p in self.pparams:
+            if not self.ptrainable[n]:
+                continue
+            _lib.call("showo_adamw", p.data_ptr(), self._pviews[n].data_ptr(), self.m[n].data_ptr(), self.v[n].data_ptr(), p.numel(),
+                      self.lr, self.betas[0], self.betas[1], self.eps, 0.0 if "bias" in n else self.wd, self.step_count, _lib.stream())
+            if getattr(mm, "_proj", None) is not None and mm._versions is not None:
+                k = n[len("mm_projector."):]
+                _lib.call("showo_projector_load", mm._proj, k.encode(), p.data_ptr(), p.numel(), _lib.stream())
+                mm._versions[k] = (p.data_ptr(), p._version)
+            else:
+                mm.mark_weights_dirty()
+
+    def _projector_backward(self, tr, mm, n, P, ex):
+        """image-gradient gather -> projector backward into the projector's bucket (adding inside a window) -> its collective"""
+        acc = 0 if self.window.is_first else 1
+        if n * P > 0:
+            numel = n * P * mm._dims[1]
+            g = getattr(self, "_img_grad", None)
+            if g is None or g.numel() != numel or g.device != self._pgrad.device:  # kept between steps: the batch geometry rarely changes
+                g = self._img_grad = torch.empty(numel, dtype=torch.float32, device=self._pgrad.device)
+            _lib.call("showo_train_image_grad", tr, _lib.ptr(g), numel, _lib.stream())
+            # a frozen tensor passes NULL: its gradient is neither computed nor written, in or outside a window, so its slot -- part of
+            # the exchange bucket and of the clipping norm -- reads zero from the buffer's creation on
+            v = [self._pviews[k].data_ptr() if self.ptrainable[k] else None for k in PROJECTOR_KEYS]
+            _lib.call("showo_projector_backward_acc", mm._proj, _lib.ptr(g), n * P, None, v[0], v[1], v[2], v[3], acc, _lib.stream())
+        elif not acc:
+            self._pgrad.zero_()  # a micro-batch without image rows opens the window: the projector's gradient starts from zero
+        if ex is not None:
+            ex.launch(self._pbucket)
+
+    def _micro_backward(self, m, tr, ids, mask, lab, B, L, batch_size_t2i, batch_size_lm, batch_size_mmu, max_seq_length, w, losses, ex,
+                        image=None):
         """forward + backward of one micro-batch with loss weights w; ex: the exchange whose bucket collectives are launched as the
-        buckets finish (None: no exchange -- no process group, or a micro-batch that does not close its window)"""
+        buckets finish (None: no exchange -- no process group, or a micro-batch that does not close its window).  image: (features
+        [n, P, in_dim], starts) of step_clip_vit -- the projector's rows are spliced into layer 0's input"""
+        if image is None:
+            return self._micro_backward_body(m, tr, ids, mask, lab, B, L, batch_size_t2i, batch_size_lm, batch_size_mmu, max_seq_length, w,
+                                             losses, ex, None)
+        mm = m.mm_projector
+        feats, starts = image
+        n, P = int(feats.shape[0]), int(feats.shape[1])
+        prev = int(getattr(mm, "_precision", 0))
+        if prev:
+            mm.set_precision(0)  # training differentiates the bf16-operand forward
+        try:
+            rows = start = None
+            if n * P > 0:
+                rows = mm._hip_forward(feats.detach().float()).contiguous()
+                start = torch.tensor(starts, dtype=torch.int32).to(ids.device, non_blocking=True)
+            return self._micro_backward_body(m, tr, ids, mask, lab, B, L, batch_size_t2i, batch_size_lm, batch_size_mmu, max_seq_length, w,
+                                             losses, ex, (mm, rows, start, n, P))
+        finally:
+            if prev:
+                mm.set_precision(prev)
+
+    def _micro_backward_body(self, m, tr, ids, mask, lab, B, L, batch_size_t2i, batch_size_lm, batch_size_mmu, max_seq_length, w, losses, ex,
+                             sp):
         s = _lib.stream
         nL = m.arch["num_hidden_layers"]
         _lib.call("showo_train_set_loss_weights", tr, w[0], w[1], w[2], 1)
         try:  # ONE scope for the announcement: a forward that raises must withdraw it too (ADVICE r4)
             try:
-                _lib.call("showo_train_forward", tr, _lib.ptr(ids), _lib.ptr(mask), _lib.ptr(lab), B, L, batch_size_t2i, batch_size_lm,
-                          batch_size_mmu, max_seq_length, None, _lib.ptr(losses), s())
+                if sp is None:
+                    _lib.call("showo_train_forward", tr, _lib.ptr(ids), _lib.ptr(mask), _lib.ptr(lab), B, L, batch_size_t2i, batch_size_lm,
+                              batch_size_mmu, max_seq_length, None, _lib.ptr(losses), s())
+                else:
+                    _lib.call("showo_train_forward_spliced", tr, _lib.ptr(ids), _lib.ptr(sp[1]), _lib.ptr(sp[2]), sp[3], sp[4], _lib.ptr(mask),
+                              _lib.ptr(lab), B, L, batch_size_t2i, batch_size_lm, batch_size_mmu, max_seq_length, None, _lib.ptr(losses), s())
             finally:
                 _lib.call("showo_trainer_use_intervals", tr, None, None)
             # `lab` is this step's own contiguous copy / view and is not written between the forward above and this call: the d(logits)
@@ -484,12 +624,17 @@ class Trainer:
         # backward stops at the lowest phase anything needs
         bt = self._bucket_trains
         lo = 0 if bt[0] else next((i for i in range(nL) if bt[1 + i]), nL)
+        through = sp is not None and self._ptrains and sp[3] * sp[4] > 0  # the projector consumes block 0's data gradient
+        if through:
+            lo = 0
         if ex is not None and bt[nL + 1]:
             ex.launch(nL + 1)
         for i in range(nL - 1, lo - 1, -1):
             _lib.call("showo_train_backward_layer", tr, i, s())
             if ex is not None and bt[i + 1]:
                 ex.launch(i + 1)  # the collective of block i overlaps the backward of block i - 1
+        if self._ptrains:  # (a micro-batch without image rows contributes nothing; its bucket still goes on the wire)
+            self._projector_backward(tr, sp[0] if sp is not None else None, sp[3] if through else 0, sp[4] if through else 0, ex)
         if bt[0]:
             _lib.call("showo_train_backward_embed", tr, s())
             if ex is not None:
@@ -501,12 +646,17 @@ class Trainer:
         ONE fixed-order HIP reduction over the library's flat gradient buffer + a scale pass that reads the coefficient from device
         memory (csrc/train_kernels.hip showo_grad_clip_norm): no ATen arithmetic, no host synchronisation, bit-reproducible.
         Returns the total norm (device scalar)."""
-        b0, bl = self.buckets[0], self.buckets[-1]
+        flat = self.buckets if self._pbucket is None else self.buckets[:self._pbucket]  # the library's flat buffer
+        b0, bl = flat[0], flat[-1]
         n = (bl.data_ptr() + bl.numel() * 4 - b0.data_ptr()) // 4
-        if sum(b.numel() for b in self.buckets) != n:
+        if sum(b.numel() for b in flat) != n:
             raise RuntimeError("gradient buckets are not one contiguous range")
         if getattr(self, "_clip_ws", None) is None:
-            self._clip_ws = torch.empty(_lib.load().showo_grad_clip_ws_doubles(), dtype=torch.float64, device=b0.device)
+            self._clip_ws = torch.empty(2 * _lib.load().showo_grad_clip_ws_doubles(), dtype=torch.float64, device=b0.device)
         out2 = torch.empty(2, dtype=torch.float32, device=b0.device)
+        if self._pbucket is not None:  # ONE norm over the Show-o and projector gradients (the reference clips model.parameters())
+            _lib.call("showo_grad_clip_norm2", b0.data_ptr(), n, self._pgrad.data_ptr(), self._pgrad.numel(), float(max_norm),
+                      _lib.ptr(self._clip_ws), _lib.ptr(out2), _lib.stream())
+            return out2[0]
         _lib.call("showo_grad_clip_norm", b0.data_ptr(), n, float(max_norm), _lib.ptr(self._clip_ws), _lib.ptr(out2), _lib.stream())
         return out2[0]

@@ -109,6 +109,44 @@ def build_training_batch(uni_prompting, config, mask_id, mask_schedule, image_to
     return input_ids, labels, mask, mask_prob, (ids_t2i.shape[0], ids_lm.shape[0], ids_mmu.shape[0])
 
 
+def image_starts(image_start, n):
+    """`image_start` of splice_image_columns / Trainer.step_clip_vit as n host ints: one integer (a Python or numpy integer, a 0-d
+    tensor) for every sequence, or n of them (a sequence or a 1-d tensor: read back with one `.tolist()`)"""
+    import numbers
+    if torch.is_tensor(image_start):
+        image_start = image_start.tolist()
+    if isinstance(image_start, numbers.Integral):
+        return [int(image_start)] * n
+    starts = [int(v) for v in image_start]
+    if len(starts) != n:
+        raise ValueError(f"image_start: {len(starts)} starts for {n} image sequences")
+    return starts
+
+
+def splice_image_columns(input_ids_mmu, labels_mmu, image_start, P, fill_id, ignore_id=-100):
+    """Full-length ids and labels of the mmu sequences for Trainer.step_clip_vit: P columns inserted at column `image_start` (an int,
+    or one int per sequence), ids filled with `fill_id` (never read: the projector's rows stand there), labels with `ignore_id`.
+    The layout the reference gets by concatenating embeddings and labels around the image rows (training/train_w_clip_vit.py:538-549
+    for llava_pretrain, image_start = 2; :577-589 for llava_tuning, image_start = 2 + SYSTEM_PROMPT_LEN).
+    input_ids_mmu, labels_mmu: [n, Lt] without the image columns.  Returns (ids [n, Lt + P], labels [n, Lt + P]), int64."""
+    ids, lab = input_ids_mmu.long(), labels_mmu.long()
+    if ids.dim() != 2 or ids.shape != lab.shape:
+        raise ValueError(f"splice_image_columns: ids {tuple(ids.shape)} and labels {tuple(lab.shape)} must be the same [n, Lt]")
+    n, Lt = ids.shape
+    P = int(P)
+    starts = image_starts(image_start, n)
+    if P < 0 or any(v < 0 or v > Lt for v in starts):
+        raise ValueError(f"splice_image_columns: image_start {image_start!r} does not fit {n} sequences of {Lt} columns")
+    st = torch.tensor(starts, dtype=torch.long, device=ids.device).view(n, 1)
+    col = torch.arange(Lt + P, device=ids.device).view(1, Lt + P)
+    image = (col >= st) & (col < st + P)
+    src = (col - P * (col >= st + P).long()).clamp(0, max(Lt - 1, 0))  # the text column a non-image column comes from
+    if Lt == 0:
+        return ids.new_full((n, P), fill_id), lab.new_full((n, P), ignore_id)
+    return (torch.where(image, ids.new_full((), fill_id), ids.gather(1, src.expand(n, -1))),
+            torch.where(image, lab.new_full((), ignore_id), lab.gather(1, src.expand(n, -1))))
+
+
 def labelled_rows(labels, batch_size_t2i, batch_size_lm, batch_size_mmu, max_seq_length):
     """The logits rows that enter one of the three losses of `Showo.forward` (reference models/modeling_showo.py:83-98), as
     ascending int64 indices into the flattened [B * L] rows.  Plain torch, works on CPU tensors: the stated rule of the row census
