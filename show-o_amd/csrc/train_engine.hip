@@ -48,14 +48,23 @@ struct LayerPlan {
 };
 struct Bound { std::string key; float *p, *m, *v; int64_t n; bool decay; };
 
+// an on / off switch of this file from the environment (unset: dflt); every caller reads its switch once per process
+bool env_flag(const char* name, bool dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) != 0 : dflt;
+}
 // SHOWO_TRAIN_TN (default 1): weight gradients by showo_gemm_tn_bf16 on the token-major tensors the backward already holds (dY, and the
 // activations saved by the forward) + showo_colsum_bf16 for the bias gradients; 0 = transpose both operands and run the k-contiguous
 // GEMM (the round-2 path: 243 transposes per step).  Read once per process: the per-layer gelu(fc1) buffers exist only in TN mode.
 bool train_tn() {
-    static int v = -1;
-    if (v < 0) { const char* e = getenv("SHOWO_TRAIN_TN"); v = e ? (atoi(e) != 0) : 1; }
-    return v != 0;
+    static const bool v = env_flag("SHOWO_TRAIN_TN", true);
+    return v;
 }
+// the batch split a forward was called with: its cross-entropy tables (and an announced d(logits)) serve a backward with the same one only
+struct Split {
+    int b_t2i = 0, b_lm = 0, b_mmu = 0, max_seq_len = 0;
+    bool operator==(const Split& o) const { return b_t2i == o.b_t2i && b_lm == o.b_lm && b_mmu == o.b_mmu && max_seq_len == o.max_seq_len; }
+};
 }  // namespace
 
 struct showo_trainer {
@@ -86,6 +95,7 @@ struct showo_trainer {
     // state of the last forward
     int B = 0, Lq = 0;
     bool have_fwd = false;
+    Split split;  // of the last forward
     uint64_t generation = 0;  // training forwards started (showo_train_generation)
     bool has_mask = false;
     bool from_embeds = false;  // last forward started from caller-provided embeddings: d(loss)/d(embeddings) = dy
@@ -113,15 +123,13 @@ struct showo_trainer {
     bool dl_valid = false;
     float dl_g[3] = {0.f, 0.f, 0.f};
     const int64_t* dl_labels = nullptr;
-    int dl_split[4] = {0, 0, 0, 0};
     // gradient accumulation (showo_train_set_accumulate): every parameter-gradient write of the backward adds into the flat buffer
     bool accumulate = false;
     // loss head on the labelled rows only (showo_train_set_loss_rows): the census of a forward with labels is an ordered compaction,
     // its row count comes back through a pinned int (the one host wait of the mode) and the head runs on the compact rows
     int loss_rows = 0;       // the mode the NEXT forward takes (0 = all rows)
     bool compact = false;    // the LAST forward ran the compact head: logits / dlogits / hf / dh hold Tc rows in row_index order
-    int Tc = 0;              // its labelled rows
-    int lr_split[4] = {0, 0, 0, 0};  // and its batch split (the backward must be asked for the same one)
+    int Tc = 0;              // its labelled rows (the backward must be asked for the forward's batch split)
     int *row_index = nullptr, *row_slot = nullptr, *scan_ws = nullptr;
     void* ce_rows_c = nullptr;
     int32_t* tc_host = nullptr;
@@ -511,11 +519,9 @@ static int train_forward_impl(showo_trainer* t, const int64_t* ids, const float*
         iv = e->iv; flag = e->flag;
     }
     // SHOWO_TRAIN_FUSED_PROJ (default 1): the fused projection launch of the inference layer, in its save-for-backward form
-    static int fused_env = -1;
-    if (fused_env < 0) { const char* env = getenv("SHOWO_TRAIN_FUSED_PROJ"); fused_env = env ? (atoi(env) != 0) : 1; }
+    static const bool fused_env = env_flag("SHOWO_TRAIN_FUSED_PROJ", true);
     // SHOWO_TRAIN_QKPREP (default 0): 1 = raw-only projection launch + showo_qk_prep (A/B of the epilogue's LayerNorm / RoPE cost)
-    static int qkprep_env = -1;
-    if (qkprep_env < 0) { const char* env = getenv("SHOWO_TRAIN_QKPREP"); qkprep_env = env ? (atoi(env) != 0) : 0; }
+    static const bool qkprep_env = env_flag("SHOWO_TRAIN_QKPREP", false);
     const bool fused_proj = fused_env && T >= 256 && e->cfg.rotary_dim == 32 && (3 * H) % 256 == 0 && (F % 8) == 0 &&
                             (int64_t)T * F * 2 < ((int64_t)1 << 32);
     for (int i = 0; i < e->nL; ++i) {
@@ -524,29 +530,25 @@ static int train_forward_impl(showo_trainer* t, const int64_t* ids, const float*
         // The layer's input (saved for ln_bwd) lives in l.x already: the previous layer's fc2 epilogue wrote it there.  The residual
         // stream ping-pongs l.x -> e->x (after dense) -> L[i + 1].x (after fc2; e->x for the last layer): no 92 MB copy per layer.
         float* xnext = (i + 1 < e->nL) ? t->L[i + 1].x : e->x;
-        bf16_t* ffn = l.a ? l.a : e->ffn;  // TN mode keeps gelu(fc1) per layer for the fc2 weight gradient
+        bf16_t* ffn = train_tn() ? l.a : e->ffn;  // TN form keeps gelu(fc1) per layer for the fc2 weight gradient
         TRY(showo_layernorm_f32_bf16(l.x, w.ln_w, w.ln_b, l.h, nullptr, T, H, e->cfg.ln_eps, s));
-        if (fused_proj) {
-            // q/k/v_proj + q/k LayerNorm + RoPE + relayout AND fc1 + gelu_new in one launch that also saves qkv and the fc1
-            // pre-activation for backward ([Wqkv ; W1] is one allocation, engine.hip); same bits as the four launches below
-            if (qkprep_env) {
-                // raw-only form: the launch stores qkv / the fc1 pre-activation / gelu and the q/k LayerNorm + RoPE + relayout run as
-                // showo_qk_prep on the saved qkv (same bits: both start from the rounded values)
-                TRY(showo_gemm_qkv_fc1_save_bf16(l.h, H, w.wqkv, H, w.bqkv, w.qln_w, w.qln_b, w.kln_w, w.kln_b, e->cosT, e->sinT, nullptr, nullptr,
-                                                 nullptr, l.qkv, 3 * H, l.f, ffn, F, F, B, L, nH, e->cfg.rotary_dim, e->cfg.ln_eps, 0, L, Lp, 0, s));
-                TRY(showo_qk_prep(l.qkv, w.qln_w, w.qln_b, w.kln_w, w.kln_b, e->cosT, e->sinT, l.Q, l.K, l.Vt, B, L, nH, e->cfg.rotary_dim,
-                                  e->cfg.ln_eps, 0, L, Lp, s));
-            } else
-            TRY(showo_gemm_qkv_fc1_save_bf16(l.h, H, w.wqkv, H, w.bqkv, w.qln_w, w.qln_b, w.kln_w, w.kln_b, e->cosT, e->sinT, l.Q, l.K, l.Vt,
-                                             l.qkv, 3 * H, l.f, ffn, F, F, B, L, nH, e->cfg.rotary_dim, e->cfg.ln_eps, 0, L, Lp, 0, s));
-            TRY(showo_attn_fwd_lse(l.Q, l.K, l.Vt, iv, flag, mask, l.attn, l.lse, B, nH, L, L, L, Lp, H, s));
-            TRY(showo_gemm_bf16(l.attn, H, w.wd, H, w.bd, 0, e->x, H, l.x, H, T, H, H, SHOWO_EPI_RESID_F32, s));
-        } else {
+        // projection stage.  Fused: q/k/v_proj + q/k LayerNorm + RoPE + relayout AND fc1 + gelu_new in one launch that also saves qkv
+        // and the fc1 pre-activation for backward ([Wqkv ; W1] is one allocation, engine.hip); its raw-only form (SHOWO_TRAIN_QKPREP)
+        // stores qkv / the fc1 pre-activation / gelu and leaves q/k LayerNorm + RoPE + relayout to showo_qk_prep on the saved qkv, as
+        // the unfused GEMM does.  Same bits in all three: each starts from the rounded values.
+        const bool prep = !fused_proj || qkprep_env;
+        if (fused_proj)
+            TRY(showo_gemm_qkv_fc1_save_bf16(l.h, H, w.wqkv, H, w.bqkv, w.qln_w, w.qln_b, w.kln_w, w.kln_b, e->cosT, e->sinT, prep ? nullptr : l.Q,
+                                             prep ? nullptr : l.K, prep ? nullptr : l.Vt, l.qkv, 3 * H, l.f, ffn, F, F, B, L, nH, e->cfg.rotary_dim,
+                                             e->cfg.ln_eps, 0, L, Lp, 0, s));
+        else
             TRY(showo_gemm_bf16(l.h, H, w.wqkv, H, w.bqkv, 0, l.qkv, 3 * H, nullptr, 0, T, 3 * H, H, SHOWO_EPI_BF16, s));
+        if (prep)
             TRY(showo_qk_prep(l.qkv, w.qln_w, w.qln_b, w.kln_w, w.kln_b, e->cosT, e->sinT, l.Q, l.K, l.Vt, B, L, nH, e->cfg.rotary_dim,
                               e->cfg.ln_eps, 0, L, Lp, s));
-            TRY(showo_attn_fwd_lse(l.Q, l.K, l.Vt, iv, flag, mask, l.attn, l.lse, B, nH, L, L, L, Lp, H, s));
-            TRY(showo_gemm_bf16(l.attn, H, w.wd, H, w.bd, 0, e->x, H, l.x, H, T, H, H, SHOWO_EPI_RESID_F32, s));
+        TRY(showo_attn_fwd_lse(l.Q, l.K, l.Vt, iv, flag, mask, l.attn, l.lse, B, nH, L, L, L, Lp, H, s));
+        TRY(showo_gemm_bf16(l.attn, H, w.wd, H, w.bd, 0, e->x, H, l.x, H, T, H, H, SHOWO_EPI_RESID_F32, s));
+        if (!fused_proj) {
             TRY(showo_gemm_bf16(l.h, H, w.w1, H, w.b1, 0, l.f, F, nullptr, 0, T, F, H, SHOWO_EPI_BF16, s));
             TRY(showo_gelu_bf16(l.f, ffn, (int64_t)T * F, s));
         }
@@ -571,32 +573,27 @@ static int train_forward_impl(showo_trainer* t, const int64_t* ids, const float*
     }
     t->compact = compact;
     t->Tc = Tc;
-    t->lr_split[0] = b_t2i; t->lr_split[1] = b_lm; t->lr_split[2] = b_mmu; t->lr_split[3] = max_seq_len;
+    t->split = Split{b_t2i, b_lm, b_mmu, max_seq_len};
     if (logits_out) SHOWO_CHECK_HIP(hipMemcpyAsync(logits_out, t->logits, (size_t)T * V * sizeof(float), hipMemcpyDeviceToDevice, s));
     t->B = B; t->Lq = L;
     t->have_fwd = true;
     t->has_mask = iv != nullptr;
     t->dl_valid = false;
     if (labels) {
-        if (compact) {  // the census ran ahead of the blocks: the cross-entropy of the Tc compact rows (none: only the 0 / 0 finalisation)
-            TRY(showo::ce_loss_compact(t->logits, V, Tc, V, t->lw[0], t->lw[1], t->lw[2], nullptr, t->ce_rows_c, t->counts, t->rowloss,
-                                       t->lw_set ? t->dlogits : nullptr, t->Vp, t->losses, s));
-            if (t->lw_set) {
-                t->dl_valid = true;
-                t->dl_labels = labels;
-                for (int k = 0; k < 3; ++k) t->dl_g[k] = t->lw[k];
-                t->dl_split[0] = b_t2i; t->dl_split[1] = b_lm; t->dl_split[2] = b_mmu; t->dl_split[3] = max_seq_len;
-            }
-        } else if (t->lw_set) {  // one pass: losses and d(sum_g w_g loss_g)/d(logits)
-            TRY(showo_ce_loss(t->logits, V, labels, B, L, V, b_t2i, b_lm, b_mmu, max_seq_len, t->lw[0], t->lw[1], t->lw[2], t->ce_rows,
-                              t->counts, t->rowloss, t->dlogits, t->Vp, t->losses, s));
+        // announced loss weights (lw_set): the one pass writes losses and d(sum_g w_g loss_g)/d(logits), remembered for the backward
+        bf16_t* dl = t->lw_set ? t->dlogits : nullptr;
+        const float* lw = t->lw;  // read by the kernels only where they write d(logits)
+        if (compact)  // the census ran ahead of the blocks: the cross-entropy of the Tc compact rows (none: only the 0 / 0 finalisation)
+            TRY(showo::ce_loss_compact(t->logits, V, Tc, V, lw[0], lw[1], lw[2], nullptr, t->ce_rows_c, t->counts, t->rowloss, dl, t->Vp,
+                                       t->losses, s));
+        else
+            TRY(showo_ce_loss(t->logits, V, labels, B, L, V, b_t2i, b_lm, b_mmu, max_seq_len, dl ? lw[0] : 0.f, dl ? lw[1] : 0.f,
+                              dl ? lw[2] : 0.f, t->ce_rows, t->counts, t->rowloss, dl, dl ? t->Vp : 0, t->losses, s));
+        if (dl) {
             t->dl_valid = true;
             t->dl_labels = labels;
-            for (int k = 0; k < 3; ++k) t->dl_g[k] = t->lw[k];
-            t->dl_split[0] = b_t2i; t->dl_split[1] = b_lm; t->dl_split[2] = b_mmu; t->dl_split[3] = max_seq_len;
-        } else
-        TRY(showo_ce_loss(t->logits, V, labels, B, L, V, b_t2i, b_lm, b_mmu, max_seq_len, 0.f, 0.f, 0.f, t->ce_rows, t->counts,
-                          t->rowloss, nullptr, 0, t->losses, s));
+            std::copy(t->lw, t->lw + 3, t->dl_g);
+        }
         // the backward works on the interval form only: a mask with more than two visibility runs in a row (never produced by
         // the reference's builders with contiguous padding) must not train silently wrong -> NaN losses, no host sync
         if (iv) poison_losses_kernel<<<1, 64, 0, s>>>(t->losses, e->flag);
@@ -654,11 +651,74 @@ extern "C" int showo_train_input_grad(showo_trainer* t, float* out, int64_t n, v
     const int acc = t->accumulate ? 1 : 0; /* parameter-gradient writers add into their slot; scratch side outputs never do */ \
     (void)F; (void)V; (void)nH; (void)Vp; (void)Tp; (void)Lp; (void)iv; (void)s; (void)acc;
 
-// weight gradient of the SHOWO_TRAIN_TN=0 path: out fp32 [M, N] (+)= (dY^T)[M, Tp] (X^T)[N, Tp]^T on the k-contiguous GEMM; accumulating =
+// weight gradient of the NT form: out fp32 [M, N] (+)= (dY^T)[M, Tp] (X^T)[N, Tp]^T on the k-contiguous GEMM; accumulating =
 // the residual epilogue with resid = out (the finished accumulator is added to the old value once)
 static int wgrad_nt(const bf16_t* dyT, const bf16_t* xT, float* out, int ldo, int M, int N, int Tp, int acc, hipStream_t s) {
     return showo_gemm_bf16(dyT, Tp, xT, Tp, nullptr, 0, out, ldo, acc ? out : nullptr, acc ? ldo : 0, M, N, Tp,
                            acc ? SHOWO_EPI_RESID_F32 : SHOWO_EPI_F32, s);
+}
+
+namespace {
+// The two forms (SHOWO_TRAIN_TN) of a weight gradient dW[M, N] (+)= dY^T X over R token rows and of its bias gradient db = column
+// sums of dY.  The backward asks image(dY) once per dY tensor, then weight(dY, X) for every weight that contracts with it.
+//   TN form: showo_gemm_tn_bf16 on the token-major tensors; image() is showo_colsum_bf16 into db, unless the launch that produced
+//            dY wrote db already (fused: showo_ln_bwd_colsum_acc for dy16, showo_dgelu_colsum_bf16_acc for d f).
+//   NT form: image() transposes dY into bigT and writes db from the same pass; weight() transposes X into xT and runs wgrad_nt.
+//            bigT holds ONE dY image and xT ONE X image at a time, so the order of the calls is part of the result: every weight()
+//            of a dY comes before the next image().  xT remembers the X it holds: h^T serves dW1 and dWqkv when both run (hold_x,
+//            asked for ahead of dW1 so that it is made at the same point whichever of the two trains).
+//   fc2's X is gelu_new(f): the NT transpose applies it (mode 1) to the saved pre-activation l.f, the TN form reads the rows the
+//   forward saved (l.a, allocated in that form only).
+struct XOp { const bf16_t* p; int mode; };
+struct WGrad {
+    showo_trainer* t;
+    int R, Tp, acc;  // token rows, their padded count (the row length of both images), 1 = add into the gradient slots
+    hipStream_t s;
+    const bf16_t* held = nullptr;  // NT: the X whose image xT holds
+
+    enum Weights { NO_WEIGHT, WEIGHT_FOLLOWS };       // some weight() of this dY follows (NT form: the image is needed for it)
+    enum TnSums { TN_SUMS_HERE, TN_SUMS_BY_PRODUCER };  // TN form: who writes db -- image(), or the launch that produced dY
+    XOp fc2_x(const LayerT& l) const { return train_tn() ? XOp{l.a, 0} : XOp{l.f, 1}; }
+    // dY [R, M]; db: bias gradient slot or NULL
+    int image(const bf16_t* dY, int M, Weights w, float* db, TnSums sums) {
+        if (train_tn()) return (db && sums == TN_SUMS_HERE) ? showo_colsum_bf16(dY, M, R, M, t->colpart, db, acc, s) : 0;
+        return (w == WEIGHT_FOLLOWS || db) ? showo_transpose_bf16(dY, M, t->bigT, R, M, Tp, 0, t->colpart, db, acc, s) : 0;
+    }
+    static Weights follows(bool any) { return any ? WEIGHT_FOLLOWS : NO_WEIGHT; }
+    int hold_x(XOp x, int N) {
+        if (train_tn() || held == x.p) return 0;
+        held = x.p;
+        return showo_transpose_bf16(x.p, N, t->xT, R, N, Tp, x.mode, nullptr, nullptr, 0, s);
+    }
+    // out [M, N] (+)= dY[R, :M]^T X[R, N]
+    int weight(const bf16_t* dY, int ldy, XOp x, int N, float* out, int M) {
+        if (train_tn()) TRY(showo_gemm_tn_bf16(dY, ldy, x.p, N, out, N, M, N, R, acc, 1, s));
+        else {
+            TRY(hold_x(x, N));
+            TRY(wgrad_nt(t->bigT, t->xT, out, N, M, N, Tp, acc, s));
+        }
+        ++t->cnt[0];
+        return 0;
+    }
+};
+}  // namespace
+
+// The LayerNorm backward that leaves dy / dy16 as block j's incoming gradient (j < 0: nothing above the embedding consumes them as a
+// block).  TN form: the launch also writes the column sums of dy16 = block j's dense / fc2 bias gradients (b2_dst, scratch when both
+// are frozen).  slot != NULL: the row-slot form over a compact dh (dy is written whole, not added to).
+static int ln_bwd_into_block(showo_trainer* t, int j, const float* x, const float* gamma, float* gln, int acc_g, const int* slot, int T,
+                             hipStream_t s) {
+    const int H = t->e->H;
+    const float eps = t->e->cfg.ln_eps;
+    const bool sums = train_tn() && j >= 0;
+    float* cb = sums ? b2_dst(t, j) : nullptr;
+    const int acc_cb = t->accumulate && cb;
+    float* dxsum = sums ? (cb ? cb : t->sc_b) : nullptr;
+    if (slot)
+        return showo::ln_bwd_slot(x, gamma, t->dh, slot, t->dy, t->dy16, t->lnpart, gln, dxsum, acc_g, acc_cb, T, H, eps, s);
+    if (sums)
+        return showo_ln_bwd_colsum_acc(x, gamma, t->dh, t->dy, t->dy, t->dy16, t->lnpart, gln, dxsum, acc_g, acc_cb, T, H, eps, s);
+    return showo_ln_bwd_acc(x, gamma, t->dh, t->dy, t->dy, t->dy16, t->lnpart, gln, acc_g, T, H, eps, s);
 }
 
 // the head phase after d(logits) is in t->dlogits: lm_head weight / bias gradients, d(final LayerNorm), dy of the top block.
@@ -672,88 +732,66 @@ static int backward_head_from_dlogits(showo_trainer* t, void* stream) {
     if (R == 0) {  // no labelled row: the head's gradients are zero (accumulating: nothing is added), no zero-sized launch
         if (!acc && t->p_blm) SHOWO_CHECK_HIP(hipMemsetAsync(t->gblm, 0, (size_t)Vp * sizeof(float), s));
         if (!acc && t->p_wlm) SHOWO_CHECK_HIP(hipMemsetAsync(t->gwlm, 0, (size_t)V * H * sizeof(float), s));
-    } else if (train_tn()) {
-        if (t->p_blm) TRY(showo_colsum_bf16(t->dlogits, Vp, R, Vp, t->colpart, t->gblm, acc, s));                         // lm_head bias grad
-        if (t->p_wlm) { TRY(showo_gemm_tn_bf16(t->dlogits, Vp, e->hf, H, t->gwlm, H, V, H, R, acc, 1, s)); ++t->cnt[0]; }   // dWlm [V,H]
     } else {
-    if (t->p_wlm || t->p_blm)  // dlogits^T + lm_head bias grad
-        TRY(showo_transpose_bf16(t->dlogits, Vp, t->bigT, R, Vp, Tp, 0, t->colpart, t->p_blm ? t->gblm : nullptr, acc, s));
-    if (t->p_wlm) {
-    TRY(showo_transpose_bf16(e->hf, H, t->xT, R, H, Tp, 0, nullptr, nullptr, 0, s));
-    TRY(wgrad_nt(t->bigT, t->xT, t->gwlm, H, V, H, Tp, acc, s));                                                       // dWlm [V,H]
-    ++t->cnt[0];
-    }
+        WGrad wg{t, R, Tp, acc, s};
+        TRY(wg.image(t->dlogits, Vp, WGrad::follows(t->p_wlm), t->p_blm ? t->gblm : nullptr, WGrad::TN_SUMS_HERE));  // lm_head bias grad
+        if (t->p_wlm) TRY(wg.weight(t->dlogits, Vp, XOp{e->hf, 0}, H, t->gwlm, V));    // dWlm [V,H]
     }
     if (!t->p_fln && !below_needs(t, e->nL)) return 0;  // nothing below the head trains (linear probe): no dgrad, no LayerNorm backward
-    float* gfln = t->p_fln ? t->gfln : t->sc_ln;
-    if (t->compact) {
-        if (R > 0) {  // compact d hf on the k-partition of the T-row launch
-            showo::gemm_pin_split_m(T);
-            const int rc = showo_gemm_bf16(t->dlogits, Vp, t->wlmT, Vp, nullptr, 0, t->dh, H, nullptr, 0, compact_gemm_rows(R, T), H, Vp, SHOWO_EPI_F32, s);
-            showo::gemm_pin_split_m(0);
-            TRY(rc);
-            ++t->cnt[1];
-        }
-        // every row of dy / dy16 is written (zeros for the rows without a label): no clear of dy, and with R == 0 dh is never read
-        float* cb = (train_tn() && e->nL > 0) ? b2_dst(t, e->nL - 1) : nullptr;
-        const bool sums = train_tn() && e->nL > 0;
-        TRY(showo::ln_bwd_slot(e->x, e->fln_w, t->dh, t->row_slot, t->dy, t->dy16, t->lnpart, gfln, sums ? (cb ? cb : t->sc_b) : nullptr,
-                               acc && t->p_fln, acc && cb, T, H, e->cfg.ln_eps, s));
-        for (const Grad& g : t->fln_clear) SHOWO_CHECK_HIP(hipMemsetAsync(g.p, 0, (size_t)g.n * sizeof(float), s));
-        return 0;
+    if (!t->compact || R > 0) {  // d hf; compact: on the k-partition of the T-row launch
+        if (t->compact) showo::gemm_pin_split_m(T);
+        const int rows = t->compact ? compact_gemm_rows(R, T) : T;
+        const int rc = showo_gemm_bf16(t->dlogits, Vp, t->wlmT, Vp, nullptr, 0, t->dh, H, nullptr, 0, rows, H, Vp, SHOWO_EPI_F32, s);
+        if (t->compact) showo::gemm_pin_split_m(0);
+        TRY(rc);
+        ++t->cnt[1];
     }
-    TRY(showo_gemm_bf16(t->dlogits, Vp, t->wlmT, Vp, nullptr, 0, t->dh, H, nullptr, 0, T, H, Vp, SHOWO_EPI_F32, s));   // d hf
-    ++t->cnt[1];
-    SHOWO_CHECK_HIP(hipMemsetAsync(t->dy, 0, (size_t)T * H * sizeof(float), s));
-    if (train_tn() && e->nL > 0) {  // + column sums of dy16 = the dense / fc2 bias gradients of the top block
-        float* cb = b2_dst(t, e->nL - 1);
-        TRY(showo_ln_bwd_colsum_acc(e->x, e->fln_w, t->dh, t->dy, t->dy, t->dy16, t->lnpart, gfln, cb ? cb : t->sc_b, acc && t->p_fln,
-                                    acc && cb, T, H, e->cfg.ln_eps, s));
-    } else
-    TRY(showo_ln_bwd_acc(e->x, e->fln_w, t->dh, t->dy, t->dy, t->dy16, t->lnpart, gfln, acc && t->p_fln, T, H, e->cfg.ln_eps, s));
+    // compact: every row of dy / dy16 is written (zeros for the rows without a label): no clear of dy, and with R == 0 dh is never read
+    if (!t->compact) SHOWO_CHECK_HIP(hipMemsetAsync(t->dy, 0, (size_t)T * H * sizeof(float), s));
+    TRY(ln_bwd_into_block(t, e->nL - 1, e->x, e->fln_w, t->p_fln ? t->gfln : t->sc_ln, acc && t->p_fln,
+                          t->compact ? t->row_slot : nullptr, T, s));
     for (const Grad& g : t->fln_clear) SHOWO_CHECK_HIP(hipMemsetAsync(g.p, 0, (size_t)g.n * sizeof(float), s));
     return 0;
 }
 
+// Both head entry points: the three loss weights on the host (g) or in device memory (g3).  A compact forward's logits are in the order
+// of its census, so its backward works from that table and those counts and must be asked for the same split; the cross-entropy pass
+// that fills d(logits) is skipped when the forward's announced one (showo_train_set_loss_weights) answers the same question.
+static int backward_head(showo_trainer* t, const int64_t* labels, const Split& sp, const float* g, const float* g3, void* stream) {
+    BW_PROLOGUE
+    const bool dev = !g;  // showo_train_backward_head_dev: the weights are g3's
+    if (!labels || (dev && !g3))
+        return set_error_msg(1, dev ? "train_backward_head_dev: labels and g3 required" : "train_backward: labels required");
+    const bool have_dl = g && t->dl_valid && t->dl_labels == labels && std::equal(g, g + 3, t->dl_g) && t->split == sp;
+    t->dl_valid = false;  // a second backward must not trust a consumed flag blindly
+    if (t->compact && !(t->split == sp))
+        return set_error_msg(1, dev ? "train_backward_head_dev: the labelled-rows forward was made with another batch split"
+                                    : "train_backward: the labelled-rows forward was made with another batch split");
+    const float g0 = g ? g[0] : 0.f, g1 = g ? g[1] : 0.f, g2 = g ? g[2] : 0.f;
+    if (!have_dl) {
+        if (t->compact)
+            TRY(showo::ce_loss_compact(t->logits, V, t->Tc, V, g0, g1, g2, g3, t->ce_rows_c, t->counts, t->rowloss, t->dlogits, Vp, nullptr, s));
+        else if (g3)
+            TRY(showo::ce_loss_dev_weights(t->logits, V, labels, B, L, V, sp.b_t2i, sp.b_lm, sp.b_mmu, sp.max_seq_len, g3, t->ce_rows, t->counts,
+                                           t->rowloss, t->dlogits, Vp, s));
+        else
+            TRY(showo_ce_loss(t->logits, V, labels, B, L, V, sp.b_t2i, sp.b_lm, sp.b_mmu, sp.max_seq_len, g0, g1, g2, t->ce_rows, t->counts,
+                              t->rowloss, t->dlogits, Vp, nullptr, s));
+    }
+    return backward_head_from_dlogits(t, stream);
+}
+
 extern "C" int showo_train_backward_head(showo_trainer* t, const int64_t* labels, int b_t2i, int b_lm, int b_mmu, int max_seq_len,
                                          float g_t2i, float g_lm, float g_mmu, void* stream) {
-    BW_PROLOGUE
-    if (!labels) return set_error_msg(1, "train_backward: labels required");
-    // ---- loss + head
-    const bool have_dl = t->dl_valid && t->dl_labels == labels && t->dl_g[0] == g_t2i && t->dl_g[1] == g_lm && t->dl_g[2] == g_mmu &&
-                         t->dl_split[0] == b_t2i && t->dl_split[1] == b_lm && t->dl_split[2] == b_mmu && t->dl_split[3] == max_seq_len;
-    t->dl_valid = false;  // dlogits^T below reuses nothing of it, but a second backward must not trust a consumed flag blindly
-    if (t->compact) {
-        // the compact logits are in the order of the forward's census: the backward works from that table and those counts
-        if (t->lr_split[0] != b_t2i || t->lr_split[1] != b_lm || t->lr_split[2] != b_mmu || t->lr_split[3] != max_seq_len)
-            return set_error_msg(1, "train_backward: the labelled-rows forward was made with another batch split");
-        if (!have_dl)
-            TRY(showo::ce_loss_compact(t->logits, V, t->Tc, V, g_t2i, g_lm, g_mmu, nullptr, t->ce_rows_c, t->counts, t->rowloss, t->dlogits, Vp,
-                                       nullptr, s));
-        return backward_head_from_dlogits(t, stream);
-    }
-    if (!have_dl)
-        TRY(showo_ce_loss(t->logits, V, labels, B, L, V, b_t2i, b_lm, b_mmu, max_seq_len, g_t2i, g_lm, g_mmu, t->ce_rows, t->counts,
-                          t->rowloss, t->dlogits, Vp, nullptr, s));
-    return backward_head_from_dlogits(t, stream);
+    const float g[3] = {g_t2i, g_lm, g_mmu};
+    return backward_head(t, labels, Split{b_t2i, b_lm, b_mmu, max_seq_len}, g, nullptr, stream);
 }
 
 // the same with the three loss weights in device memory g3[3] (the autograd path: they are the incoming gradients of the three loss
 // outputs, training/train.py:600,612, and are never read on the host).  Always runs its own cross-entropy pass over the logits.
 extern "C" int showo_train_backward_head_dev(showo_trainer* t, const int64_t* labels, int b_t2i, int b_lm, int b_mmu, int max_seq_len,
                                              const float* g3, void* stream) {
-    BW_PROLOGUE
-    if (!labels || !g3) return set_error_msg(1, "train_backward_head_dev: labels and g3 required");
-    t->dl_valid = false;
-    if (t->compact) {
-        if (t->lr_split[0] != b_t2i || t->lr_split[1] != b_lm || t->lr_split[2] != b_mmu || t->lr_split[3] != max_seq_len)
-            return set_error_msg(1, "train_backward_head_dev: the labelled-rows forward was made with another batch split");
-        TRY(showo::ce_loss_compact(t->logits, V, t->Tc, V, 0.f, 0.f, 0.f, g3, t->ce_rows_c, t->counts, t->rowloss, t->dlogits, Vp, nullptr, s));
-        return backward_head_from_dlogits(t, stream);
-    }
-    TRY(showo::ce_loss_dev_weights(t->logits, V, labels, B, L, V, b_t2i, b_lm, b_mmu, max_seq_len, g3, t->ce_rows, t->counts, t->rowloss,
-                                   t->dlogits, Vp, s));
-    return backward_head_from_dlogits(t, stream);
+    return backward_head(t, labels, Split{b_t2i, b_lm, b_mmu, max_seq_len}, nullptr, g3, stream);
 }
 
 // number of training forwards this trainer has started (showo_train_forward / _embeds, whether or not they succeeded): a backward
@@ -776,112 +814,49 @@ extern "C" int showo_train_backward_layer(showo_trainer* t, int i, void* stream)
     const bool need_dh = below || p.ln;
     const bool mlp = p.w1 || p.b1 || need_dh;
     const bool attn = p.wqkv || p.bqkv || p.qk || need_dh;
-    {
-        Layer& w = e->layers[i];
-        LayerT& l = t->L[i];
-        float* gb1 = p.b1 ? l.gb1 : t->sc_b1;
-        float* gqk = p.qk ? l.gqk : t->sc_qk;
-        if (train_tn() && l.a) {
-            // weight gradients straight from the token-major tensors: dW = dY^T X by showo_gemm_tn_bf16, db = column sums of dY
-            // db2 = dbd = column sums of dy16: written into l.gb2 (l.gbd when fc2.bias is frozen) by the LayerNorm backward that
-            // produced dy16 (showo_ln_bwd_colsum)
-            if (p.bd && p.b2) SHOWO_CHECK_HIP(hipMemcpyAsync(l.gbd, l.gb2, (size_t)H * sizeof(float), hipMemcpyDeviceToDevice, s));
-            if (p.w2) { TRY(showo_gemm_tn_bf16(t->dy16, H, l.a, F, l.gw2, F, H, F, T, acc, 1, s)); ++t->cnt[0]; }                // dW2 [H,F]
-            if (p.wd) { TRY(showo_gemm_tn_bf16(t->dy16, H, l.attn, H, l.gwd, H, H, H, T, acc, 1, s)); ++t->cnt[0]; }             // dWd [H,H]
-            if (mlp) {
-            TRY(showo_gemm_bf16(t->dy16, H, l.w2T, H, nullptr, 0, t->dff, F, nullptr, 0, T, F, H, SHOWO_EPI_BF16, s));          // d a
-            ++t->cnt[1];
-            TRY(showo_dgelu_colsum_bf16_acc(t->dff, l.f, t->dff, F, T, F, t->colpart, gb1, acc && p.b1, s));                   // d f, db1
-            if (p.w1) { TRY(showo_gemm_tn_bf16(t->dff, F, l.h, H, l.gw1, H, F, H, T, acc, 1, s)); ++t->cnt[0]; }                 // dW1 [F,H]
-            if (need_dh) {
-            TRY(showo_gemm_bf16(t->dff, F, l.w1T, F, nullptr, 0, t->dh, H, nullptr, 0, T, H, F, SHOWO_EPI_F32, s));             // dh (mlp)
-            ++t->cnt[1];
-            }
-            }
-            // attention
-            if (attn) {
-            TRY(showo_gemm_bf16(t->dy16, H, l.wdT, H, nullptr, 0, t->d_o, H, nullptr, 0, T, H, H, SHOWO_EPI_BF16, s));          // d o
-            ++t->cnt[1];
-            TRY(showo_head_transpose(l.Q, t->QT, B, nH, L, Lp, (int64_t)nH * L * 64, (int64_t)L * 64, 64, s));
-            TRY(showo_head_transpose(l.K, t->KT, B, nH, L, Lp, (int64_t)nH * L * 64, (int64_t)L * 64, 64, s));
-            TRY(showo_attn_bwd(l.Q, l.K, t->QT, t->KT, l.qkv + 2 * H, 3 * H, l.attn, t->d_o, H, t->dOT, l.lse, t->D, iv, nullptr, t->dqk, 2 * H,
-                               t->dqk + H, 2 * H, t->dqkv + 2 * H, 3 * H, B, nH, L, Lp, s));
-            TRY(showo_qkln_rope_bwd_acc(t->dqk, t->dqk + H, 2 * H, l.qkv, w.qln_w, w.kln_w, e->cosT, e->sinT, t->dqkv, t->qkpart, gqk, acc && p.qk, T, L,
-                                    nH, e->cfg.rotary_dim, e->cfg.ln_eps, s));
-            if (p.bqkv) TRY(showo_colsum_bf16(t->dqkv, 3 * H, T, 3 * H, t->colpart, l.gbqkv, acc, s));                            // dbqkv
-            if (p.wqkv) { TRY(showo_gemm_tn_bf16(t->dqkv, 3 * H, l.h, H, l.gwqkv, H, 3 * H, H, T, acc, 1, s)); ++t->cnt[0]; }     // dWqkv [3H,H]
-            if (need_dh) {
-            TRY(showo_gemm_bf16(t->dqkv, 3 * H, l.wqkvT, 3 * H, nullptr, 0, t->dh, H, t->dh, H, T, H, 3 * H, SHOWO_EPI_RESID_F32, s));  // dh += attn part
-            ++t->cnt[1];
-            }
-            }
-        } else {
-        // dy^T (+ bias grads of fc2 and dense: both are column sums of dy)
-        float* cb2 = b2_dst(t, i);
-        if (p.w2 || p.wd || cb2) TRY(showo_transpose_bf16(t->dy16, H, t->bigT, T, H, Tp, 0, t->colpart, cb2, acc, s));
-        if (p.bd && p.b2) SHOWO_CHECK_HIP(hipMemcpyAsync(l.gbd, l.gb2, (size_t)H * sizeof(float), hipMemcpyDeviceToDevice, s));
-        // MLP
-        if (p.w2) {
-        TRY(showo_transpose_bf16(l.f, F, t->xT, T, F, Tp, 1, nullptr, nullptr, 0, s));                                      // gelu(f)^T
-        TRY(wgrad_nt(t->bigT, t->xT, l.gw2, F, H, F, Tp, acc, s));                                                          // dW2 [H,F]
-        ++t->cnt[0];
-        }
-        if (p.wd) {
-        TRY(showo_transpose_bf16(l.attn, H, t->xT, T, H, Tp, 0, nullptr, nullptr, 0, s));                                   // attn^T
-        TRY(wgrad_nt(t->bigT, t->xT, l.gwd, H, H, H, Tp, acc, s));                                                          // dWd [H,H]
-        ++t->cnt[0];
-        }
-        bool hT = false;  // xT holds h^T (the operand of dW1 and dWqkv)
-        if (mlp) {
+    Layer& w = e->layers[i];
+    LayerT& l = t->L[i];
+    WGrad wg{t, T, Tp, acc, s};
+    // dy16: the dense / fc2 bias gradients are its column sums (TN form: written by the LayerNorm backward that produced dy16)
+    TRY(wg.image(t->dy16, H, WGrad::follows(p.w2 || p.wd), b2_dst(t, i), WGrad::TN_SUMS_BY_PRODUCER));
+    if (p.bd && p.b2) SHOWO_CHECK_HIP(hipMemcpyAsync(l.gbd, l.gb2, (size_t)H * sizeof(float), hipMemcpyDeviceToDevice, s));
+    if (p.w2) TRY(wg.weight(t->dy16, H, wg.fc2_x(l), F, l.gw2, H));                                                         // dW2 [H,F]
+    if (p.wd) TRY(wg.weight(t->dy16, H, XOp{l.attn, 0}, H, l.gwd, H));                                                      // dWd [H,H]
+    if (mlp) {
         TRY(showo_gemm_bf16(t->dy16, H, l.w2T, H, nullptr, 0, t->dff, F, nullptr, 0, T, F, H, SHOWO_EPI_BF16, s));          // d a
         ++t->cnt[1];
-        TRY(showo_dgelu_bf16(t->dff, l.f, t->dff, (int64_t)T * F, s));                                                      // d f
-        if (p.w1 || p.b1) TRY(showo_transpose_bf16(t->dff, F, t->bigT, T, F, Tp, 0, t->colpart, p.b1 ? l.gb1 : nullptr, acc, s));  // df^T, db1
-        if (p.w1 || p.wqkv) { TRY(showo_transpose_bf16(l.h, H, t->xT, T, H, Tp, 0, nullptr, nullptr, 0, s)); hT = true; }    // h^T
-        if (p.w1) {
-        TRY(wgrad_nt(t->bigT, t->xT, l.gw1, H, F, H, Tp, acc, s));                                                          // dW1 [F,H]
-        ++t->cnt[0];
-        }
+        if (train_tn())                                                                                                     // d f (, db1)
+            TRY(showo_dgelu_colsum_bf16_acc(t->dff, l.f, t->dff, F, T, F, t->colpart, p.b1 ? l.gb1 : t->sc_b1, acc && p.b1, s));
+        else
+            TRY(showo_dgelu_bf16(t->dff, l.f, t->dff, (int64_t)T * F, s));
+        TRY(wg.image(t->dff, F, WGrad::follows(p.w1), p.b1 ? l.gb1 : nullptr, WGrad::TN_SUMS_BY_PRODUCER));  // (dgelu_colsum above)
+        if (p.w1 || p.wqkv) TRY(wg.hold_x(XOp{l.h, 0}, H));  // NT: h^T is made HERE for dW1 and dWqkv, whichever of them trains
+        if (p.w1) TRY(wg.weight(t->dff, F, XOp{l.h, 0}, H, l.gw1, F));                                                      // dW1 [F,H]
         if (need_dh) {
-        TRY(showo_gemm_bf16(t->dff, F, l.w1T, F, nullptr, 0, t->dh, H, nullptr, 0, T, H, F, SHOWO_EPI_F32, s));             // dh (mlp)
-        ++t->cnt[1];
+            TRY(showo_gemm_bf16(t->dff, F, l.w1T, F, nullptr, 0, t->dh, H, nullptr, 0, T, H, F, SHOWO_EPI_F32, s));         // dh (mlp)
+            ++t->cnt[1];
         }
-        }
-        // attention
-        if (attn) {
+    }
+    if (attn) {
         TRY(showo_gemm_bf16(t->dy16, H, l.wdT, H, nullptr, 0, t->d_o, H, nullptr, 0, T, H, H, SHOWO_EPI_BF16, s));          // d o
         ++t->cnt[1];
         TRY(showo_head_transpose(l.Q, t->QT, B, nH, L, Lp, (int64_t)nH * L * 64, (int64_t)L * 64, 64, s));
         TRY(showo_head_transpose(l.K, t->KT, B, nH, L, Lp, (int64_t)nH * L * 64, (int64_t)L * 64, 64, s));
         TRY(showo_attn_bwd(l.Q, l.K, t->QT, t->KT, l.qkv + 2 * H, 3 * H, l.attn, t->d_o, H, t->dOT, l.lse, t->D, iv, nullptr, t->dqk, 2 * H,
                            t->dqk + H, 2 * H, t->dqkv + 2 * H, 3 * H, B, nH, L, Lp, s));
-        TRY(showo_qkln_rope_bwd_acc(t->dqk, t->dqk + H, 2 * H, l.qkv, w.qln_w, w.kln_w, e->cosT, e->sinT, t->dqkv, t->qkpart, gqk, acc && p.qk, T, L,
-                                nH, e->cfg.rotary_dim, e->cfg.ln_eps, s));
-        if (p.wqkv || p.bqkv)                                                                                                // dqkv^T, dbqkv
-            TRY(showo_transpose_bf16(t->dqkv, 3 * H, t->bigT, T, 3 * H, Tp, 0, t->colpart, p.bqkv ? l.gbqkv : nullptr, acc, s));
-        if (p.wqkv) {
-        if (!hT) TRY(showo_transpose_bf16(l.h, H, t->xT, T, H, Tp, 0, nullptr, nullptr, 0, s));
-        TRY(wgrad_nt(t->bigT, t->xT, l.gwqkv, H, 3 * H, H, Tp, acc, s));                                                    // dWqkv (xT = h^T)
-        ++t->cnt[0];
-        }
+        TRY(showo_qkln_rope_bwd_acc(t->dqk, t->dqk + H, 2 * H, l.qkv, w.qln_w, w.kln_w, e->cosT, e->sinT, t->dqkv, t->qkpart,
+                                    p.qk ? l.gqk : t->sc_qk, acc && p.qk, T, L, nH, e->cfg.rotary_dim, e->cfg.ln_eps, s));
+        TRY(wg.image(t->dqkv, 3 * H, WGrad::follows(p.wqkv), p.bqkv ? l.gbqkv : nullptr, WGrad::TN_SUMS_HERE));             // dbqkv
+        if (p.wqkv) TRY(wg.weight(t->dqkv, 3 * H, XOp{l.h, 0}, H, l.gwqkv, 3 * H));                                         // dWqkv [3H,H]
         if (need_dh) {
-        TRY(showo_gemm_bf16(t->dqkv, 3 * H, l.wqkvT, 3 * H, nullptr, 0, t->dh, H, t->dh, H, T, H, 3 * H, SHOWO_EPI_RESID_F32, s));  // dh += attn part
-        ++t->cnt[1];
+            // dh += attn part
+            TRY(showo_gemm_bf16(t->dqkv, 3 * H, l.wqkvT, 3 * H, nullptr, 0, t->dh, H, t->dh, H, T, H, 3 * H, SHOWO_EPI_RESID_F32, s));
+            ++t->cnt[1];
         }
-        }
-        }
-        // LayerNorm + residual (+ the column sums of dy16 = the dense / fc2 bias gradients of block i - 1, wherever that block trains)
-        if (need_dh) {
-        float* gln = p.ln ? l.gln : t->sc_ln;
-        if (train_tn() && i > 0 && t->L[i - 1].a) {
-            float* cb = b2_dst(t, i - 1);
-            TRY(showo_ln_bwd_colsum_acc(l.x, w.ln_w, t->dh, t->dy, t->dy, t->dy16, t->lnpart, gln, cb ? cb : t->sc_b, acc && p.ln, acc && cb,
-                                        T, H, e->cfg.ln_eps, s));
-        } else
-        TRY(showo_ln_bwd_acc(l.x, w.ln_w, t->dh, t->dy, t->dy, t->dy16, t->lnpart, gln, acc && p.ln, T, H, e->cfg.ln_eps, s));
-        }
-        for (const Grad& g : p.clear) SHOWO_CHECK_HIP(hipMemsetAsync(g.p, 0, (size_t)g.n * sizeof(float), s));
-        }
+    }
+    // LayerNorm + residual (+ the column sums of dy16 = the dense / fc2 bias gradients of block i - 1, wherever that block trains)
+    if (need_dh) TRY(ln_bwd_into_block(t, i - 1, l.x, w.ln_w, p.ln ? l.gln : t->sc_ln, acc && p.ln, nullptr, T, s));
+    for (const Grad& g : p.clear) SHOWO_CHECK_HIP(hipMemsetAsync(g.p, 0, (size_t)g.n * sizeof(float), s));
     return 0;
 }
 
@@ -903,29 +878,18 @@ extern "C" int showo_train_backward_embed(showo_trainer* t, void* stream) {
     // after a scatter of an earlier backward, not on every step
     TRY(plan_sync(t, s));
     if (!t->p_emb) return 0;
-    if (acc) {
-        // accumulating: the table keeps the window's partial sum -- no clear, and the scatter adds its position-ordered row sums into the
-        // rows this micro-batch touches; a micro-batch that started from embeddings contributes nothing to the table
-        if (t->from_embeds) return 0;
-        if (t->spliced) {
-            TRY(showo_embed_bwd_splice(t->ids, t->dy, t->gembed, t->order_ws, t->start, 1, B, L, t->sp_n, t->sp_P, H, V, s));
-        } else {
-            TRY(showo_embed_bwd_acc(t->ids, t->dy, t->gembed, t->order_ws, 1, T, H, V, s));
-        }
+    // overwriting: the table is cleared first (once, when nothing was scattered into it since).  Accumulating: it keeps the window's
+    // partial sum -- no clear, and the scatter adds its position-ordered row sums into the rows this micro-batch touches; a
+    // micro-batch that started from embeddings contributes nothing to the table
+    if (!acc) {
+        if (t->from_embeds && !t->gembed_dirty) return 0;
+        SHOWO_CHECK_HIP(hipMemsetAsync(t->gembed, 0, (size_t)V * H * sizeof(float), s));
         ++t->cnt[3];
-        t->gembed_dirty = true;
-        return 0;
+        t->gembed_dirty = false;
     }
-    if (t->from_embeds && !t->gembed_dirty) return 0;
-    SHOWO_CHECK_HIP(hipMemsetAsync(t->gembed, 0, (size_t)V * H * sizeof(float), s));
-    ++t->cnt[3];
-    t->gembed_dirty = false;
     if (t->from_embeds) return 0;
-    if (t->spliced) {
-        TRY(showo_embed_bwd_splice(t->ids, t->dy, t->gembed, t->order_ws, t->start, 0, B, L, t->sp_n, t->sp_P, H, V, s));
-    } else {
-        TRY(showo_embed_bwd(t->ids, t->dy, t->gembed, t->order_ws, T, H, V, s));
-    }
+    if (t->spliced) TRY(showo_embed_bwd_splice(t->ids, t->dy, t->gembed, t->order_ws, t->start, acc, B, L, t->sp_n, t->sp_P, H, V, s));
+    else TRY(showo_embed_bwd_acc(t->ids, t->dy, t->gembed, t->order_ws, acc, T, H, V, s));
     ++t->cnt[3];
     t->gembed_dirty = true;
     return 0;
@@ -998,8 +962,7 @@ extern "C" int showo_train_adamw_step(showo_trainer* t, float lr, float beta1, f
     if (!t) return set_error_msg(1, "train_adamw_step: null handle");
     if (t->bound.empty()) return set_error_msg(1, "train_adamw_step: no parameters bound");
     // SHOWO_TRAIN_ADAMW_MULTI (default 1): one launch over a segment table instead of one adamw + one image refresh per tensor
-    static int multi = -1;
-    if (multi < 0) { const char* env = getenv("SHOWO_TRAIN_ADAMW_MULTI"); multi = env ? (atoi(env) != 0) : 1; }
+    static const bool multi = env_flag("SHOWO_TRAIN_ADAMW_MULTI", true);
     if (multi) {
         hipStream_t s = (hipStream_t)stream;
         if (t->adam_dirty) {  // (re)build the table: segments = bound tensors with their engine destinations, chunks of ADAM_CHUNK elements

@@ -8,6 +8,7 @@ queued so that it overlaps the backward of the next block.  One process per GPU;
 three losses are per-rank means, averaged across ranks by the gradient average exactly as DDP does.
 """
 import ctypes as C
+from typing import Any, NamedTuple
 
 import torch
 
@@ -198,6 +199,28 @@ def loss_rows_mode(loss_rows):
     if not isinstance(loss_rows, str) or loss_rows not in LOSS_ROWS:
         raise ValueError(f"loss_rows must be one of {LOSS_ROWS}, got {loss_rows!r}")
     return LOSS_ROWS.index(loss_rows)
+
+
+class MicroBatch(NamedTuple):
+    """one micro-batch as the native calls take it: contiguous int64 ids / labels [B, L], the dense fp32 mask or None (train_mask),
+    split = (batch_size_t2i, batch_size_lm, batch_size_mmu, max_seq_length), w = the three loss weights of this micro-batch"""
+    ids: Any
+    mask: Any
+    labels: Any
+    B: int
+    L: int
+    split: tuple
+    w: tuple
+
+
+class SplicedImage(NamedTuple):
+    """the image rows of step_clip_vit: the projector module, its output rows fp32 [n * P, H] and the int32 start columns on the device
+    (both None when n * P == 0), n image sequences of P placeholder columns"""
+    projector: Any
+    rows: Any
+    start: Any
+    n: int
+    P: int
 
 
 class Trainer:
@@ -488,7 +511,7 @@ class Trainer:
         from .modeling_showo import sync_trainable
         # only what the native trainer was not told yet; block 0 hands its data gradient down when the projector consumes it
         sync_trainable(self.model, self.tr, self.trainable, image is not None and self._ptrains)
-        m, tr, s = self.model, self.tr, _lib.stream
+        tr = self.tr
         B, L = input_ids.shape
         ids = input_ids.to(torch.int64).contiguous()
         lab = labels.to(torch.int64).contiguous()
@@ -499,7 +522,7 @@ class Trainer:
         ex = self.exchange
         # accumulation window: the first micro-batch overwrites the gradient buffer, the others add into it; accelerate's 1 / k on the
         # micro-batch loss goes down as the loss weights, so the announced d(logits) of the forward's pass is still the one reused
-        w = win.scaled(self.coeffs)
+        mb = MicroBatch(ids, mask, lab, B, L, (batch_size_t2i, batch_size_lm, batch_size_mmu, max_seq_length), win.scaled(self.coeffs))
         closes = win.closes
         self.sync_gradients = False
         if not win.is_first:
@@ -507,8 +530,7 @@ class Trainer:
         if self._loss_rows_mode:
             _lib.call("showo_train_set_loss_rows", tr, self._loss_rows_mode)
         try:
-            self._micro_backward(m, tr, ids, mask, lab, B, L, batch_size_t2i, batch_size_lm, batch_size_mmu, max_seq_length, w, losses,
-                                 ex if closes else None, image)
+            self._micro_backward(mb, losses, ex if closes else None, image)
         finally:
             # per call, like the announcement of the loss weights: the module's autograd path shares this native trainer and overwrites
             # (and must return the full logits: it never runs the head on the labelled rows only)
@@ -572,15 +594,13 @@ class Trainer:
         if ex is not None:
             ex.launch(self._pbucket)
 
-    def _micro_backward(self, m, tr, ids, mask, lab, B, L, batch_size_t2i, batch_size_lm, batch_size_mmu, max_seq_length, w, losses, ex,
-                        image=None):
-        """forward + backward of one micro-batch with loss weights w; ex: the exchange whose bucket collectives are launched as the
-        buckets finish (None: no exchange -- no process group, or a micro-batch that does not close its window).  image: (features
-        [n, P, in_dim], starts) of step_clip_vit -- the projector's rows are spliced into layer 0's input"""
+    def _micro_backward(self, mb, losses, ex, image=None):
+        """forward + backward of one MicroBatch; ex: the exchange whose bucket collectives are launched as the buckets finish (None:
+        no exchange -- no process group, or a micro-batch that does not close its window).  image: (features [n, P, in_dim], starts)
+        of step_clip_vit -- the projector's rows are spliced into layer 0's input"""
         if image is None:
-            return self._micro_backward_body(m, tr, ids, mask, lab, B, L, batch_size_t2i, batch_size_lm, batch_size_mmu, max_seq_length, w,
-                                             losses, ex, None)
-        mm = m.mm_projector
+            return self._forward_backward(mb, losses, ex, None)
+        mm = self.model.mm_projector
         feats, starts = image
         n, P = int(feats.shape[0]), int(feats.shape[1])
         prev = int(getattr(mm, "_precision", 0))
@@ -590,32 +610,30 @@ class Trainer:
             rows = start = None
             if n * P > 0:
                 rows = mm._hip_forward(feats.detach().float()).contiguous()
-                start = torch.tensor(starts, dtype=torch.int32).to(ids.device, non_blocking=True)
-            return self._micro_backward_body(m, tr, ids, mask, lab, B, L, batch_size_t2i, batch_size_lm, batch_size_mmu, max_seq_length, w,
-                                             losses, ex, (mm, rows, start, n, P))
+                start = torch.tensor(starts, dtype=torch.int32).to(mb.ids.device, non_blocking=True)
+            return self._forward_backward(mb, losses, ex, SplicedImage(mm, rows, start, n, P))
         finally:
             if prev:
                 mm.set_precision(prev)
 
-    def _micro_backward_body(self, m, tr, ids, mask, lab, B, L, batch_size_t2i, batch_size_lm, batch_size_mmu, max_seq_length, w, losses, ex,
-                             sp):
-        s = _lib.stream
-        nL = m.arch["num_hidden_layers"]
-        _lib.call("showo_train_set_loss_weights", tr, w[0], w[1], w[2], 1)
+    def _forward_backward(self, mb, losses, ex, sp):
+        """the native calls of one micro-batch, in order; sp: the SplicedImage of step_clip_vit, or None"""
+        tr, s = self.tr, _lib.stream
+        nL = self.model.arch["num_hidden_layers"]
+        ids, mask, lab = _lib.ptr(mb.ids), _lib.ptr(mb.mask), _lib.ptr(mb.labels)
+        _lib.call("showo_train_set_loss_weights", tr, *mb.w, 1)
         try:  # ONE scope for the announcement: a forward that raises must withdraw it too (ADVICE r4)
             try:
                 if sp is None:
-                    _lib.call("showo_train_forward", tr, _lib.ptr(ids), _lib.ptr(mask), _lib.ptr(lab), B, L, batch_size_t2i, batch_size_lm,
-                              batch_size_mmu, max_seq_length, None, _lib.ptr(losses), s())
+                    _lib.call("showo_train_forward", tr, ids, mask, lab, mb.B, mb.L, *mb.split, None, _lib.ptr(losses), s())
                 else:
-                    _lib.call("showo_train_forward_spliced", tr, _lib.ptr(ids), _lib.ptr(sp[1]), _lib.ptr(sp[2]), sp[3], sp[4], _lib.ptr(mask),
-                              _lib.ptr(lab), B, L, batch_size_t2i, batch_size_lm, batch_size_mmu, max_seq_length, None, _lib.ptr(losses), s())
+                    _lib.call("showo_train_forward_spliced", tr, ids, _lib.ptr(sp.rows), _lib.ptr(sp.start), sp.n, sp.P, mask, lab, mb.B, mb.L,
+                              *mb.split, None, _lib.ptr(losses), s())
             finally:
                 _lib.call("showo_trainer_use_intervals", tr, None, None)
-            # `lab` is this step's own contiguous copy / view and is not written between the forward above and this call: the d(logits)
+            # mb.labels is this step's own contiguous copy / view and is not written between the forward above and this call: the d(logits)
             # of the forward's cross-entropy pass is reused only for the SAME forward (every forward invalidates it), pointer, split and weights.
-            _lib.call("showo_train_backward_head", tr, _lib.ptr(lab), batch_size_t2i, batch_size_lm, batch_size_mmu, max_seq_length,
-                      w[0], w[1], w[2], s())
+            _lib.call("showo_train_backward_head", tr, lab, *mb.split, *mb.w, s())
         finally:
             # the announcement is per step: a later forward with labels outside Trainer.step (the module's autograd path, an eval loop)
             # must not write the T x Vp d(logits) tensor (1.3 GB at the stage-1 batch) for a backward that never comes (ADVICE r3)
@@ -624,7 +642,7 @@ class Trainer:
         # backward stops at the lowest phase anything needs
         bt = self._bucket_trains
         lo = 0 if bt[0] else next((i for i in range(nL) if bt[1 + i]), nL)
-        through = sp is not None and self._ptrains and sp[3] * sp[4] > 0  # the projector consumes block 0's data gradient
+        through = sp is not None and self._ptrains and sp.n * sp.P > 0  # the projector consumes block 0's data gradient
         if through:
             lo = 0
         if ex is not None and bt[nL + 1]:
@@ -634,7 +652,7 @@ class Trainer:
             if ex is not None and bt[i + 1]:
                 ex.launch(i + 1)  # the collective of block i overlaps the backward of block i - 1
         if self._ptrains:  # (a micro-batch without image rows contributes nothing; its bucket still goes on the wire)
-            self._projector_backward(tr, sp[0] if sp is not None else None, sp[3] if through else 0, sp[4] if through else 0, ex)
+            self._projector_backward(tr, sp.projector if sp is not None else None, sp.n if through else 0, sp.P if through else 0, ex)
         if bt[0]:
             _lib.call("showo_train_backward_embed", tr, s())
             if ex is not None:

@@ -9,6 +9,9 @@ Showo.forward(input_embeddings=..., labels=...) -> backward -- which tests/test_
 geometry (`_case`) and shared, unchanged, by the tests that need it."""
 import ctypes as C
 import functools
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -268,6 +271,17 @@ def test_step_clip_vit_gradients_are_the_autograd_paths(geo):
     assert err <= 1e-5 * float(grads[EMBED].abs().max()) + 1e-9
     for k, p in m.named_parameters():  # the closing call updated everything, projector included
         assert not torch.equal(p, O.to_torch(_state(geo)[1])[k].cuda()), k
+
+
+def test_step_clip_vit_transpose_branch_in_a_child_process():
+    """SHOWO_TRAIN_TN=0 (read once per process): the spliced forward and backward on the transpose + NT-GEMM weight-gradient form
+    (tiny, T = 81 < 256); the native step and the autograd path share the trainer and stay bit-equal"""
+    env = dict(os.environ, SHOWO_TRAIN_TN="0")
+    here = os.path.dirname(os.path.abspath(__file__))
+    code = ("import sys; sys.path.insert(0, %r); import test_train_clip_vit_gpu as t; "
+            "t.test_step_clip_vit_gradients_are_the_autograd_paths('tiny'); print('CHILD_OK')" % here)
+    r = subprocess.run([sys.executable, "-s", "-c", code], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "CHILD_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
 
 
 @pytest.mark.parametrize("geo", list(GEOMETRIES))

@@ -11,6 +11,9 @@ State of this file: written against the kernels' stated contract and collected o
 figure is quoted here."""
 import ctypes as C
 import math
+import os
+import subprocess
+import sys
 
 import numpy as np
 import pytest
@@ -254,6 +257,17 @@ def test_tiny_fixture_losses_and_gradients():
     for a, b in zip(ll.tolist(), g["train_losses"]):
         assert abs(a - b) < 5e-3 * abs(b)
     _close_to_dense(ga, gl, A._names(m))
+
+
+def test_tiny_fixture_transpose_branch_in_a_child_process():
+    """SHOWO_TRAIN_TN=0 (read once per process): the compact head on the transpose + NT-GEMM weight-gradient form -- the R-row
+    transposes of d(logits) / hf (67 labelled rows of 135) and the slot LayerNorm backward without column sums"""
+    env = dict(os.environ, SHOWO_TRAIN_TN="0")
+    here = os.path.dirname(os.path.abspath(__file__))
+    code = ("import sys; sys.path.insert(0, %r); import test_train_loss_rows_gpu as t; t.test_tiny_fixture_losses_and_gradients(); "
+            "print('CHILD_OK')" % here)
+    r = subprocess.run([sys.executable, "-s", "-c", code], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0 and "CHILD_OK" in r.stdout, r.stdout[-2000:] + r.stderr[-4000:]
 
 
 # ---------------------------------------------------------------- 4. edges (tiny model)
