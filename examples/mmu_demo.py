@@ -1,12 +1,14 @@
 """The w_clip_vit understanding flow of the reference's `inference_mmu.py` (lines 96-175) on the MI355X path:
 
     image -> CLIP ViT-L/14-336 tower (hidden_states[-2][:,1:]) -> mm_projector -> spliced between the embedded system prompt and the
-    question -> mmu_vit visibility intervals -> prefill + KV-cached decode (greedy like the reference's top_k = 1, or --top-k / --temperature)
+    question -> mmu_vit visibility intervals -> prefill + KV-cached decode (greedy like the reference's top_k = 1, or --top-k / --temperature /
+    --top-p, all drawn on the device)
 
 Checkpoints / tokenizer are optional local directories; without them random-init weights of the true architecture and the
 synthetic decimal-id tokenizer are used (same kernels, meaningless text).
 
     python examples/mmu_demo.py --max-new-tokens 32
+    python examples/mmu_demo.py --top-k 0 --top-p 0.9 --temperature 0.8                                 # nucleus sampling
     python examples/mmu_demo.py --questions "What is in the image? *** What colour is it?"              # one prefill of the image prefix,
     python examples/mmu_demo.py --questions "What is in the image? *** What colour is it?" --follow-up  # every question appended to it
 
@@ -44,6 +46,7 @@ def main():
     ap.add_argument("--max-new-tokens", type=int, default=100)
     ap.add_argument("--top-k", type=int, default=1)
     ap.add_argument("--temperature", type=float, default=1.0)
+    ap.add_argument("--top-p", type=float, default=None, help="nucleus sampling behind the top-k filter (needs --top-k other than 1; 0: no top-k)")
     ap.add_argument("--seed", type=int, default=0)
     a = ap.parse_args()
     torch.manual_seed(a.seed)
@@ -88,7 +91,7 @@ def main():
             for q in [q.strip() for q in a.questions.split(" *** ")]:
                 q_emb = model.showo.model.embed_tokens(torch.tensor([tok([q])["input_ids"][0]], device="cuda"))
                 ans = [int(t) for t in sess.generate(input_embeddings=q_emb, max_new_tokens=a.max_new_tokens, top_k=a.top_k,
-                                                     temperature=a.temperature, eot_token=tok.eos_token_id)]
+                                                     temperature=a.temperature, eot_token=tok.eos_token_id, top_p=a.top_p)]
                 print(f"[{sess.length} rows in the cache] {q!r} -> {len(ans)} tokens:", ans[:24], "..." if len(ans) > 24 else "")
                 if a.tokenizer:
                     print(tok.decode(ans, skip_special_tokens=True))
@@ -97,7 +100,7 @@ def main():
             return
         mask = intervals_for_mmu_vit(emb, system_prompt_len=len(sys_ids))     # per-row intervals, no [1,1,L,L] tensor
         toks = model.mmu_generate(input_embeddings=emb, attention_mask=mask, max_new_tokens=a.max_new_tokens, top_k=a.top_k,
-                                  temperature=a.temperature, eot_token=tok.eos_token_id)
+                                  temperature=a.temperature, eot_token=tok.eos_token_id, top_p=a.top_p)
     out = [int(t) for t in toks]
     print(f"prompt of {emb.shape[1]} embeddings -> {len(out)} tokens:", out[:24], "..." if len(out) > 24 else "")
     if a.tokenizer:

@@ -713,6 +713,28 @@ int showo_sample_topk(const float* logits, int V, int top_k, float temperature, 
 /* showo_engine_decode_greedy with that draw instead of the arg-max; draw j of the call uses noise row / stream step0 + j. */
 int showo_engine_decode_sample(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws, int top_k,
                                float temperature, const float* exp_noise, uint64_t seed, int step0, int use_graph, void* stream);
+/* Nucleus (top-p) sampling, the reference's top_k_top_p_filtering (models/sampling.py:80-118) in front of the same draw.
+ * x_i = logits[i] / temperature (fp32 division):
+ *   1. top-k exactly as showo_sample_topk (ties with the k-th value stay; top_k <= 0 or >= V: no filter): the candidates;
+ *   2. p = softmax over the candidates;
+ *   3. token i is kept iff the probability mass of the candidates with strictly larger x is <= top_p;
+ *   token = argmax_i p'_i / E_i, p' = p renormalised over the kept set, E as in showo_sample_topk (same Philox counters).
+ * This is the reference's rule wherever no tie sits at the cut; the largest token always stays (min_tokens_to_keep = 1); the rule
+ * does not depend on a sort order; all candidates equal to the cut value stay (tie-inclusive, like top-k).  On the device the masses
+ * are integers, w_i = (uint64)(expf(x_i - max) * 2^40) added with integer atomics (bit-deterministic run to run), and
+ * kept(i) <=> (double)A_i <= (double)top_p * (double)S with A_i the sum of w above x_i and S the candidates' sum.
+ * 0 < top_p < 1 filters; top_p >= 1 is off: the launch and the bits of the call without top_p; top_p <= 0 or NaN: error 1, nothing
+ * is launched.  top_k == 1 stays the arg-max.  V < 2^24.
+ * showo_engine_decode_sample_p / showo_engine_batch_decode_sample_p: showo_engine_decode_sample / _batch_decode_sample with that
+ * filter; top_p of the batched form is a host array of nb entries (per slot; ignored where top_k[b] == 1). */
+int showo_sample_topk_topp(const float* logits, int V, int top_k, float top_p, float temperature, const float* exp_noise, uint64_t seed,
+                           int step, int64_t* tok, void* stream);
+int showo_engine_decode_sample_p(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws, int top_k, float top_p,
+                                 float temperature, const float* exp_noise, uint64_t seed, int step0, int use_graph, void* stream);
+int showo_engine_batch_decode_sample_p(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws, const int* top_k,
+                                       const float* top_p, const float* temperature, const uint64_t* seed, const int* draw0,
+                                       const float* const* exp_noise, const int* budget, int64_t eot, int* produced, int use_graph,
+                                       void* stream);
 /* greedy/top-k=1 pick on device: out int64[1] = argmax(logits) (first maximal index, like torch.topk/multinomial on a one-hot). */
 int showo_argmax_f32(const float* x, int n, int64_t* out, void* stream);
 

@@ -180,6 +180,7 @@ _PROTOS = {
     "showo_engine_batch_prefill": [c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_p],
     "showo_engine_batch_decode_greedy": [c_p, c_p, c_i, c_p, c_p, c_i, c_p],
     "showo_engine_batch_decode_sample": [c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_i, c_p],
+    "showo_engine_batch_decode_sample_p": [c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_i, c_p],
     # mmu sessions: append prompt rows to a KV cache, fork it to the slots of a decode batch
     "showo_mask_append_rows": [c_p, c_i, c_i, c_i, c_p, c_p],
     "showo_kv_fork": [c_p, c_p, c_i, c_i64, c_i64, c_p, c_p, c_i, c_i64, c_i64, c_i, c_i, c_i, c_p],
@@ -209,6 +210,8 @@ _PROTOS = {
     "showo_mask_downsample_threshold": [c_p, c_i, c_i, c_p, c_p, c_p],
     "showo_sample_topk": [c_p, c_i, c_i, c_f, c_p, c_u64, c_i, c_p, c_p],
     "showo_engine_decode_sample": [c_p, c_p, c_i, c_p, c_p, c_i, c_f, c_p, c_u64, c_i, c_i, c_p],
+    "showo_sample_topk_topp": [c_p, c_i, c_i, c_f, c_f, c_p, c_u64, c_i, c_p, c_p],
+    "showo_engine_decode_sample_p": [c_p, c_p, c_i, c_p, c_p, c_i, c_f, c_f, c_p, c_u64, c_i, c_i, c_p],
     "showo_vq_create": [c_p, C.POINTER(c_p)],
     "showo_vq_load": [c_p, C.c_char_p, c_p, c_i64, c_p],
     "showo_vq_missing": [c_p],

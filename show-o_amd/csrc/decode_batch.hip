@@ -358,6 +358,10 @@ __global__ __launch_bounds__(1024) void greedy_seam_rows_kernel(const float* __r
     for (int i = tid; i < H; i += 1024) xr[i] = src[i];
 }
 
+// shared memory of the sampled seam: the nucleus instance adds the mass histogram
+template <bool NUCLEUS> struct SeamPickSmem { RowPickSmem pick; };
+template <> struct SeamPickSmem<true> : RowNucleusSmem {};
+
 // Per-slot state of showo_engine_batch_decode_sample: set by the host before the steps are captured, advanced by the sampled seam.
 struct SlotDraw {
     const float* noise;  // NULL or [*, V] Exp(1) rows: row d replaces the Philox draw d
@@ -369,6 +373,7 @@ struct SlotDraw {
     int produced;  // tokens emitted so far in this call
     int step;      // seam launches so far in this call (the column of out_tokens)
     int active;    // 0: stopped (budget spent or <eot> emitted) or idle from the start
+    float top_p;   // >= 1: no nucleus filter (sample_topk_row); 0 < top_p < 1: sample_topk_topp_row
 };
 
 // Row of slot b for its next step: the embedding of its token while it decodes; zeros once it is idle (a fixed, finite row, so the
@@ -394,13 +399,16 @@ __global__ __launch_bounds__(256) void slot_embed_kernel(const int64_t* __restri
 // greedy seam's pick), else sample_topk_row with its own top_k / temperature / seed / draw index (the batch-1 sampler's draw) -- and
 // stores it, then either advances (position + 1, next mask row, next embedding row) or, after its last budgeted token or <eot>, goes
 // idle.  An idle slot writes -1 into its output row, keeps its position (at most lim - 1, so its K/V append never leaves the cache and
-// the rotary tables) and feeds the zero row.
+// the rotary tables) and feeds the zero row.  NUCLEUS: some slot of the call has top_p < 1; such a slot draws with sample_topk_topp_row,
+// every other slot exactly as in the instance without it.
+template <bool NUCLEUS>
 __global__ __launch_bounds__(1024) void sample_seam_rows_kernel(const float* __restrict__ logits, int V, int64_t eot, int64_t* __restrict__ tok,
                                                                 int64_t* __restrict__ out_tokens, int n_steps, int* __restrict__ pos, int lim,
                                                                 SlotDraw* __restrict__ sd, const float* __restrict__ table, float* __restrict__ x,
                                                                 int H, const int32_t* __restrict__ last_iv, const int* __restrict__ L0,
                                                                 int32_t* __restrict__ iv) {
-    __shared__ RowPickSmem sm;
+    __shared__ SeamPickSmem<NUCLEUS> smem;
+    RowPickSmem& sm = smem.pick;
     __shared__ int s_tok, s_go;
     const int b = blockIdx.x, tid = threadIdx.x;
     SlotDraw* s = sd + b;
@@ -408,8 +416,11 @@ __global__ __launch_bounds__(1024) void sample_seam_rows_kernel(const float* __r
     int pick = -1;
     if (active) {
         const float* row = logits + (int64_t)b * V;
+        const float* en = s->noise ? s->noise + (int64_t)d * V : nullptr;
         if (top_k == 1) pick = argmax_row_1024(row, V, sm);
-        else pick = sample_topk_row(row, V, top_k, s->temperature, s->noise ? s->noise + (int64_t)d * V : nullptr, s->seed, d, sm);
+        else if (NUCLEUS && s->top_p < 1.f) {
+            if constexpr (NUCLEUS) pick = sample_topk_topp_row(row, V, top_k, s->top_p, s->temperature, en, s->seed, d, smem);
+        } else pick = sample_topk_row(row, V, top_k, s->temperature, en, s->seed, d, sm);
     }
     __syncthreads();  // every thread has read *s
     if (tid == 0) {
@@ -869,10 +880,10 @@ extern "C" int showo_engine_batch_decode_greedy(showo_engine* e, int64_t* tok, i
 // The sampled form with a per-slot stop (include/showo_hip.h): slot b draws with its own top_k / temperature / seed / draw index and
 // emits at most budget[b] tokens, stopping early after `eot`; a stopped or idle slot keeps decoding a fixed row in place so that the
 // captured step stays the same for every slot.  Its cache length advances by what it produced.
-extern "C" int showo_engine_batch_decode_sample(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws,
-                                                const int* top_k, const float* temperature, const uint64_t* seed, const int* draw0,
-                                                const float* const* exp_noise, const int* budget, int64_t eot, int* produced,
-                                                int use_graph, void* stream) {
+// top_p == NULL: no slot filters (showo_engine_batch_decode_sample); else host float [nb], per slot >= 1 (off) or in (0, 1).
+static int batch_decode_sample(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws, const int* top_k,
+                               const float* top_p, const float* temperature, const uint64_t* seed, const int* draw0,
+                               const float* const* exp_noise, const int* budget, int64_t eot, int* produced, int use_graph, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     if (!e || !e->bd || e->bd->nb == 0) return set_error_msg(1, "batch_decode_sample: showo_engine_batch_begin + _batch_prefill first");
     auto* d = e->bd;
@@ -886,8 +897,12 @@ extern "C" int showo_engine_batch_decode_sample(showo_engine* e, int64_t* tok, i
     int lk_max = 0;
     int P0[MAXB], pos0[MAXB];
     SlotDraw sd[MAXB];
+    bool nucleus = false;  // some decoding, sampling slot filters by top_p
     for (int b = 0; b < nb; ++b) {
         if (budget[b] < 0 || draw0[b] < 0) return set_error_msg(1, "batch_decode_sample: budget and draw0 must be >= 0");
+        if (top_p && !(top_p[b] > 0.f)) return set_error_msg(1, "batch_decode_sample: top_p must be > 0 (>= 1: no nucleus filter)");
+        sd[b].top_p = top_p && top_p[b] < 1.f ? top_p[b] : 1.f;
+        nucleus = nucleus || (budget[b] > 0 && top_k[b] != 1 && sd[b].top_p < 1.f);
         if (budget[b] > 0 && top_k[b] != 1 && !(temperature[b] > 0.f)) return set_error_msg(1, "batch_decode_sample: temperature must be > 0");
         P0[b] = d->cache_len[b];
         const int emit = budget[b] < n_steps ? budget[b] : n_steps;  // what the slot can still emit in this call
@@ -919,8 +934,12 @@ extern "C" int showo_engine_batch_decode_sample(showo_engine* e, int64_t* tok, i
     TRY(batch_use_co(e, &co));
     auto one = [&]() -> int {
         TRY(batch_step_layers(e, op, co, lk_max, logits_ws, s));
-        sample_seam_rows_kernel<<<dim3(nb), dim3(1024), 0, s>>>(logits_ws, V, eot, tok, out_tokens, n_steps, d->pos_dev, lim, d->slots_dev,
-                                                               e->embed, e->x, H, d->last_iv_dev, d->L0_dev, d->iv_dev);
+        if (nucleus)
+            sample_seam_rows_kernel<true><<<dim3(nb), dim3(1024), 0, s>>>(logits_ws, V, eot, tok, out_tokens, n_steps, d->pos_dev, lim,
+                                                                         d->slots_dev, e->embed, e->x, H, d->last_iv_dev, d->L0_dev, d->iv_dev);
+        else
+            sample_seam_rows_kernel<false><<<dim3(nb), dim3(1024), 0, s>>>(logits_ws, V, eot, tok, out_tokens, n_steps, d->pos_dev, lim,
+                                                                          d->slots_dev, e->embed, e->x, H, d->last_iv_dev, d->L0_dev, d->iv_dev);
         SHOWO_CHECK_HIP(hipGetLastError());
         return 0;
     };
@@ -932,4 +951,21 @@ extern "C" int showo_engine_batch_decode_sample(showo_engine* e, int64_t* tok, i
         d->cache_len[b] = P0[b] + sd[b].produced;
     }
     return 0;
+}
+
+extern "C" int showo_engine_batch_decode_sample(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws,
+                                                const int* top_k, const float* temperature, const uint64_t* seed, const int* draw0,
+                                                const float* const* exp_noise, const int* budget, int64_t eot, int* produced,
+                                                int use_graph, void* stream) {
+    return batch_decode_sample(e, tok, n_steps, out_tokens, logits_ws, top_k, nullptr, temperature, seed, draw0, exp_noise, budget, eot,
+                               produced, use_graph, stream);
+}
+
+extern "C" int showo_engine_batch_decode_sample_p(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws,
+                                                  const int* top_k, const float* top_p, const float* temperature, const uint64_t* seed,
+                                                  const int* draw0, const float* const* exp_noise, const int* budget, int64_t eot,
+                                                  int* produced, int use_graph, void* stream) {
+    if (!top_p) return set_error_msg(1, "batch_decode_sample_p: bad arguments");
+    return batch_decode_sample(e, tok, n_steps, out_tokens, logits_ws, top_k, top_p, temperature, seed, draw0, exp_noise, budget, eot,
+                               produced, use_graph, stream);
 }

@@ -42,6 +42,8 @@ int sampler_step_inc(int* step_dev, hipStream_t s);
 void attn_set_decode_pos(const int* p, int lk_max = 0);
 int sample_topk_launch(const float* logits, int V, int top_k, float temperature, const float* exp_noise, int64_t noise_stride,
                        uint64_t seed, int step, const int* pos_dev, int pos_base, int64_t* tok, hipStream_t s);
+int sample_topk_topp_launch(const float* logits, int V, int top_k, float top_p, float temperature, const float* exp_noise,
+                            int64_t noise_stride, uint64_t seed, int step, const int* pos_dev, int pos_base, int64_t* tok, hipStream_t s);
 // fused decode layer (decode.hip, attention.hip)
 struct DecodePrefetch;
 bool decode_fused_shapes_ok(int H, int F);

@@ -1642,8 +1642,9 @@ extern "C" int showo_engine_use_intervals(showo_engine* e, const int32_t* iv, co
 // position and the mask row living in device memory so that ONE step can be captured into a hipGraph and replayed.
 // tok int64[1] (device): in = the token to feed first, out = the last token produced; out_tokens int64 [n_steps] (device).
 // top_k == 1: arg-max (the reference caller's setting); otherwise temperature / top-k / multinomial on the device
-// (showo_sample_topk semantics; draw j of this call uses noise row / Philox stream step0 + j).
-static int decode_loop(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws, int top_k,
+// (showo_sample_topk semantics; draw j of this call uses noise row / Philox stream step0 + j); 0 < top_p < 1 puts the nucleus filter
+// in front of the draw (showo_sample_topk_topp), top_p >= 1 is the launch of a call without it.
+static int decode_loop(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws, int top_k, float top_p,
                        float temperature, const float* exp_noise, uint64_t seed, int step0, int use_graph, void* stream) {
     hipStream_t s = (hipStream_t)stream;
     if (!e || e->cache_len <= 0) return set_error_msg(1, "decode_greedy: prefill first");
@@ -1691,8 +1692,10 @@ static int decode_loop(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_
             return showo::greedy_token_seam(logits_ws, e->V, tok, out_tokens, e->pos_dev, P0, e->embed, e->x, e->H, e->V, e->last_iv_dev,
                                             e->prompt_len, e->iv1, s);
         if (top_k == 1) TRY(showo_argmax_f32(logits_ws, e->V, tok, s));
-        else TRY(showo::sample_topk_launch(logits_ws, e->V, top_k, temperature, exp_noise, (int64_t)e->V, seed, step0, e->pos_dev, P0,
-                                           tok, s));
+        else if (top_p >= 1.f) TRY(showo::sample_topk_launch(logits_ws, e->V, top_k, temperature, exp_noise, (int64_t)e->V, seed, step0, e->pos_dev, P0,
+                                                             tok, s));
+        else TRY(showo::sample_topk_topp_launch(logits_ws, e->V, top_k, top_p, temperature, exp_noise, (int64_t)e->V, seed, step0,
+                                                e->pos_dev, P0, tok, s));
         store_token_kernel<<<1, 64, 0, s>>>(tok, out_tokens, e->pos_dev, P0);
         return showo::sampler_step_inc(e->pos_dev, s);
     };
@@ -1730,12 +1733,20 @@ static int decode_loop(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_
 
 extern "C" int showo_engine_decode_greedy(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws,
                                           int use_graph, void* stream) {
-    return decode_loop(e, tok, n_steps, out_tokens, logits_ws, 1, 1.0f, nullptr, 0, 0, use_graph, stream);
+    return decode_loop(e, tok, n_steps, out_tokens, logits_ws, 1, 1.0f, 1.0f, nullptr, 0, 0, use_graph, stream);
 }
 
 extern "C" int showo_engine_decode_sample(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws,
                                           int top_k, float temperature, const float* exp_noise, uint64_t seed, int step0,
                                           int use_graph, void* stream) {
     if (!(temperature > 0.f)) return set_error_msg(1, "decode_sample: temperature must be > 0");
-    return decode_loop(e, tok, n_steps, out_tokens, logits_ws, top_k, temperature, exp_noise, seed, step0, use_graph, stream);
+    return decode_loop(e, tok, n_steps, out_tokens, logits_ws, top_k, 1.0f, temperature, exp_noise, seed, step0, use_graph, stream);
+}
+
+extern "C" int showo_engine_decode_sample_p(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws,
+                                            int top_k, float top_p, float temperature, const float* exp_noise, uint64_t seed,
+                                            int step0, int use_graph, void* stream) {
+    if (!(temperature > 0.f)) return set_error_msg(1, "decode_sample_p: temperature must be > 0");
+    if (!(top_p > 0.f)) return set_error_msg(1, "decode_sample_p: top_p must be > 0 (>= 1: no nucleus filter)");
+    return decode_loop(e, tok, n_steps, out_tokens, logits_ws, top_k, top_p, temperature, exp_noise, seed, step0, use_graph, stream);
 }

@@ -141,4 +141,170 @@ __device__ __forceinline__ int sample_topk_row(const float* __restrict__ logits,
     return bi;
 }
 
+// ---- nucleus (top-p) draw -----------------------------------------------------------------------------------------------------------
+// sample_topk_row with the reference's top_k_top_p_filtering (models/sampling.py:80-118) between the top-k filter and the draw.
+// x_i = logits[i] / T (fp32 division).
+//   1. top-k exactly as sample_topk_row: keep x >= (top_k-th largest x), ties with the k-th value stay, top_k <= 0 or >= V: no filter.
+//      The survivors are the candidates.
+//   2. p = softmax over the candidates.
+//   3. token i is kept iff the probability mass of the candidates with STRICTLY LARGER x is <= top_p.
+//   token = argmax_i p'_i / E_i, p' = p renormalised over the kept set, E as in sample_topk_row (injected row, or Philox(seed; step, i)
+//   with the same counter layout, 0x77), lowest index among ties.
+// Rule 3 is the reference's rule wherever no tie sits at the cut (it sorts, shifts the cumulative mass right by one and drops what
+// lies beyond top_p); the largest token has no mass above it, so it always stays (min_tokens_to_keep = 1); the rule does not depend on a
+// sort order; and it is tie-inclusive: every candidate equal to the cut value stays, like the top-k rule.  Callers take this function
+// only for 0 < top_p < 1; top_p >= 1 is sample_topk_row itself.
+//
+// The cut is a radix select BY MASS over order_key: four 8-bit passes, each a 256-bin histogram of the weights of the keys that match
+// the prefix found so far, then one thread walks the bins from the top, carrying the mass above the prefix region, to the lowest
+// non-empty bin whose mass above is still within top_p.  Everything downstream compares bits, so the masses are integers (float LDS
+// atomics add in no fixed order): w_i = (uint64)(expf(x_i - mx) * 2^40), mx the candidates' max -- the scaling is exact, the
+// conversion truncates, w <= 2^40 and the sums stay below 2^64 for V < 2^24 -- added with 64-bit integer LDS atomics, and
+//   kept(i)  <=>  (double)A_i <= (double)top_p * (double)S,   A_i = sum of w over candidates with x > x_i,  S = sum of w over candidates.
+// A candidate with w == 0 (x < mx - 27.7) has A = S and is never kept.  The normaliser and the p / E arg-max then run over the kept set
+// in sample_topk_row's float reduction order.  Valid in thread 0.
+struct RowNucleusSmem {
+    RowPickSmem pick;
+    unsigned long long mass[256];
+    unsigned long long above;  // integer mass above the prefix region
+    unsigned long long total;  // S
+};
+
+__device__ __forceinline__ int sample_topk_topp_row(const float* __restrict__ logits, int V, int top_k, float top_p, float T,
+                                                    const float* __restrict__ en, uint64_t seed, int step, RowNucleusSmem& ns) {
+    RowPickSmem& sm = ns.pick;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint32_t thr = 0;  // candidates: keys >= thr
+    if (top_k > 0 && top_k < V) {
+        uint32_t prefix = 0, mask = 0;
+        unsigned k = (unsigned)top_k;
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            if (tid < 256) sm.hist[tid] = 0;
+            __syncthreads();
+            for (int i = tid; i < V; i += 1024) {
+                const uint32_t key = order_key(__fdiv_rn(logits[i], T));
+                if ((key & mask) == prefix) atomicAdd(&sm.hist[(key >> shift) & 255u], 1u);
+            }
+            __syncthreads();
+            if (tid == 0) {
+                unsigned cum = 0;
+                int b = 255;
+                for (; b > 0; --b) {
+                    if (cum + sm.hist[b] >= k) break;
+                    cum += sm.hist[b];
+                }
+                sm.sel[0] = (unsigned)b;
+                sm.sel[1] = k - cum;
+            }
+            __syncthreads();
+            prefix |= sm.sel[0] << shift;
+            mask |= 255u << shift;
+            k = sm.sel[1];
+            __syncthreads();
+        }
+        thr = prefix;
+    }
+    // max of the candidates (the largest candidate is always kept: also the max of the kept set)
+    float mx = -INFINITY;
+    for (int i = tid; i < V; i += 1024) {
+        const float x = __fdiv_rn(logits[i], T);
+        if (order_key(x) >= thr) mx = fmaxf(mx, x);
+    }
+    mx = wave_max(mx);
+    if (lane == 0) sm.red_f[wave] = mx;
+    __syncthreads();
+    mx = sm.red_f[0];
+    for (int w = 1; w < 16; ++w) mx = fmaxf(mx, sm.red_f[w]);
+    __syncthreads();
+    // the cut by mass: afterwards the kept set is { keys >= thr } again
+    {
+        uint32_t prefix = 0, mask = 0;
+        for (int shift = 24; shift >= 0; shift -= 8) {
+            if (tid < 256) ns.mass[tid] = 0ull;
+            __syncthreads();
+            for (int i = tid; i < V; i += 1024) {
+                const float x = __fdiv_rn(logits[i], T);
+                const uint32_t key = order_key(x);
+                if (key >= thr && (key & mask) == prefix) {
+                    const unsigned long long w = (unsigned long long)(expf(x - mx) * 1099511627776.0f);
+                    if (w) atomicAdd(&ns.mass[(key >> shift) & 255u], w);
+                }
+            }
+            __syncthreads();
+            if (tid == 0) {
+                if (shift == 24) {
+                    unsigned long long S = 0ull;
+                    for (int b = 0; b < 256; ++b) S += ns.mass[b];
+                    ns.total = S;
+                    ns.above = 0ull;
+                }
+                const double lim = (double)top_p * (double)ns.total;
+                unsigned long long A = ns.above, selA = A;
+                int sel = 255;
+                for (int b = 255; b >= 0; --b) {
+                    if (!((double)A <= lim)) break;  // the bins below have at least this much above them
+                    if (ns.mass[b]) { sel = b; selA = A; }
+                    A += ns.mass[b];
+                }
+                sm.sel[0] = (unsigned)sel;
+                ns.above = selA;
+            }
+            __syncthreads();
+            prefix |= sm.sel[0] << shift;
+            mask |= 255u << shift;
+            __syncthreads();
+        }
+        thr = prefix;  // >= the top-k threshold: a candidate's key
+    }
+    float sum = 0.f;
+    for (int i = tid; i < V; i += 1024) {
+        const float x = __fdiv_rn(logits[i], T);
+        if (order_key(x) >= thr) sum += expf(x - mx);
+    }
+    sum = wave_sum(sum);
+    if (lane == 0) sm.red_f[wave] = sum;
+    __syncthreads();
+    sum = 0.f;
+    for (int w = 0; w < 16; ++w) sum += sm.red_f[w];
+    __syncthreads();
+    Philox ph(seed);
+    float best = -1.f;
+    int bi = 0x7fffffff;
+    for (int i0 = tid * 4; i0 < V; i0 += 4096) {
+        float e4[4];
+        if (en) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) e4[j] = (i0 + j < V) ? en[i0 + j] : 1.f;
+        } else {
+            uint32_t r4[4];
+            ph.gen((uint32_t)(i0 >> 2), 0u, (uint32_t)step, 0x77u, r4);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) e4[j] = -logf(u32_to_unit(r4[j]));
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int i = i0 + j;
+            if (i < V) {
+                const float x = __fdiv_rn(logits[i], T);
+                if (order_key(x) >= thr) {
+                    const float sc = __fdiv_rn(__fdiv_rn(expf(x - mx), sum), e4[j]);
+                    if (sc > best || (sc == best && i < bi)) { best = sc; bi = i; }
+                }
+            }
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ob = __shfl_xor(best, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
+    }
+    if (lane == 0) { sm.red_f[wave] = best; sm.red_i[wave] = bi; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < 16; ++w)
+            if (sm.red_f[w] > best || (sm.red_f[w] == best && sm.red_i[w] < bi)) { best = sm.red_f[w]; bi = sm.red_i[w]; }
+    }
+    return bi;
+}
+
 }  // namespace showo

@@ -282,6 +282,14 @@ __global__ __launch_bounds__(1024) void sample_topk_kernel(DecSampleArgs a) {
     const int bi = sample_topk_row(a.logits, a.V, a.top_k, a.temperature, en, a.seed, step, sm);
     if (threadIdx.x == 0) a.tok[0] = bi;
 }
+// the same draw behind the nucleus filter (sample_row.h sample_topk_topp_row), 0 < top_p < 1
+__global__ __launch_bounds__(1024) void sample_topk_topp_kernel(DecSampleArgs a, float top_p) {
+    __shared__ RowNucleusSmem sm;
+    const int step = a.step + (a.pos_dev ? *a.pos_dev - a.pos_base : 0);
+    const float* en = a.exp_noise ? a.exp_noise + (int64_t)step * a.noise_stride : nullptr;
+    const int bi = sample_topk_topp_row(a.logits, a.V, a.top_k, top_p, a.temperature, en, a.seed, step, sm);
+    if (threadIdx.x == 0) a.tok[0] = bi;
+}
 }  // namespace
 
 namespace showo {
@@ -294,7 +302,27 @@ int sample_topk_launch(const float* logits, int V, int top_k, float temperature,
     SHOWO_CHECK_HIP(hipGetLastError());
     return 0;
 }
+
+// top_p >= 1: sample_topk_launch itself (the bits of a call without top_p); 0 < top_p < 1: the nucleus kernel; else error 1, no launch
+int sample_topk_topp_launch(const float* logits, int V, int top_k, float top_p, float temperature, const float* exp_noise,
+                            int64_t noise_stride, uint64_t seed, int step, const int* pos_dev, int pos_base, int64_t* tok, hipStream_t s) {
+    if (!(top_p > 0.f)) return set_error_msg(1, "sample_topk_topp: top_p must be > 0 (>= 1: no nucleus filter)");
+    if (top_p >= 1.f) return sample_topk_launch(logits, V, top_k, temperature, exp_noise, noise_stride, seed, step, pos_dev, pos_base, tok, s);
+    if (!logits || !tok || V <= 0) return set_error_msg(1, "sample_topk_topp: bad arguments");
+    if (V >= (1 << 24)) return set_error_msg(1, "sample_topk_topp: V < 2^24 supported (64-bit mass sums)");
+    if (!(temperature > 0.f)) return set_error_msg(1, "sample_topk_topp: temperature must be > 0");
+    DecSampleArgs a{logits, V, top_k, temperature, exp_noise, noise_stride, seed, step, pos_dev, pos_base, tok};
+    sample_topk_topp_kernel<<<dim3(1), dim3(1024), 0, s>>>(a, top_p);
+    SHOWO_CHECK_HIP(hipGetLastError());
+    return 0;
+}
 }  // namespace showo
+
+extern "C" int showo_sample_topk_topp(const float* logits, int V, int top_k, float top_p, float temperature, const float* exp_noise,
+                                      uint64_t seed, int step, int64_t* tok, void* stream) {
+    return showo::sample_topk_topp_launch(logits, V, top_k, top_p, temperature, exp_noise, (int64_t)V, seed, step, nullptr, 0, tok,
+                                          (hipStream_t)stream);
+}
 
 extern "C" int showo_sample_topk(const float* logits, int V, int top_k, float temperature, const float* exp_noise, uint64_t seed,
                                  int step, int64_t* tok, void* stream) {

@@ -774,9 +774,12 @@ class Showo(PretrainedMixin, nn.Module):
     # ---- Showo.mmu_generate (reference models/modeling_showo.py:183-240) -----------------------------------
     @torch.no_grad()
     def mmu_generate(self, idx=None, input_embeddings=None, attention_mask=None, max_new_tokens=100, temperature=1.0,
-                     top_k=None, eot_token=None, generator=None, _exp_noise=None):
+                     top_k=None, eot_token=None, generator=None, _exp_noise=None, top_p=None):
         """reference signature + `generator` (seeds the on-device Philox stream of the multinomial draws; default: torch's
-        global generator) and `_exp_noise` fp32 [max_new_tokens, vocab] (parity tests inject the reference's Exp(1) draws)"""
+        global generator), `_exp_noise` fp32 [max_new_tokens, vocab] (parity tests inject the reference's Exp(1) draws) and `top_p`
+        (nucleus sampling on the device behind the top-k filter, the reference's top_k_top_p_filtering: a token stays iff the mass of
+        the strictly more probable candidates is <= top_p; None or >= 1: off, <= 0: ValueError; top_k == 1 stays the arg-max)"""
+        p = _nucleus_p(top_p)
         eng = self.engine()
         greedy = top_k == 1  # the reference caller's setting (inference_mmu.py:81): multinomial of a one-hot = arg-max
         if not greedy:
@@ -796,7 +799,7 @@ class Showo(PretrainedMixin, nn.Module):
         if int(getattr(self, "_precision", 0)) == 1 and (getattr(self, "precise_recompute", False) or
                                                          not _lib.load().showo_engine_precise_fast(eng)):
             return self._mmu_generate_recompute(idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token,
-                                                greedy, None if greedy else (k, seed, noise))
+                                                greedy, None if greedy else (k, seed, noise), top_p=p)
         if input_embeddings is not None:
             if input_embeddings.shape[0] != 1:
                 raise ValueError("mmu_generate has batch-1 semantics (reference modeling_showo.py:204,229)")
@@ -827,8 +830,7 @@ class Showo(PretrainedMixin, nn.Module):
         if greedy:
             _lib.call("showo_argmax_f32", _lib.ptr(logits), self.vocab_size, _lib.ptr(tok), _lib.stream())
         else:  # logits / temperature -> top-k filter -> softmax -> multinomial (reference :220-228), one kernel
-            _lib.call("showo_sample_topk", _lib.ptr(logits), self.vocab_size, k, float(temperature), _lib.ptr(noise), seed, 0,
-                      _lib.ptr(tok), _lib.stream())
+            _sample_call(logits, self.vocab_size, k, p, temperature, noise, seed, 0, tok)
         first = int(tok.item())
         result = [torch.tensor(first, device=dev)]
         if (eot_token is not None and first == eot_token) or max_new_tokens <= 1:
@@ -847,8 +849,7 @@ class Showo(PretrainedMixin, nn.Module):
                     _lib.call("showo_engine_decode_greedy", eng, _lib.ptr(tok), n, _lib.ptr(outc), _lib.ptr(logits), use_graph,
                               _lib.stream())
                 else:
-                    _lib.call("showo_engine_decode_sample", eng, _lib.ptr(tok), n, _lib.ptr(outc), _lib.ptr(logits), k,
-                              float(temperature), _lib.ptr(noise), seed, max_new_tokens - remaining, use_graph, _lib.stream())
+                    _decode_sample_call(eng, tok, n, outc, logits, k, p, temperature, noise, seed, max_new_tokens - remaining, use_graph)
             cur.wait_stream(self._graph_stream)
             toks = outc.tolist()
             for t in toks:
@@ -857,6 +858,36 @@ class Showo(PretrainedMixin, nn.Module):
                     return result
             remaining -= n
         return result
+
+
+def _nucleus_p(top_p):
+    """the `top_p` of the mmu decode paths: None (off) for None and for top_p >= 1, the float inside (0, 1), ValueError for top_p <= 0
+    or NaN.  None takes the calls of a decode without nucleus sampling, so an unset top_p changes no bit."""
+    if top_p is None:
+        return None
+    p = float(top_p)
+    if not p > 0:
+        raise ValueError("top_p must be > 0 (>= 1 or None: no nucleus filter)")
+    return None if p >= 1 else p
+
+
+def _sample_call(logits, V, k, p, temperature, noise, seed, step, tok):
+    """one draw from a logits row: showo_sample_topk, or showo_sample_topk_topp behind the nucleus filter p"""
+    if p is None:
+        _lib.call("showo_sample_topk", _lib.ptr(logits), V, k, float(temperature), _lib.ptr(noise), seed, step, _lib.ptr(tok), _lib.stream())
+    else:
+        _lib.call("showo_sample_topk_topp", _lib.ptr(logits), V, k, p, float(temperature), _lib.ptr(noise), seed, step, _lib.ptr(tok),
+                  _lib.stream())
+
+
+def _decode_sample_call(eng, tok, n, outc, logits, k, p, temperature, noise, seed, step0, use_graph):
+    """n steps of the device loop: showo_engine_decode_sample, or showo_engine_decode_sample_p behind the nucleus filter p"""
+    if p is None:
+        _lib.call("showo_engine_decode_sample", eng, _lib.ptr(tok), n, _lib.ptr(outc), _lib.ptr(logits), k, float(temperature),
+                  _lib.ptr(noise), seed, step0, use_graph, _lib.stream())
+    else:
+        _lib.call("showo_engine_decode_sample_p", eng, _lib.ptr(tok), n, _lib.ptr(outc), _lib.ptr(logits), k, p, float(temperature),
+                  _lib.ptr(noise), seed, step0, use_graph, _lib.stream())
 
 
 # Slot scheduler of mmu_generate_batch (n >= 2 sequences at precision 0 / 2 beyond the all-greedy 2..8 case).  Slot count for more
@@ -923,9 +954,10 @@ def _mmu_batch_schedule(eng, n, slots, max_new_tokens, eot_token, chunk=_MMU_BAT
 class _MmuSlotEngine:
     """engine side of _mmu_batch_schedule: `slots` KV caches of showo_engine_batch_*, one request per slot"""
 
-    def __init__(self, model, eng, idx, input_embeddings, masks, lens, slots, temps, top_ks, seeds, noises, eot_token, dev):
+    def __init__(self, model, eng, idx, input_embeddings, masks, lens, slots, temps, top_ks, seeds, noises, eot_token, dev, top_ps=None):
         self.model, self.eng, self.idx, self.emb, self.masks, self.lens = model, eng, idx, input_embeddings, masks, lens
         self.slots, self.temps, self.top_ks, self.seeds, self.noises = slots, temps, top_ks, seeds, noises
+        self.top_ps = [None] * len(top_ks) if top_ps is None else top_ps  # per request: None or the nucleus p inside (0, 1)
         self.eot = -1 if eot_token is None else int(eot_token)
         self.dev = dev
         V = model.vocab_size
@@ -965,8 +997,8 @@ class _MmuSlotEngine:
         if k == 1:
             _lib.call("showo_argmax_f32", _lib.ptr(self.logits[s]), m.vocab_size, _lib.ptr(self.tok[s:s + 1]), _lib.stream())
         else:
-            _lib.call("showo_sample_topk", _lib.ptr(self.logits[s]), m.vocab_size, 0 if k is None else int(k), float(self.temps[r]),
-                      _lib.ptr(self.noises[r]), self.seeds[r], 0, _lib.ptr(self.tok[s:s + 1]), _lib.stream())
+            _sample_call(self.logits[s], m.vocab_size, 0 if k is None else int(k), self.top_ps[r], self.temps[r], self.noises[r],
+                         self.seeds[r], 0, self.tok[s:s + 1])
         self.occ[s] = r
         return int(self.tok[s].item())
 
@@ -980,28 +1012,33 @@ class _MmuSlotEngine:
         noise = [None if r is None or self.noises[r] is None else _lib.ptr(self.noises[r]) for r in occ]
         a_k, a_t, a_s = (C.c_int * S)(*k), (C.c_float * S)(*temp), (C.c_uint64 * S)(*seed)
         a_d, a_n, a_b, prod = (C.c_int * S)(*draw0), (C.c_void_p * S)(*noise), (C.c_int * S)(*budget), (C.c_int * S)()
+        top_p = [1.0 if r is None or self.top_ps[r] is None or self.top_ks[r] == 1 else self.top_ps[r] for r in occ]
+        nucleus = any(q < 1.0 for q in top_p)  # no slot filters: the call of a batch without nucleus sampling
+        a_p = (C.c_float * S)(*top_p)
         out = torch.empty((S, m), dtype=torch.int64, device=self.dev)
         cur = torch.cuda.current_stream()
         gs = self.model._graph_stream
         gs.wait_stream(cur)
         with torch.cuda.stream(gs):
-            _lib.call("showo_engine_batch_decode_sample", self.eng, _lib.ptr(self.tok), m, _lib.ptr(out), _lib.ptr(self.logits),
-                      *(C.cast(a, C.c_void_p) for a in (a_k, a_t, a_s, a_d, a_n, a_b)), self.eot, C.cast(prod, C.c_void_p),
-                      self.use_graph, _lib.stream())
+            _lib.call("showo_engine_batch_decode_sample_p" if nucleus else "showo_engine_batch_decode_sample", self.eng,
+                      _lib.ptr(self.tok), m, _lib.ptr(out), _lib.ptr(self.logits),
+                      *(C.cast(a, C.c_void_p) for a in ((a_k, a_p, a_t, a_s, a_d, a_n, a_b) if nucleus else (a_k, a_t, a_s, a_d, a_n, a_b))),
+                      self.eot, C.cast(prod, C.c_void_p), self.use_graph, _lib.stream())
         cur.wait_stream(gs)
         return out.tolist(), list(prod)
 
 
 @torch.no_grad()
 def mmu_generate_batch(self, idx=None, input_embeddings=None, attention_mask=None, max_new_tokens=100, temperature=1.0, top_k=None,
-                       eot_token=None, generator=None, _exp_noise=None):
+                       eot_token=None, generator=None, _exp_noise=None, top_p=None):
     """n independent `mmu_generate` calls served together (BASELINE cfg4: "batch=4 images"; the reference's mmu_generate is batch-1 and
     inference_mmu.py:87-177 walks the images one by one).  `idx` / `input_embeddings` / `attention_mask` are LISTS (one entry per
     sequence, each what a single `mmu_generate` call takes: [1, L_b] ids or [1, L_b, H] embeddings, its own mask or IntervalMask);
-    `temperature` / `top_k` are scalars or lists of n values, `_exp_noise` None or a list of n entries (None or [max_new_tokens, vocab]).
+    `temperature` / `top_k` / `top_p` are scalars or lists of n values, `_exp_noise` None or a list of n entries (None or
+    [max_new_tokens, vocab]).
 
     Returns a list of n token lists: result[b] is what `mmu_generate(<sequence b>, attention_mask=masks[b], max_new_tokens,
-    temperature[b], top_k[b], eot_token, generator=generator, _exp_noise=_exp_noise[b])` returns when those calls are made in order
+    temperature[b], top_k[b], eot_token, generator=generator, _exp_noise=_exp_noise[b], top_p=top_p[b])` returns when those calls are made in order
     b = 0, 1, ..., n-1 (the same seeds are drawn from `generator`, or torch's global generator, in the same order).  At precision 0, 2 and 3
     every n >= 2 runs on the batched engine path (csrc/decode_batch.hip: one weight stream per token step for all slots, every sequence
     bit-identical to its batch-1 run): all-greedy batches of 2..8 on showo_engine_batch_decode_greedy, anything else on up to 8 slots
@@ -1012,13 +1049,15 @@ def mmu_generate_batch(self, idx=None, input_embeddings=None, attention_mask=Non
     temps = list(temperature) if isinstance(temperature, (list, tuple)) else [temperature] * n
     top_ks = list(top_k) if isinstance(top_k, (list, tuple)) else [top_k] * n
     noises = list(_exp_noise) if _exp_noise is not None else [None] * n
-    if not (len(masks) == len(temps) == len(top_ks) == len(noises) == n):
-        raise ValueError("attention_mask / temperature / top_k / _exp_noise lists need one entry per sequence")
+    top_ps = list(top_p) if isinstance(top_p, (list, tuple)) else [top_p] * n
+    if not (len(masks) == len(temps) == len(top_ks) == len(noises) == len(top_ps) == n):
+        raise ValueError("attention_mask / temperature / top_k / top_p / _exp_noise lists need one entry per sequence")
+    top_ps = [_nucleus_p(q) for q in top_ps]
 
     def single(b):
         return self.mmu_generate(idx=None if idx is None else idx[b], input_embeddings=None if input_embeddings is None else input_embeddings[b],
                                  attention_mask=masks[b], max_new_tokens=max_new_tokens, temperature=temps[b], top_k=top_ks[b],
-                                 eot_token=eot_token, generator=generator, _exp_noise=noises[b])
+                                 eot_token=eot_token, generator=generator, _exp_noise=noises[b], top_p=top_ps[b])
 
     if int(getattr(self, "_precision", 0)) == 1 or n < 2:
         return [single(b) for b in range(n)]
@@ -1043,7 +1082,7 @@ def mmu_generate_batch(self, idx=None, input_embeddings=None, attention_mask=Non
         return [single(b) for b in range(n)]
     seeds = _mmu_batch_seeds(top_ks, generator)
     noises = [None if (k == 1 or z is None) else z.detach().float().contiguous().to(dev) for k, z in zip(top_ks, noises)]
-    se = _MmuSlotEngine(self, eng, idx, input_embeddings, masks, lens, slots, temps, top_ks, seeds, noises, eot_token, dev)
+    se = _MmuSlotEngine(self, eng, idx, input_embeddings, masks, lens, slots, temps, top_ks, seeds, noises, eot_token, dev, top_ps)
     out = _mmu_batch_schedule(se, n, slots, max_new_tokens, eot_token)
     return [[torch.tensor(t, device=dev) for t in r] for r in out]
 
@@ -1123,8 +1162,8 @@ class _SessionSlotEngine(_MmuSlotEngine):
     """engine side of _mmu_batch_schedule for MmuSession.generate_batch: a slot is filled by a fork of the session's cache plus an
     append of the request's rows instead of a prefill of a whole prompt"""
 
-    def __init__(self, model, eng, rows, lens, slots, temps, top_ks, seeds, noises, eot_token, dev):
-        super().__init__(model, eng, None, None, None, lens, slots, temps, top_ks, seeds, noises, eot_token, dev)
+    def __init__(self, model, eng, rows, lens, slots, temps, top_ks, seeds, noises, eot_token, dev, top_ps=None):
+        super().__init__(model, eng, None, None, None, lens, slots, temps, top_ks, seeds, noises, eot_token, dev, top_ps)
         self.rows = rows
 
     def fill(self, s, r):
@@ -1206,14 +1245,13 @@ class _SessionEngine:
         past an <eot>)"""
         self.rewind(length + len(toks) - 1)
 
-    def run(self, max_new_tokens, greedy, k, temperature, noise, seed, eot_token):
+    def run(self, max_new_tokens, greedy, k, temperature, noise, seed, eot_token, top_p=None):
         """Showo.mmu_generate behind its prefill: the first token from the current logits, the rest from the device loop in chunks"""
         m, eng, logits, tok = self.model, self.eng, self.logits, self.tok
         if greedy:
             _lib.call("showo_argmax_f32", _lib.ptr(logits), m.vocab_size, _lib.ptr(tok), _lib.stream())
         else:
-            _lib.call("showo_sample_topk", _lib.ptr(logits), m.vocab_size, k, float(temperature), _lib.ptr(noise), seed, 0, _lib.ptr(tok),
-                      _lib.stream())
+            _sample_call(logits, m.vocab_size, k, top_p, temperature, noise, seed, 0, tok)
         result = [int(tok.item())]
         if (eot_token is not None and result[0] == eot_token) or max_new_tokens <= 1:
             return result
@@ -1228,8 +1266,7 @@ class _SessionEngine:
                 if greedy:
                     _lib.call("showo_engine_decode_greedy", eng, _lib.ptr(tok), n, _lib.ptr(outc), _lib.ptr(logits), use_graph, _lib.stream())
                 else:
-                    _lib.call("showo_engine_decode_sample", eng, _lib.ptr(tok), n, _lib.ptr(outc), _lib.ptr(logits), k, float(temperature),
-                              _lib.ptr(noise), seed, max_new_tokens - remaining, use_graph, _lib.stream())
+                    _decode_sample_call(eng, tok, n, outc, logits, k, top_p, temperature, noise, seed, max_new_tokens - remaining, use_graph)
             cur.wait_stream(m._graph_stream)
             for t in outc.tolist():
                 result.append(t)
@@ -1238,7 +1275,7 @@ class _SessionEngine:
             remaining -= n
         return result
 
-    def run_batch(self, length, rows, lens, max_new_tokens, temps, top_ks, seeds, noises, eot_token):
+    def run_batch(self, length, rows, lens, max_new_tokens, temps, top_ks, seeds, noises, eot_token, top_ps=None):
         """n continuations of the cache [0, length) on the slots of a decode batch; None when the batch does not fit the engine"""
         n = len(rows)
         slots = _mmu_batch_slots(n)
@@ -1246,7 +1283,7 @@ class _SessionEngine:
             _lib.call("showo_engine_batch_begin", self.eng, slots, length + max(lens) + max_new_tokens + 1)
         except RuntimeError:
             return None
-        se = _SessionSlotEngine(self.model, self.eng, rows, lens, slots, temps, top_ks, seeds, noises, eot_token, self.dev)
+        se = _SessionSlotEngine(self.model, self.eng, rows, lens, slots, temps, top_ks, seeds, noises, eot_token, self.dev, top_ps)
         return _mmu_batch_schedule(se, n, slots, max_new_tokens, eot_token)
 
 
@@ -1299,9 +1336,9 @@ class _SessionRecompute:
         if len(toks) > 1:
             self.append(torch.tensor([toks[:-1]], dtype=torch.int64, device=self.dev), None, len(toks) - 1)
 
-    def run(self, max_new_tokens, greedy, k, temperature, noise, seed, eot_token):
+    def run(self, max_new_tokens, greedy, k, temperature, noise, seed, eot_token, top_p=None):
         out = self.model._mmu_generate_recompute(None, self.emb, self.mask, max_new_tokens, temperature, 1 if greedy else k, eot_token,
-                                                 greedy, None if greedy else (k, seed, noise))
+                                                 greedy, None if greedy else (k, seed, noise), top_p=top_p)
         return [int(t) for t in out]
 
 
@@ -1372,12 +1409,14 @@ class MmuSession:
             return None, None, 0
         return ids.contiguous(), None, int(ids.shape[1])
 
-    def _draw_args(self, max_new_tokens, temperature, top_k, generator, noise):
-        """(greedy, k, noise, seed) exactly as mmu_generate derives them (one seed draw per sampled call)"""
+    def _draw_args(self, max_new_tokens, temperature, top_k, generator, noise, top_p=None):
+        """(greedy, k, noise, seed, p) exactly as mmu_generate derives them (one seed draw per sampled call; p: None or the nucleus
+        top_p inside (0, 1))"""
+        p = _nucleus_p(top_p)
         if max_new_tokens < 1:
             raise ValueError("max_new_tokens must be >= 1")
         if top_k == 1:
-            return True, 1, None, 0
+            return True, 1, None, 0, p
         if not temperature > 0:
             raise ValueError("temperature must be > 0")
         if generator is not None:
@@ -1388,19 +1427,20 @@ class MmuSession:
             noise = noise.detach().float().contiguous()
             if tuple(noise.shape) != (max_new_tokens, self.model.vocab_size):
                 raise ValueError("_exp_noise must be [max_new_tokens, vocab_size]")
-        return False, 0 if top_k is None else int(top_k), noise, seed
+        return False, 0 if top_k is None else int(top_k), noise, seed, p
 
     @torch.no_grad()
     def generate(self, idx=None, input_embeddings=None, max_new_tokens=100, temperature=1.0, top_k=None, eot_token=None, generator=None,
-                 _exp_noise=None):
+                 _exp_noise=None, top_p=None):
         """Append the rows (ids [1, Ln] or embeddings [1, Ln, H]; none: continue where the last call stopped), then decode like
-        `mmu_generate`: same return type, `eot_token` cut, greedy pick for top_k == 1 and sampled draws.  Afterwards the cache holds the
+        `mmu_generate`: same return type, `eot_token` cut, greedy pick for top_k == 1 and sampled draws (`top_p`: nucleus).  Afterwards the cache holds the
         prefix, the rows and the answer up to its last token but one; the last token is pending and is fed first by the next call."""
         self._check()
         ids, emb, Ln = self._rows(idx, input_embeddings)
         if Ln == 0 and self.length != self.prefix_length:
             raise ValueError("generate: no rows and no pending token to continue from")
-        greedy, k, noise, seed = self._draw_args(max_new_tokens, temperature, top_k, generator, _exp_noise)
+        greedy, k, noise, seed, p = self._draw_args(max_new_tokens, temperature, top_k, generator, _exp_noise, top_p)
+        nucleus = {} if p is None else {"top_p": p}  # an engine stand-in without the keyword still serves every call without top_p
         start = self.length
         try:
             if Ln:
@@ -1408,7 +1448,7 @@ class MmuSession:
                 self.length += Ln
             else:
                 self._be.use_prefix_logits()
-            toks = self._be.run(max_new_tokens, greedy, k, temperature, noise, seed, eot_token)
+            toks = self._be.run(max_new_tokens, greedy, k, temperature, noise, seed, eot_token, **nucleus)
             self._be.settle(self.length, toks)
         except BaseException:
             # a call that fails midway (a full cache inside the decode loop) leaves the session where it was: the rows it wrote are
@@ -1423,9 +1463,9 @@ class MmuSession:
 
     @torch.no_grad()
     def generate_batch(self, idx=None, input_embeddings=None, max_new_tokens=100, temperature=1.0, top_k=None, eot_token=None,
-                       generator=None, _exp_noise=None):
+                       generator=None, _exp_noise=None, top_p=None):
         """n continuations of the CURRENT state: `idx` / `input_embeddings` is a list of n row blocks ([1, Ln_i] ids or [1, Ln_i, H]
-        embeddings), `temperature` / `top_k` scalars or lists, `_exp_noise` None or a list.  result[i] is what `generate(<block i>)`
+        embeddings), `temperature` / `top_k` / `top_p` scalars or lists, `_exp_noise` None or a list.  result[i] is what `generate(<block i>)`
         followed by a rewind returns when those calls are made in order (same seeds from `generator`); the session is left unchanged.
         n >= 2 at precision 0, 2, 3 runs on the slots of a decode batch, each slot a fork of this cache."""
         self._check()
@@ -1434,15 +1474,17 @@ class MmuSession:
         temps = list(temperature) if isinstance(temperature, (list, tuple)) else [temperature] * n
         top_ks = list(top_k) if isinstance(top_k, (list, tuple)) else [top_k] * n
         noises = list(_exp_noise) if _exp_noise is not None else [None] * n
-        if not (len(temps) == len(top_ks) == len(noises) == n):
-            raise ValueError("temperature / top_k / _exp_noise lists need one entry per sequence")
+        top_ps = list(top_p) if isinstance(top_p, (list, tuple)) else [top_p] * n
+        if not (len(temps) == len(top_ks) == len(noises) == len(top_ps) == n):
+            raise ValueError("temperature / top_k / top_p / _exp_noise lists need one entry per sequence")
+        top_ps = [_nucleus_p(q) for q in top_ps]
 
         def single(b):
             mark = self.mark()
             try:
                 return self.generate(idx=None if idx is None else idx[b], input_embeddings=None if input_embeddings is None else input_embeddings[b],
                                      max_new_tokens=max_new_tokens, temperature=temps[b], top_k=top_ks[b], eot_token=eot_token,
-                                     generator=generator, _exp_noise=noises[b])
+                                     generator=generator, _exp_noise=noises[b], top_p=top_ps[b])
             finally:
                 self.rewind(mark)
 
@@ -1465,7 +1507,8 @@ class MmuSession:
         seeds = _mmu_batch_seeds(top_ks, generator)
         dev = self._be.dev
         noises = [None if (k == 1 or z is None) else z.detach().float().contiguous().to(dev) for k, z in zip(top_ks, noises)]
-        out = self._be.run_batch(self.length, rows, lens, max_new_tokens, temps, top_ks, seeds, noises, eot_token)
+        nucleus = {} if all(q is None for q in top_ps) else {"top_ps": top_ps}
+        out = self._be.run_batch(self.length, rows, lens, max_new_tokens, temps, top_ks, seeds, noises, eot_token, **nucleus)
         if out is None:  # the batch's common capacity does not fit the engine: the sequential calls, drawing the same seeds again
             if gen_state is not None:
                 generator.set_state(gen_state)
@@ -1512,7 +1555,8 @@ def _dense_mask_of(attention_mask, L, device):
     return attention_mask.detach().float().reshape(1, 1, L, L).to(device)
 
 
-def _mmu_generate_recompute(self, idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, greedy, sampling):
+def _mmu_generate_recompute(self, idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, greedy, sampling,
+                            top_p=None):
     """Accuracy mode (`set_precision(1)`): the reference's OWN algorithm (models/modeling_showo.py:190-240) -- no KV cache, the whole
     sequence is run again for every token on the grown mask (new column hidden from the old rows, new row = last row + itself,
     :203-217) -- on the fp32-class engine path.  O(tokens x forward): a parity mode, not a serving mode."""
@@ -1539,8 +1583,7 @@ def _mmu_generate_recompute(self, idx, input_embeddings, attention_mask, max_new
             _lib.call("showo_argmax_f32", _lib.ptr(logits), self.vocab_size, _lib.ptr(tok), _lib.stream())
         else:
             k, seed, noise = sampling
-            _lib.call("showo_sample_topk", _lib.ptr(logits), self.vocab_size, k, float(temperature), _lib.ptr(noise), seed, step, _lib.ptr(tok),
-                      _lib.stream())
+            _sample_call(logits, self.vocab_size, k, top_p, temperature, noise, seed, step, tok)
         t = int(tok.item())
         result.append(torch.tensor(t, device=dev))
         if eot_token is not None and t == eot_token:

@@ -8,6 +8,8 @@ against the sequential calls' (same generator seed).
   python tools/mmu_batch_bench.py              # the JSON below (n = 4, 16, 32; greedy and top_k=5 / temperature=0.7)
   python tools/mmu_batch_bench.py --profile    # one batched greedy and one batched sampled n = 4 call, for a kernel trace
                                                # (rocprofv3 --kernel-trace --stats -- python tools/mmu_batch_bench.py --profile)
+  python tools/mmu_batch_bench.py --top-p 0.9  # cost of nucleus sampling: a sampled leg and the same leg with top_p, alternating in
+                                               # this process, at batch 1 and n = 4 / 16: median and min / max tokens/s over --reps calls
 
 The slot count for n > 8 is set through modeling_showo._MMU_BATCH_SLOTS for this run only."""
 import argparse
@@ -56,11 +58,59 @@ def timed(fn):
     return time.perf_counter() - t0, [[int(t) for t in r] for r in out]
 
 
+def nucleus_legs(model, embs, masks, top_p, reps):
+    """tokens/s of a sampled leg and of the same leg behind the nucleus filter, measured alternately (base, top-p, base, top-p, ...) so
+    that both see the same clocks; per leg the median and the min / max of `reps` whole calls after one warm-up call each"""
+    gen = lambda: torch.Generator(device="cuda").manual_seed(7)  # noqa: E731
+
+    def call(n, kw):
+        if n == 1:
+            return lambda: model.mmu_generate(input_embeddings=embs[0], attention_mask=masks[0], max_new_tokens=NEW, generator=gen(), **kw)
+        return lambda: model.mmu_generate_batch(input_embeddings=embs[:n], attention_mask=masks[:n], max_new_tokens=NEW, generator=gen(), **kw)
+
+    def once(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    res = {"shape": "cfg4: 631-embedding w_clip_vit prompts, 100 new tokens each, full-size seeded weights",
+           "unit": "tokens/s (whole call)", "top_p": top_p, "reps": reps}
+    for n in (1, 4, 16):
+        for name, kw in (("topk5_t0.7", SAMPLED), ("unfiltered_t1.0", dict(top_k=None, temperature=1.0))):
+            legs = {"base": call(n, kw), "top_p": call(n, dict(kw, top_p=top_p))}
+            for fn in legs.values():
+                fn()  # warm-up
+            times = {k: [] for k in legs}
+            for _ in range(reps):
+                for k, fn in legs.items():
+                    times[k].append(once(fn))
+            row = {}
+            for k, ts in times.items():
+                rate = sorted(n * NEW / t for t in ts)
+                row[k] = {"median": float(np.median(rate)), "min": rate[0], "max": rate[-1]}
+            row["top_p_overhead_percent"] = 100.0 * (row["base"]["median"] / row["top_p"]["median"] - 1.0)
+            res[f"n{n}_{name}"] = row
+            print(f"n={n} {name}: {row}", file=sys.stderr, flush=True)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--profile", action="store_true")
+    ap.add_argument("--top-p", type=float, default=None, help="measure nucleus sampling against the same sampled leg without it")
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--out", default=None, help="also write the JSON of --top-p to this file")
     a = ap.parse_args()
-    pkg, model, embs, masks = build(4 if a.profile else 32)
+    pkg, model, embs, masks = build(4 if a.profile else (16 if a.top_p is not None else 32))
+    if a.top_p is not None:
+        res = nucleus_legs(model, embs, masks, a.top_p, a.reps)
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(res, f, indent=1)
+        print(json.dumps(res))
+        return
     M = pkg.modeling_showo
     gen = lambda: torch.Generator(device="cuda").manual_seed(7)  # noqa: E731
 
