@@ -9,6 +9,7 @@ synthetic decimal-id tokenizer are used (same kernels, meaningless text).
 
     python examples/mmu_demo.py --max-new-tokens 32
     python examples/mmu_demo.py --top-k 0 --top-p 0.9 --temperature 0.8                                 # nucleus sampling
+    python examples/mmu_demo.py --logprobs                                                              # + log-probability of every token
     python examples/mmu_demo.py --questions "What is in the image? *** What colour is it?"              # one prefill of the image prefix,
     python examples/mmu_demo.py --questions "What is in the image? *** What colour is it?" --follow-up  # every question appended to it
 
@@ -34,6 +35,14 @@ from showo_amd.prompting_utils import UniversalPrompting, intervals_for_mmu_vit 
 SYSTEM_PROMPT_LEN = 28  # inference_mmu.py:36
 
 
+def report_logprobs(lps):
+    """--logprobs: the answer's log-likelihood, its per-token mean (log-perplexity) and the first values"""
+    if lps is None:
+        return
+    v = lps.tolist()
+    print(f"log-probabilities: sum {sum(v):.3f}, mean {sum(v) / len(v):.3f}:", [round(x, 3) for x in v[:24]], "..." if len(v) > 24 else "")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--showo", default=None, help="local Show-o (w_clip_vit) checkpoint directory")
@@ -47,6 +56,7 @@ def main():
     ap.add_argument("--top-k", type=int, default=1)
     ap.add_argument("--temperature", type=float, default=1.0)
     ap.add_argument("--top-p", type=float, default=None, help="nucleus sampling behind the top-k filter (needs --top-k other than 1; 0: no top-k)")
+    ap.add_argument("--logprobs", action="store_true", help="also report every answer token's log-probability (return_logprobs=True)")
     ap.add_argument("--seed", type=int, default=0)
     a = ap.parse_args()
     torch.manual_seed(a.seed)
@@ -90,9 +100,12 @@ def main():
             start = sess.mark()
             for q in [q.strip() for q in a.questions.split(" *** ")]:
                 q_emb = model.showo.model.embed_tokens(torch.tensor([tok([q])["input_ids"][0]], device="cuda"))
-                ans = [int(t) for t in sess.generate(input_embeddings=q_emb, max_new_tokens=a.max_new_tokens, top_k=a.top_k,
-                                                     temperature=a.temperature, eot_token=tok.eos_token_id, top_p=a.top_p)]
+                ans = sess.generate(input_embeddings=q_emb, max_new_tokens=a.max_new_tokens, top_k=a.top_k, temperature=a.temperature,
+                                    eot_token=tok.eos_token_id, top_p=a.top_p, return_logprobs=a.logprobs)
+                ans, lps = ans if a.logprobs else (ans, None)
+                ans = [int(t) for t in ans]
                 print(f"[{sess.length} rows in the cache] {q!r} -> {len(ans)} tokens:", ans[:24], "..." if len(ans) > 24 else "")
+                report_logprobs(lps)
                 if a.tokenizer:
                     print(tok.decode(ans, skip_special_tokens=True))
                 if not a.follow_up:
@@ -100,9 +113,11 @@ def main():
             return
         mask = intervals_for_mmu_vit(emb, system_prompt_len=len(sys_ids))     # per-row intervals, no [1,1,L,L] tensor
         toks = model.mmu_generate(input_embeddings=emb, attention_mask=mask, max_new_tokens=a.max_new_tokens, top_k=a.top_k,
-                                  temperature=a.temperature, eot_token=tok.eos_token_id, top_p=a.top_p)
+                                  temperature=a.temperature, eot_token=tok.eos_token_id, top_p=a.top_p, return_logprobs=a.logprobs)
+    toks, lps = toks if a.logprobs else (toks, None)
     out = [int(t) for t in toks]
     print(f"prompt of {emb.shape[1]} embeddings -> {len(out)} tokens:", out[:24], "..." if len(out) > 24 else "")
+    report_logprobs(lps)
     if a.tokenizer:
         print(tok.decode(out, skip_special_tokens=True))
 

@@ -735,6 +735,45 @@ int showo_engine_batch_decode_sample_p(showo_engine* e, int64_t* tok, int n_step
                                        const float* top_p, const float* temperature, const uint64_t* seed, const int* draw0,
                                        const float* const* exp_noise, const int* budget, int64_t eot, int* produced, int use_graph,
                                        void* stream);
+/* Log-probabilities.  For one fp32 logits row x[0, V) and a target token t:
+ *   lp   = x[t] - max(x) - log sum_i exp(x[i] - max(x))   the log-softmax of the RAW logits (temperature 1, in front of any top-k /
+ *                                                         top-p filter): what torch.log_softmax(x, -1)[t] returns;
+ *   rank = #{ i : x[i] > x[t] }                           strict: 0 for the arg-max and for everything tied with it.
+ * t < 0 (the -100 of the label convention): lp = 0.0f, rank = -1.  t >= V: lp = NaN, rank = -1 (the embedding kernel's poisoning of
+ * out-of-range ids).  -inf entries add nothing to the sum, a -inf target gives lp = -inf.  The maximum is subtracted before exp.
+ * One 1024-thread block per row, two passes of 16-byte loads over the row behind a peel to its alignment (max and rank, then the
+ * sum).  The sum runs over integers, w_i = (uint64)(expf(x_i - max) * 2^40) (exact scaling, truncating conversion, V < 2^24), so it
+ * does not depend on which lane met which element: the same row bits and target give the same lp bits on every run, at every row
+ * alignment and from every caller below.  |lp - exact| <= ~3e-7 (1 + |lp|): the truncation costs V 2^-40 relative to a sum >= 1.
+ * showo_logprob_rows: rows logits + r * ld (ld >= V, any 4-byte alignment), r < nrows, against targets[r]; logprob fp32 [nrows],
+ * rank int32 [nrows] or NULL.  nrows == 0 launches nothing.
+ * showo_engine_decode_sample_lp / showo_engine_batch_decode_sample_lp: showo_engine_decode_sample_p / _batch_decode_sample_p with one
+ * more launch per step, behind the token boundary and inside the captured step, that scores the token the step stored against the
+ * step's row of logits_ws: logprobs fp32 [n_steps] / [nb, n_steps] (device) is indexed like out_tokens, ranks likewise or NULL.  An
+ * idle slot's entries are 0.0f / -1 where its out_tokens entry is -1.  The token launches are those of the calls without (top_k == 1:
+ * the greedy step, token-seam form included; top_p >= 1: the plain top-k draw), so tokens keep their bits; logprobs == NULL is that
+ * call exactly.  The batched form also takes top_p == NULL (no slot filters).  Every precision the underlying loop serves.
+ * showo_engine_score: ONE forward exactly as showo_engine_forward_rows runs it (mask / showo_engine_use_intervals, every precision),
+ * then, for chunks of at most chunk_rows rows, the head over the full vocabulary into an engine-owned [chunk_rows, V] workspace and
+ * showo_logprob_rows on it: rows int32 [n] (device) index the B * L residual rows, targets int64 [n] (device), logprob [n], rank [n]
+ * or NULL.  chunk_rows <= 0: the largest chunk within 256 MB.  [n, V] is never allocated whole; n == 0 launches nothing.
+ * showo_engine_prefill_append_score: showo_engine_prefill_append on ids with the head run on all Ln appended rows: logprob[j] scores
+ * ids[j], from the logits of appended row j - 1 for j >= 1 and from logits_prev fp32 [V] (the logits of the last cached row; must
+ * not be logits_last) for j == 0 -- NaN / -1 when logits_prev is NULL.  logits_last and the cache are left as the plain append leaves
+ * them.  The engine's own cache only. */
+int showo_logprob_rows(const float* logits, int64_t ld, int nrows, int V, const int64_t* targets, float* logprob, int32_t* rank,
+                       void* stream);
+int showo_engine_decode_sample_lp(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws, int top_k, float top_p,
+                                  float temperature, const float* exp_noise, uint64_t seed, int step0, float* logprobs, int32_t* ranks,
+                                  int use_graph, void* stream);
+int showo_engine_batch_decode_sample_lp(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws, const int* top_k,
+                                        const float* top_p, const float* temperature, const uint64_t* seed, const int* draw0,
+                                        const float* const* exp_noise, const int* budget, int64_t eot, int* produced, float* logprobs,
+                                        int32_t* ranks, int use_graph, void* stream);
+int showo_engine_score(showo_engine* e, const int64_t* ids, const float* embeds, const float* mask, int B, int L, const int32_t* rows,
+                       const int64_t* targets, int n, int chunk_rows, float* logprob, int32_t* rank, void* stream);
+int showo_engine_prefill_append_score(showo_engine* e, const int64_t* ids, int Ln, const float* logits_prev, float* logprob, int32_t* rank,
+                                      float* logits_last, void* stream);
 /* greedy/top-k=1 pick on device: out int64[1] = argmax(logits) (first maximal index, like torch.topk/multinomial on a one-hot). */
 int showo_argmax_f32(const float* x, int n, int64_t* out, void* stream);
 

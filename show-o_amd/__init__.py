@@ -6,7 +6,7 @@ All arithmetic runs in hand-written HIP kernels behind the C ABI of `libshowo_hi
 (include/showo_hip.h); see DESIGN.md / INTEGRATION.md.
 """
 from .sampling import get_mask_chedule, cosine_schedule  # noqa: F401
-from .modeling_showo import Showo, gen_config  # noqa: F401
+from .modeling_showo import Showo, TokenScores, gen_config  # noqa: F401
 from .modeling_magvitv2 import MAGVITv2  # noqa: F401
 from . import _lib  # noqa: F401
 from .training import Trainer, AccumulationWindow  # noqa: F401

@@ -212,6 +212,12 @@ _PROTOS = {
     "showo_engine_decode_sample": [c_p, c_p, c_i, c_p, c_p, c_i, c_f, c_p, c_u64, c_i, c_i, c_p],
     "showo_sample_topk_topp": [c_p, c_i, c_i, c_f, c_f, c_p, c_u64, c_i, c_p, c_p],
     "showo_engine_decode_sample_p": [c_p, c_p, c_i, c_p, c_p, c_i, c_f, c_f, c_p, c_u64, c_i, c_i, c_p],
+    # log-probabilities: per-row kernel, the decode loops with one scoring launch per step, scoring of given rows
+    "showo_logprob_rows": [c_p, c_i64, c_i, c_i, c_p, c_p, c_p, c_p],
+    "showo_engine_decode_sample_lp": [c_p, c_p, c_i, c_p, c_p, c_i, c_f, c_f, c_p, c_u64, c_i, c_p, c_p, c_i, c_p],
+    "showo_engine_batch_decode_sample_lp": [c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_i, c_p],
+    "showo_engine_score": [c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_p, c_p, c_p],
+    "showo_engine_prefill_append_score": [c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p],
     "showo_vq_create": [c_p, C.POINTER(c_p)],
     "showo_vq_load": [c_p, C.c_char_p, c_p, c_i64, c_p],
     "showo_vq_missing": [c_p],

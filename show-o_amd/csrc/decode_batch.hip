@@ -449,6 +449,23 @@ __global__ __launch_bounds__(1024) void sample_seam_rows_kernel(const float* __r
     slot_embed_row(s_tok, s_go != 0, table, x + (int64_t)b * H, H, V, tid, 1024);
 }
 
+// Log-probability of what the sampled seam just stored, one block per slot: column sd[b].step - 1 of the slot's output row against its
+// logits row (the seam leaves the rows alone).  A slot that idled in the step stored -1: logprob_row's t < 0 case, 0.0f / -1.
+__global__ __launch_bounds__(1024) void logprob_slots_kernel(const float* __restrict__ logits, int V, const int64_t* __restrict__ out_tokens,
+                                                             int n_steps, const SlotDraw* __restrict__ sd, float* __restrict__ lp,
+                                                             int32_t* __restrict__ rank) {
+    __shared__ RowLogprobSmem sm;
+    const int b = blockIdx.x;
+    const int j = sd[b].step - 1;
+    if (j < 0 || j >= n_steps) return;  // block-uniform
+    const int64_t at = (int64_t)b * n_steps + j;
+    const RowLogprob o = logprob_row(logits + (int64_t)b * V, V, out_tokens[at], sm);
+    if (threadIdx.x == 0) {
+        lp[at] = o.lp;
+        if (rank) rank[at] = o.rank;
+    }
+}
+
 template <int NB>
 int launch_ln_gemvB(const LnGemvBArgs& g, hipStream_t s, int op, bool head3) {
     const int Ntot = g.N0 + g.N1;
@@ -883,7 +900,8 @@ extern "C" int showo_engine_batch_decode_greedy(showo_engine* e, int64_t* tok, i
 // top_p == NULL: no slot filters (showo_engine_batch_decode_sample); else host float [nb], per slot >= 1 (off) or in (0, 1).
 static int batch_decode_sample(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws, const int* top_k,
                                const float* top_p, const float* temperature, const uint64_t* seed, const int* draw0,
-                               const float* const* exp_noise, const int* budget, int64_t eot, int* produced, int use_graph, void* stream) {
+                               const float* const* exp_noise, const int* budget, int64_t eot, int* produced, int use_graph, void* stream,
+                               float* lps = nullptr, int32_t* ranks = nullptr) {
     hipStream_t s = (hipStream_t)stream;
     if (!e || !e->bd || e->bd->nb == 0) return set_error_msg(1, "batch_decode_sample: showo_engine_batch_begin + _batch_prefill first");
     auto* d = e->bd;
@@ -940,6 +958,7 @@ static int batch_decode_sample(showo_engine* e, int64_t* tok, int n_steps, int64
         else
             sample_seam_rows_kernel<false><<<dim3(nb), dim3(1024), 0, s>>>(logits_ws, V, eot, tok, out_tokens, n_steps, d->pos_dev, lim,
                                                                           d->slots_dev, e->embed, e->x, H, d->last_iv_dev, d->L0_dev, d->iv_dev);
+        if (lps) logprob_slots_kernel<<<dim3(nb), dim3(1024), 0, s>>>(logits_ws, V, out_tokens, n_steps, d->slots_dev, lps, ranks);
         SHOWO_CHECK_HIP(hipGetLastError());
         return 0;
     };
@@ -968,4 +987,14 @@ extern "C" int showo_engine_batch_decode_sample_p(showo_engine* e, int64_t* tok,
     if (!top_p) return set_error_msg(1, "batch_decode_sample_p: bad arguments");
     return batch_decode_sample(e, tok, n_steps, out_tokens, logits_ws, top_k, top_p, temperature, seed, draw0, exp_noise, budget, eot,
                                produced, use_graph, stream);
+}
+
+
+// showo_engine_batch_decode_sample_p (top_p may be NULL: no slot filters) that also reports how probable every token was
+extern "C" int showo_engine_batch_decode_sample_lp(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws,
+                                                   const int* top_k, const float* top_p, const float* temperature, const uint64_t* seed,
+                                                   const int* draw0, const float* const* exp_noise, const int* budget, int64_t eot,
+                                                   int* produced, float* logprobs, int32_t* ranks, int use_graph, void* stream) {
+    return batch_decode_sample(e, tok, n_steps, out_tokens, logits_ws, top_k, top_p, temperature, seed, draw0, exp_noise, budget, eot,
+                               produced, use_graph, stream, logprobs, logprobs ? ranks : nullptr);
 }

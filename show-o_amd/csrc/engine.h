@@ -44,6 +44,9 @@ int sample_topk_launch(const float* logits, int V, int top_k, float temperature,
                        uint64_t seed, int step, const int* pos_dev, int pos_base, int64_t* tok, hipStream_t s);
 int sample_topk_topp_launch(const float* logits, int V, int top_k, float top_p, float temperature, const float* exp_noise,
                             int64_t noise_stride, uint64_t seed, int step, const int* pos_dev, int pos_base, int64_t* tok, hipStream_t s);
+// sampler.hip: log-probability / rank of *tok on the logits row of the decode step that just stored it and advanced *pos_dev
+int logprob_step_launch(const float* logits, int V, const int64_t* tok, const int* pos_dev, int pos_base, float* lp, int32_t* rank,
+                        hipStream_t s);
 // fused decode layer (decode.hip, attention.hip)
 struct DecodePrefetch;
 bool decode_fused_shapes_ok(int H, int F);
@@ -209,6 +212,11 @@ struct showo_engine {
     // batched AR decode (decode_batch.hip: showo_engine_batch_begin / _batch_prefill / _batch_decode_greedy)
     struct BatchDecode;
     BatchDecode* bd = nullptr;
+    // scoring (showo_engine_score / showo_engine_prefill_append_score): [score_rows, V] logits of one chunk of rows, grown on demand;
+    // the rows 0 .. maxT - 1 as an index list; one target slot for the row in front of an append
+    float* score_ws = nullptr;
+    int64_t score_rows = 0;
+    int32_t* score_iota = nullptr;
     float* collect = nullptr;  // parity hook (showo_engine_set_collect)
     int t2i_captures = 0;  // how often a denoise step was captured (tests: a second identical call must not capture again)
     int t2i_step0[4] = {0, 0, 0, 0};  // last t2i_generate call: sequences / rows trimmed / rows run in step 0, host wait in us (showo_engine_t2i_step0)

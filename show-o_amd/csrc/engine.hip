@@ -1644,8 +1644,11 @@ extern "C" int showo_engine_use_intervals(showo_engine* e, const int32_t* iv, co
 // top_k == 1: arg-max (the reference caller's setting); otherwise temperature / top-k / multinomial on the device
 // (showo_sample_topk semantics; draw j of this call uses noise row / Philox stream step0 + j); 0 < top_p < 1 puts the nucleus filter
 // in front of the draw (showo_sample_topk_topp), top_p >= 1 is the launch of a call without it.
+// lps != NULL (showo_engine_decode_sample_lp): one more launch per step, behind the token boundary, scores the token the step stored
+// against the step's row in logits_ws (sample_row.h logprob_row) -> lps / ranks [n_steps]; NULL: no launch, the loop of a call without.
 static int decode_loop(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws, int top_k, float top_p,
-                       float temperature, const float* exp_noise, uint64_t seed, int step0, int use_graph, void* stream) {
+                       float temperature, const float* exp_noise, uint64_t seed, int step0, int use_graph, void* stream,
+                       float* lps = nullptr, int32_t* ranks = nullptr) {
     hipStream_t s = (hipStream_t)stream;
     if (!e || e->cache_len <= 0) return set_error_msg(1, "decode_greedy: prefill first");
     if (!tok || !out_tokens || !logits_ws || n_steps < 1) return set_error_msg(1, "decode_greedy: bad arguments");
@@ -1688,16 +1691,21 @@ static int decode_loop(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_
         TRY(run_layers(e, 1, 1, prec ? P0 + step_i : P0, kv_decode_cache(e), e->iv1, e->flag, nullptr, s));
         ++step_i;
         TRY(head_rows(e, nullptr, 1, 0, e->V, logits_ws, s));
-        if (seam_tok)
-            return showo::greedy_token_seam(logits_ws, e->V, tok, out_tokens, e->pos_dev, P0, e->embed, e->x, e->H, e->V, e->last_iv_dev,
-                                            e->prompt_len, e->iv1, s);
+        // the token boundary leaves the token in *tok and the position ALREADY advanced: the log-prob launch writes entry pos - 1 - P0
+        auto score = [&]() -> int { return lps ? showo::logprob_step_launch(logits_ws, e->V, tok, e->pos_dev, P0, lps, ranks, s) : 0; };
+        if (seam_tok) {
+            TRY(showo::greedy_token_seam(logits_ws, e->V, tok, out_tokens, e->pos_dev, P0, e->embed, e->x, e->H, e->V, e->last_iv_dev,
+                                         e->prompt_len, e->iv1, s));
+            return score();
+        }
         if (top_k == 1) TRY(showo_argmax_f32(logits_ws, e->V, tok, s));
         else if (top_p >= 1.f) TRY(showo::sample_topk_launch(logits_ws, e->V, top_k, temperature, exp_noise, (int64_t)e->V, seed, step0, e->pos_dev, P0,
                                                              tok, s));
         else TRY(showo::sample_topk_topp_launch(logits_ws, e->V, top_k, top_p, temperature, exp_noise, (int64_t)e->V, seed, step0,
                                                 e->pos_dev, P0, tok, s));
         store_token_kernel<<<1, 64, 0, s>>>(tok, out_tokens, e->pos_dev, P0);
-        return showo::sampler_step_inc(e->pos_dev, s);
+        TRY(showo::sampler_step_inc(e->pos_dev, s));
+        return score();
     };
     int rc = one();  // eager first step (kernel attributes, GEMV variants)
     hipGraph_t g = nullptr;
@@ -1749,4 +1757,95 @@ extern "C" int showo_engine_decode_sample_p(showo_engine* e, int64_t* tok, int n
     if (!(temperature > 0.f)) return set_error_msg(1, "decode_sample_p: temperature must be > 0");
     if (!(top_p > 0.f)) return set_error_msg(1, "decode_sample_p: top_p must be > 0 (>= 1: no nucleus filter)");
     return decode_loop(e, tok, n_steps, out_tokens, logits_ws, top_k, top_p, temperature, exp_noise, seed, step0, use_graph, stream);
+}
+
+// showo_engine_decode_sample_p that also reports how probable every token was (include/showo_hip.h)
+extern "C" int showo_engine_decode_sample_lp(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws,
+                                             int top_k, float top_p, float temperature, const float* exp_noise, uint64_t seed,
+                                             int step0, float* logprobs, int32_t* ranks, int use_graph, void* stream) {
+    if (!(temperature > 0.f)) return set_error_msg(1, "decode_sample_lp: temperature must be > 0");
+    if (!(top_p > 0.f)) return set_error_msg(1, "decode_sample_lp: top_p must be > 0 (>= 1: no nucleus filter)");
+    return decode_loop(e, tok, n_steps, out_tokens, logits_ws, top_k, top_p, temperature, exp_noise, seed, step0, use_graph, stream,
+                       logprobs, logprobs ? ranks : nullptr);
+}
+
+// ---- scoring given tokens (include/showo_hip.h; DESIGN.md, "Log-probabilities") ---------------------------------------------------------
+// [rows, V] logits workspace of one chunk: chunk_rows <= 0 picks the largest chunk within 256 MB; never more than n or the LayerNorm
+// workspace (maxT rows)
+static int score_workspace(showo_engine* e, int n, int chunk_rows, int* chunk) {
+    int64_t c = chunk_rows > 0 ? chunk_rows : ((int64_t)256 << 20) / ((int64_t)e->V * (int64_t)sizeof(float));
+    if (c < 1) c = 1;
+    if (c > n) c = n;
+    if (c > e->maxT) c = e->maxT;
+    if (c > e->score_rows) {
+        SHOWO_CHECK_HIP(hipDeviceSynchronize());  // (an earlier call's launches may still read the buffer that goes)
+        e->release(&e->score_ws);
+        e->score_rows = 0;
+        TRY(e->alloc(&e->score_ws, c * e->V));
+        e->score_rows = c;
+    }
+    *chunk = (int)c;
+    return 0;
+}
+// head + log-prob of the residual rows rows[0, n) against targets[0, n), chunk by chunk
+static int score_rows(showo_engine* e, const int32_t* rows, const int64_t* targets, int n, int chunk, float* logprob, int32_t* rank,
+                      hipStream_t s) {
+    for (int c0 = 0; c0 < n; c0 += chunk) {
+        const int m = n - c0 < chunk ? n - c0 : chunk;
+        TRY(head_rows(e, rows + c0, m, 0, e->V, e->score_ws, s));
+        TRY(showo_logprob_rows(e->score_ws, e->V, m, e->V, targets + c0, logprob + c0, rank ? rank + c0 : nullptr, s));
+    }
+    return 0;
+}
+
+extern "C" int showo_engine_score(showo_engine* e, const int64_t* ids, const float* embeds, const float* mask, int B, int L,
+                                  const int32_t* rows, const int64_t* targets, int n, int chunk_rows, float* logprob, int32_t* rank,
+                                  void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!e) return set_error_msg(1, "engine: null handle");
+    if (n == 0 || B == 0 || L == 0) return 0;
+    if (n < 0 || !rows || !targets || !logprob) return set_error_msg(1, "score: bad arguments");
+    int chunk = 0;
+    TRY(check_ready(e, B, L));
+    TRY(score_workspace(e, n, chunk_rows, &chunk));
+    TRY(hidden(e, ids, embeds, mask, B, L, s));
+    return score_rows(e, rows, targets, n, chunk, logprob, rank, s);
+}
+
+namespace {
+__global__ void iota_i32_kernel(int32_t* out, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = i;
+}
+__global__ void fill_f32_i32_kernel(float* f, float fv, int32_t* i, int32_t iv) {
+    if (threadIdx.x == 0) { *f = fv; if (i) *i = iv; }
+}
+}  // namespace
+
+extern "C" int showo_engine_prefill_append_score(showo_engine* e, const int64_t* ids, int Ln, const float* logits_prev, float* logprob,
+                                                 int32_t* rank, float* logits_last, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!e) return set_error_msg(1, "engine: null handle");
+    if (!ids || !logprob) return set_error_msg(1, "prefill_append_score: bad arguments");
+    if (logits_prev && logits_prev == logits_last) return set_error_msg(1, "prefill_append_score: logits_prev must not be logits_last");
+    int chunk = 0;
+    if (Ln > 1) {
+        if (Ln > e->maxT) return set_error_msg(5, "engine: batch/sequence exceeds the configured workspace");
+        TRY(score_workspace(e, Ln - 1, 0, &chunk));
+        if (!e->score_iota) {
+            TRY(e->alloc(&e->score_iota, e->maxT));
+            iota_i32_kernel<<<dim3((unsigned)((e->maxT + 255) / 256)), dim3(256), 0, s>>>(e->score_iota, (int)e->maxT);
+            SHOWO_CHECK_HIP(hipGetLastError());
+        }
+    }
+    TRY(showo_engine_prefill_append(e, ids, nullptr, Ln, logits_last, stream));
+    // ids[0] against the logits of the row in front of the append; ids[j] against the appended row j - 1 (the residual rows are still in x)
+    if (logits_prev) {
+        TRY(showo_logprob_rows(logits_prev, e->V, 1, e->V, ids, logprob, rank, s));
+    } else {
+        fill_f32_i32_kernel<<<1, 64, 0, s>>>(logprob, __builtin_nanf(""), rank, -1);
+        SHOWO_CHECK_HIP(hipGetLastError());
+    }
+    if (Ln > 1) TRY(score_rows(e, e->score_iota, ids + 1, Ln - 1, chunk, logprob + 1, rank ? rank + 1 : nullptr, s));
+    return 0;
 }

@@ -307,4 +307,80 @@ __device__ __forceinline__ int sample_topk_topp_row(const float* __restrict__ lo
     return bi;
 }
 
+// ---- log-probability of a given token -------------------------------------------------------------------------------------------------
+// For one fp32 logits row x[0, V) and a target t:
+//   lp   = x[t] - max(x) - log sum_i exp(x[i] - max(x))     log-softmax of the RAW logits (temperature 1, no top-k / top-p filter)
+//   rank = #{ i : x[i] > x[t] }                             strict: 0 for the arg-max and everything tied with it
+// t < 0 (the -100 of the label convention): lp = 0, rank = -1.  t >= V: lp = NaN, rank = -1 (the embedding kernel's poisoning of
+// out-of-range ids).  -inf entries add 0 to the sum; a -inf target gives lp = -inf; a row of -inf alone gives NaN.
+//
+// Two passes over the row (it was just written by the lm_head and sits in L2): max and rank, then the sum.  The row is read with
+// 16-byte loads behind a peel to its alignment (rows of a [n, 58498] block alternate between 8- and 16-byte alignment), so WHICH lane
+// meets which element depends on where the row lies.  The result must not: the same row bits give the same lp bits from every caller
+// (stand-alone, batch-1 loop, batched slot, scoring).  The max and the rank are order-free by nature; the sum is made order-free the
+// way the nucleus cut is: w_i = (uint64)(expf(x_i - max) * 2^40) -- the scaling is exact, the conversion truncates, w <= 2^40 and
+// the total stays below 2^64 for V < 2^24 -- added as integers.  The arg-max term is exactly 2^40, so the total S >= 2^40 and the
+// truncation costs at most V 2^-40 (5e-8 at V = 58498) relative: below the fp32 rounding of the final logf.  Valid in thread 0.
+struct RowLogprobSmem {
+    float red_f[16];
+    int red_i[16];
+    unsigned long long red_w[16];
+};
+struct RowLogprob {
+    float lp;
+    int rank;
+};
+
+// f(v) for every element of row[0, V): the elements in front of the first 16-byte boundary and behind the last whole quad one by
+// one, the quads in between as float4
+template <class F>
+__device__ __forceinline__ void row_for_each_1024(const float* __restrict__ row, int V, F&& f) {
+    const int tid = threadIdx.x;
+    int head = (int)(((16u - (unsigned)((uintptr_t)row & 15u)) & 15u) >> 2);
+    if (head > V) head = V;
+    const int n4 = (V - head) >> 2, tail0 = head + 4 * n4;
+    if (tid < head) f(row[tid]);
+    const float4* __restrict__ q = reinterpret_cast<const float4*>(row + head);
+    for (int i = tid; i < n4; i += 1024) {
+        const float4 v = q[i];
+        f(v.x); f(v.y); f(v.z); f(v.w);
+    }
+    if (tid < V - tail0) f(row[tail0 + tid]);
+}
+
+__device__ __forceinline__ RowLogprob logprob_row(const float* __restrict__ row, int V, int64_t target, RowLogprobSmem& sm) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    RowLogprob r{0.f, -1};
+    if (target < 0 || target >= V) {  // block-uniform
+        r.lp = target < 0 ? 0.f : __builtin_nanf("");
+        r.rank = -1;
+        return r;
+    }
+    const float xt = row[target];
+    float mx = -INFINITY;
+    int above = 0;
+    row_for_each_1024(row, V, [&](float v) { mx = fmaxf(mx, v); above += v > xt; });
+    mx = wave_max(mx);
+    for (int o = 32; o > 0; o >>= 1) above += __shfl_xor(above, o, 64);
+    if (lane == 0) { sm.red_f[wave] = mx; sm.red_i[wave] = above; }
+    __syncthreads();
+    mx = sm.red_f[0];
+    above = sm.red_i[0];
+    for (int w = 1; w < 16; ++w) { mx = fmaxf(mx, sm.red_f[w]); above += sm.red_i[w]; }
+    unsigned long long acc = 0ull;
+    if (mx > -INFINITY && mx < INFINITY)  // (a row of -inf alone, or one with +inf: x - mx is NaN; the sum stays 0 and the result is NaN)
+        row_for_each_1024(row, V, [&](float v) { acc += (unsigned long long)(expf(v - mx) * 1099511627776.0f); });
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+    if (lane == 0) sm.red_w[wave] = acc;
+    __syncthreads();
+    if (tid == 0) {
+        unsigned long long S = 0ull;
+        for (int w = 0; w < 16; ++w) S += sm.red_w[w];
+        r.lp = S ? (xt - mx) - logf((float)((double)S * (1.0 / 1099511627776.0))) : __builtin_nanf("");
+        r.rank = above;
+    }
+    __syncthreads();  // the caller may reuse sm
+    return r;
+}
+
 }  // namespace showo

@@ -318,6 +318,56 @@ int sample_topk_topp_launch(const float* logits, int V, int top_k, float top_p, 
 }
 }  // namespace showo
 
+// ------------------------------------------------------------------------------------------------------------------
+// Log-probability and rank of a given token per logits row (sample_row.h logprob_row): one 1024-thread block per row.
+// ------------------------------------------------------------------------------------------------------------------
+namespace {
+__global__ __launch_bounds__(1024) void logprob_rows_kernel(const float* __restrict__ logits, int64_t ld, int V,
+                                                            const int64_t* __restrict__ targets, float* __restrict__ lp,
+                                                            int32_t* __restrict__ rank) {
+    __shared__ RowLogprobSmem sm;
+    const int r = blockIdx.x;
+    const RowLogprob o = logprob_row(logits + (int64_t)r * ld, V, targets[r], sm);
+    if (threadIdx.x == 0) {
+        lp[r] = o.lp;
+        if (rank) rank[r] = o.rank;
+    }
+}
+// the decode loop's form: the row of the step that just stored its token (*tok) and advanced *pos; entry *pos - 1 - base
+__global__ __launch_bounds__(1024) void logprob_step_kernel(const float* __restrict__ logits, int V, const int64_t* __restrict__ tok,
+                                                            const int* __restrict__ pos, int base, float* __restrict__ lp,
+                                                            int32_t* __restrict__ rank) {
+    __shared__ RowLogprobSmem sm;
+    const RowLogprob o = logprob_row(logits, V, *tok, sm);
+    if (threadIdx.x == 0) {
+        const int j = *pos - 1 - base;
+        lp[j] = o.lp;
+        if (rank) rank[j] = o.rank;
+    }
+}
+}  // namespace
+
+namespace showo {
+int logprob_step_launch(const float* logits, int V, const int64_t* tok, const int* pos_dev, int pos_base, float* lp, int32_t* rank,
+                        hipStream_t s) {
+    if (!logits || !tok || !pos_dev || !lp || V <= 0) return set_error_msg(1, "logprob_step: bad arguments");
+    logprob_step_kernel<<<dim3(1), dim3(1024), 0, s>>>(logits, V, tok, pos_dev, pos_base, lp, rank);
+    SHOWO_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+}  // namespace showo
+
+extern "C" int showo_logprob_rows(const float* logits, int64_t ld, int nrows, int V, const int64_t* targets, float* logprob,
+                                  int32_t* rank, void* stream) {
+    if (nrows == 0) return 0;
+    if (!logits || !targets || !logprob || nrows < 0) return set_error_msg(1, "logprob_rows: bad arguments");
+    if (V < 1 || V >= (1 << 24) || ld < V) return set_error_msg(1, "logprob_rows: needs 1 <= V < 2^24 (64-bit mass sums) and ld >= V");
+    if ((uintptr_t)logits & 3) return set_error_msg(1, "logprob_rows: logits must be 4-byte aligned");
+    logprob_rows_kernel<<<dim3(nrows), dim3(1024), 0, (hipStream_t)stream>>>(logits, ld, V, targets, logprob, rank);
+    SHOWO_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
 extern "C" int showo_sample_topk_topp(const float* logits, int V, int top_k, float top_p, float temperature, const float* exp_noise,
                                       uint64_t seed, int step, int64_t* tok, void* stream) {
     return showo::sample_topk_topp_launch(logits, V, top_k, top_p, temperature, exp_noise, (int64_t)V, seed, step, nullptr, 0, tok,

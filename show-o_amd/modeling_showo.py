@@ -8,6 +8,7 @@ The torch modules below are *parameter containers only* (they give `state_dict()
 the reference's names and shapes); all arithmetic runs in HIP kernels through the C ABI.  There is no
 PyTorch fallback: without a GPU or without the built library every compute entry point raises.
 """
+import collections
 import types
 
 import torch
@@ -21,6 +22,10 @@ from .sampling import cosine_schedule, t2i_step_constants
 # reference, models/modeling_showo.py:42; PhiConfig defaults)
 PHI_1_5 = dict(hidden_size=2048, intermediate_size=8192, num_hidden_layers=24, num_attention_heads=32,
                max_position_embeddings=2048, layer_norm_eps=1e-5, rope_theta=10000.0, partial_rotary_factor=0.5)
+
+
+# what `Showo.score` / `MmuSession.score` return: log-probabilities (fp32) and ranks (int32; -1 = not scored) of the given tokens
+TokenScores = collections.namedtuple("TokenScores", ["logprobs", "ranks"])
 
 
 class _Cfg(dict):
@@ -719,6 +724,64 @@ class Showo(PretrainedMixin, nn.Module):
             return logits
         raise AssertionError("unreachable")
 
+    # ---- Showo.score: log-probabilities of given tokens, without [B, L, vocab] logits --------------------------------------
+    def _score_rows(self, ids, emb, mask, B, L, rows, targets, chunk_rows):
+        """(log-probabilities fp32 [n], ranks int32 [n]) of targets int64 [n] under the logits of the residual rows int32 [n] of one
+        forward (showo_engine_score); the caller has registered an IntervalMask, if any"""
+        n = int(rows.numel())
+        lp = torch.empty((n,), dtype=torch.float32, device=rows.device)
+        rk = torch.empty((n,), dtype=torch.int32, device=rows.device)
+        try:
+            _lib.call("showo_engine_score", self.engine(), _lib.ptr(ids), _lib.ptr(emb), _lib.ptr(mask), B, L, _lib.ptr(rows), _lib.ptr(targets), n,
+                      0 if chunk_rows is None else int(chunk_rows), _lib.ptr(lp), _lib.ptr(rk), _lib.stream())
+        finally:
+            _lib.call("showo_engine_use_intervals", self.engine(), None, None)
+        return lp, rk
+
+    @torch.no_grad()
+    def score(self, input_ids=None, input_embeddings=None, attention_mask=None, labels=None, shift=True, chunk_rows=None):
+        """How probable the tokens `labels` (int64 [B, L], -100 = not scored) are: `TokenScores(logprobs, ranks)`, fp32 / int32 [B, L].
+        shift=True (autoregressive rows): entry [b, r] scores labels[b, r] from the logits of row r - 1, column 0 is never scored;
+        shift=False (the t2i mask-prediction form, reference modeling_showo.py:83-86): entry [b, r] is scored from row r.  logprobs
+        are the log-softmax of the raw logits at the label, ranks the number of strictly larger logits; unscored entries are 0.0 / -1,
+        so `logprobs.sum(-1)` is the sequence log-likelihood.  Inputs and masks (dense or IntervalMask) as in `forward`.  One forward,
+        then the head on the scored rows alone in chunks of `chunk_rows` rows (default: 256 MB of logits at most): no [B, L, vocab]
+        tensor exists at any time."""
+        if (input_ids is None) == (input_embeddings is None):
+            raise ValueError("exactly one of input_ids / input_embeddings must be given")
+        if labels is None:
+            raise ValueError("score needs labels")
+        eng = self.engine()
+        if input_embeddings is None:
+            B, L = input_ids.shape
+            ids, emb = input_ids.to(torch.int64).contiguous(), None
+            dev = ids.device
+        else:
+            B, L = input_embeddings.shape[:2]
+            ids, emb = None, input_embeddings.detach().float().contiguous()
+            dev = emb.device
+        if tuple(labels.shape) != (B, L):
+            raise ValueError(f"labels should be of size {(B, L)}, but is {tuple(labels.shape)}")
+        if chunk_rows is not None and int(chunk_rows) < 1:
+            raise ValueError("chunk_rows must be >= 1")
+        lab = labels.to(torch.int64).to(dev).reshape(-1)
+        sel = (lab >= 0).reshape(B, L).clone()
+        if shift:
+            sel[:, 0] = False
+        at = sel.reshape(-1).nonzero().reshape(-1)
+        lp = torch.zeros((B * L,), dtype=torch.float32, device=dev)
+        rk = torch.full((B * L,), -1, dtype=torch.int32, device=dev)
+        if at.numel():
+            mask = None
+            if attention_mask is not None:
+                if tuple(attention_mask.shape) != (B, 1, L, L):
+                    raise ValueError(f"Attention mask should be of size {(B, 1, L, L)}, but is {tuple(attention_mask.shape)}")
+                mask = self._use_mask(eng, attention_mask)
+            rows = (at - 1 if shift else at).to(torch.int32).contiguous()
+            a, b = self._score_rows(ids, emb, mask, B, L, rows, lab[at].contiguous(), chunk_rows)
+            lp[at], rk[at] = a, b
+        return TokenScores(lp.reshape(B, L), rk.reshape(B, L))
+
     # ---- Showo.t2i_generate (reference models/modeling_showo.py:104-181) -----------------------------------
     def t2i_generate(self, input_ids=None, uncond_input_ids=None, attention_mask=None, temperature=1.0, timesteps=18,
                      guidance_scale=0, noise_schedule=cosine_schedule, generator=None, config=None,
@@ -774,11 +837,14 @@ class Showo(PretrainedMixin, nn.Module):
     # ---- Showo.mmu_generate (reference models/modeling_showo.py:183-240) -----------------------------------
     @torch.no_grad()
     def mmu_generate(self, idx=None, input_embeddings=None, attention_mask=None, max_new_tokens=100, temperature=1.0,
-                     top_k=None, eot_token=None, generator=None, _exp_noise=None, top_p=None):
+                     top_k=None, eot_token=None, generator=None, _exp_noise=None, top_p=None, return_logprobs=False):
         """reference signature + `generator` (seeds the on-device Philox stream of the multinomial draws; default: torch's
         global generator), `_exp_noise` fp32 [max_new_tokens, vocab] (parity tests inject the reference's Exp(1) draws) and `top_p`
         (nucleus sampling on the device behind the top-k filter, the reference's top_k_top_p_filtering: a token stays iff the mass of
-        the strictly more probable candidates is <= top_p; None or >= 1: off, <= 0: ValueError; top_k == 1 stays the arg-max)"""
+        the strictly more probable candidates is <= top_p; None or >= 1: off, <= 0: ValueError; top_k == 1 stays the arg-max).
+        `return_logprobs=True` returns `(tokens, logprobs)`: logprobs fp32 [len(tokens)] on the device, entry j the log-softmax of the
+        RAW logits (temperature 1, no filter) at token j -- one more launch per decode step (showo_engine_decode_sample_lp); the
+        tokens are those of the call without it."""
         p = _nucleus_p(top_p)
         eng = self.engine()
         greedy = top_k == 1  # the reference caller's setting (inference_mmu.py:81): multinomial of a one-hot = arg-max
@@ -799,7 +865,7 @@ class Showo(PretrainedMixin, nn.Module):
         if int(getattr(self, "_precision", 0)) == 1 and (getattr(self, "precise_recompute", False) or
                                                          not _lib.load().showo_engine_precise_fast(eng)):
             return self._mmu_generate_recompute(idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token,
-                                                greedy, None if greedy else (k, seed, noise), top_p=p)
+                                                greedy, None if greedy else (k, seed, noise), top_p=p, return_logprobs=return_logprobs)
         if input_embeddings is not None:
             if input_embeddings.shape[0] != 1:
                 raise ValueError("mmu_generate has batch-1 semantics (reference modeling_showo.py:204,229)")
@@ -831,10 +897,15 @@ class Showo(PretrainedMixin, nn.Module):
             _lib.call("showo_argmax_f32", _lib.ptr(logits), self.vocab_size, _lib.ptr(tok), _lib.stream())
         else:  # logits / temperature -> top-k filter -> softmax -> multinomial (reference :220-228), one kernel
             _sample_call(logits, self.vocab_size, k, p, temperature, noise, seed, 0, tok)
+        lps = [_logprob_of(logits, self.vocab_size, tok)] if return_logprobs else None
+
+        def done(result):
+            return (result, torch.cat(lps)[:len(result)]) if return_logprobs else result
+
         first = int(tok.item())
         result = [torch.tensor(first, device=dev)]
         if (eot_token is not None and first == eot_token) or max_new_tokens <= 1:
-            return result[:max_new_tokens]
+            return done(result[:max_new_tokens])
         use_graph, chunk = int(getattr(self, "decode_graph", 1)), 16
         if getattr(self, "_graph_stream", None) is None:
             self._graph_stream = torch.cuda.Stream()
@@ -843,9 +914,14 @@ class Showo(PretrainedMixin, nn.Module):
         while remaining > 0:
             n = min(chunk, remaining)
             outc = torch.empty((n,), dtype=torch.int64, device=dev)
+            if return_logprobs:
+                lps.append(torch.empty((n,), dtype=torch.float32, device=dev))
             self._graph_stream.wait_stream(cur)
             with torch.cuda.stream(self._graph_stream):
-                if greedy:
+                if return_logprobs:
+                    _decode_lp_call(eng, tok, n, outc, logits, greedy, None if greedy else k, p, temperature, None if greedy else noise,
+                                    0 if greedy else seed, max_new_tokens - remaining, lps[-1], use_graph)
+                elif greedy:
                     _lib.call("showo_engine_decode_greedy", eng, _lib.ptr(tok), n, _lib.ptr(outc), _lib.ptr(logits), use_graph,
                               _lib.stream())
                 else:
@@ -855,9 +931,9 @@ class Showo(PretrainedMixin, nn.Module):
             for t in toks:
                 result.append(torch.tensor(t, device=dev))
                 if eot_token is not None and t == eot_token:
-                    return result
+                    return done(result)
             remaining -= n
-        return result
+        return done(result)
 
 
 def _nucleus_p(top_p):
@@ -888,6 +964,21 @@ def _decode_sample_call(eng, tok, n, outc, logits, k, p, temperature, noise, see
     else:
         _lib.call("showo_engine_decode_sample_p", eng, _lib.ptr(tok), n, _lib.ptr(outc), _lib.ptr(logits), k, p, float(temperature),
                   _lib.ptr(noise), seed, step0, use_graph, _lib.stream())
+
+
+def _logprob_of(logits, V, tok):
+    """fp32 [1]: the log-probability of token tok[0] under the logits row (showo_logprob_rows)"""
+    lp = torch.empty((1,), dtype=torch.float32, device=logits.device)
+    _lib.call("showo_logprob_rows", _lib.ptr(logits), V, 1, V, _lib.ptr(tok), _lib.ptr(lp), None, _lib.stream())
+    return lp
+
+
+def _decode_lp_call(eng, tok, n, outc, logits, greedy, k, p, temperature, noise, seed, step0, lps, use_graph):
+    """n steps of the device loop with their log-probabilities: showo_engine_decode_sample_lp, which takes the greedy step for
+    top_k == 1 and the plain top-k draw for top_p >= 1 -- the token launches of the three calls without log-probabilities"""
+    _lib.call("showo_engine_decode_sample_lp", eng, _lib.ptr(tok), n, _lib.ptr(outc), _lib.ptr(logits), 1 if greedy else k,
+              1.0 if (greedy or p is None) else p, 1.0 if greedy else float(temperature), _lib.ptr(noise), seed, step0, _lib.ptr(lps), None,
+              use_graph, _lib.stream())
 
 
 # Slot scheduler of mmu_generate_batch (n >= 2 sequences at precision 0 / 2 beyond the all-greedy 2..8 case).  Slot count for more
@@ -954,8 +1045,11 @@ def _mmu_batch_schedule(eng, n, slots, max_new_tokens, eot_token, chunk=_MMU_BAT
 class _MmuSlotEngine:
     """engine side of _mmu_batch_schedule: `slots` KV caches of showo_engine_batch_*, one request per slot"""
 
-    def __init__(self, model, eng, idx, input_embeddings, masks, lens, slots, temps, top_ks, seeds, noises, eot_token, dev, top_ps=None):
+    def __init__(self, model, eng, idx, input_embeddings, masks, lens, slots, temps, top_ks, seeds, noises, eot_token, dev, top_ps=None,
+                 want_lp=False):
         self.model, self.eng, self.idx, self.emb, self.masks, self.lens = model, eng, idx, input_embeddings, masks, lens
+        # want_lp: every decode call goes through showo_engine_batch_decode_sample_lp; lps[r] collects request r's log-probabilities
+        self.lps = {} if want_lp else None
         self.slots, self.temps, self.top_ks, self.seeds, self.noises = slots, temps, top_ks, seeds, noises
         self.top_ps = [None] * len(top_ks) if top_ps is None else top_ps  # per request: None or the nucleus p inside (0, 1)
         self.eot = -1 if eot_token is None else int(eot_token)
@@ -1000,11 +1094,23 @@ class _MmuSlotEngine:
             _sample_call(self.logits[s], m.vocab_size, 0 if k is None else int(k), self.top_ps[r], self.temps[r], self.noises[r],
                          self.seeds[r], 0, self.tok[s:s + 1])
         self.occ[s] = r
+        if self.lps is not None:
+            self.lps[r] = [_logprob_of(self.logits[s], m.vocab_size, self.tok[s:s + 1])]
         return int(self.tok[s].item())
+
+    def logprobs(self, r, n):
+        """request r's log-probabilities, cut to its n tokens"""
+        return torch.cat(self.lps[r])[:n]
 
     def decode(self, m, budget, draw0):
         import ctypes as C
         S = self.slots
+        for s in range(S):
+            # a slot no request ever took (first tokens that were <eot> ended their sequences before they needed one) still has to hold
+            # a prefill for the batched step: it idles on a copy of request 0
+            if self.occ[s] is None and self.lps is not None:
+                self.fill(s, 0)
+                self.occ[s] = 0
         occ = [r if budget[s] > 0 else None for s, r in enumerate(self.occ)]
         k = [1 if r is None else (0 if self.top_ks[r] is None else int(self.top_ks[r])) for r in occ]
         temp = [1.0 if r is None else float(self.temps[r]) for r in occ]
@@ -1016,21 +1122,31 @@ class _MmuSlotEngine:
         nucleus = any(q < 1.0 for q in top_p)  # no slot filters: the call of a batch without nucleus sampling
         a_p = (C.c_float * S)(*top_p)
         out = torch.empty((S, m), dtype=torch.int64, device=self.dev)
+        lp = None if self.lps is None else torch.empty((S, m), dtype=torch.float32, device=self.dev)
         cur = torch.cuda.current_stream()
         gs = self.model._graph_stream
         gs.wait_stream(cur)
         with torch.cuda.stream(gs):
-            _lib.call("showo_engine_batch_decode_sample_p" if nucleus else "showo_engine_batch_decode_sample", self.eng,
-                      _lib.ptr(self.tok), m, _lib.ptr(out), _lib.ptr(self.logits),
-                      *(C.cast(a, C.c_void_p) for a in ((a_k, a_p, a_t, a_s, a_d, a_n, a_b) if nucleus else (a_k, a_t, a_s, a_d, a_n, a_b))),
-                      self.eot, C.cast(prod, C.c_void_p), self.use_graph, _lib.stream())
+            if lp is not None:
+                _lib.call("showo_engine_batch_decode_sample_lp", self.eng, _lib.ptr(self.tok), m, _lib.ptr(out), _lib.ptr(self.logits),
+                          *(C.cast(a, C.c_void_p) for a in (a_k, a_p, a_t, a_s, a_d, a_n, a_b)), self.eot, C.cast(prod, C.c_void_p),
+                          _lib.ptr(lp), None, self.use_graph, _lib.stream())
+            else:
+                _lib.call("showo_engine_batch_decode_sample_p" if nucleus else "showo_engine_batch_decode_sample", self.eng,
+                          _lib.ptr(self.tok), m, _lib.ptr(out), _lib.ptr(self.logits),
+                          *(C.cast(a, C.c_void_p) for a in ((a_k, a_p, a_t, a_s, a_d, a_n, a_b) if nucleus else (a_k, a_t, a_s, a_d, a_n, a_b))),
+                          self.eot, C.cast(prod, C.c_void_p), self.use_graph, _lib.stream())
         cur.wait_stream(gs)
+        if lp is not None:
+            for s, r in enumerate(occ):
+                if r is not None:
+                    self.lps[r].append(lp[s, :prod[s]])
         return out.tolist(), list(prod)
 
 
 @torch.no_grad()
 def mmu_generate_batch(self, idx=None, input_embeddings=None, attention_mask=None, max_new_tokens=100, temperature=1.0, top_k=None,
-                       eot_token=None, generator=None, _exp_noise=None, top_p=None):
+                       eot_token=None, generator=None, _exp_noise=None, top_p=None, return_logprobs=False):
     """n independent `mmu_generate` calls served together (BASELINE cfg4: "batch=4 images"; the reference's mmu_generate is batch-1 and
     inference_mmu.py:87-177 walks the images one by one).  `idx` / `input_embeddings` / `attention_mask` are LISTS (one entry per
     sequence, each what a single `mmu_generate` call takes: [1, L_b] ids or [1, L_b, H] embeddings, its own mask or IntervalMask);
@@ -1042,7 +1158,9 @@ def mmu_generate_batch(self, idx=None, input_embeddings=None, attention_mask=Non
     b = 0, 1, ..., n-1 (the same seeds are drawn from `generator`, or torch's global generator, in the same order).  At precision 0, 2 and 3
     every n >= 2 runs on the batched engine path (csrc/decode_batch.hip: one weight stream per token step for all slots, every sequence
     bit-identical to its batch-1 run): all-greedy batches of 2..8 on showo_engine_batch_decode_greedy, anything else on up to 8 slots
-    of showo_engine_batch_decode_sample that are refilled as sequences finish.  Precision 1 and n < 2 make the sequential calls."""
+    of showo_engine_batch_decode_sample that are refilled as sequences finish.  Precision 1 and n < 2 make the sequential calls.
+    `return_logprobs=True` returns `(tokens, logprobs)`, logprobs a list of n fp32 device tensors (result[b]'s log-probabilities, the
+    bits of the batch-1 call's); every batch, the all-greedy one included, then runs on the slots of showo_engine_batch_decode_sample_lp."""
     seqs = idx if idx is not None else input_embeddings
     n = len(seqs)
     masks = attention_mask if isinstance(attention_mask, (list, tuple)) else [attention_mask] * n
@@ -1057,11 +1175,16 @@ def mmu_generate_batch(self, idx=None, input_embeddings=None, attention_mask=Non
     def single(b):
         return self.mmu_generate(idx=None if idx is None else idx[b], input_embeddings=None if input_embeddings is None else input_embeddings[b],
                                  attention_mask=masks[b], max_new_tokens=max_new_tokens, temperature=temps[b], top_k=top_ks[b],
-                                 eot_token=eot_token, generator=generator, _exp_noise=noises[b], top_p=top_ps[b])
+                                 eot_token=eot_token, generator=generator, _exp_noise=noises[b], top_p=top_ps[b],
+                                 **({"return_logprobs": True} if return_logprobs else {}))
+
+    def singles():
+        outs = [single(b) for b in range(n)]
+        return ([o[0] for o in outs], [o[1] for o in outs]) if return_logprobs else outs
 
     if int(getattr(self, "_precision", 0)) == 1 or n < 2:
-        return [single(b) for b in range(n)]
-    if n <= _MMU_BATCH_MAX and all(k == 1 for k in top_ks):
+        return singles()
+    if n <= _MMU_BATCH_MAX and all(k == 1 for k in top_ks) and not return_logprobs:
         return self._mmu_generate_batch_greedy(idx, input_embeddings, masks, max_new_tokens, eot_token, single)
     for b in range(n):
         if seqs[b].shape[0] != 1:
@@ -1079,12 +1202,14 @@ def mmu_generate_batch(self, idx=None, input_embeddings=None, attention_mask=Non
     except RuntimeError:
         # the batch's common capacity (longest prompt + max_new_tokens) does not fit the engine (max_position_embeddings, the single-block
         # decode attention): n sequential calls fail only if a sequence actually reaches the limit before <eot>
-        return [single(b) for b in range(n)]
+        return singles()
     seeds = _mmu_batch_seeds(top_ks, generator)
     noises = [None if (k == 1 or z is None) else z.detach().float().contiguous().to(dev) for k, z in zip(top_ks, noises)]
-    se = _MmuSlotEngine(self, eng, idx, input_embeddings, masks, lens, slots, temps, top_ks, seeds, noises, eot_token, dev, top_ps)
+    se = _MmuSlotEngine(self, eng, idx, input_embeddings, masks, lens, slots, temps, top_ks, seeds, noises, eot_token, dev, top_ps,
+                        want_lp=return_logprobs)
     out = _mmu_batch_schedule(se, n, slots, max_new_tokens, eot_token)
-    return [[torch.tensor(t, device=dev) for t in r] for r in out]
+    toks = [[torch.tensor(t, device=dev) for t in r] for r in out]
+    return (toks, [se.logprobs(b, len(out[b])) for b in range(n)]) if return_logprobs else toks
 
 
 Showo.mmu_generate_batch = mmu_generate_batch
@@ -1162,8 +1287,8 @@ class _SessionSlotEngine(_MmuSlotEngine):
     """engine side of _mmu_batch_schedule for MmuSession.generate_batch: a slot is filled by a fork of the session's cache plus an
     append of the request's rows instead of a prefill of a whole prompt"""
 
-    def __init__(self, model, eng, rows, lens, slots, temps, top_ks, seeds, noises, eot_token, dev, top_ps=None):
-        super().__init__(model, eng, None, None, None, lens, slots, temps, top_ks, seeds, noises, eot_token, dev, top_ps)
+    def __init__(self, model, eng, rows, lens, slots, temps, top_ks, seeds, noises, eot_token, dev, top_ps=None, want_lp=False):
+        super().__init__(model, eng, None, None, None, lens, slots, temps, top_ks, seeds, noises, eot_token, dev, top_ps, want_lp)
         self.rows = rows
 
     def fill(self, s, r):
@@ -1245,25 +1370,36 @@ class _SessionEngine:
         past an <eot>)"""
         self.rewind(length + len(toks) - 1)
 
-    def run(self, max_new_tokens, greedy, k, temperature, noise, seed, eot_token, top_p=None):
-        """Showo.mmu_generate behind its prefill: the first token from the current logits, the rest from the device loop in chunks"""
+    def run(self, max_new_tokens, greedy, k, temperature, noise, seed, eot_token, top_p=None, return_logprobs=False):
+        """Showo.mmu_generate behind its prefill: the first token from the current logits, the rest from the device loop in chunks;
+        return_logprobs: (tokens, their log-probabilities fp32 [len(tokens)])"""
         m, eng, logits, tok = self.model, self.eng, self.logits, self.tok
         if greedy:
             _lib.call("showo_argmax_f32", _lib.ptr(logits), m.vocab_size, _lib.ptr(tok), _lib.stream())
         else:
             _sample_call(logits, m.vocab_size, k, top_p, temperature, noise, seed, 0, tok)
+        lps = [_logprob_of(logits, m.vocab_size, tok)] if return_logprobs else None
+
+        def done(result):
+            return (result, torch.cat(lps)[:len(result)]) if return_logprobs else result
+
         result = [int(tok.item())]
         if (eot_token is not None and result[0] == eot_token) or max_new_tokens <= 1:
-            return result
+            return done(result)
         use_graph, chunk = int(getattr(m, "decode_graph", 1)), 16
         cur = torch.cuda.current_stream()
         remaining = max_new_tokens - 1
         while remaining > 0:
             n = min(chunk, remaining)
             outc = torch.empty((n,), dtype=torch.int64, device=self.dev)
+            if return_logprobs:
+                lps.append(torch.empty((n,), dtype=torch.float32, device=self.dev))
             m._graph_stream.wait_stream(cur)
             with torch.cuda.stream(m._graph_stream):
-                if greedy:
+                if return_logprobs:
+                    _decode_lp_call(eng, tok, n, outc, logits, greedy, None if greedy else k, top_p, temperature, None if greedy else noise,
+                                    0 if greedy else seed, max_new_tokens - remaining, lps[-1], use_graph)
+                elif greedy:
                     _lib.call("showo_engine_decode_greedy", eng, _lib.ptr(tok), n, _lib.ptr(outc), _lib.ptr(logits), use_graph, _lib.stream())
                 else:
                     _decode_sample_call(eng, tok, n, outc, logits, k, top_p, temperature, noise, seed, max_new_tokens - remaining, use_graph)
@@ -1271,20 +1407,34 @@ class _SessionEngine:
             for t in outc.tolist():
                 result.append(t)
                 if eot_token is not None and t == eot_token:
-                    return result
+                    return done(result)
             remaining -= n
-        return result
+        return done(result)
 
-    def run_batch(self, length, rows, lens, max_new_tokens, temps, top_ks, seeds, noises, eot_token, top_ps=None):
-        """n continuations of the cache [0, length) on the slots of a decode batch; None when the batch does not fit the engine"""
+    def score(self, ids, Ln, use_prefix_logits):
+        """log-probabilities / ranks [Ln] of the rows ids [1, Ln] appended to the cache (showo_engine_prefill_append_score): row j from
+        the logits of row j - 1, row 0 from the prefill's logits (use_prefix_logits) or NaN / -1.  The rows stay in the cache: the
+        caller rewinds."""
+        lp = torch.empty((Ln,), dtype=torch.float32, device=self.dev)
+        rk = torch.empty((Ln,), dtype=torch.int32, device=self.dev)
+        last = torch.empty_like(self.logits)  # (self.logits keeps what the last append / decode step left)
+        _lib.call("showo_engine_prefill_append_score", self.eng, _lib.ptr(ids), Ln, _lib.ptr(self.logits0) if use_prefix_logits else None,
+                  _lib.ptr(lp), _lib.ptr(rk), _lib.ptr(last), _lib.stream())
+        return lp, rk
+
+    def run_batch(self, length, rows, lens, max_new_tokens, temps, top_ks, seeds, noises, eot_token, top_ps=None, return_logprobs=False):
+        """n continuations of the cache [0, length) on the slots of a decode batch; None when the batch does not fit the engine;
+        return_logprobs: (token lists, log-probability tensors)"""
         n = len(rows)
         slots = _mmu_batch_slots(n)
         try:
             _lib.call("showo_engine_batch_begin", self.eng, slots, length + max(lens) + max_new_tokens + 1)
         except RuntimeError:
             return None
-        se = _SessionSlotEngine(self.model, self.eng, rows, lens, slots, temps, top_ks, seeds, noises, eot_token, self.dev, top_ps)
-        return _mmu_batch_schedule(se, n, slots, max_new_tokens, eot_token)
+        se = _SessionSlotEngine(self.model, self.eng, rows, lens, slots, temps, top_ks, seeds, noises, eot_token, self.dev, top_ps,
+                                want_lp=return_logprobs)
+        out = _mmu_batch_schedule(se, n, slots, max_new_tokens, eot_token)
+        return (out, [se.logprobs(b, len(out[b])) for b in range(n)]) if return_logprobs else out
 
 
 class _SessionRecompute:
@@ -1336,10 +1486,25 @@ class _SessionRecompute:
         if len(toks) > 1:
             self.append(torch.tensor([toks[:-1]], dtype=torch.int64, device=self.dev), None, len(toks) - 1)
 
-    def run(self, max_new_tokens, greedy, k, temperature, noise, seed, eot_token, top_p=None):
+    def run(self, max_new_tokens, greedy, k, temperature, noise, seed, eot_token, top_p=None, return_logprobs=False):
         out = self.model._mmu_generate_recompute(None, self.emb, self.mask, max_new_tokens, temperature, 1 if greedy else k, eot_token,
-                                                 greedy, None if greedy else (k, seed, noise), top_p=top_p)
+                                                 greedy, None if greedy else (k, seed, noise), top_p=top_p, return_logprobs=return_logprobs)
+        if return_logprobs:
+            return [int(t) for t in out[0]], out[1]
         return [int(t) for t in out]
+
+    def score(self, ids, Ln, use_prefix_logits):
+        """_SessionEngine.score on the recompute path: the rows join the kept embeddings and mask, one forward scores them"""
+        L = self.emb.shape[1]
+        self.append(ids, None, Ln)
+        j0 = 0 if use_prefix_logits else 1
+        lp = torch.full((Ln,), float("nan"), dtype=torch.float32, device=self.dev)
+        rk = torch.full((Ln,), -1, dtype=torch.int32, device=self.dev)
+        if Ln > j0:
+            rows = torch.arange(L + j0 - 1, L + Ln - 1, dtype=torch.int32, device=self.dev)
+            a, b = self.model._score_rows(None, self.emb, self.mask, 1, L + Ln, rows, ids.reshape(-1)[j0:].contiguous(), None)
+            lp[j0:], rk[j0:] = a, b
+        return lp, rk
 
 
 class MmuSession:
@@ -1431,16 +1596,20 @@ class MmuSession:
 
     @torch.no_grad()
     def generate(self, idx=None, input_embeddings=None, max_new_tokens=100, temperature=1.0, top_k=None, eot_token=None, generator=None,
-                 _exp_noise=None, top_p=None):
+                 _exp_noise=None, top_p=None, return_logprobs=False):
         """Append the rows (ids [1, Ln] or embeddings [1, Ln, H]; none: continue where the last call stopped), then decode like
         `mmu_generate`: same return type, `eot_token` cut, greedy pick for top_k == 1 and sampled draws (`top_p`: nucleus).  Afterwards the cache holds the
-        prefix, the rows and the answer up to its last token but one; the last token is pending and is fed first by the next call."""
+        prefix, the rows and the answer up to its last token but one; the last token is pending and is fed first by the next call.
+        `return_logprobs=True`: `(tokens, logprobs)` as `mmu_generate` returns them."""
         self._check()
         ids, emb, Ln = self._rows(idx, input_embeddings)
         if Ln == 0 and self.length != self.prefix_length:
             raise ValueError("generate: no rows and no pending token to continue from")
         greedy, k, noise, seed, p = self._draw_args(max_new_tokens, temperature, top_k, generator, _exp_noise, top_p)
         nucleus = {} if p is None else {"top_p": p}  # an engine stand-in without the keyword still serves every call without top_p
+        if return_logprobs:
+            nucleus["return_logprobs"] = True
+        lps = None
         start = self.length
         try:
             if Ln:
@@ -1449,6 +1618,8 @@ class MmuSession:
             else:
                 self._be.use_prefix_logits()
             toks = self._be.run(max_new_tokens, greedy, k, temperature, noise, seed, eot_token, **nucleus)
+            if return_logprobs:
+                toks, lps = toks
             self._be.settle(self.length, toks)
         except BaseException:
             # a call that fails midway (a full cache inside the decode loop) leaves the session where it was: the rows it wrote are
@@ -1459,15 +1630,44 @@ class MmuSession:
             raise
         self.length += len(toks) - 1
         self._pending = toks[-1]
-        return [torch.tensor(t, device=self._be.dev) for t in toks]
+        out = [torch.tensor(t, device=self._be.dev) for t in toks]
+        return (out, lps) if return_logprobs else out
+
+    @torch.no_grad()
+    def score(self, idx):
+        """How probable the continuation `idx` (int64 [1, Ln]) is here: `TokenScores(logprobs, ranks)`, both [Ln], entry j the
+        log-probability / rank of idx[0, j] given the conversation so far and idx[0, :j] -- the pending token is fed first, as
+        `generate` feeds it.  A list of continuations is scored one after the other against the same state and returns a list.  The
+        session is left as it was (same length, same pending token): a following `generate` returns what it would have returned.
+        The rows run as an append (`showo_engine_prefill_append_score`), so the values agree with `generate(..., return_logprobs=True)`
+        to the precision's gate, not bit for bit, and a short append costs what DESIGN.md's "mmu sessions" records for it;
+        `Showo.score` on full prompts is the bulk path."""
+        self._check()
+        many = isinstance(idx, (list, tuple))
+        out = []
+        for t in (idx if many else [idx]):
+            if t.dim() != 2 or t.shape[0] != 1 or t.shape[1] < 1:
+                raise ValueError("score: a continuation is an int64 [1, Ln] tensor with Ln >= 1")
+            if self._pending is None and self.length != self.prefix_length:
+                raise ValueError("score: no pending token to continue from")
+            ids, _, Ln = self._rows(t, None)
+            j0 = 0 if self._pending is None else 1
+            try:
+                lp, rk = self._be.score(ids, Ln, self._pending is None)
+            finally:
+                if self._be.cached_rows() != self.length:
+                    self._be.rewind(self.length)
+            out.append(TokenScores(lp[j0:], rk[j0:]))
+        return out if many else out[0]
 
     @torch.no_grad()
     def generate_batch(self, idx=None, input_embeddings=None, max_new_tokens=100, temperature=1.0, top_k=None, eot_token=None,
-                       generator=None, _exp_noise=None, top_p=None):
+                       generator=None, _exp_noise=None, top_p=None, return_logprobs=False):
         """n continuations of the CURRENT state: `idx` / `input_embeddings` is a list of n row blocks ([1, Ln_i] ids or [1, Ln_i, H]
         embeddings), `temperature` / `top_k` / `top_p` scalars or lists, `_exp_noise` None or a list.  result[i] is what `generate(<block i>)`
         followed by a rewind returns when those calls are made in order (same seeds from `generator`); the session is left unchanged.
-        n >= 2 at precision 0, 2, 3 runs on the slots of a decode batch, each slot a fork of this cache."""
+        n >= 2 at precision 0, 2, 3 runs on the slots of a decode batch, each slot a fork of this cache.
+        `return_logprobs=True`: `(tokens, logprobs)`, logprobs a list of n fp32 device tensors."""
         self._check()
         seqs = idx if idx is not None else input_embeddings
         n = len(seqs)
@@ -1484,12 +1684,17 @@ class MmuSession:
             try:
                 return self.generate(idx=None if idx is None else idx[b], input_embeddings=None if input_embeddings is None else input_embeddings[b],
                                      max_new_tokens=max_new_tokens, temperature=temps[b], top_k=top_ks[b], eot_token=eot_token,
-                                     generator=generator, _exp_noise=noises[b], top_p=top_ps[b])
+                                     generator=generator, _exp_noise=noises[b], top_p=top_ps[b],
+                                     **({"return_logprobs": True} if return_logprobs else {}))
             finally:
                 self.rewind(mark)
 
+        def singles():
+            outs = [single(b) for b in range(n)]
+            return ([o[0] for o in outs], [o[1] for o in outs]) if return_logprobs else outs
+
         if n < 2 or not self._be.batched:
-            return [single(b) for b in range(n)]
+            return singles()
         if max_new_tokens < 1:
             raise ValueError("max_new_tokens must be >= 1")
         rows, lens = [], []
@@ -1508,11 +1713,16 @@ class MmuSession:
         dev = self._be.dev
         noises = [None if (k == 1 or z is None) else z.detach().float().contiguous().to(dev) for k, z in zip(top_ks, noises)]
         nucleus = {} if all(q is None for q in top_ps) else {"top_ps": top_ps}
+        if return_logprobs:
+            nucleus["return_logprobs"] = True
         out = self._be.run_batch(self.length, rows, lens, max_new_tokens, temps, top_ks, seeds, noises, eot_token, **nucleus)
         if out is None:  # the batch's common capacity does not fit the engine: the sequential calls, drawing the same seeds again
             if gen_state is not None:
                 generator.set_state(gen_state)
-            return [single(b) for b in range(n)]
+            return singles()
+        if return_logprobs:
+            out, lps = out
+            return [[torch.tensor(t, device=dev) for t in r] for r in out], lps
         return [[torch.tensor(t, device=dev) for t in r] for r in out]
 
 
@@ -1556,7 +1766,7 @@ def _dense_mask_of(attention_mask, L, device):
 
 
 def _mmu_generate_recompute(self, idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, greedy, sampling,
-                            top_p=None):
+                            top_p=None, return_logprobs=False):
     """Accuracy mode (`set_precision(1)`): the reference's OWN algorithm (models/modeling_showo.py:190-240) -- no KV cache, the whole
     sequence is run again for every token on the grown mask (new column hidden from the old rows, new row = last row + itself,
     :203-217) -- on the fp32-class engine path.  O(tokens x forward): a parity mode, not a serving mode."""
@@ -1574,7 +1784,7 @@ def _mmu_generate_recompute(self, idx, input_embeddings, attention_mask, max_new
     row = torch.empty((1,), dtype=torch.int32, device=dev)
     logits = torch.empty((self.vocab_size,), dtype=torch.float32, device=dev)
     tok = torch.empty((1,), dtype=torch.int64, device=dev)
-    result = []
+    result, lps = [], []
     for step in range(max_new_tokens):
         row.fill_(L - 1)
         _lib.call("showo_engine_forward_rows", eng, None, _lib.ptr(emb), _lib.ptr(mask), 1, L, _lib.ptr(row), 1, 0, self.vocab_size,
@@ -1584,6 +1794,8 @@ def _mmu_generate_recompute(self, idx, input_embeddings, attention_mask, max_new
         else:
             k, seed, noise = sampling
             _sample_call(logits, self.vocab_size, k, top_p, temperature, noise, seed, step, tok)
+        if return_logprobs:
+            lps.append(_logprob_of(logits, self.vocab_size, tok))
         t = int(tok.item())
         result.append(torch.tensor(t, device=dev))
         if eot_token is not None and t == eot_token:
@@ -1595,6 +1807,8 @@ def _mmu_generate_recompute(self, idx, input_embeddings, attention_mask, max_new
         mask = grown
         emb = torch.cat([emb, self.showo.model.embed_tokens.weight.detach().float()[tok].reshape(1, 1, -1)], dim=1).contiguous()
         L += 1
+    if return_logprobs:
+        return result, (torch.cat(lps) if lps else torch.empty((0,), dtype=torch.float32, device=dev))
     return result
 
 

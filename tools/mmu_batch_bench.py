@@ -10,6 +10,8 @@ against the sequential calls' (same generator seed).
                                                # (rocprofv3 --kernel-trace --stats -- python tools/mmu_batch_bench.py --profile)
   python tools/mmu_batch_bench.py --top-p 0.9  # cost of nucleus sampling: a sampled leg and the same leg with top_p, alternating in
                                                # this process, at batch 1 and n = 4 / 16: median and min / max tokens/s over --reps calls
+  python tools/mmu_batch_bench.py --logprobs   # cost of return_logprobs=True: every leg with and without it, alternating in this
+                                               # process, at batch 1 and n = 4 / 16, greedy and top_k=5: medians over --reps calls
 
 The slot count for n > 8 is set through modeling_showo._MMU_BATCH_SLOTS for this run only."""
 import argparse
@@ -96,14 +98,66 @@ def nucleus_legs(model, embs, masks, top_p, reps):
     return res
 
 
+def logprob_legs(model, embs, masks, reps):
+    """tokens/s of every leg without and with return_logprobs=True, measured alternately (off, on, off, on, ...) so that both see the
+    same clocks; per leg the median and the min / max of `reps` whole calls after one warm-up call each.  The tokens of the two legs
+    are checked to be equal.  per_token_us: the difference of the median call times over the tokens of the call (one scoring launch
+    per decode step and slot row; at n = 4 greedy the "on" leg also trades the all-greedy loop for the slot scheduler's)."""
+    gen = lambda: torch.Generator(device="cuda").manual_seed(7)  # noqa: E731
+
+    def call(n, kw):
+        if n == 1:
+            return lambda: model.mmu_generate(input_embeddings=embs[0], attention_mask=masks[0], max_new_tokens=NEW, generator=gen(), **kw)
+        return lambda: model.mmu_generate_batch(input_embeddings=embs[:n], attention_mask=masks[:n], max_new_tokens=NEW, generator=gen(), **kw)
+
+    def once(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    def ints(out, n):
+        return [int(t) for t in out] if n == 1 else [[int(t) for t in r] for r in out]
+
+    res = {"shape": "cfg4: 631-embedding w_clip_vit prompts, 100 new tokens each, full-size seeded weights",
+           "unit": "tokens/s (whole call)", "reps": reps}
+    for n in (1, 4, 16):
+        for name, kw in (("greedy", GREEDY), ("topk5_t0.7", SAMPLED)):
+            legs = {"off": call(n, kw), "on": call(n, dict(kw, return_logprobs=True))}
+            off, on = legs["off"](), legs["on"]()  # warm-up, and the feature changes no token
+            assert ints(off, n) == ints(on[0], n), (n, name)
+            times = {k: [] for k in legs}
+            for _ in range(reps):
+                for k, fn in legs.items():
+                    times[k].append(once(fn))
+            row = {}
+            for k, ts in times.items():
+                rate = sorted(n * NEW / t for t in ts)
+                row[k] = {"median": float(np.median(rate)), "min": rate[0], "max": rate[-1]}
+            row["logprobs_overhead_percent"] = 100.0 * (row["off"]["median"] / row["on"]["median"] - 1.0)
+            row["per_token_us"] = 1e6 * (float(np.median(times["on"])) - float(np.median(times["off"]))) / (n * NEW)
+            res[f"n{n}_{name}"] = row
+            print(f"n={n} {name}: {row}", file=sys.stderr, flush=True)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--profile", action="store_true")
     ap.add_argument("--top-p", type=float, default=None, help="measure nucleus sampling against the same sampled leg without it")
     ap.add_argument("--reps", type=int, default=7)
-    ap.add_argument("--out", default=None, help="also write the JSON of --top-p to this file")
+    ap.add_argument("--logprobs", action="store_true", help="measure return_logprobs=True against the same legs without it")
+    ap.add_argument("--out", default=None, help="also write the JSON of --top-p / --logprobs to this file")
     a = ap.parse_args()
-    pkg, model, embs, masks = build(4 if a.profile else (16 if a.top_p is not None else 32))
+    pkg, model, embs, masks = build(4 if a.profile else (16 if (a.top_p is not None or a.logprobs) else 32))
+    if a.logprobs:
+        res = logprob_legs(model, embs, masks, a.reps)
+        if a.out:
+            with open(a.out, "w") as f:
+                json.dump(res, f, indent=1)
+        print(json.dumps(res))
+        return
     if a.top_p is not None:
         res = nucleus_legs(model, embs, masks, a.top_p, a.reps)
         if a.out:
