@@ -129,6 +129,10 @@ int showo_gemm_counters(int64_t* out3, int reset);
  * most `polls` polls (default 32 768, ~2 ms; negative restores it), then the tile falls back to the last-arriver sum -- the same bits,
  * no abort.  0 makes every early block give up at once (test hook). */
 int showo_gemm_set_coop_polls(int polls);
+/* Store form of the fused projection's Q / K / V^T epilogue: 1 (default; negative restores it) = 16-byte stores, 0 = the narrow form
+ * (8-byte Q / K pieces, 2-byte V^T).  Same bytes at the same addresses either way: the A/B lever of tools/gemm_bench and the
+ * reference of tests/test_epilogue_stores_gpu.py.  SHOWO_GEMM_STAGE=4 selects 0 from the environment. */
+int showo_gemm_set_wide_stores(int on);
 
 /* Split-precision forms (VQGAN path): every operand is a (hi, lo) bf16 pair, x = hi + lo to ~2^-17; the MFMA
  * accumulates hi*hi + hi*lo + lo*hi in fp32.  fp32 output, optional residual.  Same layouts as the plain calls. */
@@ -297,6 +301,9 @@ int showo_mask_tokens(const int64_t* tokens, const float* noise, const int32_t* 
  * per 32 query rows, operands straight from L2), 2 = LDS-tiled form (4 waves share 64-key K / V^T tiles staged by
  * global_load_lds; 4 waves/SIMD, no register spill) */
 int showo_attn_set_impl(int impl);
+/* Output stores of the prefill / t2i attention forward: 1 (default; negative restores it) = 16-byte stores where ldo is a multiple of 8
+ * and O is 16-byte aligned, 0 = 8-byte stores always.  Same bytes either way (A/B lever, test reference; SHOWO_ATTN_WIDE=0). */
+int showo_attn_set_wide_stores(int on);
 /* AR decode step (one new token against the KV cache): 0 = fused layer, three launches (LN + qkv/fc1 GEMV; prep +
  * single-query attention with the fc2 GEMV co-scheduled on the CUs the 32 attention blocks leave idle (F = 8192 only);
  * dense GEMV + both residual adds; default), 1 = the general seven-launch layer, 2 = the fused layer as a plain chain

@@ -168,6 +168,7 @@ struct AttnArgs {
     // accuracy mode (attn_lds_body<SPLIT>): low halves of the operands (same layouts) and of the output
     const bf16_t *Qlo = nullptr, *Klo = nullptr, *Vtlo = nullptr;
     bf16_t* Olo = nullptr;
+    int wide = 0;  // host: 16-byte output stores (store_o_rows): ldo % 8 == 0 and O (and Olo) 16-byte aligned
 };
 
 // XCD-aware block order of the LDS-tiled forward.  Hardware places block `id` on XCD `id % 8`, each XCD has its own 4 MiB L2.  With
@@ -191,6 +192,26 @@ __device__ __forceinline__ void attn_block_coords(const AttnArgs& a, int& qb, in
     }
     b = bh / a.nH;
     head = bh - b * a.nH;
+}
+
+// Output rows of a 32-query fragment pair.  After packing, lane (qi, hh) holds dims 8g + 4hh + {0..3} of row qi in w[g] (g = 0..7: the
+// two 32-dim halves o0 | o1), i.e. every 16-byte group of a row is split over the two half-waves.  The narrow form stores the eight
+// 8-byte pieces as they are.  The wide form exchanges, per pair of groups (g, g + 1), the upper half-wave's group g with the lower
+// half-wave's group g + 1 (v_permlane32_swap, one per dword): lanes 0-31 then hold dims 8g..8g+7 and lanes 32-63 dims 8g+8..8g+15 --
+// four 16-byte stores per lane in place of eight 8-byte ones, same bytes, same addresses.  The store tail of this kernel is bound by
+// the number of store instructions, not by bytes.  Both half-waves of a row are active or inactive together.
+__device__ __forceinline__ void store_o_rows(bf16_t* row, int hh, const uint2 (&w)[8], bool wide, bool ok) {
+    if (wide) {
+#pragma unroll
+        for (int g = 0; g < 8; g += 2) {
+            const auto x = __builtin_amdgcn_permlane32_swap(w[g].x, w[g + 1].x, false, false);
+            const auto y = __builtin_amdgcn_permlane32_swap(w[g].y, w[g + 1].y, false, false);
+            if (ok) *reinterpret_cast<uint4*>(row + 8 * (g + hh)) = make_uint4(x[0], y[0], x[1], y[1]);
+        }
+    } else if (ok) {
+#pragma unroll
+        for (int g = 0; g < 8; ++g) *reinterpret_cast<uint2*>(row + 8 * g + 4 * hh) = w[g];
+    }
 }
 
 template <bool F16>
@@ -299,18 +320,16 @@ __global__ __launch_bounds__(256) void attn_fwd_kernel(AttnArgs a) {
     }
     float l_tot = l_run + __shfl_xor(l_run, 32, 64);
     float inv = 1.0f / l_tot;
-    if (qrow_raw < a.Lq) {
-        bf16_t* op = a.O + ((int64_t)b * a.Lq + qrow_raw) * a.ldo + head * 64 + 4 * hh;
+    {
+        uint2 w[8];
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            uint2 w0, w1;
-            w0.x = Op16<F16>::pack2(o0[4 * g] * inv, o0[4 * g + 1] * inv);
-            w0.y = Op16<F16>::pack2(o0[4 * g + 2] * inv, o0[4 * g + 3] * inv);
-            w1.x = Op16<F16>::pack2(o1[4 * g] * inv, o1[4 * g + 1] * inv);
-            w1.y = Op16<F16>::pack2(o1[4 * g + 2] * inv, o1[4 * g + 3] * inv);
-            *reinterpret_cast<uint2*>(op + 8 * g) = w0;        // d = 8g + 4hh + {0..3}
-            *reinterpret_cast<uint2*>(op + 32 + 8 * g) = w1;   // d = 32 + 8g + 4hh + {0..3}
+            w[g].x = Op16<F16>::pack2(o0[4 * g] * inv, o0[4 * g + 1] * inv);          // d = 8g + 4hh + {0..3}
+            w[g].y = Op16<F16>::pack2(o0[4 * g + 2] * inv, o0[4 * g + 3] * inv);
+            w[4 + g].x = Op16<F16>::pack2(o1[4 * g] * inv, o1[4 * g + 1] * inv);      // d = 32 + 8g + 4hh + {0..3}
+            w[4 + g].y = Op16<F16>::pack2(o1[4 * g + 2] * inv, o1[4 * g + 3] * inv);
         }
+        store_o_rows(a.O + ((int64_t)b * a.Lq + qrow) * a.ldo + head * 64, hh, w, a.wide != 0, qrow_raw < a.Lq);
     }
 }
 
@@ -564,28 +583,28 @@ __device__ __forceinline__ void attn_lds_body(const AttnArgs& a, bf16_t* sm, int
     float l_tot = l_run + __shfl_xor(l_run, 32, 64);
     float inv = 1.0f / l_tot;
     if (a.lse && hh == 0 && qrow_raw < a.Lq) a.lse[bh * a.Lq + qrow_raw] = m_run + __logf(l_tot);
-    if (qrow_raw < a.Lq) {
-        bf16_t* op = a.O + ((int64_t)b * a.Lq + qrow_raw) * a.ldo + head * 64 + 4 * hh;
+    {
+        const int64_t orow = ((int64_t)b * a.Lq + (qrow_raw < a.Lq ? qrow_raw : a.Lq - 1)) * a.ldo + head * 64;
+        uint2 w[8];
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
-            uint2 w0, w1;
-            w0.x = Op16<F16>::pack2(o0[4 * g] * inv, o0[4 * g + 1] * inv);
-            w0.y = Op16<F16>::pack2(o0[4 * g + 2] * inv, o0[4 * g + 3] * inv);
-            w1.x = Op16<F16>::pack2(o1[4 * g] * inv, o1[4 * g + 1] * inv);
-            w1.y = Op16<F16>::pack2(o1[4 * g + 2] * inv, o1[4 * g + 3] * inv);
-            *reinterpret_cast<uint2*>(op + 8 * g) = w0;
-            *reinterpret_cast<uint2*>(op + 32 + 8 * g) = w1;
-            if constexpr (SPLIT) {
-                bf16_t* ol = a.Olo + ((int64_t)b * a.Lq + qrow_raw) * a.ldo + head * 64 + 4 * hh;
-                uint2 l0, l1;
-                l0.x = cvt_pk_bf16<F16>(o0[4 * g] * inv - bf2f((bf16_t)(w0.x & 0xffffu)), o0[4 * g + 1] * inv - bf2f((bf16_t)(w0.x >> 16)));
-                l0.y = cvt_pk_bf16<F16>(o0[4 * g + 2] * inv - bf2f((bf16_t)(w0.y & 0xffffu)), o0[4 * g + 3] * inv - bf2f((bf16_t)(w0.y >> 16)));
-                l1.x = cvt_pk_bf16<F16>(o1[4 * g] * inv - bf2f((bf16_t)(w1.x & 0xffffu)), o1[4 * g + 1] * inv - bf2f((bf16_t)(w1.x >> 16)));
-                l1.y = cvt_pk_bf16<F16>(o1[4 * g + 2] * inv - bf2f((bf16_t)(w1.y & 0xffffu)), o1[4 * g + 3] * inv - bf2f((bf16_t)(w1.y >> 16)));
-                *reinterpret_cast<uint2*>(ol + 8 * g) = l0;
-                *reinterpret_cast<uint2*>(ol + 32 + 8 * g) = l1;
-            }
+            w[g].x = Op16<F16>::pack2(o0[4 * g] * inv, o0[4 * g + 1] * inv);
+            w[g].y = Op16<F16>::pack2(o0[4 * g + 2] * inv, o0[4 * g + 3] * inv);
+            w[4 + g].x = Op16<F16>::pack2(o1[4 * g] * inv, o1[4 * g + 1] * inv);
+            w[4 + g].y = Op16<F16>::pack2(o1[4 * g + 2] * inv, o1[4 * g + 3] * inv);
         }
+        if constexpr (SPLIT) {  // low halves first: they are computed from the unexchanged high halves
+            uint2 l[8];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                l[g].x = cvt_pk_bf16<F16>(o0[4 * g] * inv - bf2f((bf16_t)(w[g].x & 0xffffu)), o0[4 * g + 1] * inv - bf2f((bf16_t)(w[g].x >> 16)));
+                l[g].y = cvt_pk_bf16<F16>(o0[4 * g + 2] * inv - bf2f((bf16_t)(w[g].y & 0xffffu)), o0[4 * g + 3] * inv - bf2f((bf16_t)(w[g].y >> 16)));
+                l[4 + g].x = cvt_pk_bf16<F16>(o1[4 * g] * inv - bf2f((bf16_t)(w[4 + g].x & 0xffffu)), o1[4 * g + 1] * inv - bf2f((bf16_t)(w[4 + g].x >> 16)));
+                l[4 + g].y = cvt_pk_bf16<F16>(o1[4 * g + 2] * inv - bf2f((bf16_t)(w[4 + g].y & 0xffffu)), o1[4 * g + 3] * inv - bf2f((bf16_t)(w[4 + g].y >> 16)));
+            }
+            store_o_rows(a.Olo + orow, hh, l, a.wide != 0, qrow_raw < a.Lq);
+        }
+        store_o_rows(a.O + orow, hh, w, a.wide != 0, qrow_raw < a.Lq);
     }
 }
 
@@ -911,6 +930,16 @@ extern "C" int showo_mask_compress(const float* mask, int32_t* iv, int32_t* flag
     return 0;
 }
 static int g_attn_forced = -1;
+static int g_attn_wide = -1;  // 16-byte output stores of the forward: -1 = read SHOWO_ATTN_WIDE once (default on), 0 / 1 = forced
+
+extern "C" int showo_attn_set_wide_stores(int on) {
+    g_attn_wide = on < 0 ? 1 : (on != 0);
+    return 0;
+}
+static int attn_wide_ok(const void* O, const void* Olo, int ldo) {
+    if (g_attn_wide < 0) { const char* e = getenv("SHOWO_ATTN_WIDE"); g_attn_wide = e ? (atoi(e) != 0) : 1; }
+    return g_attn_wide && (ldo % 8) == 0 && ((reinterpret_cast<uintptr_t>(O) | reinterpret_cast<uintptr_t>(Olo)) & 15) == 0;
+}
 
 extern "C" int showo_attn_set_impl(int impl) {
     g_attn_forced = (impl >= 1 && impl <= 2) ? impl : 0;  // 1 gather, 2 LDS-tiled
@@ -937,6 +966,7 @@ static int attn_fwd_impl(const uint16_t* Q, const uint16_t* K, const uint16_t* V
     a.Q = Q; a.K = K; a.Vt = Vt; a.iv = iv; a.flag = flag; a.dense = dense_mask; a.O = O;
     a.B = B; a.nH = nH; a.Lq = Lq; a.Lk = Lk; a.Lcap = Lcap; a.Lp = Lp; a.ldo = ldo; a.lse = lse;
     a.pos_dev = (Lq == 1) ? g_decode_pos_dev : nullptr;
+    a.wide = attn_wide_ok(O, nullptr, ldo);
     int qblocks = (Lq + 31) / 32;
     ProfScope prof(PROF_ATTN, 4.0 * B * nH * (double)Lq * Lk * 64, (hipStream_t)stream);  // dense QK^T + PV flops
     if (g_attn_forced < 0) { const char* e = getenv("SHOWO_ATTN_IMPL"); g_attn_forced = e ? atoi(e) : 0; }
@@ -992,6 +1022,7 @@ extern "C" int showo_attn_fwd_split(const uint16_t* Q, const uint16_t* Qlo, cons
     a.Q = Q; a.K = K; a.Vt = Vt; a.iv = iv; a.flag = flag; a.dense = dense_mask; a.O = O;
     a.B = B; a.nH = nH; a.Lq = Lq; a.Lk = Lk; a.Lcap = Lcap; a.Lp = Lp; a.ldo = ldo; a.lse = nullptr; a.pos_dev = nullptr;
     a.Qlo = Qlo; a.Klo = Klo; a.Vtlo = Vtlo; a.Olo = Olo;
+    a.wide = attn_wide_ok(O, Olo, ldo);
     const int qblocks = (Lq + 31) / 32, nqb = (qblocks + 3) / 4;
     ProfScope prof(PROF_ATTN, 3.0 * 4.0 * B * nH * (double)Lq * Lk * 64, (hipStream_t)stream);  // executed flops: three products
     static bool attr_set = false;

@@ -171,6 +171,7 @@ int g_gemm_gn = 4;  // n-panels per XCD tile group (same-process sweep on the be
 int g_gemm_bm = 0;  // 0 = read SHOWO_GEMM_BM once; -1 = choose per shape; a variant code = force it
 int g_gemm_splitk = -1;  // SHOWO_GEMM_SPLITK: 0 = off, 1 (default) = launches with <= 128 tiles split K until ~256 blocks exist
 int g_gemm_stage = -1;  // bf16 epilogue stores staged through LDS: -1 = read SHOWO_GEMM_STAGE once (default on), 0 / 1 = forced
+int g_gemm_wide = -1;   // Q / K / V^T stores of the projection epilogue: 0 = the narrow form (8-byte Q / K, 2-byte V^T: A/B runs, tests), else 16-byte (showo_gemm_set_wide_stores)
 int g_gemm_pf = -1; // L2 prefetch of the weight panel: -1 = read SHOWO_GEMM_PF once (default OFF: measured -3...-8 % in the harness
                     // with cold weights and within noise in the pipeline, profiles/r2_gemm_harness.txt), 0 / 1 = forced (showo_gemm_tune)
 
@@ -324,8 +325,19 @@ int gemm2p_dispatch(GemmArgs g, int epilogue, hipStream_t s) {
     if (epilogue == EPI_QKV && g.raw && g.pre) g_cnt_qkv_save++;
     g.gn = g_gemm_gn > 0 ? g_gemm_gn : 1;
     if (g_gemm_pf < 0) { const char* e = getenv("SHOWO_GEMM_PF"); g_gemm_pf = e ? (atoi(e) != 0) : 0; }
-    if (g_gemm_stage < 0) { const char* e = getenv("SHOWO_GEMM_STAGE"); g_gemm_stage = e ? atoi(e) : 1; }
-    g.flags = (g_gemm_pf ? 2 : 0) | (g_gemm_stage ? 0 : 8) | (g_gemm_stage == 2 ? 32 : 0) | (g_gemm_stage == 3 ? 64 : 0);  // SHOWO_GEMM_STAGE: 0 direct stores, 1 (default) staged except Q / K, 2 all, 3 = 1 with V^T direct
+    if (g_gemm_stage < 0) {  // SHOWO_GEMM_STAGE: 0 direct stores, 1 (default) staged except Q / K, 2 all, 3 = 1 with V^T direct, 4 = 1 with the narrow Q / K / V^T stores
+        const char* e = getenv("SHOWO_GEMM_STAGE");
+        g_gemm_stage = e ? atoi(e) : 1;
+        if (g_gemm_stage == 4) { g_gemm_stage = 1; if (g_gemm_wide < 0) g_gemm_wide = 0; }
+    }
+    g.flags = (g_gemm_pf ? 2 : 0) | (g_gemm_stage ? 0 : 8) | (g_gemm_stage == 2 ? 32 : 0) | (g_gemm_stage == 3 ? 64 : 0);
+    if (epilogue == EPI_QKV && g_gemm_wide != 0) {
+        // 16-byte Q / K / V^T stores of the projection epilogue (qkv_head_rows): every row of Q and K is 128 bytes and Lp is a multiple
+        // of 64, so the base addresses decide.  Bit 8: the same for the raw rows of the save form.
+        auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+        if (g.Q && al16(g.Q) && al16(g.Kd) && al16(g.Vt) && (g.Lp % 8) == 0) g.flags |= 128;
+        if (g.Q && g.raw && al16(g.raw) && (g.ldraw % 8) == 0) g.flags |= 256;
+    }
     g.dbg = nullptr;
     g.coop_polls = g_gemm_coop_polls;
     if (g.op && epilogue == EPI_QKV && (g.raw || g.pre)) return set_error_msg(1, "gemm: the save-for-backward projection has bf16 operands only");
@@ -344,6 +356,14 @@ int gemm2p_dispatch(GemmArgs g, int epilogue, hipStream_t s) {
 extern "C" int showo_gemm_set_coop_polls(int polls) {
     std::lock_guard<std::mutex> lock(showo::g_gemm_mu);
     showo::g_gemm_coop_polls = polls < 0 ? (1 << 15) : polls;
+    return 0;
+}
+
+// A/B lever and test reference of the projection epilogue's store forms: 0 = the narrow stores (8-byte Q / K pieces, 2-byte V^T), 1 = the
+// 16-byte stores, < 0 = the default (16-byte).  Both forms write the same bytes to the same addresses.
+extern "C" int showo_gemm_set_wide_stores(int on) {
+    std::lock_guard<std::mutex> lock(showo::g_gemm_mu);
+    showo::g_gemm_wide = on < 0 ? 1 : (on != 0);
     return 0;
 }
 

@@ -292,13 +292,242 @@ static __device__ __forceinline__ void splitk_coop_finish(const GemmArgs& g, f32
     }
 }
 
+// Pairs the 8-byte pieces of two neighbouring 16x16 C fragments (a = fragment i, b = fragment i + 1 of one token row: this lane's
+// dims 16i + 4fg + {0..3} and 16(i+1) + 4fg + {0..3}) into ONE 16-byte piece per lane.  v_permlane16_swap exchanges the odd 16-lane
+// rows of its first operand with the even rows of its second, so afterwards (a.x, a.y, b.x, b.y) is 8 CONSECUTIVE dims: of fragment
+// i in the even-fg lanes, of fragment i + 1 in the odd-fg lanes, at dim 16 (i + (fg & 1)) + 8 (fg >> 1) -- two uint4 stores per pair
+// where there were four uint2 stores (the 16x16 analogue of the 32x32 half exchange: the store tail is bound by the number of store
+// instructions, not by bytes).  The four lanes of a token are all active or all inactive wherever this is called.
+static __device__ __forceinline__ uint4 pair_frags16(uint2 a, uint2 b) {
+    const auto x = __builtin_amdgcn_permlane16_swap(a.x, b.x, false, false);
+    const auto y = __builtin_amdgcn_permlane16_swap(a.y, b.y, false, false);
+    return make_uint4(x[0], y[0], x[1], y[1]);
+}
+
+// row stride (elements) of the transposed V staging image of a wave tile.  MF <= 6: a multiple of 8 with room for the position
+// alignment of two token segments (below); 2 VRS dwords = 16 (2 MF + 3) = 16 mod 32, so the four fg groups of a transposed write land
+// on two bank groups (two-way, as with the former 16 MF + 2).  Taller tiles keep 16 MF + 2 (MF 7) / 128 (MF 8) and the 2-byte stores.
+template <int MF>
+constexpr int vt_stage_stride() { return MF <= 6 ? 16 * MF + 24 : (MF < 8 ? 16 * MF + 2 : 128); }
+
+// q / k / v columns of the fused projection (EPI_QKV with Q / K / V^T outputs): bias, per-head q / k LayerNorm(64), partial RoPE, 1/8
+// folded into Q and the head-major relayout, for the wave's 64 columns (one head of q, k or v) x 16 MF rows.  FULL: every row of the
+// wave tile lies inside M (all but the last m-tile of a launch), so no store carries a row predicate.
+template <int MF, bool F16, bool FULL>
+static __device__ __forceinline__ void qkv_head_rows(const GemmArgs& g, f32x4 (&acc)[4][8], int nbase, int mrow0, int fr, int fg,
+                                                      bf16_t* stg_qk, bf16_t* stg_v) {
+    const int lane_ = fg * 16 + fr;
+    constexpr int VRS = vt_stage_stride<MF>();
+    const int rrow = lane_ >> 3, rchunk = lane_ & 7;
+    const bool wide = (g.flags & 128) != 0;      // 16-byte Q / K / V^T stores (host: the three bases are 16-byte aligned)
+    const bool wide_raw = (g.flags & 256) != 0;  // the same for the raw rows of the save form
+    const int pdim = (fg & 1) * 16 + (fg >> 1) * 8;  // first dim of this lane's 16-byte piece inside a fragment pair (pair_frags16)
+    const int Hq = g.nH * 64;
+    const int which = nbase / Hq;  // 0 = q, 1 = k, 2 = v (wave-uniform)
+    const int head = (nbase - which * Hq) >> 6;
+    // V^T, position-aligned staging (wave-uniform geometry).  The wave tile's valid tokens t in [0, tend) are one or two runs of
+    // consecutive positions (segments: the tail of sequence b0 from l0, then sequence b0 + 1 from 0, split at token tb).  Token t of
+    // segment s is staged at image column t + sh_s with sh_s chosen so that column = position (mod 8) and segment 1 starts in a fresh
+    // 16-byte chunk (column c1): every 16-byte chunk of an image row is then a 16-byte-aligned chunk of V^T[bh][d][.].
+    const int tend = (FULL ? mrow0 + 16 * MF : min(mrow0 + 16 * MF, g.M)) - mrow0;
+    const int b0 = mrow0 / g.L, l0 = mrow0 - b0 * g.L, tb = g.L - l0;
+    const int sh0 = (g.pos0 + l0) & 7, c1 = (tb + sh0 + 7) & ~7, sh1 = c1 + (g.pos0 & 7) - tb;
+    // more than two segments in the tile (L < 16 MF), a tile taller than the slice allows, or an empty tile: the 2-byte form
+    const bool vwide = wide && MF <= 6 && stg_v != nullptr && tend > 0 && tb + g.L >= tend;
+    float bn[4][4], lw[4][4], lb[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        load_bias4(g, nbase + i * 16 + fg * 4, bn[i]);
+        if (which < 2) {
+            const float4 w4 = *reinterpret_cast<const float4*>((which ? g.kw : g.qw) + i * 16 + fg * 4);
+            const float4 b4 = *reinterpret_cast<const float4*>((which ? g.kb : g.qb) + i * 16 + fg * 4);
+            lw[i][0] = w4.x; lw[i][1] = w4.y; lw[i][2] = w4.z; lw[i][3] = w4.w;
+            lb[i][0] = b4.x; lb[i][1] = b4.y; lb[i][2] = b4.z; lb[i][3] = b4.w;
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < MF; ++j) {
+        const int m = mrow0 + j * 16 + fr;
+        const bool valid = FULL || m < g.M;
+        const int mm = valid ? m : g.M - 1;
+        const int b = mm / g.L, l = mm - b * g.L, pos = g.pos0 + l;
+        const int64_t bh = (int64_t)b * g.nH + head;
+        float x[4][4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) x[i][r] = acc[i][j][r] + bn[i][r];
+        if (g.raw) {  // training forward: save bf16(qkv) for backward and continue from the rounded values
+            uint2 pk[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                pk[i].x = Op16<F16>::pack2(x[i][0], x[i][1]);
+                pk[i].y = Op16<F16>::pack2(x[i][2], x[i][3]);
+                x[i][0] = Op16<F16>::lo_of(pk[i].x); x[i][1] = Op16<F16>::hi_of(pk[i].x);
+                x[i][2] = Op16<F16>::lo_of(pk[i].y); x[i][3] = Op16<F16>::hi_of(pk[i].y);
+            }
+            bf16_t* rp = g.raw + (int64_t)mm * g.ldraw + nbase;
+            if (wide_raw) {
+#pragma unroll
+                for (int i = 0; i < 4; i += 2) {
+                    const uint4 v = pair_frags16(pk[i], pk[i + 1]);
+                    if (valid) *reinterpret_cast<uint4*>(rp + i * 16 + pdim) = v;
+                }
+            } else if (valid) {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) *reinterpret_cast<uint2*>(rp + i * 16 + fg * 4) = pk[i];
+            }
+        }
+        if (which == 2) {  // V^T[bh][d][pos]
+            if (stg_v) {  // staged transposed: [d][token] in the wave's LDS slice, stored below with the lanes along `pos`
+                const int t = j * 16 + fr;
+                const int col = vwide ? t + (t < tb ? sh0 : sh1) : t;
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) stg_v[(i * 16 + fg * 4 + r) * VRS + col] = Op16<F16>::cvt(x[i][r]);
+            } else if (valid) {
+                bf16_t* vp = g.Vt + bh * 64 * g.Lp + pos;
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) vp[(int64_t)(i * 16 + fg * 4 + r) * g.Lp] = Op16<F16>::cvt(x[i][r]);
+            }
+            continue;
+        }
+        float sum = 0.f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) sum += (x[i][0] + x[i][1]) + (x[i][2] + x[i][3]);
+        sum = sum4_lanes16(sum);
+        const float mean = sum * (1.0f / 64.0f);
+        float sq = 0.f;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) { x[i][r] -= mean; sq += x[i][r] * x[i][r]; }
+        sq = sum4_lanes16(sq);
+        const float rstd = 1.0f / sqrtf(sq * (1.0f / 64.0f) + g.eps);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) x[i][r] = x[i][r] * rstd * lw[i][r] + lb[i][r];
+        // partial rotary over dims [0, 32): rotate_half pairs d with d + 16 = fragments i = 0 and 1 of this lane
+        const float4 c0 = *reinterpret_cast<const float4*>(g.cosT + (int64_t)pos * 32 + fg * 4);
+        const float4 s0 = *reinterpret_cast<const float4*>(g.sinT + (int64_t)pos * 32 + fg * 4);
+        const float4 c1r = *reinterpret_cast<const float4*>(g.cosT + (int64_t)pos * 32 + 16 + fg * 4);
+        const float4 s1r = *reinterpret_cast<const float4*>(g.sinT + (int64_t)pos * 32 + 16 + fg * 4);
+        const float cc0[4] = {c0.x, c0.y, c0.z, c0.w}, ss0[4] = {s0.x, s0.y, s0.z, s0.w};
+        const float cc1[4] = {c1r.x, c1r.y, c1r.z, c1r.w}, ss1[4] = {s1r.x, s1r.y, s1r.z, s1r.w};
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float y0 = x[0][r], y1 = x[1][r];
+            x[0][r] = y0 * cc0[r] - y1 * ss0[r];
+            x[1][r] = y1 * cc1[r] + y0 * ss1[r];
+        }
+        const float sc = which == 0 ? 0.125f : 1.0f;  // 1/sqrt(64) folded into Q (exact in bf16)
+        uint2 pk[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            pk[i].x = Op16<F16>::pack2(x[i][0] * sc, x[i][1] * sc);
+            pk[i].y = Op16<F16>::pack2(x[i][2] * sc, x[i][3] * sc);
+        }
+        if (stg_qk) {  // staged: the token's 64 values go to row j * 16 + fr of the wave's slice, stored as full 128-B rows below
+#pragma unroll
+            for (int i = 0; i < 4; ++i) stage_frag_bf16(stg_qk, j * 16 + fr, i, fg, pk[i]);
+            continue;
+        }
+        bf16_t* dst = which == 0 ? g.Q + (bh * g.L + l) * 64 : g.Kd + (bh * g.Lcap + pos) * 64;
+        if (wide) {  // two 16-byte stores per token row and lane
+#pragma unroll
+            for (int i = 0; i < 4; i += 2) {
+                const uint4 v = pair_frags16(pk[i], pk[i + 1]);
+                if (valid) *reinterpret_cast<uint4*>(dst + i * 16 + pdim) = v;
+            }
+        } else if (valid) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) *reinterpret_cast<uint2*>(dst + i * 16 + fg * 4) = pk[i];
+        }
+    }
+    if (stg_v && which == 2 && vwide) {
+        // V^T rows are contiguous along `pos`.  The image is position-aligned (above), so its 16-byte chunks go out whole: 16 lanes
+        // along the chunks of an image row, 4 rows (head dims) per instruction, 16 instructions for the 64 dims.  A chunk that a
+        // segment covers only in part -- the first and the last chunk of a segment: the columns next to it belong to the cached text
+        // rows or to tokens that another wave or block stores at the same time -- is written afterwards, 2 bytes per lane, and only
+        // inside the segment.
+        constexpr int NCH = VRS / 8;
+        const int64_t hrow = (int64_t)64 * g.Lp;
+        // segment s: image columns [slo, shi] (empty if shi < slo); V^T column = image column + sdel (a multiple of 8)
+        const int slo[2] = {sh0, c1 + (g.pos0 & 7)};
+        const int shi[2] = {min(tb, tend) - 1 + sh0, tend - 1 + sh1};
+        const int sdel[2] = {g.pos0 + l0 - sh0, g.pos0 - tb - sh1};
+        {
+            const int ch = lane_ & 15, dsub = lane_ >> 4;
+            const int s = ch * 8 >= c1 ? 1 : 0;
+            const bool whole = ch < NCH && slo[s] <= ch * 8 && ch * 8 + 7 <= shi[s];
+            const bf16_t* src = stg_v + dsub * VRS + ch * 8;
+            bf16_t* dstv = g.Vt + ((int64_t)(b0 + s) * g.nH + head) * hrow + (int64_t)dsub * g.Lp + sdel[s] + ch * 8;
+            if (whole) {
+#pragma unroll
+                for (int it = 0; it < 16; ++it)
+                    *reinterpret_cast<uint4*>(dstv + (int64_t)(it * 4) * g.Lp) = *reinterpret_cast<const uint4*>(src + it * 4 * VRS);
+            }
+        }
+        const int el = lane_ & 7, d8 = lane_ >> 3;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int s = e >> 1;
+            if (shi[s] < slo[s]) continue;  // (wave-uniform, as is everything up to `col`)
+            const int cf = slo[s] >> 3, cl = shi[s] >> 3;
+            const int ck = (e & 1) ? cl : cf;
+            if ((e & 1) && cl == cf) continue;                           // the segment's only chunk: done as its first
+            if (slo[s] <= ck * 8 && ck * 8 + 7 <= shi[s]) continue;      // whole: stored above
+            const int col = ck * 8 + el;
+            if (col < slo[s] || col > shi[s]) continue;
+            const bf16_t* src = stg_v + d8 * VRS + col;
+            bf16_t* dstv = g.Vt + ((int64_t)(b0 + s) * g.nH + head) * hrow + (int64_t)d8 * g.Lp + sdel[s] + col;
+#pragma unroll
+            for (int it = 0; it < 8; ++it) dstv[(int64_t)(it * 8) * g.Lp] = src[it * 8 * VRS];
+        }
+    } else if (stg_v && which == 2) {
+        // 2-byte form: the lanes along the tile's tokens, one store instruction = up to 64 consecutive positions of ONE head dimension
+        bf16_t* vb[2];
+        bool vok[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int mt = h * 64 + lane_, m = mrow0 + mt;
+            vok[h] = mt < 16 * MF && m < g.M;
+            const int mm = vok[h] ? m : 0;
+            const int b = mm / g.L, l = mm - b * g.L;
+            vb[h] = g.Vt + ((int64_t)b * g.nH + head) * 64 * g.Lp + g.pos0 + l;
+        }
+#pragma unroll 8
+        for (int dd = 0; dd < 64; ++dd) {
+#pragma unroll
+            for (int h = 0; h < 2; ++h)
+                if (h * 64 < 16 * MF && vok[h]) vb[h][(int64_t)dd * g.Lp] = stg_v[dd * VRS + h * 64 + lane_];
+        }
+    }
+    if (stg_qk && which < 2) {  // one (token, head) row = 128 B contiguous in Q / K: a wave instruction stores 8 of them
+#pragma unroll
+        for (int t = 0; t < 2 * MF; ++t) {
+            const int row = t * 8 + rrow, m = mrow0 + row;
+            const uint4 v = unstage_row16(stg_qk, row, rchunk);
+            if (m < g.M) {
+                const int b = m / g.L, l = m - b * g.L;
+                const int64_t bh = (int64_t)b * g.nH + head;
+                bf16_t* dst = which == 0 ? g.Q + (bh * g.L + l) * 64 : g.Kd + (bh * g.Lcap + g.pos0 + l) * 64;
+                *reinterpret_cast<uint4*>(dst + rchunk * 8) = v;
+            }
+        }
+    }
+}
+
 // epilogue of the 256-wide phase-split kernels: the wave holds 4 (n) x MF (m) 16x16 fragments; mrow0 = first row of
 // the wave's m range, n0 + wn*64 = its first column.
 template <int EPI, int MF, bool F16 = false>
 static __device__ __forceinline__ void epilogue8p(const GemmArgs& g, f32x4 (&acc)[4][8], int n0, int wn, int mrow0, int fr, int fg,
                                                    bf16_t* stg = nullptr) {  // stg: this wave's 16 KiB LDS slice (or nullptr: direct stores)
     const int lane_ = fg * 16 + fr;
-    constexpr int VRS = MF < 8 ? 16 * MF + 2 : 128;  // row stride (elements) of the transposed V staging image: +2 breaks the 4-way bank conflict
     const int rrow = lane_ >> 3, rchunk = lane_ & 7;  // read-back role: row inside an 8-row group, 16-B chunk of the 128-B row
     // Q / K rows keep their direct stores unless flags bit 5 is set: staging them measured -3...-5 % on the fused projection (the
     // per-token LayerNorm / RoPE math, not the stores, dominates those tiles; profiles/r2_gemm_harness.txt, r2n)
@@ -396,142 +625,9 @@ static __device__ __forceinline__ void epilogue8p(const GemmArgs& g, f32x4 (&acc
                 }
             }
         } else if (nbase < g.N) {
-            const int Hq = g.nH * 64;
-            const int which = nbase / Hq;  // 0 = q, 1 = k, 2 = v (wave-uniform)
-            const int head = (nbase - which * Hq) >> 6;
-            float bn[4][4], lw[4][4], lb[4][4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                load_bias4(g, nbase + i * 16 + fg * 4, bn[i]);
-                if (which < 2) {
-                    const float4 w4 = *reinterpret_cast<const float4*>((which ? g.kw : g.qw) + i * 16 + fg * 4);
-                    const float4 b4 = *reinterpret_cast<const float4*>((which ? g.kb : g.qb) + i * 16 + fg * 4);
-                    lw[i][0] = w4.x; lw[i][1] = w4.y; lw[i][2] = w4.z; lw[i][3] = w4.w;
-                    lb[i][0] = b4.x; lb[i][1] = b4.y; lb[i][2] = b4.z; lb[i][3] = b4.w;
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < MF; ++j) {
-                const int m = mrow0 + j * 16 + fr;
-                const bool valid = m < g.M;
-                const int mm = valid ? m : g.M - 1;
-                const int b = mm / g.L, l = mm - b * g.L, pos = g.pos0 + l;
-                const int64_t bh = (int64_t)b * g.nH + head;
-                float x[4][4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) x[i][r] = acc[i][j][r] + bn[i][r];
-                if (g.raw) {  // training forward: save bf16(qkv) for backward and continue from the rounded values
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        uint2 pk;
-                        pk.x = Op16<F16>::pack2(x[i][0], x[i][1]);
-                        pk.y = Op16<F16>::pack2(x[i][2], x[i][3]);
-                        x[i][0] = Op16<F16>::lo_of(pk.x); x[i][1] = Op16<F16>::hi_of(pk.x);
-                        x[i][2] = Op16<F16>::lo_of(pk.y); x[i][3] = Op16<F16>::hi_of(pk.y);
-                        if (valid) *reinterpret_cast<uint2*>(g.raw + (int64_t)m * g.ldraw + nbase + i * 16 + fg * 4) = pk;
-                    }
-                }
-                if (which == 2) {  // V^T[bh][d][pos]
-                    if (stg_v) {  // staged transposed: [d][token] in the wave's LDS slice, stored below with the lanes along `pos`
-#pragma unroll
-                        for (int i = 0; i < 4; ++i)
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) stg_v[(i * 16 + fg * 4 + r) * VRS + j * 16 + fr] = Op16<F16>::cvt(x[i][r]);
-                    } else if (valid) {
-                        bf16_t* vp = g.Vt + bh * 64 * g.Lp + pos;
-#pragma unroll
-                        for (int i = 0; i < 4; ++i)
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) vp[(int64_t)(i * 16 + fg * 4 + r) * g.Lp] = Op16<F16>::cvt(x[i][r]);
-                    }
-                    continue;
-                }
-                float sum = 0.f;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) sum += (x[i][0] + x[i][1]) + (x[i][2] + x[i][3]);
-                sum = sum4_lanes16(sum);
-                const float mean = sum * (1.0f / 64.0f);
-                float sq = 0.f;
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) { x[i][r] -= mean; sq += x[i][r] * x[i][r]; }
-                sq = sum4_lanes16(sq);
-                const float rstd = 1.0f / sqrtf(sq * (1.0f / 64.0f) + g.eps);
-#pragma unroll
-                for (int i = 0; i < 4; ++i)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) x[i][r] = x[i][r] * rstd * lw[i][r] + lb[i][r];
-                // partial rotary over dims [0, 32): rotate_half pairs d with d + 16 = fragments i = 0 and 1 of this lane
-                const float4 c0 = *reinterpret_cast<const float4*>(g.cosT + (int64_t)pos * 32 + fg * 4);
-                const float4 s0 = *reinterpret_cast<const float4*>(g.sinT + (int64_t)pos * 32 + fg * 4);
-                const float4 c1 = *reinterpret_cast<const float4*>(g.cosT + (int64_t)pos * 32 + 16 + fg * 4);
-                const float4 s1 = *reinterpret_cast<const float4*>(g.sinT + (int64_t)pos * 32 + 16 + fg * 4);
-                const float cc0[4] = {c0.x, c0.y, c0.z, c0.w}, ss0[4] = {s0.x, s0.y, s0.z, s0.w};
-                const float cc1[4] = {c1.x, c1.y, c1.z, c1.w}, ss1[4] = {s1.x, s1.y, s1.z, s1.w};
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float y0 = x[0][r], y1 = x[1][r];
-                    x[0][r] = y0 * cc0[r] - y1 * ss0[r];
-                    x[1][r] = y1 * cc1[r] + y0 * ss1[r];
-                }
-                const float sc = which == 0 ? 0.125f : 1.0f;  // 1/sqrt(64) folded into Q (exact in bf16)
-                if (stg_qk) {  // staged: the token's 64 values go to row j * 16 + fr of the wave's slice, stored as full 128-B rows below
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        uint2 pk;
-                        pk.x = Op16<F16>::pack2(x[i][0] * sc, x[i][1] * sc);
-                        pk.y = Op16<F16>::pack2(x[i][2] * sc, x[i][3] * sc);
-                        stage_frag_bf16(stg_qk, j * 16 + fr, i, fg, pk);
-                    }
-                    continue;
-                }
-                if (!valid) continue;
-                bf16_t* dst = which == 0 ? g.Q + (bh * g.L + l) * 64 : g.Kd + (bh * g.Lcap + pos) * 64;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    uint2 pk;
-                    pk.x = Op16<F16>::pack2(x[i][0] * sc, x[i][1] * sc);
-                    pk.y = Op16<F16>::pack2(x[i][2] * sc, x[i][3] * sc);
-                    *reinterpret_cast<uint2*>(dst + i * 16 + fg * 4) = pk;
-                }
-            }
-            if (stg_v && which == 2) {
-                // V^T rows are contiguous along `pos`: with the lanes along the tile's tokens one store instruction writes up to 64
-                // consecutive positions of ONE head dimension (1-2 lines) instead of one position of 64 dimensions (64 lines).
-                // `pos` starts at an odd offset in the t2i loop (129 text rows), so the stores stay 2 bytes wide.
-                bf16_t* vb[2];
-                bool vok[2];
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    const int mt = h * 64 + lane_, m = mrow0 + mt;
-                    vok[h] = mt < 16 * MF && m < g.M;
-                    const int mm = vok[h] ? m : 0;
-                    const int b = mm / g.L, l = mm - b * g.L;
-                    vb[h] = g.Vt + ((int64_t)b * g.nH + head) * 64 * g.Lp + g.pos0 + l;
-                }
-#pragma unroll 8
-                for (int dd = 0; dd < 64; ++dd) {
-#pragma unroll
-                    for (int h = 0; h < 2; ++h)
-                        if (h * 64 < 16 * MF && vok[h]) vb[h][(int64_t)dd * g.Lp] = stg_v[dd * VRS + h * 64 + lane_];
-                }
-            }
-            if (stg_qk && which < 2) {  // one (token, head) row = 128 B contiguous in Q / K: a wave instruction stores 8 of them
-#pragma unroll
-                for (int t = 0; t < 2 * MF; ++t) {
-                    const int row = t * 8 + rrow, m = mrow0 + row;
-                    const uint4 v = unstage_row16(stg_qk, row, rchunk);
-                    if (m < g.M) {
-                        const int b = m / g.L, l = m - b * g.L;
-                        const int64_t bh = (int64_t)b * g.nH + head;
-                        bf16_t* dst = which == 0 ? g.Q + (bh * g.L + l) * 64 : g.Kd + (bh * g.Lcap + g.pos0 + l) * 64;
-                        *reinterpret_cast<uint4*>(dst + rchunk * 8) = v;
-                    }
-                }
-            }
+            // block-uniform: all but the last m-tile of a launch lie wholly inside M and take the form without row predicates
+            if (mrow0 + 16 * MF <= g.M) qkv_head_rows<MF, F16, true>(g, acc, nbase, mrow0, fr, fg, stg_qk, stg_v);
+            else qkv_head_rows<MF, F16, false>(g, acc, nbase, mrow0, fr, fg, stg_qk, stg_v);
         }
     } else {
         if constexpr (EPI == SHOWO_EPI_BF16 || EPI == SHOWO_EPI_GELU_BF16) {

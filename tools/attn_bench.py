@@ -1,9 +1,10 @@
 """Micro-benchmark of the prefill / t2i attention launch at the shape the 18-step t2i loop runs it (BASELINE cfg2 with prefix reuse:
 B = 16 CFG-doubled rows, 32 heads, 258 query rows <soi> + 256 image tokens + <eoi>, 387 keys; per-row visibility interval as
 synthetic.t2i_inputs builds it: conditional rows see their 2..37 text tokens + the image block, unconditional rows the image block).
-usage: python tools/attn_bench.py [--variants 0,1,2] [--reps 200] [--op 0|1] [--B 16 --Lq 258 --Lk 387]
+usage: python tools/attn_bench.py [--variants 0,1,2] [--wide 0,1] [--reps 200] [--op 0|1] [--B 16 --Lq 258 --Lk 387]
 Prints us per launch and TF/s (4 B nH Lq Lk 64 flops) per implementation (showo_attn_set_impl: 0 = by shape, 1 = gather form,
-2 = LDS-tiled, 3 = LDS-tiled at 3 waves / SIMD), and the max |difference| of every implementation's output against the first."""
+2 = LDS-tiled, 3 = LDS-tiled at 3 waves / SIMD) and output store form (--wide, showo_attn_set_wide_stores: 1 = 16-byte stores, the
+default; 0 = 8-byte stores), and the max |difference| of every run's output against the first."""
 import argparse
 import os
 import sys
@@ -19,6 +20,7 @@ L = showo_amd._lib
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--variants", default="0")
+    ap.add_argument("--wide", default="1", help="output store forms to time, e.g. 0,1,0,1")
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--op", type=int, default=0)
     ap.add_argument("--B", type=int, default=16)
@@ -53,8 +55,9 @@ def main():
 
     flops = 4.0 * B * nH * Lq * Lk * 64
     ref = None
-    for v in [int(x) for x in a.variants.split(",")]:
+    for w, v in [(int(w), int(x)) for w in a.wide.split(",") for x in a.variants.split(",")]:
         L.call("showo_attn_set_impl", v)
+        L.call("showo_attn_set_wide_stores", w)
         O.zero_()
         launch()
         torch.cuda.synchronize()
@@ -63,7 +66,7 @@ def main():
             ref = out
         diff = float((out - ref).abs().max())
         if a.once:
-            print(f"variant {v}: one launch; max |o - o_variant0| = {diff:.3e}")
+            print(f"variant {v} wide {w}: one launch; max |o - o_variant0| = {diff:.3e}")
             continue
         for _ in range(300):  # steady state (clocks, L2 / Infinity-Cache contents): the first ~100 launches of a process run 8-10 % slower
             launch()
@@ -76,8 +79,9 @@ def main():
             e1.record()
             torch.cuda.synchronize()
             best = min(best, e0.elapsed_time(e1) / a.reps * 1e3)
-        print(f"variant {v}: {best:7.2f} us per launch = {flops / best / 1e6:6.1f} TF/s; max |o - o_variant0| = {diff:.3e} (|o| max {float(ref.abs().max()):.2f})")
+        print(f"variant {v} wide {w}: {best:7.2f} us per launch = {flops / best / 1e6:6.1f} TF/s; max |o - o_variant0| = {diff:.3e} (|o| max {float(ref.abs().max()):.2f})")
     L.call("showo_attn_set_impl", 0)
+    L.call("showo_attn_set_wide_stores", -1)
 
 
 if __name__ == "__main__":

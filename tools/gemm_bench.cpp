@@ -284,7 +284,10 @@ int main(int argc, char** argv) {
 
     // ---- fused entry points: K-concatenated residual GEMM and the [Wqkv ; W1] projection, checked against the separate launches
     if (quick != 3 && quick != 4 && quick < 7) for (int M : {4128, 6192, 700}) {
-        const int H = 2048, F = 8192, nH = 32, B = M == 700 ? 2 : 16, L = M / B, Lp = ((L + 63) / 64) * 64;
+        // GEMM_BENCH_POS0: first position of the projected rows (129 = the t2i loop behind its cached text rows; default 0).  The narrow
+        // Q / K / V^T stores of the projection epilogue are selected by SHOWO_GEMM_STAGE=4 (A/B of the 16-byte stores).
+        const int P0 = getenv("GEMM_BENCH_POS0") ? atoi(getenv("GEMM_BENCH_POS0")) : 0;
+        const int H = 2048, F = 8192, nH = 32, B = M == 700 ? 2 : 16, L = M / B, Lc = P0 + L, Lp = ((Lc + 63) / 64) * 64;
         const int Mx = B * L;
         uint16_t *attn, *ffn, *Wd, *W2, *Wcat, *h, *Wq1, *Q0, *K0, *V0, *Q1, *K1, *V1, *f0, *f1;
         float *x0, *x1, *bd, *b2, *bsum, *bq1, *lnp, *cosT, *sinT;
@@ -347,8 +350,9 @@ int main(int argc, char** argv) {
         const int Nq = 3 * H;
         CK(hipMalloc(&h, (size_t)Mx * H * 2)); CK(hipMalloc(&Wq1, (size_t)RW * (Nq + F) * H * 2)); CK(hipMalloc(&bq1, (Nq + F) * 4));
         CK(hipMalloc(&lnp, 4 * 64 * 4)); CK(hipMalloc(&cosT, 2048 * 32 * 4)); CK(hipMalloc(&sinT, 2048 * 32 * 4));
-        const size_t nqk = (size_t)B * nH * L * 64, nvt = (size_t)B * nH * 64 * Lp;
-        CK(hipMalloc(&Q0, nqk * 2)); CK(hipMalloc(&K0, nqk * 2)); CK(hipMalloc(&V0, nvt * 2)); CK(hipMalloc(&Q1, nqk * 2)); CK(hipMalloc(&K1, nqk * 2)); CK(hipMalloc(&V1, nvt * 2));
+        const size_t nqk = (size_t)B * nH * L * 64, nkk = (size_t)B * nH * Lc * 64, nvt = (size_t)B * nH * 64 * Lp;
+        CK(hipMalloc(&Q0, nqk * 2)); CK(hipMalloc(&K0, nkk * 2)); CK(hipMalloc(&V0, nvt * 2)); CK(hipMalloc(&Q1, nqk * 2)); CK(hipMalloc(&K1, nkk * 2)); CK(hipMalloc(&V1, nvt * 2));
+        CK(hipMemsetAsync(K0, 0, nkk * 2, st)); CK(hipMemsetAsync(K1, 0, nkk * 2, st));
         CK(hipMalloc(&f0, (size_t)Mx * F * 2)); CK(hipMalloc(&f1, (size_t)Mx * F * 2));
         fill_kernel<<<1024, 256, 0, st>>>(h, (size_t)Mx * H, 21u, 1.0f);
         fill_kernel<<<1024, 256, 0, st>>>(Wq1, (size_t)(Nq + F) * H, 22u, 0.02f);
@@ -367,15 +371,15 @@ int main(int argc, char** argv) {
         for (int v : vars) for (int gn : gns) {
             RC(showo_gemm_tune(gn, (v << 8) | 4, nullptr));
             CK(hipMemsetAsync(V0, 0, nvt * 2, st)); CK(hipMemsetAsync(V1, 0, nvt * 2, st));
-            RC(showo_gemm_qkv_bf16(h, H, Wq1, H, bq1, lnp, lnp + 64, lnp + 128, lnp + 192, cosT, sinT, Q0, K0, V0, B, L, nH, 32, 1e-5f, 0, L, Lp, st));
+            RC(showo_gemm_qkv_bf16(h, H, Wq1, H, bq1, lnp, lnp + 64, lnp + 128, lnp + 192, cosT, sinT, Q0, K0, V0, B, L, nH, 32, 1e-5f, P0, Lc, Lp, st));
             RC(showo_gemm_bf16(h, H, Wq1 + (size_t)Nq * H, H, bq1 + Nq, 0, f0, F, nullptr, 0, Mx, F, H, 1, st));
-            RC(showo_gemm_qkv_fc1_bf16(h, H, Wq, H, bq1, lnp, lnp + 64, lnp + 128, lnp + 192, cosT, sinT, Q1, K1, V1, f1, F, F, B, L, nH, 32, 1e-5f, 0, L, Lp, tl, st));
+            RC(showo_gemm_qkv_fc1_bf16(h, H, Wq, H, bq1, lnp, lnp + 64, lnp + 128, lnp + 192, cosT, sinT, Q1, K1, V1, f1, F, F, B, L, nH, 32, 1e-5f, P0, Lc, Lp, tl, st));
             CK(hipStreamSynchronize(st));
             auto same = [&](const uint16_t* a, const uint16_t* b, size_t n) { std::vector<uint16_t> x(n), y(n); CK(hipMemcpy(x.data(), a, n * 2, hipMemcpyDeviceToHost)); CK(hipMemcpy(y.data(), b, n * 2, hipMemcpyDeviceToHost)); return memcmp(x.data(), y.data(), n * 2) == 0; };
-            const bool ok = same(Q0, Q1, nqk) && same(K0, K1, nqk) && same(V0, V1, nvt) && same(f0, f1, (size_t)Mx * F);
+            const bool ok = same(Q0, Q1, nqk) && same(K0, K1, nkk) && same(V0, V1, nvt) && same(f0, f1, (size_t)Mx * F);
             const int iters = 10;
             CK(hipEventRecord(e0, st));
-            for (int i = 0; i < iters; ++i) RC(showo_gemm_qkv_fc1_bf16(h, H, Wq + (size_t)(i % RW) * qstride, H, bq1, lnp, lnp + 64, lnp + 128, lnp + 192, cosT, sinT, Q1, K1, V1, f1, F, F, B, L, nH, 32, 1e-5f, 0, L, Lp, tl, st));
+            for (int i = 0; i < iters; ++i) RC(showo_gemm_qkv_fc1_bf16(h, H, Wq + (size_t)(i % RW) * qstride, H, bq1, lnp, lnp + 64, lnp + 128, lnp + 192, cosT, sinT, Q1, K1, V1, f1, F, F, B, L, nH, 32, 1e-5f, P0, Lc, Lp, tl, st));
             CK(hipEventRecord(e1, st)); CK(hipEventSynchronize(e1));
             float ms; CK(hipEventElapsedTime(&ms, e0, e1));
             printf(" %d/gn%d:%.0fTF%s", v, gn, 2.0 * Mx * (Nq + F) * H * iters / (ms * 1e-3) / 1e12, ok ? "" : "**MISMATCH**");
@@ -389,7 +393,7 @@ int main(int argc, char** argv) {
                                              for (int rep = 0; rep < 3; ++rep) { CK(hipEventRecord(e0, st)); for (int i = 0; i < 40; ++i) fn(i);
                                                  CK(hipEventRecord(e1, st)); CK(hipEventSynchronize(e1)); float m_; CK(hipEventElapsedTime(&m_, e0, e1)); best = std::min(best, m_ * 1000.f / 40); }
                                              return best; };
-                const float tq = t_us([&](int i) { RC(showo_gemm_qkv_bf16(h, H, Wq1 + (size_t)(i % RW) * qstride, H, bq1, lnp, lnp + 64, lnp + 128, lnp + 192, cosT, sinT, Q1, K1, V1, B, L, nH, 32, 1e-5f, 0, L, Lp, st)); });
+                const float tq = t_us([&](int i) { RC(showo_gemm_qkv_bf16(h, H, Wq1 + (size_t)(i % RW) * qstride, H, bq1, lnp, lnp + 64, lnp + 128, lnp + 192, cosT, sinT, Q1, K1, V1, B, L, nH, 32, 1e-5f, P0, Lc, Lp, st)); });
                 const float tqp = t_us([&](int i) { RC(showo_gemm_bf16(h, H, Wq1 + (size_t)(i % RW) * qstride, H, bq1, 0, f1, Nq, nullptr, 0, Mx, Nq, H, 0, st)); });
                 const float tf = t_us([&](int i) { RC(showo_gemm_bf16(h, H, Wq1 + (size_t)(i % RW) * qstride + (size_t)Nq * H, H, bq1 + Nq, 0, f1, F, nullptr, 0, Mx, F, H, 1, st)); });
                 const float tfp = t_us([&](int i) { RC(showo_gemm_bf16(h, H, Wq1 + (size_t)(i % RW) * qstride + (size_t)Nq * H, H, bq1 + Nq, 0, f1, F, nullptr, 0, Mx, F, H, 0, st)); });
