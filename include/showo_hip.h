@@ -133,6 +133,12 @@ int showo_gemm_set_coop_polls(int polls);
  * (8-byte Q / K pieces, 2-byte V^T).  Same bytes at the same addresses either way: the A/B lever of tools/gemm_bench and the
  * reference of tests/test_epilogue_stores_gpu.py.  SHOWO_GEMM_STAGE=4 selects 0 from the environment. */
 int showo_gemm_set_wide_stores(int on);
+/* Residual epilogue (SHOWO_EPI_RESID_F32) of the production GEMM family: 1 (default; negative restores it) = a wave tile that lies inside
+ * M and N issues the residual loads of a group of fragments back to back, waits, adds and stores the group; 0 = one load, add and
+ * store per fragment.  Needs 16-byte aligned out / resid rows and no per-row bias (otherwise the per-fragment form runs).  The same
+ * additions on the same values either way: the A/B lever of tools/gemm_bench and the reference of tests/test_resid_epilogue_gpu.py.
+ * SHOWO_GEMM_RESID_BATCH=0 selects 0 from the environment. */
+int showo_gemm_set_resid_batch(int on);
 
 /* Split-precision forms (VQGAN path): every operand is a (hi, lo) bf16 pair, x = hi + lo to ~2^-17; the MFMA
  * accumulates hi*hi + hi*lo + lo*hi in fp32.  fp32 output, optional residual.  Same layouts as the plain calls. */

@@ -172,6 +172,7 @@ int g_gemm_bm = 0;  // 0 = read SHOWO_GEMM_BM once; -1 = choose per shape; a var
 int g_gemm_splitk = -1;  // SHOWO_GEMM_SPLITK: 0 = off, 1 (default) = launches with <= 128 tiles split K until ~256 blocks exist
 int g_gemm_stage = -1;  // bf16 epilogue stores staged through LDS: -1 = read SHOWO_GEMM_STAGE once (default on), 0 / 1 = forced
 int g_gemm_wide = -1;   // Q / K / V^T stores of the projection epilogue: 0 = the narrow form (8-byte Q / K, 2-byte V^T: A/B runs, tests), else 16-byte (showo_gemm_set_wide_stores)
+int g_gemm_resid_batch = -1;  // residual epilogue of full wave tiles: -1 = read SHOWO_GEMM_RESID_BATCH once (default on), 0 = one load / add / store per fragment (A/B runs, tests), else the residual loads of a fragment group back to back (showo_gemm_set_resid_batch)
 int g_gemm_pf = -1; // L2 prefetch of the weight panel: -1 = read SHOWO_GEMM_PF once (default OFF: measured -3...-8 % in the harness
                     // with cold weights and within noise in the pipeline, profiles/r2_gemm_harness.txt), 0 / 1 = forced (showo_gemm_tune)
 
@@ -338,6 +339,10 @@ int gemm2p_dispatch(GemmArgs g, int epilogue, hipStream_t s) {
         if (g.Q && al16(g.Q) && al16(g.Kd) && al16(g.Vt) && (g.Lp % 8) == 0) g.flags |= 128;
         if (g.Q && g.raw && al16(g.raw) && (g.ldraw % 8) == 0) g.flags |= 256;
     }
+    if (g_gemm_resid_batch < 0) { const char* e = getenv("SHOWO_GEMM_RESID_BATCH"); g_gemm_resid_batch = e ? (atoi(e) != 0) : 1; }
+    // batched residual loads (gemm_common.h resid_tile_batched): vec_out already says that out, resid and both leading dimensions allow
+    // 16-byte access; the kernel adds the per-tile condition (the wave tile inside M and N)
+    if (epilogue == SHOWO_EPI_RESID_F32 && g_gemm_resid_batch && g.vec_out && !g.bias_per_row && g.resid) g.flags |= 512;
     g.dbg = nullptr;
     g.coop_polls = g_gemm_coop_polls;
     if (g.op && epilogue == EPI_QKV && (g.raw || g.pre)) return set_error_msg(1, "gemm: the save-for-backward projection has bf16 operands only");
@@ -364,6 +369,15 @@ extern "C" int showo_gemm_set_coop_polls(int polls) {
 extern "C" int showo_gemm_set_wide_stores(int on) {
     std::lock_guard<std::mutex> lock(showo::g_gemm_mu);
     showo::g_gemm_wide = on < 0 ? 1 : (on != 0);
+    return 0;
+}
+
+// A/B lever and test reference of the residual epilogue: 0 = one residual load, add and store per fragment, 1 = the loads of a fragment
+// group issued back to back (full wave tiles of 16-byte aligned launches only), < 0 = the default (1).  Same additions on the same
+// values either way.
+extern "C" int showo_gemm_set_resid_batch(int on) {
+    std::lock_guard<std::mutex> lock(showo::g_gemm_mu);
+    showo::g_gemm_resid_batch = on < 0 ? 1 : (on != 0);
     return 0;
 }
 

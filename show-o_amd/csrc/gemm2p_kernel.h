@@ -276,6 +276,9 @@ __global__ __launch_bounds__(512) void gemm2p_kernel(GemmArgs g) {
     __shared__ int s_last;
     __shared__ int s_ml[2];  // splitk_coop_finish's mode / last-arriver flags: shared by BOTH wave groups
     constexpr int NFS = 4 * (MF0 > MF1 ? MF0 : MF1);
+    // residual epilogue: one fragment column per load group up to 6 + 6 fragments; the taller tiles keep the per-fragment form (a group
+    // of 7-8 loads next to their k-loop's registers costs 200-400 bytes of scratch)
+    constexpr int RGI = MF0 <= 6 ? 1 : 0;
     if (MF0 == MF1 || wm == 0) {
         Q2_RUN(MF0);
         if (wm == 0) bar_raw_fn();  // re-align the barrier counts of the two groups
@@ -284,7 +287,7 @@ __global__ __launch_bounds__(512) void gemm2p_kernel(GemmArgs g) {
         }
         if (g.splits > 1 && !splitk_exchange<MF0, NFS>(g, acc, tm * tilesN + tn, split, &s_last)) return;
         if constexpr (EPI == EPI_QKV_SPLIT) epilogue_qkv_split<MF0>(g, acc, n0, wn, m0 + gbase, fr, fg, g_stage ? smem + wave * 8192 : nullptr);
-        else epilogue8p<EPI, MF0, F16>(g, acc, n0, wn, m0 + gbase, fr, fg, g_stage ? smem + wave * 8192 : nullptr);
+        else epilogue8p<EPI, MF0, F16, RGI>(g, acc, n0, wn, m0 + gbase, fr, fg, g_stage ? smem + wave * 8192 : nullptr);
     } else {
         Q2_RUN(MF1);
         if constexpr (EPI != EPI_QKV && EPI != EPI_QKV_SPLIT) {
@@ -292,7 +295,7 @@ __global__ __launch_bounds__(512) void gemm2p_kernel(GemmArgs g) {
         }
         if (g.splits > 1 && !splitk_exchange<MF1, NFS>(g, acc, tm * tilesN + tn, split, &s_last)) return;
         if constexpr (EPI == EPI_QKV_SPLIT) epilogue_qkv_split<MF1>(g, acc, n0, wn, m0 + gbase, fr, fg, g_stage ? smem + wave * 8192 : nullptr);
-        else epilogue8p<EPI, MF1, F16>(g, acc, n0, wn, m0 + gbase, fr, fg, g_stage ? smem + wave * 8192 : nullptr);
+        else epilogue8p<EPI, MF1, F16, RGI>(g, acc, n0, wn, m0 + gbase, fr, fg, g_stage ? smem + wave * 8192 : nullptr);
     }
 #undef Q2_RUN
     asm volatile("" ::"v"(pfreg));  // keeps the prefetch destination register reserved for the whole loop

@@ -522,9 +522,49 @@ static __device__ __forceinline__ void qkv_head_rows(const GemmArgs& g, f32x4 (&
     }
 }
 
+// Residual epilogue (SHOWO_EPI_RESID_F32) of a wave tile that lies wholly inside M and N, with 16-byte aligned rows (flags bit 9,
+// set by the host: vec_out, no per-row bias).  store_frag loads one float4 of the residual, adds and stores, fragment by fragment;
+// out and resid may be the same buffer (the engine's residual stream is updated in place), so the compiler keeps every load behind
+// the store in front of it and a wave walks 4 MF dependent round trips (load, vmcnt(0) -- which also drains the earlier store --
+// add, store).  Here the residual loads of a GROUP of fragments are issued back to back ahead of the group's first store; nothing
+// orders them among themselves, so the loads of a group are in flight together and the stores follow without a load between them.
+// A lane reads exactly the elements it later writes, so out == resid stays legal.  Same additions on the same values: same bits.
+// Group = GI fragment columns x MF rows, chosen by the kernel (epilogue8p's RGI) as the largest that leaves every instance without
+// new scratch at two waves per SIMD: the whole wave tile (GI = 4, up to 96 residual registers next to 96 accumulators) in the n-split
+// ring kernels, one column in the m-split ring kernels and in gemm2p up to 6 + 6 fragments.
+template <int MF, int GI>
+static __device__ __forceinline__ void resid_tile_batched(const GemmArgs& g, f32x4 (&acc)[4][8], int nbase, int mrow0, int fr, int fg) {
+    static_assert(GI == 1 || GI == 2 || GI == 4, "fragment columns per group");
+    const float* rs = g.resid + (int64_t)(mrow0 + fr) * g.ldr + nbase + fg * 4;
+    float* o = reinterpret_cast<float*>(g.out) + (int64_t)(mrow0 + fr) * g.ldo + nbase + fg * 4;
+    float bn[4][4];  // all four columns' bias ahead of the first store, for the same reason
+#pragma unroll
+    for (int i = 0; i < 4; ++i) load_bias4(g, nbase + i * 16 + fg * 4, bn[i]);
+#pragma unroll
+    for (int i0 = 0; i0 < 4; i0 += GI) {
+        float4 rv[GI][MF];
+#pragma unroll
+        for (int i = 0; i < GI; ++i)
+#pragma unroll
+            for (int j = 0; j < MF; ++j) rv[i][j] = *reinterpret_cast<const float4*>(rs + (int64_t)(j * 16) * g.ldr + (i0 + i) * 16);
+#pragma unroll
+        for (int i = 0; i < GI; ++i) {
+#pragma unroll
+            for (int j = 0; j < MF; ++j) {
+                float v[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) v[r] = acc[i0 + i][j][r] + bn[i0 + i][r] + 0.f;  // store_frag's expression (bias per row = 0)
+                v[0] += rv[i][j].x; v[1] += rv[i][j].y; v[2] += rv[i][j].z; v[3] += rv[i][j].w;
+                *reinterpret_cast<float4*>(o + (int64_t)(j * 16) * g.ldo + (i0 + i) * 16) = make_float4(v[0], v[1], v[2], v[3]);
+            }
+        }
+    }
+}
+
 // epilogue of the 256-wide phase-split kernels: the wave holds 4 (n) x MF (m) 16x16 fragments; mrow0 = first row of
 // the wave's m range, n0 + wn*64 = its first column.
-template <int EPI, int MF, bool F16 = false>
+// RGI: fragment columns per load group of the batched residual epilogue (resid_tile_batched; 0 = the per-fragment form only)
+template <int EPI, int MF, bool F16 = false, int RGI = 0>
 static __device__ __forceinline__ void epilogue8p(const GemmArgs& g, f32x4 (&acc)[4][8], int n0, int wn, int mrow0, int fr, int fg,
                                                    bf16_t* stg = nullptr) {  // stg: this wave's 16 KiB LDS slice (or nullptr: direct stores)
     const int lane_ = fg * 16 + fr;
@@ -658,6 +698,13 @@ static __device__ __forceinline__ void epilogue8p(const GemmArgs& g, f32x4 (&acc
                     const uint4 v = unstage_row16(stg, row, rchunk);
                     if (m < g.M && n < g.N) *reinterpret_cast<uint4*>(o + (int64_t)m * g.ldo + n) = v;
                 }
+                return;
+            }
+        }
+        if constexpr (EPI == SHOWO_EPI_RESID_F32 && RGI > 0) {
+            // wave-uniform: the wave tile inside M and N (all but the last m-tile and a ragged last n-tile of a launch)
+            if ((g.flags & 512) && mrow0 + 16 * MF <= g.M && n0 + wn * 64 + 64 <= g.N) {
+                resid_tile_batched<MF, RGI>(g, acc, n0 + wn * 64, mrow0, fr, fg);
                 return;
             }
         }

@@ -152,6 +152,57 @@ int main(int argc, char** argv) {
             }
         return 0;
     }
+    if (quick == 9) {  // residual epilogue, batched loads (showo_gemm_set_resid_batch 1) against the per-fragment form (0), alternating in one
+                       // process: the dense|fc2 launch (N 2048, K 2048 + 8192) at the t2i loop's 4128 rows and step 0's 6192 rows, in place like
+                       // the engine.  us per launch, best of 3 x 40; gap = residual epilogue - plain fp32 epilogue of the same GEMM (the yardstick)
+        std::vector<int> vars = {4160};
+        if (const char* e = getenv("GEMM_BENCH_VARS")) { vars.clear(); std::string t(e); size_t p0 = 0; while (p0 < t.size()) { size_t q = t.find(',', p0); if (q == std::string::npos) q = t.size(); vars.push_back(atoi(t.substr(p0, q - p0).c_str())); p0 = q + 1; } }
+        const int H = 2048, F = 8192, K = H + F, RW = 8;
+        for (int M : {4128, 6192}) {
+            uint16_t *A, *W; float *bias, *x, *x0, *o0, *o1;
+            const size_t nO = (size_t)M * H;
+            CK(hipMalloc(&A, (size_t)M * K * 2)); CK(hipMalloc(&W, (size_t)RW * H * K * 2)); CK(hipMalloc(&bias, H * 4));
+            CK(hipMalloc(&x, nO * 4)); CK(hipMalloc(&x0, nO * 4)); CK(hipMalloc(&o0, nO * 4)); CK(hipMalloc(&o1, nO * 4));
+            fill_kernel<<<1024, 256, 0, st>>>(A, (size_t)M * K, 31u, 1.0f);
+            fill_kernel<<<1024, 256, 0, st>>>(W, (size_t)H * K, 32u, 0.02f);
+            for (int r = 1; r < RW; ++r) CK(hipMemcpyAsync(W + (size_t)r * H * K, W, (size_t)H * K * 2, hipMemcpyDeviceToDevice, st));
+            std::vector<float> hb(H), hx(nO);
+            for (int i = 0; i < H; ++i) hb[i] = 0.01f * ((i * 37) % 101 - 50);
+            for (size_t i = 0; i < nO; ++i) hx[i] = 0.001f * (float)((i * 2654435761u) % 2001) - 1.0f;
+            CK(hipMemcpy(bias, hb.data(), H * 4, hipMemcpyHostToDevice)); CK(hipMemcpy(x0, hx.data(), nO * 4, hipMemcpyHostToDevice));
+            auto t_us = [&](auto&& fn) { float best = 1e30f; for (int i = 0; i < 4; ++i) fn(i);
+                                         for (int rep = 0; rep < 3; ++rep) { CK(hipEventRecord(e0, st)); for (int i = 0; i < 40; ++i) fn(i);
+                                             CK(hipEventRecord(e1, st)); CK(hipEventSynchronize(e1)); float m_; CK(hipEventElapsedTime(&m_, e0, e1)); best = std::min(best, m_ * 1000.f / 40); }
+                                         return best; };
+            RC(showo_gemm_set_impl(0));
+            for (int v : vars) {
+                RC(showo_gemm_tune(8, (v << 8) | 4, nullptr));
+                // bits: both forms from the same residual, out of place
+                RC(showo_gemm_set_resid_batch(0)); RC(showo_gemm_bf16(A, K, W, K, bias, 0, o0, H, x0, H, M, H, K, 3, st));
+                RC(showo_gemm_set_resid_batch(1)); RC(showo_gemm_bf16(A, K, W, K, bias, 0, o1, H, x0, H, M, H, K, 3, st));
+                CK(hipStreamSynchronize(st));
+                std::vector<float> h0(nO), h1(nO);
+                CK(hipMemcpy(h0.data(), o0, nO * 4, hipMemcpyDeviceToHost)); CK(hipMemcpy(h1.data(), o1, nO * 4, hipMemcpyDeviceToHost));
+                const bool same = memcmp(h0.data(), h1.data(), nO * 4) == 0;
+                printf("dense|fc2 M=%d N=%d K=%d variant %d: bits old == new: %s\n", M, H, K, v, same ? "yes" : "**MISMATCH**");
+                for (int round = 0; round < 2; ++round)
+                    for (int batch : {0, 1}) {
+                        RC(showo_gemm_set_resid_batch(batch));
+                        CK(hipMemcpyAsync(x, x0, nO * 4, hipMemcpyDeviceToDevice, st));
+                        const float tr = t_us([&](int i) { RC(showo_gemm_bf16(A, K, W + (size_t)(i % RW) * H * K, K, bias, 0, x, H, x, H, M, H, K, 3, st)); });
+                        CK(hipMemcpyAsync(x, x0, nO * 4, hipMemcpyDeviceToDevice, st));
+                        const float tk = t_us([&](int i) { RC(showo_gemm_kcat_bf16(A, K, H, A + H, K, F, W + (size_t)(i % RW) * H * K, K, bias, x, H, x, H, M, H, 3, 0, st)); });
+                        const float tp = t_us([&](int i) { RC(showo_gemm_bf16(A, K, W + (size_t)(i % RW) * H * K, K, bias, 0, o0, H, nullptr, 0, M, H, K, 2, st)); });
+                        printf("  %s run %d [us: resid-epi %.1f (kcat entry %.1f) plain %.1f gap %.1f]\n", batch ? "new" : "old", round + 1, tr, tk, tp, tr - tp);
+                        fflush(stdout);
+                    }
+            }
+            RC(showo_gemm_set_resid_batch(-1));
+            for (void* p : {(void*)A, (void*)W, (void*)bias, (void*)x, (void*)x0, (void*)o0, (void*)o1}) CK(hipFree(p));
+        }
+        RC(showo_gemm_tune(8, 2, nullptr));
+        return 0;
+    }
     if (quick == 5) {  // weight-gradient shapes: showo_gemm_tn_bf16 on token-major operands vs two transposes + the k-contiguous GEMM
         struct TS { int M, N, T; const char* name; };
         const TS ts[] = {{256, 256, 200, "edge 1 tile"}, {264, 520, 1000, "edge ragged"}, {512, 768, 2100, "split-K"}, {2048, 8192, 11223, "dW2"},
