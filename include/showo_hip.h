@@ -325,8 +325,10 @@ int showo_decode_set_impl(int impl);
  * SHOWO_DECODE_PF_DENSE / SHOWO_DECODE_PF_BLOCKS.  Takes effect at the next decode call (its graph is captured per call). */
 int showo_decode_set_prefetch(int next_mb, int dense, int blocks);
 /* Grid knobs of the decode launches for sweeps in one process (defaults <- environment): name in
- * { "co_blocks", "batch_co_blocks", "batch_ln_blocks", "ln_blocks", "out_blocks" }.  Results never depend on them (every grid walks
- * the output columns with a stride; each column is reduced by one wave in one fixed order). */
+ * { "co_blocks", "batch_co_blocks", "batch_ln_blocks", "ln_blocks", "out_blocks", "wide_ln_blocks", "wide_out_ksplit" }.  Results
+ * never depend on the grid caps (every grid walks the output columns with a stride; each column is reduced by one wave in one fixed
+ * order).  "wide_out_ksplit" (1..8, wide batches only) is the number of blocks that share a column group's K range: it fixes the
+ * order of the fp32 additions, so results are deterministic for a given value and may differ in the last bits between values. */
 int showo_decode_set_tuning(const char* name, int value);
 int showo_attn_fwd(const uint16_t* Q, const uint16_t* K, const uint16_t* Vt, const int32_t* iv, const int32_t* flag,
                    const float* dense_mask, uint16_t* O, int B, int nH, int Lq, int Lk, int Lcap, int Lp, int ldo,
@@ -653,6 +655,24 @@ int showo_engine_decode_greedy(showo_engine* e, int64_t* tok, int n_steps, int64
  *     out_tokens int64 [nb, n_steps], logits_ws fp32 [nb, vocab]; every sequence advances n_steps tokens (the caller cuts at <eot>);
  *     one hipGraph replay per step with the nb positions in device memory.  Precision 0 (bf16) or 2 (fp16 operands). */
 int showo_engine_batch_begin(showo_engine* e, int nb, int cap_tokens);
+/* Wide decode batch (opt-in; csrc/decode_wide.hip): showo_engine_batch_begin for 1 <= nb <= 32 sequences at precision 0, and the batch's
+ * decode steps run two MFMA skinny GEMMs per layer (16 sequences per v_mfma_f32_16x16x32_bf16 column block) instead of one dot2
+ * chain per sequence.  Every other showo_engine_batch_* entry serves a wide batch unchanged.  Contract of a wide batch: results are
+ * deterministic, and a sequence's tokens, logits and log-probabilities do not depend on nb, on its slot or on the other slots
+ * (an MFMA output column reads only its own sequence; the K order is fixed) -- but they are NOT the bits of the batch-1 run: same
+ * rounding points (16-bit LayerNorm output, qkv, gelu(fc1), attention output; fp32 accumulators, residual, logits), another fp32
+ * summation order.  Precision != 0 is refused here and by the decode entries. */
+int showo_engine_batch_begin_wide(showo_engine* e, int nb, int cap_tokens);
+/* The two kernels of the wide step alone (test hooks; arguments as ln_gemvB / out_gemvB take them, nb = 1..32 rows):
+ *   ln_gemm:  h = LayerNorm(x [nb, H] fp32) as bf16 (the bits of showo_layernorm_f32_op16); out0 [nb, ld0] = bf16(W0 h + b0) or, when
+ *             outf is given, outf [nb, ld0] = fp32(W0 h + b0); out1 [nb, ld1] = bf16(gelu_new(W1 h + b1)) (N1 = 0: absent).
+ *             H <= 2048, H % 32 == 0, N0 % 16 == 0 when N1 > 0.
+ *   out_gemm: x [nb, N] fp32 += (Wd attn + bd) + (W2 ffn + b2), attn [nb, K0] / ffn [nb, K1] bf16, K0 % 32 == K1 % 32 == 0. */
+int showo_decode_wide_ln_gemm(const float* x, const float* lnw, const float* lnb, float eps, int H, const uint16_t* W0, const float* b0,
+                              uint16_t* out0, float* outf, int N0, int ld0, const uint16_t* W1, const float* b1, uint16_t* out1, int N1,
+                              int ld1, int nb, void* stream);
+int showo_decode_wide_out_gemm(float* x, const uint16_t* Wd, const uint16_t* attn, const float* bd, int K0, const uint16_t* W2,
+                               const uint16_t* ffn, const float* b2, int K1, int N, int nb, void* stream);
 int showo_engine_batch_prefill(showo_engine* e, int b, const int64_t* ids, const float* embeds, const float* mask, int L,
                                float* logits_last, void* stream);
 int showo_engine_batch_decode_greedy(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws, int use_graph,

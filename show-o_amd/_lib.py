@@ -180,6 +180,7 @@ _PROTOS = {
     "showo_engine_decode_step": [c_p, c_p, c_p, c_p, c_p],
     "showo_engine_decode_greedy": [c_p, c_p, c_i, c_p, c_p, c_i, c_p],
     "showo_engine_batch_begin": [c_p, c_i, c_i],
+    "showo_engine_batch_begin_wide": [c_p, c_i, c_i],
     "showo_engine_batch_prefill": [c_p, c_i, c_p, c_p, c_p, c_i, c_p, c_p],
     "showo_engine_batch_decode_greedy": [c_p, c_p, c_i, c_p, c_p, c_i, c_p],
     "showo_engine_batch_decode_sample": [c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_i, c_p],
@@ -221,6 +222,9 @@ _PROTOS = {
     "showo_engine_batch_decode_sample_lp": [c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_i, c_p],
     "showo_engine_score": [c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_p, c_p, c_p],
     "showo_engine_prefill_append_score": [c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p],
+    # wide decode batches (csrc/decode_wide.hip): the two MFMA kernels alone
+    "showo_decode_wide_ln_gemm": [c_p, c_p, c_p, c_f, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_p],
+    "showo_decode_wide_out_gemm": [c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_p],
     "showo_vq_create": [c_p, C.POINTER(c_p)],
     "showo_vq_load": [c_p, C.c_char_p, c_p, c_i64, c_p],
     "showo_vq_missing": [c_p],

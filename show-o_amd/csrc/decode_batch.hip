@@ -17,6 +17,7 @@
 #include "engine.h"
 #include "decode_common.h"
 #include "sample_row.h"
+#include "decode_wide.h"
 #include <cstdlib>
 #include <string>
 
@@ -40,26 +41,8 @@ int attn_decode_fused_batch(const bf16_t* qkv, const float* qw, const float* qb,
 
 namespace {
 
-constexpr int MAXB = 8;
-
-struct LnGemvBArgs {
-    const float* x;  // [NB, H] fp32 residual rows
-    const float *lnw, *lnb;
-    float eps;
-    int H;
-    const bf16_t* W0;  // [N0, H] -> out0[b][n] = bf16(W0 h_b + b0) (ld0) or outf[b][n] = fp32(...) (ld0)
-    const float* b0;
-    bf16_t* out0;
-    float* outf;
-    int N0, ld0;
-    const bf16_t* W1;  // [N1, H] -> out1[b][n] = bf16(gelu_new(W1 h_b + b1)) (ld1)
-    const float* b1;
-    bf16_t* out1;
-    int N1, ld1;
-    const bf16_t* W0lo = nullptr;  // HEAD3 instances (precision 2's lm_head): low halves of W0's rows, same layout
-    const float* s0 = nullptr;     // Q8 instances (precision 3): W0 / W1 are int8 row-major, s0 [N0] / s1 [N1] their row scales
-    const float* s1 = nullptr;
-};
+constexpr int MAXB = 32;   // per-slot storage: a wide batch (showo_engine_batch_begin_wide, decode_wide.hip) holds up to 32 sequences
+constexpr int NARROW_B = 8;  // the dot2 kernels of this file serve 1..8
 
 // REG (NB <= 4): after the LayerNorm every lane keeps ITS 32 activation values of each sequence in registers as 16 packed bf16 pairs
 // (the k positions lane * 8 + u * 512 + j are the same for every weight row), so a weight row costs 16 NB v_dot2c_f32_bf16 per lane, no
@@ -616,17 +599,22 @@ struct showo_engine::BatchDecode {
     float* y2 = nullptr;  // [nb, H] fc2 + b2 of the current layer (co-scheduled form)
     SlotDraw* slots_dev = nullptr;  // [MAXB] per-slot draw / stop state of showo_engine_batch_decode_sample
     int precision = 0;    // the precision the caches were prefilled under (element type of K / V^T)
+    bool wide = false;    // begun by showo_engine_batch_begin_wide: the step runs the MFMA kernels of decode_wide.hip
+    showo::WideWs wws;    // their workspace (one per engine: its decode steps are ordered on one stream)
 };
 
 namespace showo {
 void engine_batch_free(showo_engine* e) {
-    if (e && e->bd) { delete e->bd; e->bd = nullptr; }  // device buffers live in e->allocs
+    if (e && e->bd) { showo::wide_ws_free(&e->bd->wws); delete e->bd; e->bd = nullptr; }  // the other device buffers live in e->allocs
 }
 }  // namespace showo
 
-extern "C" int showo_engine_batch_begin(showo_engine* e, int nb, int cap_tokens) {
+static int batch_begin(showo_engine* e, int nb, int cap_tokens, bool wide) {
     if (!e) return set_error_msg(1, "engine: null handle");
-    if (nb < 1 || nb > MAXB) return set_error_msg(1, "batch_begin: 1..8 sequences");
+    if (!wide && (nb < 1 || nb > NARROW_B)) return set_error_msg(1, "batch_begin: 1..8 sequences");
+    if (wide && (nb < 1 || nb > MAXB)) return set_error_msg(1, "batch_begin_wide: 1..32 sequences");
+    if (wide && e->precision != 0) return set_error_msg(1, "batch_begin_wide: the wide decode batch runs at precision 0 (bf16 operands) only");
+    if (wide && ((e->H % 32) || (e->F % 32))) return set_error_msg(1, "batch_begin_wide: hidden and ffn must be multiples of 32");
     if (!decode_fused_shapes_ok(e->H, e->F)) return set_error_msg(1, "batch_begin: hidden <= 2048 and ffn <= 8192 (multiples of 8) required");
     if (nb > e->maxT) return set_error_msg(5, "batch_begin: more sequences than workspace rows");
     int cap = ((cap_tokens + 63) / 64) * 64;
@@ -654,10 +642,14 @@ extern "C" int showo_engine_batch_begin(showo_engine* e, int nb, int cap_tokens)
         TRY(e->alloc(&d->pos_dev, MAXB)); TRY(e->alloc(&d->L0_dev, MAXB)); TRY(e->alloc(&d->base_dev, MAXB));
         TRY(e->alloc(&d->last_iv_dev, 4 * MAXB)); TRY(e->alloc(&d->iv_dev, 4 * MAXB));
     }
-    d->nb = nb; d->cap = cap;
+    if (wide) TRY(showo::wide_ws_reserve(&d->wws, e->H, e->H));
+    d->nb = nb; d->cap = cap; d->wide = wide;
     for (int b = 0; b < MAXB; ++b) { d->prompt_len[b] = 0; d->cache_len[b] = 0; }
     return 0;
 }
+
+extern "C" int showo_engine_batch_begin(showo_engine* e, int nb, int cap_tokens) { return batch_begin(e, nb, cap_tokens, false); }
+extern "C" int showo_engine_batch_begin_wide(showo_engine* e, int nb, int cap_tokens) { return batch_begin(e, nb, cap_tokens, true); }
 
 namespace showo {
 int engine_prefill_into(showo_engine* e, const int64_t* ids, const float* embeds, const float* mask, int L, bf16_t* k, bf16_t* vt,
@@ -745,6 +737,7 @@ int batch_decode_checks(showo_engine* e, const char* what) {
     auto* d = e->bd;
     auto fail = [&](int code, const char* msg) { return set_error_msg(code, (std::string(what) + ": " + msg).c_str()); };
     if (e->precision == 1) return fail(1, "precision 0 (bf16 operands) or 2 (fp16 operands)");
+    if (d->wide && e->precision != 0) return fail(1, "a wide batch (showo_engine_batch_begin_wide) runs at precision 0 (bf16 operands) only");
     if (e->precision == 3 && (int)e->q8_loaded.size() != e->nL * 6 + 1)
         return fail(4, "(precision 3) the int8 weight images are missing or stale: upload the weights again");
     const int op = e->precision == 2 ? SHOWO_OP_F16 : SHOWO_OP_BF16;
@@ -773,6 +766,14 @@ int batch_step_layers(showo_engine* e, int op, bool co, int lk_max, float* logit
         showo::Layer& l = e->layers[li];
         LnGemvBArgs a{e->x, l.ln_w, l.ln_b, e->cfg.ln_eps, H, l.wqkv, l.bqkv, e->qkv, nullptr, 3 * H, 3 * H, l.w1, l.b1, e->ffn, F, F};
         OutGemvBArgs o{e->x, l.wd, e->attn, l.bd, H, H, l.w2, e->ffn, l.b2, F, F, H, d->y2};
+        if (d->wide) {  // ln_gemmW -> attention (heads x nb blocks) -> out_gemmW: the MFMA step of decode_wide.hip
+            TRY(showo::ln_gemmW(nb, a, d->wws, s));
+            TRY(showo::attn_decode_fused_batch(e->qkv, l.qln_w, l.qln_b, l.kln_w, l.kln_b, e->cosT, e->sinT, d->k + li * lstride,
+                                               d->vt + li * lstride, d->iv_dev, e->attn, nb, nH, e->cfg.rotary_dim, e->cfg.ln_eps,
+                                               d->pos_dev, lk_max, d->cap, d->cap, s, 0));
+            TRY(showo::out_gemmW(nb, o, d->wws, s));
+            continue;
+        }
         if (q8) {  // precision 3: the same launches stream the int8 images (pointers travel as bf16_t*; the scales select the instances)
             a.W0 = reinterpret_cast<const bf16_t*>(l.qqkv); a.W1 = reinterpret_cast<const bf16_t*>(l.q1); a.s0 = l.sqkv; a.s1 = l.s1;
             o.W0 = reinterpret_cast<const bf16_t*>(l.qd); o.W1 = reinterpret_cast<const bf16_t*>(l.q2); o.s0 = l.sd; o.s1 = l.s2;
@@ -796,6 +797,10 @@ int batch_step_layers(showo_engine* e, int op, bool co, int lk_max, float* logit
             TRY(out_gemvB(nb, o, s, op));
         }
     }
+    if (d->wide) {
+        LnGemvBArgs h{e->x, e->fln_w, e->fln_b, e->cfg.ln_eps, H, e->wlm, e->blm, nullptr, logits_ws, V, V, nullptr, nullptr, nullptr, 0, 0};
+        return showo::ln_gemmW(nb, h, d->wws, s);
+    }
     if (op) {  // precision 2: the lm_head is the split-bf16 product (its images stay bf16 (hi, lo) at that precision)
         TRY(showo::decode_split_head(e->x, e->fln_w, e->fln_b, e->cfg.ln_eps, H, e->wlm, e->wlm_lo, e->blm, logits_ws, V, V, nb, s));
     } else {
@@ -815,7 +820,7 @@ int batch_use_co(showo_engine* e, bool* co) {
         co_on = env ? (atoi(env) != 0) : 1;
     }
     const int nb = e->bd->nb;
-    *co = co_on && e->F == 8192 && e->H <= 2048 && nb >= 2 && nb <= 4 && (size_t)nb * e->F * 2 <= 128 * 1024;
+    *co = !e->bd->wide && co_on && e->F == 8192 && e->H <= 2048 && nb >= 2 && nb <= 4 && (size_t)nb * e->F * 2 <= 128 * 1024;
     if (*co && !e->bd->y2) TRY(e->alloc(&e->bd->y2, (int64_t)MAXB * e->H));
     return 0;
 }

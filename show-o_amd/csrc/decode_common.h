@@ -177,6 +177,26 @@ struct OutGemvBArgs {
     const float* s1 = nullptr;
 };
 
+// LayerNorm + two GEMV / GEMM outputs of the batched decode step (decode_batch.hip ln_gemvB_kernel, decode_wide.hip ln_gemmW_kernel)
+struct LnGemvBArgs {
+    const float* x;  // [NB, H] fp32 residual rows
+    const float *lnw, *lnb;
+    float eps;
+    int H;
+    const bf16_t* W0;  // [N0, H] -> out0[b][n] = bf16(W0 h_b + b0) (ld0) or outf[b][n] = fp32(...) (ld0)
+    const float* b0;
+    bf16_t* out0;
+    float* outf;
+    int N0, ld0;
+    const bf16_t* W1;  // [N1, H] -> out1[b][n] = bf16(gelu_new(W1 h_b + b1)) (ld1)
+    const float* b1;
+    bf16_t* out1;
+    int N1, ld1;
+    const bf16_t* W0lo = nullptr;  // HEAD3 instances (precision 2's lm_head): low halves of W0's rows, same layout
+    const float* s0 = nullptr;     // Q8 instances (precision 3): W0 / W1 are int8 row-major, s0 [N0] / s1 [N1] their row scales
+    const float* s1 = nullptr;
+};
+
 // wave_sum of up to four accumulators at once, each with wave_sum's own order of additions (partners 32, 16, 8, 4, 2, 1 away: the same
 // bits).  The 32 / 16 steps run on every accumulator with gfx950's row-swap instructions (VALU only); after them a lane holds, for
 // each b, the sum over its 4-lane group {l, l^16, l^32, l^48}, so lane group g = lane >> 4 continues with accumulator g alone: ONE

@@ -80,6 +80,8 @@ struct DecodeTuning {
     int batch_ln_blocks = 1024; // grid cap of ln_gemvB_kernel<NB <= 4> (register activations)           SHOWO_DECODE_BATCH_LN_BLOCKS
     int ln_blocks = 1024;       // grid cap of ln_gemv2_kernel<2>                                        SHOWO_DECODE_LN_BLOCKS
     int out_blocks = 256;       // grid cap of out_gemv2_kernel / out_gemvB / out_dense_y2B              SHOWO_DECODE_OUT_BLOCKS
+    int wide_ln_blocks = 256;   // grid cap of ln_gemmW_kernel (4 waves x 32 columns per block trip)     SHOWO_DECODE_WIDE_LN_BLOCKS
+    int wide_out_ksplit = 4;    // blocks per column group of out_gemmW_kernel (1..8)                    SHOWO_DECODE_WIDE_OUT_KSPLIT
 };
 DecodeTuning& decode_tuning();
 int greedy_token_seam(const float* logits, int n, int64_t* tok, int64_t* out_tokens, int* pos, int base, const float* table, float* x, int H,

@@ -622,6 +622,8 @@ DecodeTuning& decode_tuning() {
         env("SHOWO_DECODE_BATCH_LN_BLOCKS", &t.batch_ln_blocks);
         env("SHOWO_DECODE_LN_BLOCKS", &t.ln_blocks);
         env("SHOWO_DECODE_OUT_BLOCKS", &t.out_blocks);
+        env("SHOWO_DECODE_WIDE_LN_BLOCKS", &t.wide_ln_blocks);
+        env("SHOWO_DECODE_WIDE_OUT_KSPLIT", &t.wide_out_ksplit);
     }
     return t;
 }
@@ -635,6 +637,8 @@ extern "C" int showo_decode_set_tuning(const char* name, int value) {
     else if (n == "batch_ln_blocks") t.batch_ln_blocks = value;
     else if (n == "ln_blocks") t.ln_blocks = value;
     else if (n == "out_blocks") t.out_blocks = value;
+    else if (n == "wide_ln_blocks") t.wide_ln_blocks = value;
+    else if (n == "wide_out_ksplit") t.wide_out_ksplit = value;
     else return set_error_msg(1, "showo_decode_set_tuning: unknown knob");
     return 0;
 }

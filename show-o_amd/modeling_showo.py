@@ -994,6 +994,23 @@ def _mmu_batch_slots(n):
     return n if n <= _MMU_BATCH_MAX else _MMU_BATCH_SLOTS
 
 
+# Wide decode batches (opt-in, `slots=S`): 9..32 slots of showo_engine_batch_begin_wide (csrc/decode_wide.hip, precision 0)
+_MMU_WIDE_MIN, _MMU_WIDE_MAX = 9, 32
+
+
+def _mmu_wide_slots(slots, n, precision):
+    """the `slots` argument of mmu_generate_batch / MmuSession.generate_batch: None (the call without it: slots is None, or n <= 8
+    requests) or the slot count min(slots, n) of a wide batch; ValueError for anything but None or an int in 9..32, and for a
+    precision other than 0"""
+    if slots is None:
+        return None
+    if isinstance(slots, bool) or not isinstance(slots, int) or not _MMU_WIDE_MIN <= slots <= _MMU_WIDE_MAX:
+        raise ValueError(f"slots must be None or an int in {_MMU_WIDE_MIN}..{_MMU_WIDE_MAX} (a wide decode batch)")
+    if int(precision) != 0:
+        raise ValueError("slots (a wide decode batch) needs precision 0 (bf16 operands)")
+    return None if n <= _MMU_BATCH_MAX else min(slots, n)
+
+
 def _mmu_batch_seeds(top_ks, generator):
     """the Philox seed of every sampled sequence, drawn as n sequential mmu_generate calls draw them: one draw per sequence with
     top_k != 1, in sequence order, none for greedy ones (None)"""
@@ -1146,7 +1163,7 @@ class _MmuSlotEngine:
 
 @torch.no_grad()
 def mmu_generate_batch(self, idx=None, input_embeddings=None, attention_mask=None, max_new_tokens=100, temperature=1.0, top_k=None,
-                       eot_token=None, generator=None, _exp_noise=None, top_p=None, return_logprobs=False):
+                       eot_token=None, generator=None, _exp_noise=None, top_p=None, return_logprobs=False, slots=None):
     """n independent `mmu_generate` calls served together (BASELINE cfg4: "batch=4 images"; the reference's mmu_generate is batch-1 and
     inference_mmu.py:87-177 walks the images one by one).  `idx` / `input_embeddings` / `attention_mask` are LISTS (one entry per
     sequence, each what a single `mmu_generate` call takes: [1, L_b] ids or [1, L_b, H] embeddings, its own mask or IntervalMask);
@@ -1160,9 +1177,17 @@ def mmu_generate_batch(self, idx=None, input_embeddings=None, attention_mask=Non
     bit-identical to its batch-1 run): all-greedy batches of 2..8 on showo_engine_batch_decode_greedy, anything else on up to 8 slots
     of showo_engine_batch_decode_sample that are refilled as sequences finish.  Precision 1 and n < 2 make the sequential calls.
     `return_logprobs=True` returns `(tokens, logprobs)`, logprobs a list of n fp32 device tensors (result[b]'s log-probabilities, the
-    bits of the batch-1 call's); every batch, the all-greedy one included, then runs on the slots of showo_engine_batch_decode_sample_lp."""
+    bits of the batch-1 call's); every batch, the all-greedy one included, then runs on the slots of showo_engine_batch_decode_sample_lp.
+
+    `slots=S` (an int in 9..32, precision 0 only; anything else but None: ValueError) opts in to a WIDE decode batch for n > 8 requests:
+    the same slot scheduler on min(S, n) slots of showo_engine_batch_begin_wide, whose steps run MFMA skinny GEMMs (csrc/decode_wide.hip:
+    16 slots per instruction instead of one dot2 chain per slot).  Contract of a wide call: results are deterministic run to run; a
+    request's tokens and log-probabilities do not depend on S, on n, on the slot it lands in or on what the other slots hold (an MFMA
+    output column reads only its own sequence, the K order is fixed); they are NOT promised to equal the batch-1 bits -- same bf16
+    rounding points, another fp32 summation order, so a near-tie may resolve differently.  With n <= 8 the call is the one without `slots`."""
     seqs = idx if idx is not None else input_embeddings
     n = len(seqs)
+    wide = _mmu_wide_slots(slots, n, getattr(self, "_precision", 0))
     masks = attention_mask if isinstance(attention_mask, (list, tuple)) else [attention_mask] * n
     temps = list(temperature) if isinstance(temperature, (list, tuple)) else [temperature] * n
     top_ks = list(top_k) if isinstance(top_k, (list, tuple)) else [top_k] * n
@@ -1196,9 +1221,9 @@ def mmu_generate_batch(self, idx=None, input_embeddings=None, attention_mask=Non
     eng = self.engine()
     dev = seqs[0].device
     lens = [int(t.shape[1]) for t in seqs]
-    slots = _mmu_batch_slots(n)
+    slots = wide if wide else _mmu_batch_slots(n)
     try:
-        _lib.call("showo_engine_batch_begin", eng, slots, max(lens) + max_new_tokens + 1)
+        _lib.call("showo_engine_batch_begin_wide" if wide else "showo_engine_batch_begin", eng, slots, max(lens) + max_new_tokens + 1)
     except RuntimeError:
         # the batch's common capacity (longest prompt + max_new_tokens) does not fit the engine (max_position_embeddings, the single-block
         # decode attention): n sequential calls fail only if a sequence actually reaches the limit before <eot>
@@ -1422,13 +1447,16 @@ class _SessionEngine:
                   _lib.ptr(lp), _lib.ptr(rk), _lib.ptr(last), _lib.stream())
         return lp, rk
 
-    def run_batch(self, length, rows, lens, max_new_tokens, temps, top_ks, seeds, noises, eot_token, top_ps=None, return_logprobs=False):
+    def run_batch(self, length, rows, lens, max_new_tokens, temps, top_ks, seeds, noises, eot_token, top_ps=None, return_logprobs=False,
+                  slots=None):
         """n continuations of the cache [0, length) on the slots of a decode batch; None when the batch does not fit the engine;
-        return_logprobs: (token lists, log-probability tensors)"""
+        return_logprobs: (token lists, log-probability tensors); slots: the slot count of a wide batch (_mmu_wide_slots)"""
         n = len(rows)
-        slots = _mmu_batch_slots(n)
+        wide = slots
+        slots = wide if wide else _mmu_batch_slots(n)
         try:
-            _lib.call("showo_engine_batch_begin", self.eng, slots, length + max(lens) + max_new_tokens + 1)
+            _lib.call("showo_engine_batch_begin_wide" if wide else "showo_engine_batch_begin", self.eng, slots,
+                      length + max(lens) + max_new_tokens + 1)
         except RuntimeError:
             return None
         se = _SessionSlotEngine(self.model, self.eng, rows, lens, slots, temps, top_ks, seeds, noises, eot_token, self.dev, top_ps,
@@ -1662,15 +1690,19 @@ class MmuSession:
 
     @torch.no_grad()
     def generate_batch(self, idx=None, input_embeddings=None, max_new_tokens=100, temperature=1.0, top_k=None, eot_token=None,
-                       generator=None, _exp_noise=None, top_p=None, return_logprobs=False):
+                       generator=None, _exp_noise=None, top_p=None, return_logprobs=False, slots=None):
         """n continuations of the CURRENT state: `idx` / `input_embeddings` is a list of n row blocks ([1, Ln_i] ids or [1, Ln_i, H]
         embeddings), `temperature` / `top_k` / `top_p` scalars or lists, `_exp_noise` None or a list.  result[i] is what `generate(<block i>)`
         followed by a rewind returns when those calls are made in order (same seeds from `generator`); the session is left unchanged.
         n >= 2 at precision 0, 2, 3 runs on the slots of a decode batch, each slot a fork of this cache.
-        `return_logprobs=True`: `(tokens, logprobs)`, logprobs a list of n fp32 device tensors."""
+        `return_logprobs=True`: `(tokens, logprobs)`, logprobs a list of n fp32 device tensors.
+        `slots=S` (an int in 9..32, precision 0; else ValueError): n > 8 continuations run on min(S, n) slots of a WIDE decode batch
+        (`Showo.mmu_generate_batch` states its contract: deterministic, independent of S / n / slot / neighbours, bf16-class and not
+        the batch-1 bits); n <= 8 is the call without `slots`."""
         self._check()
         seqs = idx if idx is not None else input_embeddings
         n = len(seqs)
+        wide = _mmu_wide_slots(slots, n, getattr(self.model, "_precision", 0))
         temps = list(temperature) if isinstance(temperature, (list, tuple)) else [temperature] * n
         top_ks = list(top_k) if isinstance(top_k, (list, tuple)) else [top_k] * n
         noises = list(_exp_noise) if _exp_noise is not None else [None] * n
@@ -1715,6 +1747,8 @@ class MmuSession:
         nucleus = {} if all(q is None for q in top_ps) else {"top_ps": top_ps}
         if return_logprobs:
             nucleus["return_logprobs"] = True
+        if wide:
+            nucleus["slots"] = wide
         out = self._be.run_batch(self.length, rows, lens, max_new_tokens, temps, top_ks, seeds, noises, eot_token, **nucleus)
         if out is None:  # the batch's common capacity does not fit the engine: the sequential calls, drawing the same seeds again
             if gen_state is not None:

@@ -12,6 +12,10 @@ against the sequential calls' (same generator seed).
                                                # this process, at batch 1 and n = 4 / 16: median and min / max tokens/s over --reps calls
   python tools/mmu_batch_bench.py --logprobs   # cost of return_logprobs=True: every leg with and without it, alternating in this
                                                # process, at batch 1 and n = 4 / 16, greedy and top_k=5: medians over --reps calls
+  python tools/mmu_batch_bench.py --slots 16,32   # wide decode batches (slots=S, csrc/decode_wide.hip) against the call without
+                                               # `slots`, alternating in this process, n = 16 / 32 / 64, greedy and top_k=5: medians over
+                                               # --reps calls, and the time of one decode step; writes profiles/wide_decode_bench.json
+  python tools/mmu_batch_bench.py --profile-wide 32   # one wide greedy n = S call of 17 tokens, for a kernel trace of the wide step
 
 The slot count for n > 8 is set through modeling_showo._MMU_BATCH_SLOTS for this run only."""
 import argparse
@@ -142,6 +146,65 @@ def logprob_legs(model, embs, masks, reps):
     return res
 
 
+def wide_legs(model, embs, masks, slot_counts, reps):
+    """tokens/s of mmu_generate_batch without `slots` (the baseline: 8 slots of the dot2 kernels) and with slots=S for every S, measured
+    alternately (None, S1, S2, None, ...) so that all legs see the same clocks; per leg the median and min / max of `reps` whole calls
+    after one warm-up call each, and ratio = median / the baseline's median.  step_ms: the time of one decode step of S = n slots,
+    from the difference of a 100-token and a 36-token greedy call (64 steps, the prefills cancel).  A wide call is not the baseline's
+    bits (another fp32 summation order), so tokens are compared only between the wide legs: they must agree with each other."""
+    gen = lambda: torch.Generator(device="cuda").manual_seed(7)  # noqa: E731
+
+    def call(n, kw, S, new=NEW):
+        extra = {} if S is None else {"slots": S}
+        return lambda: model.mmu_generate_batch(input_embeddings=embs[:n], attention_mask=masks[:n], max_new_tokens=new, generator=gen(),
+                                                **kw, **extra)
+
+    def once(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    res = {"shape": "cfg4: 631-embedding w_clip_vit prompts, 100 new tokens each, full-size seeded weights",
+           "unit": "tokens/s (whole call)", "reps": reps, "slots": slot_counts}
+    for n in (16, 32, 64):
+        for name, kw in (("greedy", GREEDY), ("topk5_t0.7", SAMPLED)):
+            legs = {"none": call(n, kw, None)}
+            for S in slot_counts:
+                legs[f"slots{S}"] = call(n, kw, S)
+            first = {k: [[int(t) for t in r] for r in fn()] for k, fn in legs.items()}  # warm-up
+            wide = [first[f"slots{S}"] for S in slot_counts]
+            assert all(w == wide[0] for w in wide), (n, name, "the wide legs disagree")
+            agree = sum(a == b for a, b in zip(first["none"], wide[0]))
+            times = {k: [] for k in legs}
+            for _ in range(reps):
+                for k, fn in legs.items():
+                    times[k].append(once(fn))
+            row = {"requests_with_the_baseline_tokens": f"{agree}/{n}"}
+            for k, ts in times.items():
+                rate = sorted(n * NEW / t for t in ts)
+                row[k] = {"median": float(np.median(rate)), "min": rate[0], "max": rate[-1]}
+            for S in slot_counts:
+                row[f"slots{S}"]["ratio"] = row[f"slots{S}"]["median"] / row["none"]["median"]
+            res[f"n{n}_{name}"] = row
+            print(f"n={n} {name}: {row}", file=sys.stderr, flush=True)
+    steps = {}
+    for S in [8] + list(slot_counts):
+        n = S
+        extra = None if S == 8 else S
+        long_, short = call(n, GREEDY, extra, 100), call(n, GREEDY, extra, 36)
+        long_(), short()
+        tl, ts = [], []
+        for _ in range(3):
+            tl.append(once(long_))
+            ts.append(once(short))
+        steps[f"slots{S}_n{n}"] = 1e3 * (float(np.median(tl)) - float(np.median(ts))) / 64
+    res["step_ms"] = steps
+    print(f"step_ms: {steps}", file=sys.stderr, flush=True)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--profile", action="store_true")
@@ -149,7 +212,25 @@ def main():
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--logprobs", action="store_true", help="measure return_logprobs=True against the same legs without it")
     ap.add_argument("--out", default=None, help="also write the JSON of --top-p / --logprobs to this file")
+    ap.add_argument("--slots", default=None, help="comma-separated wide slot counts (9..32) to measure against the call without `slots`")
+    ap.add_argument("--profile-wide", type=int, default=None, help="one wide greedy call of 17 tokens on this many slots, for a kernel trace")
     a = ap.parse_args()
+    if a.profile_wide is not None:
+        S = a.profile_wide
+        pkg, model, embs, masks = build(S)
+        for _ in range(2):
+            model.mmu_generate_batch(input_embeddings=embs[:S], attention_mask=masks[:S], max_new_tokens=17, top_k=1, slots=S)
+        torch.cuda.synchronize()
+        print(json.dumps({"profiled": f"mmu_generate_batch n={S} greedy slots={S}, 17 tokens, twice"}))
+        return
+    if a.slots is not None:
+        pkg, model, embs, masks = build(64)
+        res = wide_legs(model, embs, masks, [int(t) for t in a.slots.split(",")], a.reps)
+        out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "wide_decode_bench.json")
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1)
+        print(json.dumps(res))
+        return
     pkg, model, embs, masks = build(4 if a.profile else (16 if (a.top_p is not None or a.logprobs) else 32))
     if a.logprobs:
         res = logprob_legs(model, embs, masks, a.reps)
