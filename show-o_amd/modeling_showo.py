@@ -9,6 +9,7 @@ the reference's names and shapes); all arithmetic runs in HIP kernels through th
 PyTorch fallback: without a GPU or without the built library every compute entry point raises.
 """
 import collections
+import contextlib
 import types
 
 import torch
@@ -802,10 +803,7 @@ class Showo(PretrainedMixin, nn.Module):
         ml, tp = t2i_step_constants(timesteps, N, temperature, noise_schedule)
         ml_a = (C.c_float * timesteps)(*ml)
         tp_a = (C.c_float * timesteps)(*tp)
-        if generator is not None:
-            seed = int(torch.randint(0, 2 ** 62, (1,), generator=generator, device=generator.device).item())
-        else:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+        seed = _draw_seed(generator)
         out = torch.empty((B, N), dtype=torch.int64, device=input_ids.device)
         # the denoise steps run as replays of ONE captured hipGraph (cached on the engine across calls) unless use_graph=0 is
         # passed or per-launch event timing is on (the engine then runs the steps eagerly)
@@ -821,14 +819,8 @@ class Showo(PretrainedMixin, nn.Module):
                       flags, _lib.ptr(out), _lib.stream())
 
         if use_graph:
-            # hipGraph replay of the denoise step: stream capture needs a non-default stream
-            if getattr(self, "_graph_stream", None) is None:
-                self._graph_stream = torch.cuda.Stream()
-            cur = torch.cuda.current_stream()
-            self._graph_stream.wait_stream(cur)
-            with torch.cuda.stream(self._graph_stream):
+            with _graph_stream_of(self):  # hipGraph replay of the denoise step: stream capture needs a non-default stream
                 run()
-            cur.wait_stream(self._graph_stream)
         else:
             run()
         _lib.call("showo_engine_use_intervals", eng, None, None)
@@ -845,20 +837,9 @@ class Showo(PretrainedMixin, nn.Module):
         `return_logprobs=True` returns `(tokens, logprobs)`: logprobs fp32 [len(tokens)] on the device, entry j the log-softmax of the
         RAW logits (temperature 1, no filter) at token j -- one more launch per decode step (showo_engine_decode_sample_lp); the
         tokens are those of the call without it."""
-        p = _nucleus_p(top_p)
+        # greedy (top_k == 1) is the reference caller's setting (inference_mmu.py:81): multinomial of a one-hot = arg-max
+        greedy, k, noise, seed, p = _draw_params(self, max_new_tokens, temperature, top_k, top_p, generator, _exp_noise)
         eng = self.engine()
-        greedy = top_k == 1  # the reference caller's setting (inference_mmu.py:81): multinomial of a one-hot = arg-max
-        if not greedy:
-            if not temperature > 0:
-                raise ValueError("temperature must be > 0")
-            k = 0 if top_k is None else int(top_k)
-            if generator is not None:
-                seed = int(torch.randint(0, 2 ** 62, (1,), generator=generator, device=generator.device).item())
-            else:
-                seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-            noise = None if _exp_noise is None else _exp_noise.detach().float().contiguous()
-            if noise is not None and tuple(noise.shape) != (max_new_tokens, self.vocab_size):
-                raise ValueError("_exp_noise must be [max_new_tokens, vocab_size]")
         dev = idx.device if idx is not None else input_embeddings.device
         # accuracy mode: KV-cached like precision 0 when the engine runs it on the production kernels (Phi-1.5's shape); otherwise -- or
         # with `self.precise_recompute = True` -- the reference's own no-cache algorithm on the fp32-class path
@@ -867,73 +848,17 @@ class Showo(PretrainedMixin, nn.Module):
             return self._mmu_generate_recompute(idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token,
                                                 greedy, None if greedy else (k, seed, noise), top_p=p, return_logprobs=return_logprobs)
         if input_embeddings is not None:
-            if input_embeddings.shape[0] != 1:
-                raise ValueError("mmu_generate has batch-1 semantics (reference modeling_showo.py:204,229)")
-            L = input_embeddings.shape[1]
-            emb = input_embeddings.detach().float().contiguous()
-            ids = None
-        else:
-            if idx.shape[0] != 1:
-                raise ValueError("mmu_generate has batch-1 semantics (reference modeling_showo.py:204,229)")
-            L = idx.shape[1]
-            ids = idx.to(torch.int64).contiguous()
-            emb = None
-        from .prompting_utils import IntervalMask
-        if isinstance(attention_mask, IntervalMask):  # prompting_utils.intervals_for_mmu / _mmu_vit: no [1,1,L,L] tensor at all
-            mask = self._use_mask(eng, attention_mask)
-        else:
-            mask = None if attention_mask is None else attention_mask.detach().float().reshape(1, 1, L, L).contiguous()
+            idx = None
+        if (idx if idx is not None else input_embeddings).shape[0] != 1:
+            raise ValueError("mmu_generate has batch-1 semantics (reference modeling_showo.py:204,229)")
         logits = torch.empty((self.vocab_size,), dtype=torch.float32, device=dev)
         tok = torch.empty((1,), dtype=torch.int64, device=dev)
-        try:
-            _lib.call("showo_engine_prefill", eng, _lib.ptr(ids), _lib.ptr(emb), _lib.ptr(mask), L, _lib.ptr(logits), _lib.stream())
-        finally:
-            _lib.call("showo_engine_use_intervals", eng, None, None)
-        # logits / temperature does not change the arg-max for temperature > 0; top_k=1 makes the reference's multinomial a
-        # deterministic arg-max.  The first token comes from the prefill logits; the continuation runs in
-        # chunks of `chunk` steps entirely on the device (embed -> 24 layers on the KV cache -> lm_head -> arg-max), one
-        # hipGraph replay per step, and the host looks at the tokens (for <eot>) once per chunk.
-        if greedy:
-            _lib.call("showo_argmax_f32", _lib.ptr(logits), self.vocab_size, _lib.ptr(tok), _lib.stream())
-        else:  # logits / temperature -> top-k filter -> softmax -> multinomial (reference :220-228), one kernel
-            _sample_call(logits, self.vocab_size, k, p, temperature, noise, seed, 0, tok)
-        lps = [_logprob_of(logits, self.vocab_size, tok)] if return_logprobs else None
-
-        def done(result):
-            return (result, torch.cat(lps)[:len(result)]) if return_logprobs else result
-
-        first = int(tok.item())
-        result = [torch.tensor(first, device=dev)]
-        if (eot_token is not None and first == eot_token) or max_new_tokens <= 1:
-            return done(result[:max_new_tokens])
-        use_graph, chunk = int(getattr(self, "decode_graph", 1)), 16
-        if getattr(self, "_graph_stream", None) is None:
-            self._graph_stream = torch.cuda.Stream()
-        cur = torch.cuda.current_stream()
-        remaining = max_new_tokens - 1
-        while remaining > 0:
-            n = min(chunk, remaining)
-            outc = torch.empty((n,), dtype=torch.int64, device=dev)
-            if return_logprobs:
-                lps.append(torch.empty((n,), dtype=torch.float32, device=dev))
-            self._graph_stream.wait_stream(cur)
-            with torch.cuda.stream(self._graph_stream):
-                if return_logprobs:
-                    _decode_lp_call(eng, tok, n, outc, logits, greedy, None if greedy else k, p, temperature, None if greedy else noise,
-                                    0 if greedy else seed, max_new_tokens - remaining, lps[-1], use_graph)
-                elif greedy:
-                    _lib.call("showo_engine_decode_greedy", eng, _lib.ptr(tok), n, _lib.ptr(outc), _lib.ptr(logits), use_graph,
-                              _lib.stream())
-                else:
-                    _decode_sample_call(eng, tok, n, outc, logits, k, p, temperature, noise, seed, max_new_tokens - remaining, use_graph)
-            cur.wait_stream(self._graph_stream)
-            toks = outc.tolist()
-            for t in toks:
-                result.append(torch.tensor(t, device=dev))
-                if eot_token is not None and t == eot_token:
-                    return done(result)
-            remaining -= n
-        return done(result)
+        # (an IntervalMask, prompting_utils.intervals_for_mmu / _mmu_vit: no [1,1,L,L] tensor at all)
+        _prefill(eng, *_prompt_args(self, eng, idx, input_embeddings, attention_mask), logits)
+        out = _decode_batch1(self, eng, logits, tok, max_new_tokens, (greedy, k, p, temperature, noise, seed), eot_token, return_logprobs)
+        toks, lps = out if return_logprobs else (out, None)
+        toks = [torch.tensor(t, device=dev) for t in toks]
+        return (toks, lps) if return_logprobs else toks
 
 
 def _nucleus_p(top_p):
@@ -947,6 +872,68 @@ def _nucleus_p(top_p):
     return None if p >= 1 else p
 
 
+def _draw_seed(generator):
+    """one Philox seed for the on-device draws, from `generator` (on its device) or from torch's global generator"""
+    kw = {} if generator is None else {"generator": generator, "device": generator.device}
+    return int(torch.randint(0, 2 ** 62, (1,), **kw).item())
+
+
+def _draw_params(model, max_new_tokens, temperature, top_k, top_p, generator, noise):
+    """(greedy, k, noise, seed, p) of one mmu_generate call: greedy for top_k == 1 (k 1, no noise, seed 0: what the arg-max entries and
+    showo_engine_decode_sample_lp take), else k (0: no top-k filter), the fp32 `_exp_noise` [max_new_tokens, vocab] and ONE seed drawn
+    from the generator; p: None or the nucleus top_p inside (0, 1).  Checks in this order: top_p, temperature, (seed draw), noise shape."""
+    p = _nucleus_p(top_p)
+    if top_k == 1:
+        return True, 1, None, 0, p
+    if not temperature > 0:
+        raise ValueError("temperature must be > 0")
+    seed = _draw_seed(generator)
+    if noise is not None:
+        noise = noise.detach().float().contiguous()
+        if tuple(noise.shape) != (max_new_tokens, model.vocab_size):
+            raise ValueError("_exp_noise must be [max_new_tokens, vocab_size]")
+    return False, 0 if top_k is None else int(top_k), noise, seed, p
+
+
+@contextlib.contextmanager
+def _graph_stream_of(model):
+    """the body runs on the model's side stream (hipGraph capture and replay need a non-default stream), behind the work queued on the
+    current stream; the current stream then waits for it.  The stream is made on first use and kept on the model."""
+    gs = getattr(model, "_graph_stream", None)
+    if gs is None:
+        gs = model._graph_stream = torch.cuda.Stream()
+    cur = torch.cuda.current_stream()
+    gs.wait_stream(cur)
+    with torch.cuda.stream(gs):
+        yield
+    cur.wait_stream(gs)
+
+
+def _prompt_args(model, eng, idx, input_embeddings, attention_mask):
+    """(ids, emb, mask, L) of one batch-1 prompt as the prefill entries take it: int64 ids [1, L] or fp32 embeddings [1, L, H], and the
+    dense mask as fp32 [1, 1, L, L].  An IntervalMask is registered with the engine instead (mask None) until _prefill resets it."""
+    from .prompting_utils import IntervalMask
+    ids = None if idx is None else idx.to(torch.int64).contiguous()
+    emb = None if input_embeddings is None else input_embeddings.detach().float().contiguous()
+    L = (ids if ids is not None else emb).shape[1]
+    if isinstance(attention_mask, IntervalMask):
+        mask = model._use_mask(eng, attention_mask)
+    else:
+        mask = None if attention_mask is None else attention_mask.detach().float().reshape(1, 1, L, L).contiguous()
+    return ids, emb, mask, L
+
+
+def _prefill(eng, ids, emb, mask, L, logits, slot=None):
+    """the prompt into the engine's decode cache (showo_engine_prefill) or into `slot` of the running batch (showo_engine_batch_prefill),
+    its last row's logits into `logits`; the engine forgets the registered IntervalMask whether or not the call succeeds.  Returns L."""
+    entry, head = ("showo_engine_prefill", (eng,)) if slot is None else ("showo_engine_batch_prefill", (eng, slot))
+    try:
+        _lib.call(entry, *head, _lib.ptr(ids), _lib.ptr(emb), _lib.ptr(mask), L, _lib.ptr(logits), _lib.stream())
+    finally:
+        _lib.call("showo_engine_use_intervals", eng, None, None)
+    return L
+
+
 def _sample_call(logits, V, k, p, temperature, noise, seed, step, tok):
     """one draw from a logits row: showo_sample_topk, or showo_sample_topk_topp behind the nucleus filter p"""
     if p is None:
@@ -956,16 +943,6 @@ def _sample_call(logits, V, k, p, temperature, noise, seed, step, tok):
                   _lib.stream())
 
 
-def _decode_sample_call(eng, tok, n, outc, logits, k, p, temperature, noise, seed, step0, use_graph):
-    """n steps of the device loop: showo_engine_decode_sample, or showo_engine_decode_sample_p behind the nucleus filter p"""
-    if p is None:
-        _lib.call("showo_engine_decode_sample", eng, _lib.ptr(tok), n, _lib.ptr(outc), _lib.ptr(logits), k, float(temperature),
-                  _lib.ptr(noise), seed, step0, use_graph, _lib.stream())
-    else:
-        _lib.call("showo_engine_decode_sample_p", eng, _lib.ptr(tok), n, _lib.ptr(outc), _lib.ptr(logits), k, p, float(temperature),
-                  _lib.ptr(noise), seed, step0, use_graph, _lib.stream())
-
-
 def _logprob_of(logits, V, tok):
     """fp32 [1]: the log-probability of token tok[0] under the logits row (showo_logprob_rows)"""
     lp = torch.empty((1,), dtype=torch.float32, device=logits.device)
@@ -973,12 +950,61 @@ def _logprob_of(logits, V, tok):
     return lp
 
 
-def _decode_lp_call(eng, tok, n, outc, logits, greedy, k, p, temperature, noise, seed, step0, lps, use_graph):
-    """n steps of the device loop with their log-probabilities: showo_engine_decode_sample_lp, which takes the greedy step for
-    top_k == 1 and the plain top-k draw for top_p >= 1 -- the token launches of the three calls without log-probabilities"""
-    _lib.call("showo_engine_decode_sample_lp", eng, _lib.ptr(tok), n, _lib.ptr(outc), _lib.ptr(logits), 1 if greedy else k,
-              1.0 if (greedy or p is None) else p, 1.0 if greedy else float(temperature), _lib.ptr(noise), seed, step0, _lib.ptr(lps), None,
-              use_graph, _lib.stream())
+_GREEDY_DRAW = (True, 1, None, 1.0, None, 0)  # a draw (greedy, k, p, temperature, noise, seed) that is the arg-max
+
+
+def _first_token(logits, V, tok, draw, want_lp=False):
+    """launch the pick of a sequence's first token from its prefill logits into the one-element view `tok`: the arg-max, or draw 0 of
+    `draw` (logits / temperature -> top-k filter -> softmax -> multinomial, reference :220-228, one kernel).  want_lp: also launch its
+    log-probability and return it (fp32 [1]).  Nothing is read back: the caller decides when to synchronise."""
+    greedy, k, p, temperature, noise, seed = draw
+    if greedy:
+        _lib.call("showo_argmax_f32", _lib.ptr(logits), V, _lib.ptr(tok), _lib.stream())
+    else:
+        _sample_call(logits, V, k, p, temperature, noise, seed, 0, tok)
+    return _logprob_of(logits, V, tok) if want_lp else None
+
+
+def _decode_batch1(model, eng, logits, tok, max_new_tokens, draw, eot_token, want_lp):
+    """One sequence behind its prefill (`logits`: its last row's): the int tokens, cut behind <eot>; want_lp: (tokens, their
+    log-probabilities fp32 [len(tokens)]).  logits / temperature does not change the arg-max for temperature > 0 and top_k=1 makes the
+    reference's multinomial a deterministic arg-max.  The first token comes from the prefill logits; the continuation
+    runs in chunks of `chunk` steps entirely on the device (embed -> 24 layers on the KV cache -> lm_head -> pick), one hipGraph
+    replay per step, and the host looks at the tokens (for <eot>) once per chunk."""
+    greedy, k, p, temperature, noise, seed = draw
+    lps = [_first_token(logits, model.vocab_size, tok, draw, want_lp)]
+
+    def done(result):
+        return (result, torch.cat(lps)[:len(result)]) if want_lp else result
+
+    result = [int(tok.item())]
+    if (eot_token is not None and result[0] == eot_token) or max_new_tokens <= 1:
+        return done(result[:max_new_tokens])
+    use_graph, chunk = int(getattr(model, "decode_graph", 1)), 16
+    remaining = max_new_tokens - 1
+    while remaining > 0:
+        n, step0 = min(chunk, remaining), max_new_tokens - remaining
+        outc = torch.empty((n,), dtype=torch.int64, device=tok.device)
+        if want_lp:
+            lps.append(torch.empty((n,), dtype=torch.float32, device=tok.device))
+        head = (eng, _lib.ptr(tok), n, _lib.ptr(outc), _lib.ptr(logits))
+        with _graph_stream_of(model):
+            if want_lp:  # one entry: it takes the greedy step for top_k == 1 and the plain top-k draw for top_p >= 1
+                _lib.call("showo_engine_decode_sample_lp", *head, k, 1.0 if (greedy or p is None) else p,
+                          1.0 if greedy else float(temperature), _lib.ptr(noise), seed, step0, _lib.ptr(lps[-1]), None, use_graph, _lib.stream())
+            elif greedy:
+                _lib.call("showo_engine_decode_greedy", *head, use_graph, _lib.stream())
+            elif p is None:
+                _lib.call("showo_engine_decode_sample", *head, k, float(temperature), _lib.ptr(noise), seed, step0, use_graph, _lib.stream())
+            else:
+                _lib.call("showo_engine_decode_sample_p", *head, k, p, float(temperature), _lib.ptr(noise), seed, step0, use_graph,
+                          _lib.stream())
+        for t in outc.tolist():
+            result.append(t)
+            if eot_token is not None and t == eot_token:
+                return done(result)
+        remaining -= n
+    return done(result)
 
 
 # Slot scheduler of mmu_generate_batch (n >= 2 sequences at precision 0 / 2 beyond the all-greedy 2..8 case).  Slot count for more
@@ -1016,12 +1042,7 @@ def _mmu_batch_seeds(top_ks, generator):
     top_k != 1, in sequence order, none for greedy ones (None)"""
     seeds = []
     for k in top_ks:
-        if k == 1:
-            seeds.append(None)
-        elif generator is not None:
-            seeds.append(int(torch.randint(0, 2 ** 62, (1,), generator=generator, device=generator.device).item()))
-        else:
-            seeds.append(int(torch.randint(0, 2 ** 62, (1,)).item()))
+        seeds.append(None if k == 1 else _draw_seed(generator))
     return seeds
 
 
@@ -1076,8 +1097,6 @@ class _MmuSlotEngine:
         self.tok = torch.empty((slots,), dtype=torch.int64, device=dev)
         self.occ = [None] * slots
         self.use_graph = int(getattr(model, "decode_graph", 1))
-        if getattr(model, "_graph_stream", None) is None:
-            model._graph_stream = torch.cuda.Stream()
 
     def prefill(self, s, r):
         self.fill(s, r)
@@ -1085,34 +1104,17 @@ class _MmuSlotEngine:
 
     def fill(self, s, r):
         """request r into slot s: its K / V^T in the slot's cache, its last row's logits in self.logits[s]"""
-        from .prompting_utils import IntervalMask
-        m, eng, L = self.model, self.eng, self.lens[r]
-        ids = emb = None
-        if self.idx is not None:
-            ids = self.idx[r].to(torch.int64).contiguous()
-        else:
-            emb = self.emb[r].detach().float().contiguous()
-        am = self.masks[r]
-        mask = m._use_mask(eng, am) if isinstance(am, IntervalMask) else (
-            None if am is None else am.detach().float().reshape(1, 1, L, L).contiguous())
-        try:
-            _lib.call("showo_engine_batch_prefill", eng, s, _lib.ptr(ids), _lib.ptr(emb), _lib.ptr(mask), L, _lib.ptr(self.logits[s]),
-                      _lib.stream())
-        finally:
-            _lib.call("showo_engine_use_intervals", eng, None, None)
+        ids, emb = (self.idx[r], None) if self.idx is not None else (None, self.emb[r])
+        _prefill(self.eng, *_prompt_args(self.model, self.eng, ids, emb, self.masks[r]), self.logits[s], slot=s)
 
     def first(self, s, r):
         """request r's first token, drawn from self.logits[s]"""
-        m = self.model
         k = self.top_ks[r]
-        if k == 1:
-            _lib.call("showo_argmax_f32", _lib.ptr(self.logits[s]), m.vocab_size, _lib.ptr(self.tok[s:s + 1]), _lib.stream())
-        else:
-            _sample_call(self.logits[s], m.vocab_size, 0 if k is None else int(k), self.top_ps[r], self.temps[r], self.noises[r],
-                         self.seeds[r], 0, self.tok[s:s + 1])
+        draw = (k == 1, 0 if k is None else int(k), self.top_ps[r], self.temps[r], self.noises[r], self.seeds[r])
+        lp = _first_token(self.logits[s], self.model.vocab_size, self.tok[s:s + 1], draw, self.lps is not None)
         self.occ[s] = r
         if self.lps is not None:
-            self.lps[r] = [_logprob_of(self.logits[s], m.vocab_size, self.tok[s:s + 1])]
+            self.lps[r] = [lp]
         return int(self.tok[s].item())
 
     def logprobs(self, r, n):
@@ -1140,10 +1142,7 @@ class _MmuSlotEngine:
         a_p = (C.c_float * S)(*top_p)
         out = torch.empty((S, m), dtype=torch.int64, device=self.dev)
         lp = None if self.lps is None else torch.empty((S, m), dtype=torch.float32, device=self.dev)
-        cur = torch.cuda.current_stream()
-        gs = self.model._graph_stream
-        gs.wait_stream(cur)
-        with torch.cuda.stream(gs):
+        with _graph_stream_of(self.model):
             if lp is not None:
                 _lib.call("showo_engine_batch_decode_sample_lp", self.eng, _lib.ptr(self.tok), m, _lib.ptr(out), _lib.ptr(self.logits),
                           *(C.cast(a, C.c_void_p) for a in (a_k, a_p, a_t, a_s, a_d, a_n, a_b)), self.eot, C.cast(prod, C.c_void_p),
@@ -1153,12 +1152,66 @@ class _MmuSlotEngine:
                           _lib.ptr(self.tok), m, _lib.ptr(out), _lib.ptr(self.logits),
                           *(C.cast(a, C.c_void_p) for a in ((a_k, a_p, a_t, a_s, a_d, a_n, a_b) if nucleus else (a_k, a_t, a_s, a_d, a_n, a_b))),
                           self.eot, C.cast(prod, C.c_void_p), self.use_graph, _lib.stream())
-        cur.wait_stream(gs)
         if lp is not None:
             for s, r in enumerate(occ):
                 if r is not None:
                     self.lps[r].append(lp[s, :prod[s]])
         return out.tolist(), list(prod)
+
+
+def _per_request(n, temperature, top_k, top_p, exp_noise, attention_mask=None):
+    """(temps, top_ks, top_ps, noises, masks) of a batch call: every scalar-or-list argument as a list with one entry per request (a
+    scalar serves all n, `_exp_noise` None is no table for anyone), top_ps through _nucleus_p; ValueError for a list of another length"""
+    def spread(v):
+        return list(v) if isinstance(v, (list, tuple)) else [v] * n
+
+    temps, top_ks, top_ps, masks = spread(temperature), spread(top_k), spread(top_p), spread(attention_mask)
+    noises = list(exp_noise) if exp_noise is not None else [None] * n
+    if not (len(masks) == len(temps) == len(top_ks) == len(noises) == len(top_ps) == n):
+        raise ValueError("attention_mask / temperature / top_k / top_p / _exp_noise lists need one entry per sequence")
+    return temps, top_ks, [_nucleus_p(q) for q in top_ps], noises, masks
+
+
+def _check_request(model, max_new_tokens, temperature, top_k, noise):
+    """the checks mmu_generate makes on one sampled request's temperature and `_exp_noise`, made before a batch starts"""
+    if top_k != 1 and not temperature > 0:
+        raise ValueError("temperature must be > 0")
+    if top_k != 1 and noise is not None and tuple(noise.shape) != (max_new_tokens, model.vocab_size):
+        raise ValueError("_exp_noise must be [max_new_tokens, vocab_size]")
+
+
+def _batch_noises(top_ks, noises, dev):
+    """the `_exp_noise` tables of the sampled requests as contiguous fp32 tensors on the device (None: greedy, or no table)"""
+    return [None if (k == 1 or z is None) else z.detach().float().contiguous().to(dev) for k, z in zip(top_ks, noises)]
+
+
+def _singles(single, n, return_logprobs):
+    """the sequential form of a batch call: single(0), ..., single(n - 1) in order; return_logprobs: (token lists, log-probabilities)"""
+    outs = [single(b) for b in range(n)]
+    return ([o[0] for o in outs], [o[1] for o in outs]) if return_logprobs else outs
+
+
+def _batch_begin(eng, slots, capacity, wide=False):
+    """open a decode batch of `slots` KV caches of `capacity` rows (showo_engine_batch_begin / _begin_wide).  False: the batch's common
+    capacity (longest prompt + max_new_tokens) does not fit the engine (max_position_embeddings, the single-block decode attention) --
+    the caller then makes n sequential calls, which fail only if a sequence actually reaches the limit before <eot>"""
+    try:
+        _lib.call("showo_engine_batch_begin_wide" if wide else "showo_engine_batch_begin", eng, slots, capacity)
+    except RuntimeError:
+        return False
+    return True
+
+
+def _run_on_slots(eng, n, wide, capacity, slot_engine, max_new_tokens, eot_token, want_lp):
+    """n requests on the slots of a decode batch (`wide`: the slot count of a wide one, else up to 8): begin, `slot_engine(slots)` as the
+    engine side of _mmu_batch_schedule, the schedule.  The int token lists in request order, want_lp: (token lists, log-probability
+    tensors); None when the batch does not fit the engine (nothing but the begin has happened then)."""
+    slots = wide if wide else _mmu_batch_slots(n)
+    if not _batch_begin(eng, slots, capacity, bool(wide)):
+        return None
+    se = slot_engine(slots)
+    out = _mmu_batch_schedule(se, n, slots, max_new_tokens, eot_token)
+    return (out, [se.logprobs(b, len(out[b])) for b in range(n)]) if want_lp else out
 
 
 @torch.no_grad()
@@ -1188,14 +1241,7 @@ def mmu_generate_batch(self, idx=None, input_embeddings=None, attention_mask=Non
     seqs = idx if idx is not None else input_embeddings
     n = len(seqs)
     wide = _mmu_wide_slots(slots, n, getattr(self, "_precision", 0))
-    masks = attention_mask if isinstance(attention_mask, (list, tuple)) else [attention_mask] * n
-    temps = list(temperature) if isinstance(temperature, (list, tuple)) else [temperature] * n
-    top_ks = list(top_k) if isinstance(top_k, (list, tuple)) else [top_k] * n
-    noises = list(_exp_noise) if _exp_noise is not None else [None] * n
-    top_ps = list(top_p) if isinstance(top_p, (list, tuple)) else [top_p] * n
-    if not (len(masks) == len(temps) == len(top_ks) == len(noises) == len(top_ps) == n):
-        raise ValueError("attention_mask / temperature / top_k / top_p / _exp_noise lists need one entry per sequence")
-    top_ps = [_nucleus_p(q) for q in top_ps]
+    temps, top_ks, top_ps, noises, masks = _per_request(n, temperature, top_k, top_p, _exp_noise, attention_mask)
 
     def single(b):
         return self.mmu_generate(idx=None if idx is None else idx[b], input_embeddings=None if input_embeddings is None else input_embeddings[b],
@@ -1203,38 +1249,28 @@ def mmu_generate_batch(self, idx=None, input_embeddings=None, attention_mask=Non
                                  eot_token=eot_token, generator=generator, _exp_noise=noises[b], top_p=top_ps[b],
                                  **({"return_logprobs": True} if return_logprobs else {}))
 
-    def singles():
-        outs = [single(b) for b in range(n)]
-        return ([o[0] for o in outs], [o[1] for o in outs]) if return_logprobs else outs
-
     if int(getattr(self, "_precision", 0)) == 1 or n < 2:
-        return singles()
+        return _singles(single, n, return_logprobs)
     if n <= _MMU_BATCH_MAX and all(k == 1 for k in top_ks) and not return_logprobs:
         return self._mmu_generate_batch_greedy(idx, input_embeddings, masks, max_new_tokens, eot_token, single)
     for b in range(n):
         if seqs[b].shape[0] != 1:
             raise ValueError("every sequence of mmu_generate_batch is one batch-1 mmu_generate call (reference modeling_showo.py:204,229)")
-        if top_ks[b] != 1 and not temps[b] > 0:
-            raise ValueError("temperature must be > 0")
-        if top_ks[b] != 1 and noises[b] is not None and tuple(noises[b].shape) != (max_new_tokens, self.vocab_size):
-            raise ValueError("_exp_noise must be [max_new_tokens, vocab_size]")
+        _check_request(self, max_new_tokens, temps[b], top_ks[b], noises[b])
     eng = self.engine()
     dev = seqs[0].device
     lens = [int(t.shape[1]) for t in seqs]
-    slots = wide if wide else _mmu_batch_slots(n)
-    try:
-        _lib.call("showo_engine_batch_begin_wide" if wide else "showo_engine_batch_begin", eng, slots, max(lens) + max_new_tokens + 1)
-    except RuntimeError:
-        # the batch's common capacity (longest prompt + max_new_tokens) does not fit the engine (max_position_embeddings, the single-block
-        # decode attention): n sequential calls fail only if a sequence actually reaches the limit before <eot>
-        return singles()
-    seeds = _mmu_batch_seeds(top_ks, generator)
-    noises = [None if (k == 1 or z is None) else z.detach().float().contiguous().to(dev) for k, z in zip(top_ks, noises)]
-    se = _MmuSlotEngine(self, eng, idx, input_embeddings, masks, lens, slots, temps, top_ks, seeds, noises, eot_token, dev, top_ps,
-                        want_lp=return_logprobs)
-    out = _mmu_batch_schedule(se, n, slots, max_new_tokens, eot_token)
+
+    def slot_engine(slots):  # (the seeds are drawn behind a begin that succeeded: the sequential calls draw their own)
+        return _MmuSlotEngine(self, eng, idx, input_embeddings, masks, lens, slots, temps, top_ks, _mmu_batch_seeds(top_ks, generator),
+                              _batch_noises(top_ks, noises, dev), eot_token, dev, top_ps, want_lp=return_logprobs)
+
+    out = _run_on_slots(eng, n, wide, max(lens) + max_new_tokens + 1, slot_engine, max_new_tokens, eot_token, return_logprobs)
+    if out is None:
+        return _singles(single, n, return_logprobs)
+    out, lps = out if return_logprobs else (out, None)
     toks = [[torch.tensor(t, device=dev) for t in r] for r in out]
-    return (toks, [se.logprobs(b, len(out[b])) for b in range(n)]) if return_logprobs else toks
+    return (toks, lps) if return_logprobs else toks
 
 
 Showo.mmu_generate_batch = mmu_generate_batch
@@ -1245,51 +1281,28 @@ def _mmu_generate_batch_greedy(self, idx, input_embeddings, masks, max_new_token
     """all-greedy batch of 2..8 sequences: one slot per sequence on showo_engine_batch_decode_greedy (the cfg4 bench leg)"""
     seqs = idx if idx is not None else input_embeddings
     n = len(seqs)
-    from .prompting_utils import IntervalMask
     eng = self.engine()
     dev = seqs[0].device
-    lens = [int(t.shape[1]) for t in seqs]
-    try:
-        _lib.call("showo_engine_batch_begin", eng, n, max(lens) + max_new_tokens + 1)
-    except RuntimeError:
-        # the batch's common capacity (longest prompt + max_new_tokens) does not fit the engine (max_position_embeddings, the single-block
-        # decode attention): n sequential calls fail only if a sequence actually reaches the limit before <eot> (ADVICE r5)
+    if not _batch_begin(eng, n, max(int(t.shape[1]) for t in seqs) + max_new_tokens + 1):
         return [single(b) for b in range(n)]
     logits = torch.empty((n, self.vocab_size), dtype=torch.float32, device=dev)
     tok = torch.empty((n,), dtype=torch.int64, device=dev)
     for b in range(n):
         if seqs[b].shape[0] != 1:
             raise ValueError("every sequence of mmu_generate_batch is one batch-1 mmu_generate call (reference modeling_showo.py:204,229)")
-        ids = emb = None
-        if idx is not None:
-            ids = idx[b].to(torch.int64).contiguous()
-        else:
-            emb = input_embeddings[b].detach().float().contiguous()
-        am = masks[b]
-        if isinstance(am, IntervalMask):
-            mask = self._use_mask(eng, am)
-        else:
-            mask = None if am is None else am.detach().float().reshape(1, 1, lens[b], lens[b]).contiguous()
-        try:
-            _lib.call("showo_engine_batch_prefill", eng, b, _lib.ptr(ids), _lib.ptr(emb), _lib.ptr(mask), lens[b], _lib.ptr(logits[b]), _lib.stream())
-        finally:
-            _lib.call("showo_engine_use_intervals", eng, None, None)
-        _lib.call("showo_argmax_f32", _lib.ptr(logits[b]), self.vocab_size, _lib.ptr(tok[b:b + 1]), _lib.stream())
-    first = tok.tolist()
+        ids, emb = (idx[b], None) if idx is not None else (None, input_embeddings[b])
+        _prefill(eng, *_prompt_args(self, eng, ids, emb, masks[b]), logits[b], slot=b)
+        _first_token(logits[b], self.vocab_size, tok[b:b + 1], _GREEDY_DRAW)
+    first = tok.tolist()  # one read for all n first tokens
     results = [[torch.tensor(t, device=dev)] for t in first]
     done = [(eot_token is not None and t == eot_token) or max_new_tokens <= 1 for t in first]
     use_graph, chunk = int(getattr(self, "decode_graph", 1)), 16
-    if getattr(self, "_graph_stream", None) is None:
-        self._graph_stream = torch.cuda.Stream()
-    cur = torch.cuda.current_stream()
     remaining = max_new_tokens - 1
     while remaining > 0 and not all(done):
         m = min(chunk, remaining)
         outc = torch.empty((n, m), dtype=torch.int64, device=dev)
-        self._graph_stream.wait_stream(cur)
-        with torch.cuda.stream(self._graph_stream):
+        with _graph_stream_of(self):
             _lib.call("showo_engine_batch_decode_greedy", eng, _lib.ptr(tok), m, _lib.ptr(outc), _lib.ptr(logits), use_graph, _lib.stream())
-        cur.wait_stream(self._graph_stream)
         rows = outc.tolist()
         for b in range(n):
             for t in rows[b]:
@@ -1300,8 +1313,6 @@ def _mmu_generate_batch_greedy(self, idx, input_embeddings, masks, max_new_token
                     done[b] = True
         remaining -= m
     return [r[:max_new_tokens] for r in results]
-
-
 
 
 Showo._mmu_generate_batch_greedy = _mmu_generate_batch_greedy
@@ -1337,8 +1348,6 @@ class _SessionEngine:
         self.logits = torch.empty((model.vocab_size,), dtype=torch.float32, device=self.dev)
         self.logits0 = None
         self.tok = torch.empty((1,), dtype=torch.int64, device=self.dev)
-        if getattr(model, "_graph_stream", None) is None:
-            model._graph_stream = torch.cuda.Stream()
 
     def state(self):
         """(cache length, prompt length, capacity, epoch) of the engine's decode cache"""
@@ -1362,19 +1371,7 @@ class _SessionEngine:
         return self.state()[0]
 
     def prefill(self, idx, input_embeddings, attention_mask):
-        from .prompting_utils import IntervalMask
-        m, eng = self.model, self.eng
-        ids = None if idx is None else idx.to(torch.int64).contiguous()
-        emb = None if input_embeddings is None else input_embeddings.detach().float().contiguous()
-        L = (ids if ids is not None else emb).shape[1]
-        if isinstance(attention_mask, IntervalMask):
-            mask = m._use_mask(eng, attention_mask)
-        else:
-            mask = None if attention_mask is None else attention_mask.detach().float().reshape(1, 1, L, L).contiguous()
-        try:
-            _lib.call("showo_engine_prefill", eng, _lib.ptr(ids), _lib.ptr(emb), _lib.ptr(mask), L, _lib.ptr(self.logits), _lib.stream())
-        finally:
-            _lib.call("showo_engine_use_intervals", eng, None, None)
+        L = _prefill(self.eng, *_prompt_args(self.model, self.eng, idx, input_embeddings, attention_mask), self.logits)
         self.logits0 = self.logits.clone()
         return L
 
@@ -1398,43 +1395,8 @@ class _SessionEngine:
     def run(self, max_new_tokens, greedy, k, temperature, noise, seed, eot_token, top_p=None, return_logprobs=False):
         """Showo.mmu_generate behind its prefill: the first token from the current logits, the rest from the device loop in chunks;
         return_logprobs: (tokens, their log-probabilities fp32 [len(tokens)])"""
-        m, eng, logits, tok = self.model, self.eng, self.logits, self.tok
-        if greedy:
-            _lib.call("showo_argmax_f32", _lib.ptr(logits), m.vocab_size, _lib.ptr(tok), _lib.stream())
-        else:
-            _sample_call(logits, m.vocab_size, k, top_p, temperature, noise, seed, 0, tok)
-        lps = [_logprob_of(logits, m.vocab_size, tok)] if return_logprobs else None
-
-        def done(result):
-            return (result, torch.cat(lps)[:len(result)]) if return_logprobs else result
-
-        result = [int(tok.item())]
-        if (eot_token is not None and result[0] == eot_token) or max_new_tokens <= 1:
-            return done(result)
-        use_graph, chunk = int(getattr(m, "decode_graph", 1)), 16
-        cur = torch.cuda.current_stream()
-        remaining = max_new_tokens - 1
-        while remaining > 0:
-            n = min(chunk, remaining)
-            outc = torch.empty((n,), dtype=torch.int64, device=self.dev)
-            if return_logprobs:
-                lps.append(torch.empty((n,), dtype=torch.float32, device=self.dev))
-            m._graph_stream.wait_stream(cur)
-            with torch.cuda.stream(m._graph_stream):
-                if return_logprobs:
-                    _decode_lp_call(eng, tok, n, outc, logits, greedy, None if greedy else k, top_p, temperature, None if greedy else noise,
-                                    0 if greedy else seed, max_new_tokens - remaining, lps[-1], use_graph)
-                elif greedy:
-                    _lib.call("showo_engine_decode_greedy", eng, _lib.ptr(tok), n, _lib.ptr(outc), _lib.ptr(logits), use_graph, _lib.stream())
-                else:
-                    _decode_sample_call(eng, tok, n, outc, logits, k, top_p, temperature, noise, seed, max_new_tokens - remaining, use_graph)
-            cur.wait_stream(m._graph_stream)
-            for t in outc.tolist():
-                result.append(t)
-                if eot_token is not None and t == eot_token:
-                    return done(result)
-            remaining -= n
-        return done(result)
+        return _decode_batch1(self.model, self.eng, self.logits, self.tok, max_new_tokens, (greedy, k, top_p, temperature, noise, seed),
+                              eot_token, return_logprobs)
 
     def score(self, ids, Ln, use_prefix_logits):
         """log-probabilities / ranks [Ln] of the rows ids [1, Ln] appended to the cache (showo_engine_prefill_append_score): row j from
@@ -1451,18 +1413,12 @@ class _SessionEngine:
                   slots=None):
         """n continuations of the cache [0, length) on the slots of a decode batch; None when the batch does not fit the engine;
         return_logprobs: (token lists, log-probability tensors); slots: the slot count of a wide batch (_mmu_wide_slots)"""
-        n = len(rows)
-        wide = slots
-        slots = wide if wide else _mmu_batch_slots(n)
-        try:
-            _lib.call("showo_engine_batch_begin_wide" if wide else "showo_engine_batch_begin", self.eng, slots,
-                      length + max(lens) + max_new_tokens + 1)
-        except RuntimeError:
-            return None
-        se = _SessionSlotEngine(self.model, self.eng, rows, lens, slots, temps, top_ks, seeds, noises, eot_token, self.dev, top_ps,
-                                want_lp=return_logprobs)
-        out = _mmu_batch_schedule(se, n, slots, max_new_tokens, eot_token)
-        return (out, [se.logprobs(b, len(out[b])) for b in range(n)]) if return_logprobs else out
+        def slot_engine(slots):
+            return _SessionSlotEngine(self.model, self.eng, rows, lens, slots, temps, top_ks, seeds, noises, eot_token, self.dev, top_ps,
+                                      want_lp=return_logprobs)
+
+        return _run_on_slots(self.eng, len(rows), slots, length + max(lens) + max_new_tokens + 1, slot_engine, max_new_tokens, eot_token,
+                             return_logprobs)
 
 
 class _SessionRecompute:
@@ -1481,8 +1437,7 @@ class _SessionRecompute:
     def cached_rows(self):
         return self.emb.shape[1]
 
-    def embed(self, token):
-        return self.model.showo.model.embed_tokens.weight.detach()[int(token)].float().reshape(1, 1, -1)
+    embed = _SessionEngine.embed
 
     def prefill(self, idx, input_embeddings, attention_mask):
         if input_embeddings is not None:
@@ -1499,12 +1454,7 @@ class _SessionRecompute:
     def append(self, ids, emb, Ln):
         if emb is None:
             emb = self.model.showo.model.embed_tokens.weight.detach().float()[ids]
-        L = self.emb.shape[1]
-        neg = float(torch.finfo(torch.float32).min)
-        grown = torch.full((1, 1, L + Ln, L + Ln), neg, dtype=torch.float32, device=self.dev)
-        grown[0, 0, :L, :L] = self.mask[0, 0]
-        grown[0, 0, L:, :L] = self.mask[0, 0, L - 1]  # every new row: the last row + causal among the new ones
-        grown[0, 0, L:, L:].masked_fill_(torch.ones((Ln, Ln), dtype=torch.bool, device=self.dev).tril(), 0.0)
+        grown = _grow_mask(self.mask, self.emb.shape[1], Ln)
         self.emb, self.mask = torch.cat([self.emb, emb.reshape(1, Ln, -1)], dim=1).contiguous(), grown
 
     def rewind(self, length):
@@ -1603,24 +1553,12 @@ class MmuSession:
         return ids.contiguous(), None, int(ids.shape[1])
 
     def _draw_args(self, max_new_tokens, temperature, top_k, generator, noise, top_p=None):
-        """(greedy, k, noise, seed, p) exactly as mmu_generate derives them (one seed draw per sampled call; p: None or the nucleus
-        top_p inside (0, 1))"""
+        """mmu_generate's _draw_params, with the session's own check (a session call emits at least one token) between the top_p
+        check and the others; a checked p passes _nucleus_p unchanged"""
         p = _nucleus_p(top_p)
         if max_new_tokens < 1:
             raise ValueError("max_new_tokens must be >= 1")
-        if top_k == 1:
-            return True, 1, None, 0, p
-        if not temperature > 0:
-            raise ValueError("temperature must be > 0")
-        if generator is not None:
-            seed = int(torch.randint(0, 2 ** 62, (1,), generator=generator, device=generator.device).item())
-        else:
-            seed = int(torch.randint(0, 2 ** 62, (1,)).item())
-        if noise is not None:
-            noise = noise.detach().float().contiguous()
-            if tuple(noise.shape) != (max_new_tokens, self.model.vocab_size):
-                raise ValueError("_exp_noise must be [max_new_tokens, vocab_size]")
-        return False, 0 if top_k is None else int(top_k), noise, seed, p
+        return _draw_params(self.model, max_new_tokens, temperature, top_k, p, generator, noise)
 
     @torch.no_grad()
     def generate(self, idx=None, input_embeddings=None, max_new_tokens=100, temperature=1.0, top_k=None, eot_token=None, generator=None,
@@ -1703,13 +1641,7 @@ class MmuSession:
         seqs = idx if idx is not None else input_embeddings
         n = len(seqs)
         wide = _mmu_wide_slots(slots, n, getattr(self.model, "_precision", 0))
-        temps = list(temperature) if isinstance(temperature, (list, tuple)) else [temperature] * n
-        top_ks = list(top_k) if isinstance(top_k, (list, tuple)) else [top_k] * n
-        noises = list(_exp_noise) if _exp_noise is not None else [None] * n
-        top_ps = list(top_p) if isinstance(top_p, (list, tuple)) else [top_p] * n
-        if not (len(temps) == len(top_ks) == len(noises) == len(top_ps) == n):
-            raise ValueError("temperature / top_k / top_p / _exp_noise lists need one entry per sequence")
-        top_ps = [_nucleus_p(q) for q in top_ps]
+        temps, top_ks, top_ps, noises, _ = _per_request(n, temperature, top_k, top_p, _exp_noise)
 
         def single(b):
             mark = self.mark()
@@ -1721,12 +1653,8 @@ class MmuSession:
             finally:
                 self.rewind(mark)
 
-        def singles():
-            outs = [single(b) for b in range(n)]
-            return ([o[0] for o in outs], [o[1] for o in outs]) if return_logprobs else outs
-
         if n < 2 or not self._be.batched:
-            return singles()
+            return _singles(single, n, return_logprobs)
         if max_new_tokens < 1:
             raise ValueError("max_new_tokens must be >= 1")
         rows, lens = [], []
@@ -1734,16 +1662,13 @@ class MmuSession:
             ids, emb, Ln = self._rows(idx[b] if idx is not None else None, input_embeddings[b] if input_embeddings is not None else None)
             if Ln == 0:
                 raise ValueError("generate_batch: every sequence needs rows (or the session a pending token)")
-            if top_ks[b] != 1 and not temps[b] > 0:
-                raise ValueError("temperature must be > 0")
-            if top_ks[b] != 1 and noises[b] is not None and tuple(noises[b].shape) != (max_new_tokens, self.model.vocab_size):
-                raise ValueError("_exp_noise must be [max_new_tokens, vocab_size]")
+            _check_request(self.model, max_new_tokens, temps[b], top_ks[b], noises[b])
             rows.append((ids, emb))
             lens.append(Ln)
         gen_state = None if generator is None else generator.get_state()
         seeds = _mmu_batch_seeds(top_ks, generator)
         dev = self._be.dev
-        noises = [None if (k == 1 or z is None) else z.detach().float().contiguous().to(dev) for k, z in zip(top_ks, noises)]
+        noises = _batch_noises(top_ks, noises, dev)
         nucleus = {} if all(q is None for q in top_ps) else {"top_ps": top_ps}
         if return_logprobs:
             nucleus["return_logprobs"] = True
@@ -1753,11 +1678,10 @@ class MmuSession:
         if out is None:  # the batch's common capacity does not fit the engine: the sequential calls, drawing the same seeds again
             if gen_state is not None:
                 generator.set_state(gen_state)
-            return singles()
-        if return_logprobs:
-            out, lps = out
-            return [[torch.tensor(t, device=dev) for t in r] for r in out], lps
-        return [[torch.tensor(t, device=dev) for t in r] for r in out]
+            return _singles(single, n, return_logprobs)
+        out, lps = out if return_logprobs else (out, None)
+        toks = [[torch.tensor(t, device=dev) for t in r] for r in out]
+        return (toks, lps) if return_logprobs else toks
 
 
 def mmu_session(self, idx=None, input_embeddings=None, attention_mask=None):
@@ -1799,6 +1723,17 @@ def _dense_mask_of(attention_mask, L, device):
     return attention_mask.detach().float().reshape(1, 1, L, L).to(device)
 
 
+def _grow_mask(mask, L, Ln):
+    """the dense [1, 1, L, L] mask grown by Ln decode rows: the new columns hidden from the old rows (the reference pads them with
+    finfo(dtype).min, :206-209), every new row = the last row + causal among the new ones (:203-217)"""
+    neg = float(torch.finfo(torch.float32).min)
+    grown = torch.full((1, 1, L + Ln, L + Ln), neg, dtype=torch.float32, device=mask.device)
+    grown[0, 0, :L, :L] = mask[0, 0]
+    grown[0, 0, L:, :L] = mask[0, 0, L - 1]
+    grown[0, 0, L:, L:].masked_fill_(torch.ones((Ln, Ln), dtype=torch.bool, device=mask.device).tril(), 0.0)
+    return grown
+
+
 def _mmu_generate_recompute(self, idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, greedy, sampling,
                             top_p=None, return_logprobs=False):
     """Accuracy mode (`set_precision(1)`): the reference's OWN algorithm (models/modeling_showo.py:190-240) -- no KV cache, the whole
@@ -1814,7 +1749,6 @@ def _mmu_generate_recompute(self, idx, input_embeddings, attention_mask, max_new
         emb = self.showo.model.embed_tokens.weight.detach().float()[idx.to(torch.int64)].contiguous()
     L = emb.shape[1]
     mask = _dense_mask_of(attention_mask, L, dev)
-    neg = float(torch.finfo(torch.float32).min)  # the reference pads the new column with finfo(dtype).min (:206-209)
     row = torch.empty((1,), dtype=torch.int32, device=dev)
     logits = torch.empty((self.vocab_size,), dtype=torch.float32, device=dev)
     tok = torch.empty((1,), dtype=torch.int64, device=dev)
@@ -1834,11 +1768,7 @@ def _mmu_generate_recompute(self, idx, input_embeddings, attention_mask, max_new
         result.append(torch.tensor(t, device=dev))
         if eot_token is not None and t == eot_token:
             break
-        grown = torch.full((1, 1, L + 1, L + 1), neg, dtype=torch.float32, device=dev)
-        grown[0, 0, :L, :L] = mask[0, 0]
-        grown[0, 0, L, :L] = mask[0, 0, L - 1]
-        grown[0, 0, L, L] = 0.0
-        mask = grown
+        mask = _grow_mask(mask, L, 1)
         emb = torch.cat([emb, self.showo.model.embed_tokens.weight.detach().float()[tok].reshape(1, 1, -1)], dim=1).contiguous()
         L += 1
     if return_logprobs:
