@@ -1108,11 +1108,10 @@ int attn_decode_co_batch(const bf16_t* qkv, const float* qw, const float* qb, co
 }
 int attn_decode_fused(const bf16_t* qkv, const float* qw, const float* qb, const float* kw, const float* kb, const float* cosT,
                       const float* sinT, bf16_t* K, bf16_t* Vt, const int32_t* iv, bf16_t* O, int nH, int rot, float eps, int pos,
-                      int Lcap, int Lp, hipStream_t s, const bf16_t* W2, const bf16_t* ffn, const float* b2, int F, int Hout, float* y2,
-                      int co_blocks, const DecodePrefetch* pfp, int op, const float* s2) {
+                      int Lcap, int Lp, hipStream_t s, const OutGemvArgs* fc2, int co_blocks, const DecodePrefetch* pfp, int op) {
     if ((Lp % 64) || Lp <= pos || Lcap <= pos) return set_error_msg(1, "decode attention: bad Lp/Lcap");
     DecodePrefetch pf{};
-    if (pfp && W2) pf = *pfp;
+    if (pfp && fc2) pf = *pfp;
     AttnArgs a;
     a.Q = nullptr; a.K = K; a.Vt = Vt; a.iv = iv; a.flag = nullptr; a.dense = nullptr; a.O = O;
     a.B = 1; a.nH = nH; a.Lq = 1; a.Lk = pos + 1; a.Lcap = Lcap; a.Lp = Lp; a.ldo = nH * 64; a.lse = nullptr;
@@ -1121,12 +1120,13 @@ int attn_decode_fused(const bf16_t* qkv, const float* qw, const float* qb, const
     DecPrep f{qkv, qw, qb, kw, kb, cosT, sinT, rot, pos, eps};
     const size_t smem = (size_t)(((g_decode_pos_dev ? Lcap : pos + 1) + 511) & ~511) * sizeof(float);
     if (smem > 60000) return set_error_msg(5, "decode attention: cache longer than the single-block kernel supports");
-    if (W2) {  // co-scheduled fc2 role (see attn_decode_co_kernel): needs K1 = 4 x 2048
-        if (F != 8192 || !y2 || !ffn || !b2) return set_error_msg(1, "decode attention: co-scheduled fc2 needs F = 8192 and y2");
-        if (s2 && op) return set_error_msg(1, "decode attention: int8 fc2 weights take bf16 activations");
-        showo::OutGemvArgs g{nullptr, nullptr, nullptr, nullptr, 0, W2, ffn, b2, F, Hout, y2, nullptr, s2};
+    if (fc2) {  // co-scheduled fc2 role (see attn_decode_co_kernel): needs K1 = 4 x 2048; s1: W1 is fc2's int8 image (precision 3)
+        const int F = fc2->K1;
+        if (!fc2->W1 || F != 8192 || !fc2->y2 || !fc2->a1 || !fc2->b1) return set_error_msg(1, "decode attention: co-scheduled fc2 needs F = 8192 and y2");
+        if (fc2->s1 && op) return set_error_msg(1, "decode attention: int8 fc2 weights take bf16 activations");
+        showo::OutGemvArgs g{nullptr, nullptr, nullptr, nullptr, 0, fc2->W1, fc2->a1, fc2->b1, F, fc2->N, fc2->y2, nullptr, fc2->s1};
         const size_t smem2 = smem > (size_t)F * sizeof(bf16_t) ? smem : (size_t)F * sizeof(bf16_t);
-        if (s2) attn_decode_co_kernel<false, true><<<dim3(nH + co_blocks + pf.blocks, 1), dim3(1024), smem2, s>>>(a, f, g, pf);
+        if (fc2->s1) attn_decode_co_kernel<false, true><<<dim3(nH + co_blocks + pf.blocks, 1), dim3(1024), smem2, s>>>(a, f, g, pf);
         else if (op) attn_decode_co_kernel<true><<<dim3(nH + co_blocks + pf.blocks, 1), dim3(1024), smem2, s>>>(a, f, g, pf);
         else attn_decode_co_kernel<false><<<dim3(nH + co_blocks + pf.blocks, 1), dim3(1024), smem2, s>>>(a, f, g, pf);
     } else if (op) {

@@ -3,8 +3,15 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <cstdlib>
 
 namespace showo {
+
+// an integer switch or knob from the environment (unset: dflt); every caller reads its own once per process and caches it
+inline int env_flag(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
 
 typedef uint16_t bf16_t;  // raw bfloat16 bits
 typedef short s16x8 __attribute__((ext_vector_type(8)));

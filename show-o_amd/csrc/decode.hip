@@ -11,6 +11,10 @@
 // lm_head), a wave owns whole output columns and splits K over its lanes exactly like gemv_kernel (gemm.hip) -- same
 // lane split, same accumulation order, same epilogue expressions -- so the fused step is bit-identical to the unfused one.
 // The next 4 x 16-B weight loads of a wave are always in flight while the current ones are multiplied.
+//
+// Host side of this file: decode_layer_ops / decode_head_ops (which weight images a layer's launches stream), the launchers
+// decode_ln_gemv2 / decode_out_gemv2 (argument structs of decode_common.h), and decode_layers_b1, the ONE batch-1 layer step that
+// run_layers (engine.hip) calls for a one-token step.  The KV cache and the token loop around it are in decode_engine.hip.
 #include "common.h"
 #include "engine.h"
 #include "decode_common.h"
@@ -121,7 +125,7 @@ __global__ __launch_bounds__(256) void ln_gemv2_kernel(LnGemvArgs g) {  // H <= 
 
 // C = 2048-element chunks per output column (dense chunks first, then fc2 chunks), ALL of them in flight per wave: a wave
 // streams 20 KB per column at the real shape and only 8 waves per CU exist, so depth is what hides the HBM latency.
-// MODE 0: x[n] = (x[n] + (dense + bd)) + (fc2 + b2) in one launch.  The forked decode layer (engine.hip) splits it so that fc2 --
+// MODE 0: x[n] = (x[n] + (dense + bd)) + (fc2 + b2) in one launch.  The co-scheduled decode layer (decode_layers_b1) splits it so that fc2 --
 // which does not depend on the attention -- streams its 33.5 MB of weights WHILE the attention kernel runs:
 //   MODE 1 (K0 = 0): y2[n] = fc2 + b2            (side stream, next to the attention kernel)
 //   MODE 2 (K1 = 0): x[n] = (x[n] + (dense + bd)) + y2[n]   (after the join)
@@ -187,84 +191,101 @@ namespace showo {
 
 bool decode_fused_shapes_ok(int H, int F) { return (H % 8) == 0 && (F % 8) == 0 && H <= 2048 && F <= 8192; }
 
+DecodeLayerOps decode_layer_ops(const showo_engine* e, int li) {
+    const Layer& l = e->layers[li];
+    auto q = [](const int8_t* w) { return reinterpret_cast<const bf16_t*>(w); };
+    if (e->precision == 3) return DecodeLayerOps{q(l.qqkv), q(l.q1), q(l.qd), q(l.q2), l.sqkv, l.s1, l.sd, l.s2, l.bqkv, l.b1, l.bd, l.b2};
+    return DecodeLayerOps{l.wqkv, l.w1, l.wd, l.w2, nullptr, nullptr, nullptr, nullptr, l.bqkv, l.b1, l.bd, l.b2};
+}
+DecodeHeadOps decode_head_ops(const showo_engine* e, int col0) {
+    if (e->precision == 3) return DecodeHeadOps{reinterpret_cast<const bf16_t*>(e->qlm + (int64_t)col0 * e->H), e->slm + col0, e->blm + col0};
+    return DecodeHeadOps{e->wlm + (int64_t)col0 * e->H, nullptr, e->blm + col0};
+}
+
 // x -> LN(lnw, lnb) -> { out0 = bf16(W0 h + b0) | outf = fp32(W0 h + b0) } and out1 = bf16(gelu(W1 h + b1))  (N1 may be 0)
-int decode_ln_gemv2(const float* x, const float* lnw, const float* lnb, float eps, int H, const bf16_t* W0, const float* b0,
-                    bf16_t* out0, float* outf, int N0, const bf16_t* W1, const float* b1, bf16_t* out1, int N1, hipStream_t s, int op,
-                    const float* s0, const float* s1) {
-    LnGemvArgs g{x, lnw, lnb, eps, H, W0, b0, out0, outf, N0, W1, b1, out1, N1, s0, s1};
-    if (s0 && (op || (N1 && !s1) || (H % 16)))
+int decode_ln_gemv2(const LnGemvBArgs& a, hipStream_t s, int op) {
+    LnGemvArgs g{a.x, a.lnw, a.lnb, a.eps, a.H, a.W0, a.b0, a.out0, a.outf, a.N0, a.W1, a.b1, a.out1, a.N1, a.s0, a.s1};
+    if (g.s0 && (op || (g.N1 && !g.s1) || (g.H % 16)))
         return set_error_msg(1, "decode_ln_gemv2: int8 weights take bf16 activations, a scale per matrix and H % 16 == 0");
     // two weight rows in flight per wave (12 rows per block; a wave's third row is requested behind its first FMA).  Four rows -- the whole
     // layer matrix requested at kernel start -- measured SLOWER on cfg4 (0.983-0.992 vs 0.958-0.969 ms per token, round 2: 123 VGPRs halve
     // the resident waves and the single burst queues behind itself); that instance left the library in round 6.
-    const dim3 grid(pick_blocks(N0 + N1, 12, showo::decode_tuning().ln_blocks));
+    const dim3 grid(pick_blocks(g.N0 + g.N1, 12, showo::decode_tuning().ln_blocks));
+    const size_t smem = (size_t)g.H * sizeof(bf16_t);
     // (int8 instance: four rows in flight per wave -- the bytes in flight of the bf16 instance's two -- measured no faster on cfg4 in a
     // one-process A/B; that instance is not built)
-    if (s0) ln_gemv2_kernel<2, false, true><<<grid, dim3(256), (size_t)H * sizeof(bf16_t), s>>>(g);
-    else if (op) ln_gemv2_kernel<2, true><<<grid, dim3(256), (size_t)H * sizeof(bf16_t), s>>>(g);
-    else ln_gemv2_kernel<2><<<grid, dim3(256), (size_t)H * sizeof(bf16_t), s>>>(g);
+    if (g.s0) ln_gemv2_kernel<2, false, true><<<grid, dim3(256), smem, s>>>(g);
+    else if (op) ln_gemv2_kernel<2, true><<<grid, dim3(256), smem, s>>>(g);
+    else ln_gemv2_kernel<2><<<grid, dim3(256), smem, s>>>(g);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return set_error_hip(e, "ln_gemv2 launch", __FILE__, __LINE__);
     return 0;
 }
 
-// x[n] += (W0[n,:] a0 + b0[n]);  x[n] += (W1[n,:] a1 + b1[n])
-int decode_out_gemv2(float* x, const bf16_t* W0, const bf16_t* a0, const float* b0, int K0, const bf16_t* W1, const bf16_t* a1,
-                     const float* b1, int K1, int N, hipStream_t s, int mode, float* y2, int op, const float* s0, const float* s1) {
-    OutGemvArgs g{x, W0, a0, b0, K0, W1, a1, b1, K1, N, y2, s0, s1};
-    if ((s0 || s1) && (op || (mode != 1 && !s0) || (mode != 2 && !s1) || (K0 % 16) || (K1 % 16)))
-        return set_error_msg(1, "decode_out_gemv2: int8 weights take bf16 activations, a scale per matrix and K % 16 == 0");
-    if (mode == 1) g.K0 = 0;
-    if (mode == 2) g.K1 = 0;
-    if (mode && !y2) return set_error_msg(1, "decode_out_gemv2: y2 required");
-    const int C = (g.K0 + 2047) / 2048 + (g.K1 + 2047) / 2048;
-    const dim3 grid(pick_blocks(N, 8, showo::decode_tuning().out_blocks));
-    const size_t smem = (size_t)(g.K0 + g.K1) * sizeof(bf16_t);
-    if (s0 || s1) {  // int8 weight images (precision 3)
-        if (mode == 1 && C == 4) out_gemv2_kernel<4, 1, false, true><<<grid, dim3(512), smem, s>>>(g);
-        else if (mode == 1 && C >= 1 && C <= 3) out_gemv2_kernel<3, 1, false, true><<<grid, dim3(512), smem, s>>>(g);
-        else if (mode == 2 && C == 1) out_gemv2_kernel<1, 2, false, true><<<grid, dim3(512), smem, s>>>(g);
-        else if (mode != 0) return set_error_msg(1, "decode_out_gemv2: unsupported K0/K1 for the forked layer");
-        else switch (C) {
-            case 2: out_gemv2_kernel<2, 0, false, true><<<grid, dim3(512), smem, s>>>(g); break;
-            case 3: out_gemv2_kernel<3, 0, false, true><<<grid, dim3(512), smem, s>>>(g); break;
-            case 4: out_gemv2_kernel<4, 0, false, true><<<grid, dim3(512), smem, s>>>(g); break;
-            case 5: out_gemv2_kernel<5, 0, false, true><<<grid, dim3(512), smem, s>>>(g); break;
-            default: return set_error_msg(1, "decode_out_gemv2: unsupported K0/K1 (decode_fused_shapes_ok)");
-        }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return set_error_hip(e, "out_gemv2 launch", __FILE__, __LINE__);
-        return 0;
-    }
-    if (op) {  // IEEE-half operands (precision 2): the shapes of the fused layer at Phi-1.5's size
-        if (mode == 1 && C == 4) out_gemv2_kernel<4, 1, true><<<grid, dim3(512), smem, s>>>(g);
-        else if (mode == 1 && C >= 1 && C <= 3) out_gemv2_kernel<3, 1, true><<<grid, dim3(512), smem, s>>>(g);
-        else if (mode == 2 && C == 1) out_gemv2_kernel<1, 2, true><<<grid, dim3(512), smem, s>>>(g);
-        else if (mode != 0) return set_error_msg(1, "decode_out_gemv2: unsupported K0/K1 for the forked layer");
-        else switch (C) {
-            case 2: out_gemv2_kernel<2, 0, true><<<grid, dim3(512), smem, s>>>(g); break;
-            case 3: out_gemv2_kernel<3, 0, true><<<grid, dim3(512), smem, s>>>(g); break;
-            case 4: out_gemv2_kernel<4, 0, true><<<grid, dim3(512), smem, s>>>(g); break;
-            case 5: out_gemv2_kernel<5, 0, true><<<grid, dim3(512), smem, s>>>(g); break;
-            default: return set_error_msg(1, "decode_out_gemv2: unsupported K0/K1 (decode_fused_shapes_ok)");
-        }
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return set_error_hip(e, "out_gemv2 launch", __FILE__, __LINE__);
-        return 0;
-    }
-    if (mode == 1 && C == 4) out_gemv2_kernel<4, 1><<<grid, dim3(512), smem, s>>>(g);
-    else if (mode == 1 && C >= 1 && C <= 3) out_gemv2_kernel<3, 1><<<grid, dim3(512), smem, s>>>(g);
-    else if (mode == 2 && C == 1) out_gemv2_kernel<1, 2><<<grid, dim3(512), smem, s>>>(g);
+// the (mode, C) instances of one operand type: the forked layer's two halves at Phi-1.5's shape, the one-launch form for C = 2..5
+template <bool F16, bool Q8>
+static int launch_out_gemv2(const OutGemvArgs& g, int mode, int C, dim3 grid, size_t smem, hipStream_t s) {
+    if (mode == 1 && C == 4) out_gemv2_kernel<4, 1, F16, Q8><<<grid, dim3(512), smem, s>>>(g);
+    else if (mode == 1 && C >= 1 && C <= 3) out_gemv2_kernel<3, 1, F16, Q8><<<grid, dim3(512), smem, s>>>(g);
+    else if (mode == 2 && C == 1) out_gemv2_kernel<1, 2, F16, Q8><<<grid, dim3(512), smem, s>>>(g);
     else if (mode != 0) return set_error_msg(1, "decode_out_gemv2: unsupported K0/K1 for the forked layer");
     else switch (C) {
-        case 2: out_gemv2_kernel<2, 0><<<grid, dim3(512), smem, s>>>(g); break;
-        case 3: out_gemv2_kernel<3, 0><<<grid, dim3(512), smem, s>>>(g); break;
-        case 4: out_gemv2_kernel<4, 0><<<grid, dim3(512), smem, s>>>(g); break;
-        case 5: out_gemv2_kernel<5, 0><<<grid, dim3(512), smem, s>>>(g); break;
+        case 2: out_gemv2_kernel<2, 0, F16, Q8><<<grid, dim3(512), smem, s>>>(g); break;
+        case 3: out_gemv2_kernel<3, 0, F16, Q8><<<grid, dim3(512), smem, s>>>(g); break;
+        case 4: out_gemv2_kernel<4, 0, F16, Q8><<<grid, dim3(512), smem, s>>>(g); break;
+        case 5: out_gemv2_kernel<5, 0, F16, Q8><<<grid, dim3(512), smem, s>>>(g); break;
         default: return set_error_msg(1, "decode_out_gemv2: unsupported K0/K1 (decode_fused_shapes_ok)");
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return set_error_hip(e, "out_gemv2 launch", __FILE__, __LINE__);
+    return 0;
+}
+
+// x[n] += (W0[n,:] a0 + b0[n]);  x[n] += (W1[n,:] a1 + b1[n])
+int decode_out_gemv2(const OutGemvArgs& args, hipStream_t s, int mode, int op) {
+    OutGemvArgs g = args;
+    const bool q8 = g.s0 || g.s1;  // int8 weight images (precision 3)
+    if (q8 && (op || (mode != 1 && !g.s0) || (mode != 2 && !g.s1) || (g.K0 % 16) || (g.K1 % 16)))
+        return set_error_msg(1, "decode_out_gemv2: int8 weights take bf16 activations, a scale per matrix and K % 16 == 0");
+    if (mode == 1) g.K0 = 0;
+    if (mode == 2) g.K1 = 0;
+    if (mode && !g.y2) return set_error_msg(1, "decode_out_gemv2: y2 required");
+    const int C = (g.K0 + 2047) / 2048 + (g.K1 + 2047) / 2048;
+    const dim3 grid(pick_blocks(g.N, 8, showo::decode_tuning().out_blocks));
+    const size_t smem = (size_t)(g.K0 + g.K1) * sizeof(bf16_t);
+    if (q8) return launch_out_gemv2<false, true>(g, mode, C, grid, smem, s);
+    if (op) return launch_out_gemv2<true, false>(g, mode, C, grid, smem, s);  // IEEE-half operands (precision 2)
+    return launch_out_gemv2<false, false>(g, mode, C, grid, smem, s);
+}
+
+// AR decode step: three launches per layer.  Co-scheduled layer (co, the default at Phi-1.5's shape): the attention launch carries extra
+// blocks that stream the fc2 weights into y2 (attention.hip, attn_decode_co_kernel) -- fc2 does not depend on the attention (Phi's block
+// is parallel-residual) -- and the third launch adds dense(attn) and y2:
+//   LN + qkv GEMV + fc1 GEMV  ->  [ attention (32 blocks) || fc2 GEMV -> y2 (co_blocks) ]  ->  dense GEMV + both residual adds
+// Same arithmetic and parenthesisation as the plain chain (x = (x + (dense + bd)) + (fc2 + b2)): bit-identical results.
+// Measured (one box, cfg4): chain 857-861 tokens/s; co-scheduled 922-928 with 224 fc2 blocks, 965 with 128, 969 with 96.  (A stream
+// fork / join of the same overlap was SLOWER than the chain, 705-711 vs 843-846 tokens/s -- every fork / join edge of the per-token
+// graph costs more than the overlap buys -- and left the library in round 6; so did folding the third launch into the second behind an
+// in-launch hand-off, profiles/r6_decode_merge_ab.txt.)  !co (SHOWO_DECODE_FORK=0 / showo_decode_set_impl(2), other shapes): the chain.
+int decode_layers_b1(showo_engine* e, int op, const KVDest& kv, const int32_t* iv, int pos0, bool co, hipStream_t s) {
+    const int H = e->H, F = e->F;
+    const int co_blocks = showo::decode_tuning().co_blocks;
+    if (co && !e->y2) TRY(e->alloc(&e->y2, H));
+    for (int li = 0; li < e->nL; ++li) {
+        const Layer& l = e->layers[li];
+        const DecodeLayerOps w = decode_layer_ops(e, li);
+        LnGemvBArgs a{e->x, l.ln_w, l.ln_b, e->cfg.ln_eps, H, w.Wqkv, w.bqkv, e->qkv, nullptr, 3 * H, 3 * H, w.W1, w.b1, e->ffn, F, F};
+        a.s0 = w.sqkv; a.s1 = w.s1;
+        const OutGemvArgs o{e->x, w.Wd, e->attn, w.bd, H, w.W2, e->ffn, w.b2, F, H, co ? e->y2 : nullptr, w.sd, w.s2};
+        TRY(decode_ln_gemv2(a, s, op));
+        // the prefetch role reads ahead in the bf16 / fp16 images: none where the launches stream the int8 images instead
+        DecodePrefetch pf{};
+        if (co && !w.sqkv) decode_prefetch_plan(e, li, &pf);
+        TRY(attn_decode_fused(e->qkv, l.qln_w, l.qln_b, l.kln_w, l.kln_b, e->cosT, e->sinT, kv.k + li * kv.k_lstride, kv.vt + li * kv.v_lstride,
+                              iv, e->attn, e->nH, e->cfg.rotary_dim, e->cfg.ln_eps, pos0, kv.Lcap, kv.Lp, s, co ? &o : nullptr, co ? co_blocks : 0,
+                              co && !w.sqkv ? &pf : nullptr, op));
+        TRY(decode_out_gemv2(o, s, co ? 2 : 0, op));
+    }
     return 0;
 }
 

@@ -13,31 +13,17 @@
 // A wave owns whole output columns and splits K over its lanes EXACTLY like the batch-1 kernels of decode.hip (same lane split, same
 // accumulation order per sequence, same epilogue expressions), so every sequence gets the bits its batch-1 run gets: tokens AND
 // logits of showo_engine_batch_decode_greedy equal NB separate showo_engine_decode_greedy runs (tests/test_decode_batch_gpu.py).
-// The whole step replays as a hipGraph with the NB positions in device memory.
+// The whole step replays as a hipGraph with the NB positions in device memory (engine.h replay_steps, shared with the batch-1 loop of
+// decode_engine.hip).  The weight images of a layer come from decode_layer_ops (decode.hip), the prefill / append of a slot from
+// engine_prefill_into / engine_append_into (decode_engine.hip); every NB-templated launch goes through dispatch_int below.
 #include "engine.h"
 #include "decode_common.h"
 #include "sample_row.h"
 #include "decode_wide.h"
-#include <cstdlib>
 #include <string>
+#include <type_traits>
 
 using namespace showo;
-
-namespace showo {
-int attn_decode_co_batch(const bf16_t* qkv, const float* qw, const float* qb, const float* kw, const float* kb, const float* cosT,
-                         const float* sinT, bf16_t* K, bf16_t* Vt, const int32_t* iv, bf16_t* O, int B, int nH, int rot, float eps,
-                         const int* pos_dev, int lk_max, int Lcap, int Lp, const OutGemvBArgs& fc2, int co_blocks, hipStream_t s,
-                         const DecodePrefetch* pf, int op = 0);
-int attn_decode_fused_batch(const bf16_t* qkv, const float* qw, const float* qb, const float* kw, const float* kb, const float* cosT,
-                            const float* sinT, bf16_t* K, bf16_t* Vt, const int32_t* iv, bf16_t* O, int B, int nH, int rot, float eps,
-                            const int* pos_dev, int lk_max, int Lcap, int Lp, hipStream_t s, int op = 0);
-}
-
-#define TRY(expr)            \
-    do {                     \
-        int _rc = (expr);    \
-        if (_rc) return _rc; \
-    } while (0)
 
 namespace {
 
@@ -449,52 +435,40 @@ __global__ __launch_bounds__(1024) void logprob_slots_kernel(const float* __rest
     }
 }
 
+// f(std::integral_constant<int, n>) for the run-time n in LO..HI: the compile-time instance of a sequence count or chunk count
+template <int LO, int HI, class F>
+int dispatch_int(int n, const char* range_msg, F&& f) {
+    if constexpr (LO > HI) return set_error_msg(1, range_msg);
+    else return n == LO ? f(std::integral_constant<int, LO>{}) : dispatch_int<LO + 1, HI>(n, range_msg, f);
+}
+
 template <int NB>
 int launch_ln_gemvB(const LnGemvBArgs& g, hipStream_t s, int op, bool head3) {
     const int Ntot = g.N0 + g.N1;
-    if (g.s0) {  // int8 weight images (precision 3): the grids of the bf16 instances
-        if (op || head3 || (g.N1 && !g.s1) || (g.H % 16)) return set_error_msg(1, "ln_gemvB: int8 weights take bf16 activations, a scale per matrix and H % 16 == 0");
-        if (NB <= 4) {
-            int blocks = (Ntot + 7) / 8;
-            const int cap = showo::decode_tuning().batch_ln_blocks;
-            if (blocks > cap) blocks = cap;
-            ln_gemvB_kernel<NB, (NB <= 4), false, false, true><<<dim3(blocks), dim3(256), (size_t)NB * g.H * sizeof(bf16_t), s>>>(g);
-        } else {
-            int blocks = (Ntot + 11) / 12;
-            if (blocks > 1280) blocks = 1280;
-            ln_gemvB_kernel<NB, false, false, false, true><<<dim3(blocks), dim3(256), (size_t)NB * g.H * sizeof(bf16_t), s>>>(g);
-        }
-    } else if (head3) {  // precision 2's lm_head: (hi, lo) activations in LDS, (hi, lo) bf16 weight rows
-        if (!g.W0lo || !g.outf || g.N1) return set_error_msg(1, "ln_gemvB: the split head writes fp32 logits from (hi, lo) weight rows");
-        int blocks = (Ntot + 11) / 12;
-        if (blocks > 1280) blocks = 1280;
-        ln_gemvB_kernel<NB, false, false, true><<<dim3(blocks), dim3(256), (size_t)NB * 2 * g.H * sizeof(bf16_t), s>>>(g);
-    } else if (NB <= 4) {  // register-resident activations (16 NB packed registers per lane): up to 4 blocks per CU resident
-        int blocks = (Ntot + 7) / 8;
-        const int cap = showo::decode_tuning().batch_ln_blocks;
-        if (blocks > cap) blocks = cap;
-        if (op) ln_gemvB_kernel<NB, (NB <= 4), true><<<dim3(blocks), dim3(256), (size_t)NB * g.H * sizeof(bf16_t), s>>>(g);
-        else ln_gemvB_kernel<NB, (NB <= 4)><<<dim3(blocks), dim3(256), (size_t)NB * g.H * sizeof(bf16_t), s>>>(g);
-    } else {
-        int blocks = (Ntot + 11) / 12;
-        if (blocks > 1280) blocks = 1280;
-        if (op) ln_gemvB_kernel<NB, false, true><<<dim3(blocks), dim3(256), (size_t)NB * g.H * sizeof(bf16_t), s>>>(g);
-        else ln_gemvB_kernel<NB, false><<<dim3(blocks), dim3(256), (size_t)NB * g.H * sizeof(bf16_t), s>>>(g);
-    }
+    const bool q8 = g.s0 != nullptr;  // int8 weight images (precision 3): the grids of the bf16 instances
+    if (q8 && (op || head3 || (g.N1 && !g.s1) || (g.H % 16)))
+        return set_error_msg(1, "ln_gemvB: int8 weights take bf16 activations, a scale per matrix and H % 16 == 0");
+    // precision 2's lm_head: (hi, lo) activations in LDS, (hi, lo) bf16 weight rows
+    if (head3 && (!g.W0lo || !g.outf || g.N1)) return set_error_msg(1, "ln_gemvB: the split head writes fp32 logits from (hi, lo) weight rows");
+    // register-resident activations (NB <= 4, 16 NB packed registers per lane): up to 4 blocks per CU resident; else 12 rows per block
+    const bool reg = NB <= 4 && !head3;
+    const int want = reg ? (Ntot + 7) / 8 : (Ntot + 11) / 12, cap = reg ? showo::decode_tuning().batch_ln_blocks : 1280;
+    const dim3 grid(want < cap ? want : cap);
+    const size_t smem = (size_t)NB * g.H * sizeof(bf16_t) * (head3 ? 2 : 1);
+    // (both forms are named for every NB, as they always were: the LDS-form instances of NB <= 4 are built and never launched)
+    auto go = [&](auto kreg, auto klds) {
+        if (reg) kreg<<<grid, dim3(256), smem, s>>>(g);
+        else klds<<<grid, dim3(256), smem, s>>>(g);
+    };
+    if (q8) go(ln_gemvB_kernel<NB, (NB <= 4), false, false, true>, ln_gemvB_kernel<NB, false, false, false, true>);
+    else if (head3) ln_gemvB_kernel<NB, false, false, true><<<grid, dim3(256), smem, s>>>(g);
+    else if (op) go(ln_gemvB_kernel<NB, (NB <= 4), true>, ln_gemvB_kernel<NB, false, true>);
+    else go(ln_gemvB_kernel<NB, (NB <= 4)>, ln_gemvB_kernel<NB, false>);
     return hipGetLastError() == hipSuccess ? 0 : set_error_msg(7, "ln_gemvB launch failed");
 }
 int ln_gemvB(int nb, const LnGemvBArgs& g, hipStream_t s, int op = 0, bool head3 = false) {
-    switch (nb) {
-        case 1: return launch_ln_gemvB<1>(g, s, op, head3);
-        case 2: return launch_ln_gemvB<2>(g, s, op, head3);
-        case 3: return launch_ln_gemvB<3>(g, s, op, head3);
-        case 4: return launch_ln_gemvB<4>(g, s, op, head3);
-        case 5: return launch_ln_gemvB<5>(g, s, op, head3);
-        case 6: return launch_ln_gemvB<6>(g, s, op, head3);
-        case 7: return launch_ln_gemvB<7>(g, s, op, head3);
-        case 8: return launch_ln_gemvB<8>(g, s, op, head3);
-    }
-    return set_error_msg(1, "batched decode: 1..8 sequences");
+    return dispatch_int<1, NARROW_B>(nb, "batched decode: 1..8 sequences",
+                                     [&](auto NB) { return launch_ln_gemvB<decltype(NB)::value>(g, s, op, head3); });
 }
 
 template <int C, int NB, bool F16, bool Q8 = false>
@@ -513,63 +487,31 @@ int launch_out_gemvB(const OutGemvBArgs& g, hipStream_t s) {
     kfn<<<dim3(blocks), dim3(512), smem, s>>>(g);
     return hipGetLastError() == hipSuccess ? 0 : set_error_msg(7, "out_gemvB launch failed");
 }
-template <int NB>
-int out_gemvB_c(const OutGemvBArgs& g, hipStream_t s, int op) {
-    const int C = (g.K0 + 2047) / 2048 + (g.K1 + 2047) / 2048;
-    if (g.s0 || g.s1) {  // int8 weight images (precision 3)
-        if (op || !g.s0 || !g.s1 || (g.K0 % 16) || (g.K1 % 16)) return set_error_msg(1, "out_gemvB: int8 weights take bf16 activations, both scales and K % 16 == 0");
-        switch (C) {
-            case 2: return launch_out_gemvB<2, NB, false, true>(g, s);
-            case 3: return launch_out_gemvB<3, NB, false, true>(g, s);
-            case 4: return launch_out_gemvB<4, NB, false, true>(g, s);
-            case 5: return launch_out_gemvB<5, NB, false, true>(g, s);
-        }
-        return set_error_msg(1, "batched decode: unsupported K0 / K1 (decode_fused_shapes_ok)");
-    }
-    switch (C) {
-        case 2: return op ? launch_out_gemvB<2, NB, true>(g, s) : launch_out_gemvB<2, NB, false>(g, s);
-        case 3: return op ? launch_out_gemvB<3, NB, true>(g, s) : launch_out_gemvB<3, NB, false>(g, s);
-        case 4: return op ? launch_out_gemvB<4, NB, true>(g, s) : launch_out_gemvB<4, NB, false>(g, s);
-        case 5: return op ? launch_out_gemvB<5, NB, true>(g, s) : launch_out_gemvB<5, NB, false>(g, s);
-    }
-    return set_error_msg(1, "batched decode: unsupported K0 / K1 (decode_fused_shapes_ok)");
+int out_gemvB(int nb, const OutGemvBArgs& g, hipStream_t s, int op) {
+    const bool q8 = g.s0 || g.s1;  // int8 weight images (precision 3)
+    return dispatch_int<1, NARROW_B>(nb, "batched decode: 1..8 sequences", [&](auto NB) {
+        if (q8 && (op || !g.s0 || !g.s1 || (g.K0 % 16) || (g.K1 % 16)))
+            return set_error_msg(1, "out_gemvB: int8 weights take bf16 activations, both scales and K % 16 == 0");
+        return dispatch_int<2, 5>((g.K0 + 2047) / 2048 + (g.K1 + 2047) / 2048, "batched decode: unsupported K0 / K1 (decode_fused_shapes_ok)", [&](auto C) {
+            constexpr int c = decltype(C)::value, n = decltype(NB)::value;
+            return q8 ? launch_out_gemvB<c, n, false, true>(g, s) : op ? launch_out_gemvB<c, n, true>(g, s) : launch_out_gemvB<c, n, false>(g, s);
+        });
+    });
 }
 int out_dense_y2B(int nb, const OutGemvBArgs& g, hipStream_t s, int op) {
     int blocks = (g.N + 7) / 8;
     if (blocks > showo::decode_tuning().out_blocks) blocks = showo::decode_tuning().out_blocks;
-    if (g.s0) {  // int8 image of the dense matrix (precision 3)
-        if (op || (g.K0 % 16)) return set_error_msg(1, "out_dense_y2B: int8 weights take bf16 activations and K % 16 == 0");
-        switch (nb) {
-            case 2: out_dense_y2B_kernel<2, false, true><<<dim3(blocks), dim3(512), 0, s>>>(g); break;
-            case 3: out_dense_y2B_kernel<3, false, true><<<dim3(blocks), dim3(512), 0, s>>>(g); break;
-            case 4: out_dense_y2B_kernel<4, false, true><<<dim3(blocks), dim3(512), 0, s>>>(g); break;
-            default: return set_error_msg(1, "batched decode: the co-scheduled layer serves 2..4 sequences");
-        }
-        return hipGetLastError() == hipSuccess ? 0 : set_error_msg(7, "out_dense_y2B launch failed");
-    }
-    switch (nb * 2 + (op ? 1 : 0)) {
-        case 4: out_dense_y2B_kernel<2><<<dim3(blocks), dim3(512), 0, s>>>(g); break;
-        case 6: out_dense_y2B_kernel<3><<<dim3(blocks), dim3(512), 0, s>>>(g); break;
-        case 8: out_dense_y2B_kernel<4><<<dim3(blocks), dim3(512), 0, s>>>(g); break;
-        case 5: out_dense_y2B_kernel<2, true><<<dim3(blocks), dim3(512), 0, s>>>(g); break;
-        case 7: out_dense_y2B_kernel<3, true><<<dim3(blocks), dim3(512), 0, s>>>(g); break;
-        case 9: out_dense_y2B_kernel<4, true><<<dim3(blocks), dim3(512), 0, s>>>(g); break;
-        default: return set_error_msg(1, "batched decode: the co-scheduled layer serves 2..4 sequences");
-    }
+    const bool q8 = g.s0 != nullptr;  // int8 image of the dense matrix (precision 3)
+    if (q8 && (op || (g.K0 % 16))) return set_error_msg(1, "out_dense_y2B: int8 weights take bf16 activations and K % 16 == 0");
+    const int rc = dispatch_int<2, 4>(nb, "batched decode: the co-scheduled layer serves 2..4 sequences", [&](auto NB) {
+        constexpr int n = decltype(NB)::value;
+        if (q8) out_dense_y2B_kernel<n, false, true><<<dim3(blocks), dim3(512), 0, s>>>(g);
+        else if (op) out_dense_y2B_kernel<n, true><<<dim3(blocks), dim3(512), 0, s>>>(g);
+        else out_dense_y2B_kernel<n><<<dim3(blocks), dim3(512), 0, s>>>(g);
+        return 0;
+    });
+    if (rc) return rc;
     return hipGetLastError() == hipSuccess ? 0 : set_error_msg(7, "out_dense_y2B launch failed");
-}
-int out_gemvB(int nb, const OutGemvBArgs& g, hipStream_t s, int op) {
-    switch (nb) {
-        case 1: return out_gemvB_c<1>(g, s, op);
-        case 2: return out_gemvB_c<2>(g, s, op);
-        case 3: return out_gemvB_c<3>(g, s, op);
-        case 4: return out_gemvB_c<4>(g, s, op);
-        case 5: return out_gemvB_c<5>(g, s, op);
-        case 6: return out_gemvB_c<6>(g, s, op);
-        case 7: return out_gemvB_c<7>(g, s, op);
-        case 8: return out_gemvB_c<8>(g, s, op);
-    }
-    return set_error_msg(1, "batched decode: 1..8 sequences");
 }
 
 }  // namespace
@@ -651,12 +593,6 @@ static int batch_begin(showo_engine* e, int nb, int cap_tokens, bool wide) {
 extern "C" int showo_engine_batch_begin(showo_engine* e, int nb, int cap_tokens) { return batch_begin(e, nb, cap_tokens, false); }
 extern "C" int showo_engine_batch_begin_wide(showo_engine* e, int nb, int cap_tokens) { return batch_begin(e, nb, cap_tokens, true); }
 
-namespace showo {
-int engine_prefill_into(showo_engine* e, const int64_t* ids, const float* embeds, const float* mask, int L, bf16_t* k, bf16_t* vt,
-                        int64_t k_lstride, int64_t v_lstride, int cap, int* last_iv_out, float* logits_last, hipStream_t s,
-                        bf16_t* k_lo, bf16_t* vt_lo);
-}
-
 extern "C" int showo_engine_batch_prefill(showo_engine* e, int b, const int64_t* ids, const float* embeds, const float* mask, int L,
                                           float* logits_last, void* stream) {
     if (!e || !e->bd || e->bd->nb == 0) return set_error_msg(1, "batch_prefill: showo_engine_batch_begin first");
@@ -676,12 +612,6 @@ extern "C" int showo_engine_batch_prefill(showo_engine* e, int b, const int64_t*
 }
 
 // ---- mmu sessions: a slot that starts as a copy of the engine's decode cache, and more prompt rows onto a slot ---------------------
-namespace showo {
-int engine_append_into(showo_engine* e, const int64_t* ids, const float* embeds, int Ln, int P, const int* last_iv, int L0, bf16_t* k,
-                       bf16_t* vt, int64_t k_lstride, int64_t v_lstride, int cap, float* logits_last, hipStream_t s, bf16_t* k_lo,
-                       bf16_t* vt_lo);
-}
-
 extern "C" int showo_engine_batch_slot_ptrs(showo_engine* e, int b, uint16_t** k, uint16_t** vt, int64_t* k_lstride, int64_t* v_lstride,
                                             int* cap) {
     if (!e || !e->bd || e->bd->nb == 0) return set_error_msg(1, "batch_slot_ptrs: showo_engine_batch_begin first");
@@ -764,8 +694,10 @@ int batch_step_layers(showo_engine* e, int op, bool co, int lk_max, float* logit
     const int co_blocks = showo::decode_tuning().batch_co_blocks;  // 128 role blocks + 32 nb attention blocks = one block per CU at nb = 4
     for (int li = 0; li < e->nL; ++li) {
         showo::Layer& l = e->layers[li];
-        LnGemvBArgs a{e->x, l.ln_w, l.ln_b, e->cfg.ln_eps, H, l.wqkv, l.bqkv, e->qkv, nullptr, 3 * H, 3 * H, l.w1, l.b1, e->ffn, F, F};
-        OutGemvBArgs o{e->x, l.wd, e->attn, l.bd, H, H, l.w2, e->ffn, l.b2, F, F, H, d->y2};
+        const showo::DecodeLayerOps w = showo::decode_layer_ops(e, li);  // (a wide batch runs at precision 0: the bf16 images)
+        LnGemvBArgs a{e->x, l.ln_w, l.ln_b, e->cfg.ln_eps, H, w.Wqkv, w.bqkv, e->qkv, nullptr, 3 * H, 3 * H, w.W1, w.b1, e->ffn, F, F};
+        a.s0 = w.sqkv; a.s1 = w.s1;
+        const OutGemvBArgs o{e->x, w.Wd, e->attn, w.bd, H, H, w.W2, e->ffn, w.b2, F, F, H, d->y2, w.sd, w.s2};
         if (d->wide) {  // ln_gemmW -> attention (heads x nb blocks) -> out_gemmW: the MFMA step of decode_wide.hip
             TRY(showo::ln_gemmW(nb, a, d->wws, s));
             TRY(showo::attn_decode_fused_batch(e->qkv, l.qln_w, l.qln_b, l.kln_w, l.kln_b, e->cosT, e->sinT, d->k + li * lstride,
@@ -773,10 +705,6 @@ int batch_step_layers(showo_engine* e, int op, bool co, int lk_max, float* logit
                                                d->pos_dev, lk_max, d->cap, d->cap, s, 0));
             TRY(showo::out_gemmW(nb, o, d->wws, s));
             continue;
-        }
-        if (q8) {  // precision 3: the same launches stream the int8 images (pointers travel as bf16_t*; the scales select the instances)
-            a.W0 = reinterpret_cast<const bf16_t*>(l.qqkv); a.W1 = reinterpret_cast<const bf16_t*>(l.q1); a.s0 = l.sqkv; a.s1 = l.s1;
-            o.W0 = reinterpret_cast<const bf16_t*>(l.qd); o.W1 = reinterpret_cast<const bf16_t*>(l.q2); o.s0 = l.sd; o.s1 = l.s2;
         }
         TRY(ln_gemvB(nb, a, s, op));
         if (co) {
@@ -804,8 +732,9 @@ int batch_step_layers(showo_engine* e, int op, bool co, int lk_max, float* logit
     if (op) {  // precision 2: the lm_head is the split-bf16 product (its images stay bf16 (hi, lo) at that precision)
         TRY(showo::decode_split_head(e->x, e->fln_w, e->fln_b, e->cfg.ln_eps, H, e->wlm, e->wlm_lo, e->blm, logits_ws, V, V, nb, s));
     } else {
-        LnGemvBArgs h{e->x, e->fln_w, e->fln_b, e->cfg.ln_eps, H, e->wlm, e->blm, nullptr, logits_ws, V, V, nullptr, nullptr, nullptr, 0, 0};
-        if (q8) { h.W0 = reinterpret_cast<const bf16_t*>(e->qlm); h.s0 = e->slm; }
+        const showo::DecodeHeadOps w = showo::decode_head_ops(e);
+        LnGemvBArgs h{e->x, e->fln_w, e->fln_b, e->cfg.ln_eps, H, w.W, w.b, nullptr, logits_ws, V, V, nullptr, nullptr, nullptr, 0, 0};
+        h.s0 = w.s;
         TRY(ln_gemvB(nb, h, s));
     }
     return 0;
@@ -814,48 +743,13 @@ int batch_step_layers(showo_engine* e, int op, bool co, int lk_max, float* logit
 // co-scheduled layer (fc2 streams next to the latency-bound attention blocks): Phi-1.5's shape, 2..4 sequences (the fc2 role keeps
 // nb x 8192 bf16 activations in LDS); SHOWO_DECODE_BATCH_CO=0 / other shapes: three plain launches per layer
 int batch_use_co(showo_engine* e, bool* co) {
-    static int co_on = -1;
-    if (co_on < 0) {
-        const char* env = getenv("SHOWO_DECODE_BATCH_CO");
-        co_on = env ? (atoi(env) != 0) : 1;
-    }
+    static const int co_on = showo::env_flag("SHOWO_DECODE_BATCH_CO", 1);
     const int nb = e->bd->nb;
     *co = !e->bd->wide && co_on && e->F == 8192 && e->H <= 2048 && nb >= 2 && nb <= 4 && (size_t)nb * e->F * 2 <= 128 * 1024;
     if (*co && !e->bd->y2) TRY(e->alloc(&e->bd->y2, (int64_t)MAXB * e->H));
     return 0;
 }
 
-// n_steps runs of one(): the first eagerly (kernel attributes), the rest as replays of one captured step (use_graph) or eagerly
-template <class Step>
-int run_batch_steps(Step&& one, int n_steps, int use_graph, hipStream_t s) {
-    int rc = one();
-    hipGraph_t g = nullptr;
-    hipGraphExec_t ge = nullptr;
-    const bool graph = use_graph && n_steps > 1 && !showo::g_prof_on_query();
-    if (!rc && graph) {
-        hipError_t he = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
-        if (he == hipSuccess) {
-            rc = one();
-            hipError_t he2 = hipStreamEndCapture(s, &g);
-            if (!rc && he2 != hipSuccess) rc = set_error_hip(he2, "hipStreamEndCapture", __FILE__, __LINE__);
-        } else {
-            rc = set_error_hip(he, "hipStreamBeginCapture", __FILE__, __LINE__);
-        }
-        if (!rc) {
-            hipError_t he3 = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
-            if (he3 != hipSuccess) rc = set_error_hip(he3, "hipGraphInstantiate", __FILE__, __LINE__);
-        }
-        for (int i = 1; !rc && i < n_steps; ++i) {
-            hipError_t he4 = hipGraphLaunch(ge, s);
-            if (he4 != hipSuccess) rc = set_error_hip(he4, "hipGraphLaunch", __FILE__, __LINE__);
-        }
-    } else {
-        for (int i = 1; !rc && i < n_steps; ++i) rc = one();
-    }
-    if (ge) { hipStreamSynchronize(s); hipGraphExecDestroy(ge); }
-    if (g) hipGraphDestroy(g);
-    return rc;
-}
 }  // namespace
 
 // tok int64 [nb] (device): in = the token each sequence feeds first (e.g. the arg-max of its prefill logits), out = the last tokens
@@ -894,7 +788,7 @@ extern "C" int showo_engine_batch_decode_greedy(showo_engine* e, int64_t* tok, i
         SHOWO_CHECK_HIP(hipGetLastError());
         return 0;
     };
-    TRY(run_batch_steps(one, n_steps, use_graph, s));
+    TRY(showo::replay_steps(one, n_steps, use_graph != 0, s));
     for (int b = 0; b < nb; ++b) d->cache_len[b] = P0[b] + n_steps;
     return 0;
 }
@@ -967,7 +861,7 @@ static int batch_decode_sample(showo_engine* e, int64_t* tok, int n_steps, int64
         SHOWO_CHECK_HIP(hipGetLastError());
         return 0;
     };
-    TRY(run_batch_steps(one, n_steps, use_graph, s));
+    TRY(showo::replay_steps(one, n_steps, use_graph != 0, s));
     SHOWO_CHECK_HIP(hipMemcpyAsync(sd, d->slots_dev, sizeof(SlotDraw) * nb, hipMemcpyDeviceToHost, s));
     SHOWO_CHECK_HIP(hipStreamSynchronize(s));
     for (int b = 0; b < nb; ++b) {

@@ -1,4 +1,5 @@
-// Internal layout of the transformer engine (shared by engine.hip and train_engine.hip).
+// Internal layout of the transformer engine and the functions its files share (engine.hip, decode.hip, decode_engine.hip,
+// decode_batch.hip, train_engine.hip), each declared once; hipGraph capture / replay helpers at the end.
 #pragma once
 #include "common.h"
 #include "../../include/showo_hip.h"
@@ -47,23 +48,70 @@ int sample_topk_topp_launch(const float* logits, int V, int top_k, float top_p, 
 // sampler.hip: log-probability / rank of *tok on the logits row of the decode step that just stored it and advanced *pos_dev
 int logprob_step_launch(const float* logits, int V, const int64_t* tok, const int* pos_dev, int pos_base, float* lp, int32_t* rank,
                         hipStream_t s);
-// fused decode layer (decode.hip, attention.hip)
+// ---- the decode step's launches, each declared here once (decode.hip, decode_batch.hip, attention.hip; argument structs in
+// decode_common.h).  op: SHOWO_OP_BF16 | SHOWO_OP_F16 -- the element type of weights and 16-bit activations; non-null row scales in an
+// argument struct say that its weight pointers are int8 images (precision 3, op 0).
 struct DecodePrefetch;
+struct LnGemvBArgs;
+struct OutGemvArgs;
+struct OutGemvBArgs;
+// K / V^T destination of a pass over the layers: the per-call workspace (layer stride 0) or a per-layer cache -- the AR decode cache
+// (one sequence), a slot of a decode batch, or the t2i prefix-reuse cache (whole batch)
+struct KVDest {
+    bf16_t *k, *vt;
+    int64_t k_lstride, v_lstride;  // elements between consecutive layers
+    int Lcap, Lp;                  // key rows per head in k, columns per row in vt
+    bf16_t *k_lo = nullptr, *vt_lo = nullptr;  // accuracy mode: low halves (same layout and strides)
+};
+// What a layer's decode launches stream: the bf16 / fp16 images, or under precision 3 the int8 images (they travel as bf16_t*) and
+// their row scales (null otherwise); the lm_head likewise.  The ONE place that picks between them.
+struct DecodeLayerOps {
+    const bf16_t *Wqkv, *W1, *Wd, *W2;
+    const float *sqkv, *s1, *sd, *s2;
+    const float *bqkv, *b1, *bd, *b2;
+};
+struct DecodeHeadOps {
+    const bf16_t* W;
+    const float *s, *b;
+};
+DecodeLayerOps decode_layer_ops(const ::showo_engine* e, int li);
+DecodeHeadOps decode_head_ops(const ::showo_engine* e, int col0 = 0);  // the rows from vocabulary entry col0 on
 bool decode_fused_shapes_ok(int H, int F);
-int decode_ln_gemv2(const float* x, const float* lnw, const float* lnb, float eps, int H, const bf16_t* W0, const float* b0,
-                    bf16_t* out0, float* outf, int N0, const bf16_t* W1, const float* b1, bf16_t* out1, int N1, hipStream_t s,
-                    int op = 0,  // op: SHOWO_OP_BF16 | SHOWO_OP_F16 -- the element type of weights and 16-bit activations (all decode entry points)
-                    const float* s0 = nullptr, const float* s1 = nullptr);  // row scales: W0 / W1 are then int8 images (precision 3, op 0)
+// batch-1 launches: a.ld0 / a.ld1 / a.W0lo are not read
+int decode_ln_gemv2(const LnGemvBArgs& a, hipStream_t s, int op = 0);
+int decode_out_gemv2(const OutGemvArgs& g, hipStream_t s, int mode = 0, int op = 0);  // mode: out_gemv2_kernel's MODE
 int decode_split_head(const float* x, const float* lnw, const float* lnb, float eps, int H, const bf16_t* Whi, const bf16_t* Wlo,
                       const float* bias, float* logits, int N, int ld, int nb, hipStream_t s);  // decode_batch.hip: precision 2's head on a decode step
-int decode_out_gemv2(float* x, const bf16_t* W0, const bf16_t* a0, const float* b0, int K0, const bf16_t* W1, const bf16_t* a1,
-                     const float* b1, int K1, int N, hipStream_t s, int mode = 0, float* y2 = nullptr, int op = 0,
-                     const float* s0 = nullptr, const float* s1 = nullptr);  // row scales of int8 W0 / W1 (precision 3)
+// fc2 != nullptr: the co-scheduled fc2 role (its W1 / a1 / b1 / K1 / N / y2 / s1 members) on co_blocks extra blocks, pf its prefetch role
 int attn_decode_fused(const bf16_t* qkv, const float* qw, const float* qb, const float* kw, const float* kb, const float* cosT,
                       const float* sinT, bf16_t* K, bf16_t* Vt, const int32_t* iv, bf16_t* O, int nH, int rot, float eps, int pos,
-                      int Lcap, int Lp, hipStream_t s, const bf16_t* W2 = nullptr, const bf16_t* ffn = nullptr, const float* b2 = nullptr,
-                      int F = 0, int Hout = 0, float* y2 = nullptr, int co_blocks = 0, const DecodePrefetch* pf = nullptr, int op = 0,
-                      const float* s2 = nullptr);  // s2: W2 is the int8 image of fc2 and s2 its row scales (precision 3)
+                      int Lcap, int Lp, hipStream_t s, const OutGemvArgs* fc2 = nullptr, int co_blocks = 0,
+                      const DecodePrefetch* pf = nullptr, int op = 0);
+int attn_decode_co_batch(const bf16_t* qkv, const float* qw, const float* qb, const float* kw, const float* kb, const float* cosT,
+                         const float* sinT, bf16_t* K, bf16_t* Vt, const int32_t* iv, bf16_t* O, int B, int nH, int rot, float eps,
+                         const int* pos_dev, int lk_max, int Lcap, int Lp, const OutGemvBArgs& fc2, int co_blocks, hipStream_t s,
+                         const DecodePrefetch* pf, int op = 0);
+int attn_decode_fused_batch(const bf16_t* qkv, const float* qw, const float* qb, const float* kw, const float* kb, const float* cosT,
+                            const float* sinT, bf16_t* K, bf16_t* Vt, const int32_t* iv, bf16_t* O, int B, int nH, int rot, float eps,
+                            const int* pos_dev, int lk_max, int Lcap, int Lp, hipStream_t s, int op = 0);
+// the layers of one batch-1 decode step (decode.hip): per layer LN + qkv / fc1 GEMV -> attention (co: with the fc2 role) -> dense / fc2
+// GEMV + both residual adds.  The caller (run_layers, engine.hip) has decided that the fused step applies.
+int decode_layers_b1(::showo_engine* e, int op, const KVDest& kv, const int32_t* iv, int pos0, bool co, hipStream_t s);
+// engine.hip, for the KV-cached decode (decode_engine.hip, decode_batch.hip)
+int run_layers(::showo_engine* e, int B, int L, int pos0, const KVDest& kv, const int32_t* iv, const int32_t* flag, const float* dense,
+               hipStream_t s);
+int head_rows(::showo_engine* e, const int32_t* rows, int nrows, int col0, int ncols, float* logits, hipStream_t s);
+int embed_in(::showo_engine* e, const int64_t* ids, const float* embeds, int T, hipStream_t s);
+int check_ready(::showo_engine* e, int B, int L);
+bool precise_fast_ok(const ::showo_engine* e);
+// decode_engine.hip
+KVDest kv_decode_cache(::showo_engine* e);
+int engine_prefill_into(::showo_engine* e, const int64_t* ids, const float* embeds, const float* mask, int L, bf16_t* k, bf16_t* vt,
+                        int64_t k_lstride, int64_t v_lstride, int cap, int* last_iv_out, float* logits_last, hipStream_t s,
+                        bf16_t* k_lo, bf16_t* vt_lo);
+int engine_append_into(::showo_engine* e, const int64_t* ids, const float* embeds, int Ln, int P, const int* last_iv, int L0, bf16_t* k,
+                       bf16_t* vt, int64_t k_lstride, int64_t v_lstride, int cap, float* logits_last, hipStream_t s, bf16_t* k_lo,
+                       bf16_t* vt_lo);
 // int8 weight format helpers (quant.hip)
 int q8_dequant_bf16(const int8_t* q, const float* scale, int64_t N, int64_t K, bf16_t* w, hipStream_t s);
 int q8_validate(const int8_t* q, const float* scale, int64_t N, int64_t K, int* bad, hipStream_t s);  // bad: 2 device ints of the caller
@@ -248,3 +296,48 @@ struct showo_engine {
     }
 };
 
+#ifndef TRY
+#define TRY(expr)            \
+    do {                     \
+        int _rc = (expr);    \
+        if (_rc) return _rc; \
+    } while (0)
+#endif
+
+namespace showo {
+// ---- hipGraph capture and replay of one step (the decode loops, the t2i denoise step) ----------------------------------------------
+// fn() queues one step on s; it runs inside a thread-local stream capture and *exec becomes the instantiated graph (nullptr on failure)
+template <class Step>
+int capture_step(hipStream_t s, Step&& fn, hipGraphExec_t* exec) {
+    *exec = nullptr;
+    hipGraph_t g = nullptr;
+    SHOWO_CHECK_HIP(hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+    int rc = fn();
+    hipError_t he2 = hipStreamEndCapture(s, &g);
+    if (!rc && he2 != hipSuccess) rc = set_error_hip(he2, "hipStreamEndCapture", __FILE__, __LINE__);
+    if (!rc) {
+        hipError_t he3 = hipGraphInstantiate(exec, g, nullptr, nullptr, 0);
+        if (he3 != hipSuccess) { *exec = nullptr; rc = set_error_hip(he3, "hipGraphInstantiate", __FILE__, __LINE__); }
+    }
+    if (g) hipGraphDestroy(g);
+    return rc;
+}
+// n_steps runs of fn(): the first eagerly (kernel attributes, launch variants), the rest as replays of one captured step (use_graph; never
+// under per-launch profiling) or eagerly.  A captured step is synchronised and destroyed before the call returns.
+template <class Step>
+int replay_steps(Step&& fn, int n_steps, bool use_graph, hipStream_t s) {
+    int rc = fn();
+    hipGraphExec_t ge = nullptr;
+    if (!rc && use_graph && n_steps > 1 && !g_prof_on_query()) {
+        rc = capture_step(s, fn, &ge);
+        for (int i = 1; !rc && i < n_steps; ++i) {
+            hipError_t he = hipGraphLaunch(ge, s);
+            if (he != hipSuccess) rc = set_error_hip(he, "hipGraphLaunch", __FILE__, __LINE__);
+        }
+    } else {
+        for (int i = 1; !rc && i < n_steps; ++i) rc = fn();
+    }
+    if (ge) { hipStreamSynchronize(s); hipGraphExecDestroy(ge); }
+    return rc;
+}
+}  // namespace showo

@@ -1,9 +1,8 @@
 // Show-o transformer engine: packed bf16 weights + workspaces resident in HBM, whole-module entry points.
 // Replaces (reference): PhiForCausalLM/PhiModel forward (models/phi.py:953-1183), Showo.forward without
 // labels (models/modeling_showo.py:76-79), Showo.t2i_generate (models/modeling_showo.py:104-181) and the
-// incremental form of Showo.mmu_generate (models/modeling_showo.py:183-240; the reference re-runs the whole
-// sequence per token, here K/V of earlier rows are cached, which is exact because the mask it grows never
-// lets an old row see a new column, modeling_showo.py:203-217).
+// layer stack and head under the incremental form of Showo.mmu_generate (models/modeling_showo.py:183-240; its KV cache
+// and token loop are in decode_engine.hip, the launches of a one-token step in decode.hip).
 //
 // Data layout in HBM (T = B*L tokens, H hidden, F ffn):
 //   x      fp32 [T,H]    residual stream (kept fp32; both GEMM epilogues accumulate into it in place)
@@ -50,14 +49,6 @@ __global__ void rows_index_kernel(int32_t* rows, int nseq, int L, int img_start,
     if (i >= nseq * N) return;
     int b = i / N, n = i - b * N;
     rows[i] = b * L + img_start + n;
-}
-__global__ void set_iv_kernel(int32_t* iv, int a, int b, int c, int d) {
-    if (threadIdx.x == 0) { iv[0] = a; iv[1] = b; iv[2] = c; iv[3] = d; }
-}
-// V^T columns [c0, c1) of every (layer, head, d) row of one sequence's cache: grid (nH * 64 rows, layers), row pitch = Lp
-__global__ void zero_vt_cols_kernel(bf16_t* vt, int64_t lstride, int Lp, int c0, int c1) {
-    bf16_t* r = vt + blockIdx.y * lstride + (int64_t)blockIdx.x * Lp;
-    for (int c = c0 + threadIdx.x; c < c1; c += blockDim.x) r[c] = 0;
 }
 // ---- t2i prefix reuse: rows [0, prefix) of every sequence (pads + text; causal, never see an image column) are step-invariant
 __global__ void gather_ids_kernel(const int64_t* __restrict__ all, int64_t* __restrict__ act, int nseq, int L, int prefix) {
@@ -159,20 +150,6 @@ __global__ void bcast_seq_kernel(T* __restrict__ base, int64_t lstride, int inne
     const T v = *src;
     for (int d = 1; d <= ndst; ++d) src[d * seq_stride] = v;
 }
-// mask row of the token at position *pos: the last prompt row extended by the columns [L0, pos] (modeling_showo.py:203-217)
-__global__ void decode_iv_kernel(const int32_t* __restrict__ last_iv, int L0, const int* __restrict__ pos, int32_t* __restrict__ iv) {
-    if (threadIdx.x != 0) return;
-    int a = last_iv[0], b = last_iv[1], c = last_iv[2], d = last_iv[3];
-    const int P = *pos;
-    if (b == L0 && a < b) b = P + 1;
-    else if (d == L0 && c < d) d = P + 1;
-    else if (!(c < d)) { c = L0; d = P + 1; }
-    else if (!(a < b)) { a = L0; b = P + 1; }
-    iv[0] = a; iv[1] = b; iv[2] = c; iv[3] = d;
-}
-__global__ void store_token_kernel(const int64_t* __restrict__ tok, int64_t* __restrict__ out, const int* __restrict__ pos, int base) {
-    if (threadIdx.x == 0) out[*pos - base] = *tok;
-}
 // per-call constants of the graph-replayed denoise loop, passed BY VALUE as kernel arguments (no host staging buffer to keep alive,
 // no stream synchronisation): sched[0..n) = mask_len_f | temperature per step, hdr = step index | pad | seed lo | seed hi
 struct SchedArgs { float v[512]; int hdr[4]; int n; };
@@ -186,12 +163,6 @@ __global__ void copy_i64_kernel(const int64_t* s, int64_t* d, int n) {
 }
 
 }  // namespace
-
-#define TRY(expr)            \
-    do {                     \
-        int _rc = (expr);    \
-        if (_rc) return _rc; \
-    } while (0)
 
 // bcast_seq_kernel in the widest unit that every stride, offset and length (given in elements of E) is a multiple of
 template <class E>
@@ -560,14 +531,7 @@ static bool fused_layer_enabled() {
     return v != 0;
 }
 
-// ---- the 24-layer stack.  K / V^T go to the per-call workspace (layer stride 0) or to a per-layer cache:
-//      the AR decode cache (one sequence) or the t2i prefix-reuse cache (whole batch).
-struct KVDest {
-    bf16_t *k, *vt;
-    int64_t k_lstride, v_lstride;  // elements between consecutive layers
-    int Lcap, Lp;                  // key rows per head in k, columns per row in vt
-    bf16_t *k_lo = nullptr, *vt_lo = nullptr;  // accuracy mode: low halves (same layout and strides)
-};
+// ---- the 24-layer stack.  K / V^T go to a KVDest (engine.h): the per-call workspace here, or a per-layer cache.
 static KVDest kv_workspace(showo_engine* e, int L) { return KVDest{e->K, e->Vt, 0, 0, L, ((L + 63) / 64) * 64, e->p_Klo, e->p_Vtlo}; }
 namespace showo { int g_decode_impl = 0; }
 static int g_decode_chain = 0;  // 1: the fused layer as a plain three-launch chain (no co-scheduled fc2 role)
@@ -576,11 +540,6 @@ extern "C" int showo_decode_set_impl(int impl) {
     showo::g_decode_impl = impl == 1;
     g_decode_chain = impl == 2;
     return 0;
-}
-
-static KVDest kv_decode_cache(showo_engine* e) {
-    return KVDest{e->kcache, e->vtcache, (int64_t)e->nH * e->cache_cap * 64, (int64_t)e->nH * 64 * e->cache_cap, e->cache_cap, e->cache_cap,
-                  e->kcache_lo, e->vtcache_lo};
 }
 
 // parity hook (showo_engine_set_collect): copy the fp32 residual stream after layer `slot - 1` (slot 0 = the embeddings)
@@ -594,13 +553,11 @@ static int collect_x(showo_engine* e, int slot, int T, hipStream_t s) {
 static int g_pf_mb = -1, g_pf_dense = 0, g_pf_blocks = 64;  // off by default (measured negative: profiles/r5_decode_dot2_sweep.txt)
 static void decode_prefetch_env() {
     if (g_pf_mb >= 0) return;
-    const char* m = getenv("SHOWO_DECODE_PF_MB");
-    g_pf_mb = m ? atoi(m) : 0;
+    g_pf_mb = env_flag("SHOWO_DECODE_PF_MB", 0);
     if (g_pf_mb < 0) g_pf_mb = 0;
-    const char* d = getenv("SHOWO_DECODE_PF_DENSE");
-    if (d) g_pf_dense = atoi(d) != 0;
-    const char* b = getenv("SHOWO_DECODE_PF_BLOCKS");
-    if (b && atoi(b) > 0) g_pf_blocks = atoi(b);
+    g_pf_dense = env_flag("SHOWO_DECODE_PF_DENSE", g_pf_dense) != 0;
+    const int b = env_flag("SHOWO_DECODE_PF_BLOCKS", 0);
+    if (b > 0) g_pf_blocks = b;
 }
 extern "C" int showo_decode_set_prefetch(int next_mb, int dense, int blocks) {
     if (next_mb < 0 || blocks < 0 || blocks > 1024) return set_error_msg(1, "showo_decode_set_prefetch: next_mb >= 0, 0 <= blocks <= 1024");
@@ -683,7 +640,7 @@ static bool precise_fast_shape_ok(const showo_engine* e) {
     return g_precise_fast && e->cfg.rotary_dim == 32 && (3 * e->H) % 256 == 0 && e->H % 64 == 0 && e->F % 64 == 0 && e->H % 4 == 0;
 }
 // ... and its images / workspaces exist (showo_engine_set_precision(e, 1) made them)
-static bool precise_fast_ok(const showo_engine* e) { return precise_fast_shape_ok(e) && e->p_h3 != nullptr; }
+bool showo::precise_fast_ok(const showo_engine* e) { return precise_fast_shape_ok(e) && e->p_h3 != nullptr; }
 extern "C" int showo_engine_set_precision(showo_engine* e, int precision) {
     if (!e) return set_error_msg(1, "engine: null handle");
     if (precision < 0 || precision > 3)
@@ -928,7 +885,7 @@ extern "C" int showo_engine_set_range_check(showo_engine* e, int64_t* count) {
     return 0;
 }
 
-static int run_layers(showo_engine* e, int B, int L, int pos0, const KVDest& kv, const int32_t* iv, const int32_t* flag,
+int showo::run_layers(showo_engine* e, int B, int L, int pos0, const KVDest& kv, const int32_t* iv, const int32_t* flag,
                       const float* dense, hipStream_t s) {
     const int H = e->H, F = e->F, nH = e->nH;
     const int T = B * L;
@@ -956,63 +913,10 @@ static int run_layers(showo_engine* e, int B, int L, int pos0, const KVDest& kv,
         return set_error_msg(5, "engine (precision 3): the int8 decode step serves KV caches of up to 14 488 tokens");
     // (the fused three-launch decode layer of decode.hip has instances for both operand types since round 6)
     if (T == 1 && showo::g_decode_impl == 0 && !dense && showo::decode_fused_shapes_ok(H, F) && (size_t)Lcap * 4 + 2048 <= 60000) {
-        // AR decode step (decode.hip): three launches per layer.  Co-scheduled layer (default): the attention launch carries extra
-        // blocks that stream the fc2 weights into y2 (attention.hip, attn_decode_co_kernel) -- fc2 does not depend on the attention
-        // (Phi's block is parallel-residual) -- and the third launch adds dense(attn) and y2:
-        //   LN + qkv GEMV + fc1 GEMV  ->  [ attention (32 blocks) || fc2 GEMV -> y2 (co_blocks) ]  ->  dense GEMV + both residual adds
-        // Same arithmetic and parenthesisation as the plain chain (x = (x + (dense + bd)) + (fc2 + b2)): bit-identical results.
-        // Measured (gpurun_out/bench_mmu_r2p_*, one box, cfg4): chain 857-861 tokens/s; co-scheduled 922-928 with 224 fc2 blocks, 965
-        // with 128, 969 with 96.  (A stream fork / join of the same overlap was SLOWER than the chain, 705-711 vs 843-846 tokens/s --
-        // every fork / join edge of the per-token graph costs more than the overlap buys -- and left the library in round 6; so did
-        // folding the third launch into the second behind an in-launch hand-off, profiles/r6_decode_merge_ab.txt.)
-        // SHOWO_DECODE_FORK=0 / showo_decode_set_impl(2): the plain chain.
-        static int co_on = -1;
-        if (co_on < 0) {
-            const char* env = getenv("SHOWO_DECODE_FORK");
-            co_on = env ? (atoi(env) != 0) : 1;
-        }
-        const int co_blocks = showo::decode_tuning().co_blocks;
-        const bool co = co_on && F == 8192 && !g_decode_chain;
-        if (co && !e->y2) TRY(e->alloc(&e->y2, H));
-        for (int li = 0; li < e->nL; ++li) {
-            showo::Layer& l = e->layers[li];
-            bf16_t* Kd = kv.k + li * kv.k_lstride;
-            bf16_t* Vd = kv.vt + li * kv.v_lstride;
-            if (q8) {
-                // the same three launches on the int8 images (pointers travel as bf16_t*; the row scales select the int8 instances).
-                // No prefetch role: it would read ahead in the bf16 images, which these launches never stream.
-                const bf16_t *Wqkv = reinterpret_cast<const bf16_t*>(l.qqkv), *W1 = reinterpret_cast<const bf16_t*>(l.q1),
-                             *Wd = reinterpret_cast<const bf16_t*>(l.qd), *W2 = reinterpret_cast<const bf16_t*>(l.q2);
-                TRY(showo::decode_ln_gemv2(e->x, l.ln_w, l.ln_b, e->cfg.ln_eps, H, Wqkv, l.bqkv, e->qkv, nullptr, 3 * H, W1, l.b1, e->ffn, F, s, 0,
-                                           l.sqkv, l.s1));
-                if (co) {
-                    TRY(showo::attn_decode_fused(e->qkv, l.qln_w, l.qln_b, l.kln_w, l.kln_b, e->cosT, e->sinT, Kd, Vd, iv, e->attn, nH,
-                                                 e->cfg.rotary_dim, e->cfg.ln_eps, pos0, Lcap, Lp, s, W2, e->ffn, l.b2, F, H, e->y2, co_blocks, nullptr, 0, l.s2));
-                    TRY(showo::decode_out_gemv2(e->x, Wd, e->attn, l.bd, H, W2, e->ffn, l.b2, F, H, s, 2, e->y2, 0, l.sd, l.s2));
-                } else {
-                    TRY(showo::attn_decode_fused(e->qkv, l.qln_w, l.qln_b, l.kln_w, l.kln_b, e->cosT, e->sinT, Kd, Vd, iv, e->attn, nH,
-                                                 e->cfg.rotary_dim, e->cfg.ln_eps, pos0, Lcap, Lp, s, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, nullptr, 0));
-                    TRY(showo::decode_out_gemv2(e->x, Wd, e->attn, l.bd, H, W2, e->ffn, l.b2, F, H, s, 0, nullptr, 0, l.sd, l.s2));
-                }
-                continue;
-            }
-            if (co) {
-                TRY(showo::decode_ln_gemv2(e->x, l.ln_w, l.ln_b, e->cfg.ln_eps, H, l.wqkv, l.bqkv, e->qkv, nullptr, 3 * H, l.w1, l.b1,
-                                           e->ffn, F, s, op));
-                showo::DecodePrefetch pf;
-                showo::decode_prefetch_plan(e, li, &pf);
-                TRY(showo::attn_decode_fused(e->qkv, l.qln_w, l.qln_b, l.kln_w, l.kln_b, e->cosT, e->sinT, Kd, Vd, iv, e->attn, nH,
-                                             e->cfg.rotary_dim, e->cfg.ln_eps, pos0, Lcap, Lp, s, l.w2, e->ffn, l.b2, F, H, e->y2, co_blocks, &pf, op));
-                TRY(showo::decode_out_gemv2(e->x, l.wd, e->attn, l.bd, H, l.w2, e->ffn, l.b2, F, H, s, 2, e->y2, op));
-                continue;
-            }
-            TRY(showo::decode_ln_gemv2(e->x, l.ln_w, l.ln_b, e->cfg.ln_eps, H, l.wqkv, l.bqkv, e->qkv, nullptr, 3 * H, l.w1, l.b1,
-                                       e->ffn, F, s, op));
-            TRY(showo::attn_decode_fused(e->qkv, l.qln_w, l.qln_b, l.kln_w, l.kln_b, e->cosT, e->sinT, Kd, Vd, iv, e->attn, nH,
-                                         e->cfg.rotary_dim, e->cfg.ln_eps, pos0, Lcap, Lp, s, nullptr, nullptr, nullptr, 0, 0, nullptr, 0, nullptr, op));
-            TRY(showo::decode_out_gemv2(e->x, l.wd, e->attn, l.bd, H, l.w2, e->ffn, l.b2, F, H, s, 0, nullptr, op));
-        }
-        return 0;
+        // AR decode step: three launches per layer (decode.hip, decode_layers_b1), the co-scheduled form unless SHOWO_DECODE_FORK=0 /
+        // showo_decode_set_impl(2) ask for the plain chain
+        static const int co_on = env_flag("SHOWO_DECODE_FORK", 1);
+        return showo::decode_layers_b1(e, op, kv, iv, pos0, co_on && F == 8192 && !g_decode_chain, s);
     }
     // Prefill / t2i layers: TWO GEMM launches.  Phi's block is parallel-residual (phi.py:774-790): q/k/v_proj and fc1 read the
     // same LayerNorm output -> one [Wqkv ; W1] projection with a column-split epilogue; dense and fc2 add into the same residual
@@ -1070,7 +974,7 @@ static int run_layers(showo_engine* e, int B, int L, int pos0, const KVDest& kv,
     return 0;
 }
 
-static int check_ready(showo_engine* e, int B, int L) {
+int showo::check_ready(showo_engine* e, int B, int L) {
     if (!e) return set_error_msg(1, "engine: null handle");
     if (showo_engine_missing(e) != 0) return set_error_msg(4, "engine: weights missing (showo_engine_missing() != 0)");
     if ((int64_t)B * L > e->maxT || B > e->cfg.max_batch || L > e->cfg.max_seq || L > e->cfg.max_pos)
@@ -1078,7 +982,7 @@ static int check_ready(showo_engine* e, int B, int L) {
     return 0;
 }
 
-static int embed_in(showo_engine* e, const int64_t* ids, const float* embeds, int T, hipStream_t s) {
+int showo::embed_in(showo_engine* e, const int64_t* ids, const float* embeds, int T, hipStream_t s) {
     if ((ids == nullptr) == (embeds == nullptr)) return set_error_msg(1, "engine: exactly one of ids / embeds must be given");
     if (ids) return showo_embed_f32(ids, e->embed, e->x, T, e->H, e->V, s);
     SHOWO_CHECK_HIP(hipMemcpyAsync(e->x, embeds, (size_t)T * e->H * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -1098,7 +1002,7 @@ static int hidden(showo_engine* e, const int64_t* ids, const float* embeds, cons
     return run_layers(e, B, L, 0, kv_workspace(e, L), iv, flag, mask, s);
 }
 
-static int head_rows(showo_engine* e, const int32_t* rows, int nrows, int col0, int ncols, float* logits, hipStream_t s) {
+int showo::head_rows(showo_engine* e, const int32_t* rows, int nrows, int col0, int ncols, float* logits, hipStream_t s) {
     if (col0 < 0 || ncols <= 0 || col0 + ncols > e->V) return set_error_msg(1, "engine: bad vocabulary slice");
     if (e->precision == 1) return precise_fast_ok(e) ? head_rows_precise_fast(e, rows, nrows, col0, ncols, logits, s)
                                                        : head_rows_precise(e, rows, nrows, col0, ncols, logits, s);
@@ -1111,16 +1015,15 @@ static int head_rows(showo_engine* e, const int32_t* rows, int nrows, int col0, 
                                             e->wlm_lo + (int64_t)col0 * e->H, e->blm + col0, logits, ncols, ncols, 1, s);
         return head_rows_precise_fast(e, rows, nrows, col0, ncols, logits, s);  // (any shape)
     }
-    if (e->precision == 3 && nrows == 1 && !rows && showo::g_decode_impl == 0 && showo::decode_fused_shapes_ok(e->H, e->F)) {
-        // decode step under precision 3: the same launch on the int8 image of the lm_head
-        if (!e->q8_loaded.count("showo.lm_head.weight"))
+    if (nrows == 1 && !rows && showo::g_decode_impl == 0 && showo::decode_fused_shapes_ok(e->H, e->F)) {
+        // decode step: LN + lm_head in one launch, under precision 3 on the int8 image of the lm_head
+        if (e->precision == 3 && !e->q8_loaded.count("showo.lm_head.weight"))
             return set_error_msg(4, "engine (precision 3): the int8 image of the lm_head is missing or stale: upload the weights again");
-        return showo::decode_ln_gemv2(e->x, e->fln_w, e->fln_b, e->cfg.ln_eps, e->H, reinterpret_cast<const bf16_t*>(e->qlm + (int64_t)col0 * e->H),
-                                      e->blm + col0, nullptr, logits, ncols, nullptr, nullptr, nullptr, 0, s, 0, e->slm + col0, nullptr);
+        const showo::DecodeHeadOps w = showo::decode_head_ops(e, col0);
+        showo::LnGemvBArgs h{e->x, e->fln_w, e->fln_b, e->cfg.ln_eps, e->H, w.W, w.b, nullptr, logits, ncols, ncols, nullptr, nullptr, nullptr, 0, 0};
+        h.s0 = w.s;
+        return showo::decode_ln_gemv2(h, s);
     }
-    if (nrows == 1 && !rows && showo::g_decode_impl == 0 && showo::decode_fused_shapes_ok(e->H, e->F))  // decode step: LN + lm_head in one launch
-        return showo::decode_ln_gemv2(e->x, e->fln_w, e->fln_b, e->cfg.ln_eps, e->H, e->wlm + (int64_t)col0 * e->H, e->blm + col0,
-                                      nullptr, logits, ncols, nullptr, nullptr, nullptr, 0, s);
     TRY(showo_layernorm_f32_bf16(e->x, e->fln_w, e->fln_b, e->hf, rows, nrows, e->H, e->cfg.ln_eps, s));
     return showo_gemm_bf16(e->hf, e->H, e->wlm + (int64_t)col0 * e->H, e->H, e->blm + col0, 0, logits, ncols, nullptr, 0,
                            nrows, ncols, e->H, SHOWO_EPI_F32, s);
@@ -1374,22 +1277,11 @@ extern "C" int showo_engine_t2i_generate(showo_engine* e, int64_t* ids_cond, int
             if (!rc) rc = showo::sampler_step_inc(e->step_dev, s);
         }
         if (!rc && !hit) {
-            hipGraph_t g = nullptr;
             hipGraphExec_t exec = nullptr;
-            hipError_t he = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
-            if (he == hipSuccess) {
-                rc = denoise_step(-1, !reuse);
-                if (!rc) rc = showo::sampler_step_inc(e->step_dev, s);
-                hipError_t he2 = hipStreamEndCapture(s, &g);
-                if (!rc && he2 != hipSuccess) rc = set_error_hip(he2, "hipStreamEndCapture", __FILE__, __LINE__);
-            } else {
-                rc = set_error_hip(he, "hipStreamBeginCapture", __FILE__, __LINE__);
-            }
-            if (!rc) {
-                hipError_t he3 = hipGraphInstantiate(&exec, g, nullptr, nullptr, 0);
-                if (he3 != hipSuccess) { exec = nullptr; rc = set_error_hip(he3, "hipGraphInstantiate", __FILE__, __LINE__); }
-            }
-            if (g) hipGraphDestroy(g);
+            rc = showo::capture_step(s, [&]() -> int {
+                const int rs = denoise_step(-1, !reuse);
+                return rs ? rs : showo::sampler_step_inc(e->step_dev, s);
+            }, &exec);
             if (!rc) {
                 if ((int)e->t2i_graphs.size() >= showo_engine::T2I_GRAPH_SLOTS) {  // evict the least recently used graph
                     size_t lru = 0;
@@ -1425,214 +1317,6 @@ extern "C" int showo_engine_t2i_generate(showo_engine* e, int64_t* ids_cond, int
     return 0;
 }
 
-// ---- KV-cached decode ---------------------------------------------------------------------------------
-static int ensure_cache(showo_engine* e, int need) {
-    if (need <= e->cache_cap) return 0;
-    int cap = ((need + 63) / 64) * 64;
-    if (cap > e->cfg.max_pos) cap = ((e->cfg.max_pos + 63) / 64) * 64;
-    if (need > cap) return set_error_msg(5, "decode: sequence exceeds max_position_embeddings");
-    if (e->cache_cap != 0) return set_error_msg(5, "decode: cache capacity exceeded");
-    // allocate once at the maximum the position table allows (2048 tokens: 2 x 201 MB at full size)
-    cap = ((e->cfg.max_pos + 63) / 64) * 64;
-    int64_t n = (int64_t)e->nL * e->nH * cap * 64;
-    TRY(e->alloc(&e->kcache, n));
-    TRY(e->alloc(&e->vtcache, n));
-    hipMemset(e->kcache, 0, (size_t)n * sizeof(bf16_t));
-    hipMemset(e->vtcache, 0, (size_t)n * sizeof(bf16_t));
-    e->cache_cap = cap;
-    return 0;
-}
-// accuracy mode: low halves of the decode cache (same capacity), allocated when the first precision-1 prefill arrives
-static int ensure_cache_lo(showo_engine* e) {
-    if (e->kcache_lo || e->cache_cap == 0) return 0;
-    const int64_t n = (int64_t)e->nL * e->nH * e->cache_cap * 64;
-    TRY(e->alloc(&e->kcache_lo, n));
-    TRY(e->alloc(&e->vtcache_lo, n));
-    hipMemset(e->kcache_lo, 0, (size_t)n * sizeof(bf16_t));
-    hipMemset(e->vtcache_lo, 0, (size_t)n * sizeof(bf16_t));
-    return 0;
-}
-
-// prefill of ONE sequence into a given per-layer K / V^T destination (the engine's own decode cache, or a slot of a decode batch):
-// runs the prompt, leaves K / V^T of every layer there, returns the last prompt row's visibility intervals and its logits
-namespace showo {
-int engine_prefill_into(showo_engine* e, const int64_t* ids, const float* embeds, const float* mask, int L, bf16_t* k, bf16_t* vt,
-                        int64_t k_lstride, int64_t v_lstride, int cap, int* last_iv_out, float* logits_last, hipStream_t s,
-                        bf16_t* k_lo, bf16_t* vt_lo) {
-    TRY(embed_in(e, ids, embeds, L, s));
-    const int32_t *iv = nullptr, *flag = nullptr;
-    if (mask) {
-        TRY(showo_mask_compress(mask, e->iv, e->flag, 1, L, L, s));
-        iv = e->iv; flag = e->flag;
-    } else if (e->ext_iv) {  // caller-built intervals (showo_engine_use_intervals, e.g. from showo_mask_mmu_vit)
-        iv = e->ext_iv; flag = e->ext_flag;
-    }
-    // The prefill attention multiplies the V^T columns of its last 64-key tile beyond L by P = 0, which is 0 only if they are finite.
-    // The projection epilogue of >= 256-row prefills writes columns [0, L) alone, and a cache is zeroed once, when it is allocated: an
-    // earlier, longer prompt with a NaN activation may have left NaN in [L, 64 * ceil(L / 64)).
-    const int c1 = ((L + 63) / 64) * 64 < cap ? ((L + 63) / 64) * 64 : cap;
-    if (c1 > L) {
-        zero_vt_cols_kernel<<<dim3(e->nH * 64, e->nL), 64, 0, s>>>(vt, v_lstride, cap, L, c1);
-        SHOWO_CHECK_HIP(hipGetLastError());
-        if (vt_lo) {
-            zero_vt_cols_kernel<<<dim3(e->nH * 64, e->nL), 64, 0, s>>>(vt_lo, v_lstride, cap, L, c1);
-            SHOWO_CHECK_HIP(hipGetLastError());
-        }
-    }
-    TRY(run_layers(e, 1, L, 0, KVDest{k, vt, k_lstride, v_lstride, cap, cap, k_lo, vt_lo}, iv, flag, mask, s));
-    if (iv) {
-        int32_t f = 0;
-        SHOWO_CHECK_HIP(hipMemcpyAsync(last_iv_out, iv + (int64_t)(L - 1) * 4, 16, hipMemcpyDeviceToHost, s));
-        if (flag) SHOWO_CHECK_HIP(hipMemcpyAsync(&f, flag, 4, hipMemcpyDeviceToHost, s));
-        SHOWO_CHECK_HIP(hipStreamSynchronize(s));
-        if (f) return set_error_msg(6, "decode: prompt mask is not interval-representable; KV-cached decode unsupported");
-    } else {
-        last_iv_out[0] = 0; last_iv_out[1] = L; last_iv_out[2] = 0; last_iv_out[3] = 0;
-    }
-    set_iv_kernel<<<1, 64, 0, s>>>(e->rows, L - 1, 0, 0, 0);  // rows[0] = L-1
-    return head_rows(e, e->rows, 1, 0, e->V, logits_last, s);
-}
-}  // namespace showo
-
-extern "C" int showo_engine_prefill(showo_engine* e, const int64_t* ids, const float* embeds, const float* mask, int L,
-                                    float* logits_last, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    TRY(check_ready(e, 1, L));
-    if (e->precision == 1 && !precise_fast_ok(e))
-        return set_error_msg(1, "prefill: in accuracy mode the KV-cached decode needs the production-kernel form (showo_engine_precise_fast)");
-    TRY(ensure_cache(e, L + 1));
-    if (e->precision == 1) TRY(ensure_cache_lo(e));
-    const KVDest kv = kv_decode_cache(e);
-    ++e->cache_epoch;  // from here on the cache belongs to this prompt (also when the call fails half way)
-    TRY(showo::engine_prefill_into(e, ids, embeds, mask, L, kv.k, kv.vt, kv.k_lstride, kv.v_lstride, kv.Lcap, e->last_iv, logits_last, s,
-                                   kv.k_lo, kv.vt_lo));
-    e->prompt_len = L;
-    e->cache_len = L;
-    e->cache_precision = e->precision;
-    return 0;
-}
-
-// a cache prefilled under one precision must not be decoded under another -- precision 1 would attend with zero low halves
-// (bf16-grade results while get_precision() says 1), precision 2 would read bf16 keys as fp16
-static int check_cache_precision(const showo_engine* e) {
-    if (e->cache_precision != e->precision)
-        return set_error_msg(1, "decode: the KV cache was prefilled under another precision (showo_engine_set_precision changed since "
-                                "showo_engine_prefill): prefill again");
-    return 0;
-}
-
-extern "C" int showo_engine_decode_step(showo_engine* e, const int64_t* id, const float* embed, float* logits_last, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    if (!e || e->cache_len <= 0) return set_error_msg(1, "decode_step: prefill first");
-    TRY(check_cache_precision(e));
-    const int P = e->cache_len;  // position of the new token
-    if (P + 1 > e->cache_cap || P + 1 > e->cfg.max_pos) return set_error_msg(5, "decode_step: cache full");
-    TRY(embed_in(e, id, embed, 1, s));
-    // mask row of the new token = last prompt row + [prompt_len, P] (modeling_showo.py:203-217)
-    int a = e->last_iv[0], b = e->last_iv[1], c = e->last_iv[2], d = e->last_iv[3];
-    const int L0 = e->prompt_len;
-    if (b == L0 && a < b) b = P + 1;
-    else if (d == L0 && c < d) d = P + 1;
-    else if (!(c < d)) { c = L0; d = P + 1; }
-    else if (!(a < b)) { a = L0; b = P + 1; }
-    else return set_error_msg(6, "decode_step: mask row needs more than two intervals");
-    set_iv_kernel<<<1, 64, 0, s>>>(e->iv1, a, b, c, d);
-    hipMemsetAsync(e->flag, 0, 4, s);
-    if (e->precision == 1) TRY(ensure_cache_lo(e));
-    TRY(run_layers(e, 1, 1, P, kv_decode_cache(e), e->iv1, e->flag, nullptr, s));
-    e->cache_len = P + 1;
-    return head_rows(e, nullptr, 1, 0, e->V, logits_last, s);
-}
-
-// ---- mmu sessions: more prompt rows onto a cache (include/showo_hip.h; DESIGN.md, "mmu sessions") -------------------------------------
-static int zero_vt_tail(showo_engine* e, bf16_t* vt, bf16_t* vt_lo, int64_t v_lstride, int cap, int c0, int c1, hipStream_t s) {
-    if (c1 > cap) c1 = cap;
-    if (c1 <= c0) return 0;
-    zero_vt_cols_kernel<<<dim3(e->nH * 64, e->nL), 64, 0, s>>>(vt, v_lstride, cap, c0, c1);
-    if (vt_lo) zero_vt_cols_kernel<<<dim3(e->nH * 64, e->nL), 64, 0, s>>>(vt_lo, v_lstride, cap, c0, c1);
-    SHOWO_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
-// Ln rows of ONE sequence at positions P .. P + Ln - 1 of a per-layer K / V^T destination that holds the rows below P (the engine's
-// decode cache, or a slot of a decode batch): every row attends as a decode row (last prefill row + causal), K / V^T of the new rows
-// land behind the old ones, logits_last = the logits of the last new row.  Ln == 1 is the decode step's layer and head launches behind the tail zeroing.
-namespace showo {
-int engine_append_into(showo_engine* e, const int64_t* ids, const float* embeds, int Ln, int P, const int* last_iv, int L0, bf16_t* k,
-                       bf16_t* vt, int64_t k_lstride, int64_t v_lstride, int cap, float* logits_last, hipStream_t s, bf16_t* k_lo,
-                       bf16_t* vt_lo) {
-    if (showo_engine_missing(e) != 0) return set_error_msg(4, "engine: weights missing (showo_engine_missing() != 0)");
-    if (Ln < 1 || !logits_last) return set_error_msg(1, "prefill_append: needs Ln >= 1 and a logits buffer");
-    if (Ln > e->maxT) return set_error_msg(5, "engine: batch/sequence exceeds the configured workspace");
-    if (P + Ln + 1 > cap || P + Ln + 1 > e->cfg.max_pos) return set_error_msg(5, "prefill_append: cache full");
-    int32_t lv[4] = {last_iv[0], last_iv[1], last_iv[2], last_iv[3]};
-    if (!((lv[1] == L0 && lv[0] < lv[1]) || (lv[3] == L0 && lv[2] < lv[3]) || !(lv[2] < lv[3]) || !(lv[0] < lv[1])))
-        return set_error_msg(6, "prefill_append: mask row needs more than two intervals");
-    TRY(embed_in(e, ids, embeds, Ln, s));
-    // the attention of the new rows reads whole 64-key tiles: the V^T columns behind the last new row meet P = 0 and must be finite
-    // (decode steps leave them as they found them, engine_prefill_into's comment says what may be there)
-    TRY(zero_vt_tail(e, vt, vt_lo, v_lstride, cap, P + Ln, ((P + Ln + 63) / 64) * 64, s));
-    const KVDest kv{k, vt, k_lstride, v_lstride, cap, cap, k_lo, vt_lo};
-    SHOWO_CHECK_HIP(hipMemsetAsync(e->flag, 0, 4, s));
-    if (Ln == 1) {  // showo_engine_decode_step
-        int a = lv[0], b = lv[1], c = lv[2], d = lv[3];
-        if (b == L0 && a < b) b = P + 1;
-        else if (d == L0 && c < d) d = P + 1;
-        else if (!(c < d)) { c = L0; d = P + 1; }
-        else { a = L0; b = P + 1; }
-        set_iv_kernel<<<1, 64, 0, s>>>(e->iv1, a, b, c, d);
-        TRY(run_layers(e, 1, 1, P, kv, e->iv1, e->flag, nullptr, s));
-        return head_rows(e, nullptr, 1, 0, e->V, logits_last, s);
-    }
-    TRY(showo_mask_append_rows(lv, L0, P, Ln, e->iv, s));
-    TRY(run_layers(e, 1, Ln, P, kv, e->iv, e->flag, nullptr, s));
-    set_iv_kernel<<<1, 64, 0, s>>>(e->rows, Ln - 1, 0, 0, 0);  // rows[0] = Ln - 1
-    return head_rows(e, e->rows, 1, 0, e->V, logits_last, s);
-}
-}  // namespace showo
-
-extern "C" int showo_engine_prefill_append(showo_engine* e, const int64_t* ids, const float* embeds, int Ln, float* logits_last,
-                                           void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    if (!e || e->cache_len <= 0) return set_error_msg(1, "prefill_append: prefill first");
-    TRY(check_cache_precision(e));
-    if (e->precision == 1) TRY(ensure_cache_lo(e));
-    const KVDest kv = kv_decode_cache(e);
-    const int P = e->cache_len;
-    TRY(showo::engine_append_into(e, ids, embeds, Ln, P, e->last_iv, e->prompt_len, kv.k, kv.vt, kv.k_lstride, kv.v_lstride, kv.Lcap,
-                                  logits_last, s, kv.k_lo, kv.vt_lo));
-    e->cache_len = P + Ln;
-    return 0;
-}
-
-extern "C" int showo_engine_cache_rewind(showo_engine* e, int len, void* stream) {
-    if (!e || e->cache_len <= 0) return set_error_msg(1, "cache_rewind: prefill first");
-    if (len < e->prompt_len || len > e->cache_len) return set_error_msg(1, "cache_rewind: prompt_len <= len <= cache length required");
-    const KVDest kv = kv_decode_cache(e);
-    TRY(zero_vt_tail(e, kv.vt, kv.vt_lo, kv.v_lstride, kv.Lcap, len, ((e->cache_len + 63) / 64) * 64, (hipStream_t)stream));
-    e->cache_len = len;
-    return 0;
-}
-
-extern "C" int showo_engine_cache_state(const showo_engine* e, int* cache_len, int* prompt_len, int* cap, int64_t* epoch) {
-    if (!e) return set_error_msg(1, "engine: null handle");
-    if (cache_len) *cache_len = e->cache_len;
-    if (prompt_len) *prompt_len = e->prompt_len;
-    if (cap) *cap = e->cache_cap;
-    if (epoch) *epoch = e->cache_epoch;
-    return 0;
-}
-
-extern "C" int showo_engine_cache_ptrs(showo_engine* e, uint16_t** k, uint16_t** vt, int64_t* k_lstride, int64_t* v_lstride) {
-    if (!e || !e->kcache) return set_error_msg(1, "cache_ptrs: no decode cache yet (prefill first)");
-    const KVDest kv = kv_decode_cache(e);
-    if (k) *k = kv.k;
-    if (vt) *vt = kv.vt;
-    if (k_lstride) *k_lstride = kv.k_lstride;
-    if (v_lstride) *v_lstride = kv.v_lstride;
-    return 0;
-}
-
 // Visibility intervals built on the device (showo_mask_predict_next / _mmu / _mmu_vit) instead of a dense mask: the next
 // forward / forward_rows / t2i_generate calls that pass mask == NULL attend with iv int32 [B,L,4] (NULL restores causal).
 extern "C" int showo_engine_use_intervals(showo_engine* e, const int32_t* iv, const int32_t* flag) {
@@ -1640,137 +1324,6 @@ extern "C" int showo_engine_use_intervals(showo_engine* e, const int32_t* iv, co
     e->ext_iv = iv;
     e->ext_flag = iv ? flag : nullptr;
     return 0;
-}
-
-// Continuation loop: n_steps times { embed(tok) -> 24 layers against the KV cache -> lm_head -> next token -> tok }, the
-// position and the mask row living in device memory so that ONE step can be captured into a hipGraph and replayed.
-// tok int64[1] (device): in = the token to feed first, out = the last token produced; out_tokens int64 [n_steps] (device).
-// top_k == 1: arg-max (the reference caller's setting); otherwise temperature / top-k / multinomial on the device
-// (showo_sample_topk semantics; draw j of this call uses noise row / Philox stream step0 + j); 0 < top_p < 1 puts the nucleus filter
-// in front of the draw (showo_sample_topk_topp), top_p >= 1 is the launch of a call without it.
-// lps != NULL (showo_engine_decode_sample_lp): one more launch per step, behind the token boundary, scores the token the step stored
-// against the step's row in logits_ws (sample_row.h logprob_row) -> lps / ranks [n_steps]; NULL: no launch, the loop of a call without.
-static int decode_loop(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws, int top_k, float top_p,
-                       float temperature, const float* exp_noise, uint64_t seed, int step0, int use_graph, void* stream,
-                       float* lps = nullptr, int32_t* ranks = nullptr) {
-    hipStream_t s = (hipStream_t)stream;
-    if (!e || e->cache_len <= 0) return set_error_msg(1, "decode_greedy: prefill first");
-    if (!tok || !out_tokens || !logits_ws || n_steps < 1) return set_error_msg(1, "decode_greedy: bad arguments");
-    TRY(check_cache_precision(e));
-    const int P0 = e->cache_len;
-    if (P0 + n_steps > e->cache_cap || P0 + n_steps > e->cfg.max_pos) return set_error_msg(5, "decode_greedy: cache full");
-    {   // the decode_step precondition: the mask row must stay a two-interval row
-        int a = e->last_iv[0], b = e->last_iv[1], c = e->last_iv[2], d = e->last_iv[3];
-        const int L0 = e->prompt_len;
-        if (!((b == L0 && a < b) || (d == L0 && c < d) || !(c < d) || !(a < b)))
-            return set_error_msg(6, "decode_greedy: mask row needs more than two intervals");
-    }
-    if (!e->pos_dev) { TRY(e->alloc(&e->pos_dev, 4)); TRY(e->alloc(&e->last_iv_dev, 4)); }
-    SHOWO_CHECK_HIP(hipMemcpyAsync(e->pos_dev, &P0, sizeof(int), hipMemcpyHostToDevice, s));
-    SHOWO_CHECK_HIP(hipMemcpyAsync(e->last_iv_dev, e->last_iv, 4 * sizeof(int32_t), hipMemcpyHostToDevice, s));
-    SHOWO_CHECK_HIP(hipMemsetAsync(e->flag, 0, 4, s));
-    SHOWO_CHECK_HIP(hipStreamSynchronize(s));  // P0 / last_iv are host temporaries of this call
-    // accuracy mode: the production-kernel layers take the position from the host (no device-side position in those launches), so the
-    // steps run eagerly with pos = P0 + i; the token boundary (seam / sampler) keeps pos_dev in step with it
-    const bool prec = e->precision == 1;
-    if (prec) TRY(ensure_cache_lo(e));
-    int step_i = 0;
-    if (!prec) showo::attn_set_decode_pos(e->pos_dev, P0 + n_steps);
-    // Greedy loop (top_k == 1, the reference caller's setting): the token boundary -- arg-max merge, token store, position increment, next
-    // embedding row, next mask row -- is one launch (basic.hip, greedy_token_seam_kernel) at the END of a step, so a step is
-    // [layers, lm_head, arg-max partials, boundary] and only the first step embeds its token up front.  SHOWO_DECODE_TOKSEAM=0: the
-    // five separate launches.
-    static int tokseam = -1;
-    if (tokseam < 0) { const char* env = getenv("SHOWO_DECODE_TOKSEAM"); tokseam = env ? (atoi(env) != 0) : 1; }
-    const bool seam_tok = tokseam && top_k == 1 && e->V >= 16384;
-    auto pre = [&]() -> int {
-        TRY(showo_embed_f32(tok, e->embed, e->x, 1, e->H, e->V, s));
-        decode_iv_kernel<<<1, 64, 0, s>>>(e->last_iv_dev, e->prompt_len, e->pos_dev, e->iv1);
-        return 0;
-    };
-    if (seam_tok) TRY(pre());
-    auto one = [&]() -> int {
-        if (!seam_tok) TRY(pre());
-        // host-side P only sizes nothing here (grids depend on L = 1); the kernels read the position from pos_dev
-        TRY(run_layers(e, 1, 1, prec ? P0 + step_i : P0, kv_decode_cache(e), e->iv1, e->flag, nullptr, s));
-        ++step_i;
-        TRY(head_rows(e, nullptr, 1, 0, e->V, logits_ws, s));
-        // the token boundary leaves the token in *tok and the position ALREADY advanced: the log-prob launch writes entry pos - 1 - P0
-        auto score = [&]() -> int { return lps ? showo::logprob_step_launch(logits_ws, e->V, tok, e->pos_dev, P0, lps, ranks, s) : 0; };
-        if (seam_tok) {
-            TRY(showo::greedy_token_seam(logits_ws, e->V, tok, out_tokens, e->pos_dev, P0, e->embed, e->x, e->H, e->V, e->last_iv_dev,
-                                         e->prompt_len, e->iv1, s));
-            return score();
-        }
-        if (top_k == 1) TRY(showo_argmax_f32(logits_ws, e->V, tok, s));
-        else if (top_p >= 1.f) TRY(showo::sample_topk_launch(logits_ws, e->V, top_k, temperature, exp_noise, (int64_t)e->V, seed, step0, e->pos_dev, P0,
-                                                             tok, s));
-        else TRY(showo::sample_topk_topp_launch(logits_ws, e->V, top_k, top_p, temperature, exp_noise, (int64_t)e->V, seed, step0,
-                                                e->pos_dev, P0, tok, s));
-        store_token_kernel<<<1, 64, 0, s>>>(tok, out_tokens, e->pos_dev, P0);
-        TRY(showo::sampler_step_inc(e->pos_dev, s));
-        return score();
-    };
-    int rc = one();  // eager first step (kernel attributes, GEMV variants)
-    hipGraph_t g = nullptr;
-    hipGraphExec_t ge = nullptr;
-    const bool graph = use_graph && n_steps > 1 && !showo::g_prof_on_query() && !prec;
-    if (!rc && graph) {
-        hipError_t he = hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal);
-        if (he == hipSuccess) {
-            rc = one();
-            hipError_t he2 = hipStreamEndCapture(s, &g);
-            if (!rc && he2 != hipSuccess) rc = set_error_hip(he2, "hipStreamEndCapture", __FILE__, __LINE__);
-        } else {
-            rc = set_error_hip(he, "hipStreamBeginCapture", __FILE__, __LINE__);
-        }
-        if (!rc) {
-            hipError_t he3 = hipGraphInstantiate(&ge, g, nullptr, nullptr, 0);
-            if (he3 != hipSuccess) rc = set_error_hip(he3, "hipGraphInstantiate", __FILE__, __LINE__);
-        }
-        for (int i = 1; !rc && i < n_steps; ++i) {
-            hipError_t he4 = hipGraphLaunch(ge, s);
-            if (he4 != hipSuccess) rc = set_error_hip(he4, "hipGraphLaunch", __FILE__, __LINE__);
-        }
-    } else {
-        for (int i = 1; !rc && i < n_steps; ++i) rc = one();
-    }
-    showo::attn_set_decode_pos(nullptr);
-    if (ge) { hipStreamSynchronize(s); hipGraphExecDestroy(ge); }
-    if (g) hipGraphDestroy(g);
-    if (rc) return rc;
-    e->cache_len = P0 + n_steps;
-    return 0;
-}
-
-extern "C" int showo_engine_decode_greedy(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws,
-                                          int use_graph, void* stream) {
-    return decode_loop(e, tok, n_steps, out_tokens, logits_ws, 1, 1.0f, 1.0f, nullptr, 0, 0, use_graph, stream);
-}
-
-extern "C" int showo_engine_decode_sample(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws,
-                                          int top_k, float temperature, const float* exp_noise, uint64_t seed, int step0,
-                                          int use_graph, void* stream) {
-    if (!(temperature > 0.f)) return set_error_msg(1, "decode_sample: temperature must be > 0");
-    return decode_loop(e, tok, n_steps, out_tokens, logits_ws, top_k, 1.0f, temperature, exp_noise, seed, step0, use_graph, stream);
-}
-
-extern "C" int showo_engine_decode_sample_p(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws,
-                                            int top_k, float top_p, float temperature, const float* exp_noise, uint64_t seed,
-                                            int step0, int use_graph, void* stream) {
-    if (!(temperature > 0.f)) return set_error_msg(1, "decode_sample_p: temperature must be > 0");
-    if (!(top_p > 0.f)) return set_error_msg(1, "decode_sample_p: top_p must be > 0 (>= 1: no nucleus filter)");
-    return decode_loop(e, tok, n_steps, out_tokens, logits_ws, top_k, top_p, temperature, exp_noise, seed, step0, use_graph, stream);
-}
-
-// showo_engine_decode_sample_p that also reports how probable every token was (include/showo_hip.h)
-extern "C" int showo_engine_decode_sample_lp(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws,
-                                             int top_k, float top_p, float temperature, const float* exp_noise, uint64_t seed,
-                                             int step0, float* logprobs, int32_t* ranks, int use_graph, void* stream) {
-    if (!(temperature > 0.f)) return set_error_msg(1, "decode_sample_lp: temperature must be > 0");
-    if (!(top_p > 0.f)) return set_error_msg(1, "decode_sample_lp: top_p must be > 0 (>= 1: no nucleus filter)");
-    return decode_loop(e, tok, n_steps, out_tokens, logits_ws, top_k, top_p, temperature, exp_noise, seed, step0, use_graph, stream,
-                       logprobs, logprobs ? ranks : nullptr);
 }
 
 // ---- scoring given tokens (include/showo_hip.h; DESIGN.md, "Log-probabilities") ---------------------------------------------------------

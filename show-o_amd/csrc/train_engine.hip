@@ -48,11 +48,6 @@ struct LayerPlan {
 };
 struct Bound { std::string key; float *p, *m, *v; int64_t n; bool decay; };
 
-// an on / off switch of this file from the environment (unset: dflt); every caller reads its switch once per process
-bool env_flag(const char* name, bool dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) != 0 : dflt;
-}
 // SHOWO_TRAIN_TN (default 1): weight gradients by showo_gemm_tn_bf16 on the token-major tensors the backward already holds (dY, and the
 // activations saved by the forward) + showo_colsum_bf16 for the bias gradients; 0 = transpose both operands and run the k-contiguous
 // GEMM (the round-2 path: 243 transposes per step).  Read once per process: the per-layer gelu(fc1) buffers exist only in TN mode.
