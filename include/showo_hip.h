@@ -155,10 +155,34 @@ int showo_conv3x3_bf16x3(const uint16_t* x, const uint16_t* xlo, const uint16_t*
 int showo_conv3x3_bf16x3_gn(const uint16_t* x, const uint16_t* xlo, const uint16_t* w, const uint16_t* wlo, const float* bias,
                             const float* resid, float* out, double* stats, int B, int Hin, int Win, int Cin, int Cout, int mode,
                             void* stream);
+/* The same, leaving the statistics as partials when there are at most SHOWO_GN_FOLD_MAX per image: *pending = their count (at
+ * stats + B * 64, for showo_gn_apply_part) or 0 when stats holds the final sums. */
+int showo_conv3x3_bf16x3_gn_lazy(const uint16_t* x, const uint16_t* xlo, const uint16_t* w, const uint16_t* wlo, const float* bias,
+                                 const float* resid, float* out, double* stats, int B, int Hin, int Win, int Cin, int Cout, int mode,
+                                 int* pending, void* stream);
+/* Thin-Cout 3x3 convolution (stride 1, pad 1) on split operands, for decoder.conv_out (128 -> 3 channels at the image resolution): one
+ * pass over the (hi, lo) activation image with the weights in registers and fp32 FMAs (x_hi * (w_hi + w_lo) + x_lo * w_hi: the three
+ * products of the split kernels), instead of a 128-wide MFMA n-tile for 3 columns.  x / xlo NHWC [B, H, W, Cin], w / wlo
+ * [Cout][3][3][Cin], out fp32 NHWC [B, H, W, Cout] = conv + bias.  Cout <= 4, Cin % 32 == 0, Cin <= 256.  The summation order differs
+ * from the MFMA kernel: same accuracy class (3e-5 of the output scale against fp64), not the same bits. */
+int showo_conv3x3_thin_bf16x3(const uint16_t* x, const uint16_t* xlo, const uint16_t* w, const uint16_t* wlo, const float* bias,
+                              float* out, int B, int H, int W, int Cin, int Cout, void* stream);
+/* Strided batch of showo_gemm_bf16x3: image z < batch uses A + z * sA (hi and lo), W + z * sW (hi and lo), out + z * sOut,
+ * resid + z * sResid and bias + z * sBias (strides in elements; 0 = shared by every image).  One launch with the image index as the
+ * grid's second dimension; every image runs the tiles of its own (M, N, K) launch, so the result has the bits of `batch` calls of
+ * showo_gemm_bf16x3.  Operand strides must be multiples of 8 elements. */
+int showo_gemm_bf16x3_batched(const uint16_t* A, const uint16_t* Alo, int lda, int64_t sA, const uint16_t* W, const uint16_t* Wlo,
+                              int ldw, int64_t sW, const float* bias, int bias_per_row, int64_t sBias, float* out, int ldo,
+                              int64_t sOut, const float* resid, int ldr, int64_t sResid, int M, int N, int K, int batch,
+                              void* stream);
 /* Launches so far of the split conv kernel that stages the activation operand once per (ky, channel chunk) for all three kx taps
- * (gemm.hip conv3t_split_kernel: modes 0 / 1, Wout a multiple of 16 that divides or is a multiple of 256, Hout * Wout % 256 == 0, launches
- * that do not split K; SHOWO_CONV_3TAP=0 turns it off).  Tests assert their coverage with it. */
+ * (gemm.hip conv3t_split_kernel: modes 0 / 1, Wout a multiple of 16 that divides or is a multiple of 256, Hout * Wout % 256 == 0;
+ * SHOWO_CONV_3TAP=0 turns it off).  Tests assert their coverage with it. */
 int64_t showo_conv3t_launches(void);
+/* Of those, the launches that split K: the 3-tap kernel takes the split launches of the 16 x 16 / 32 x 32 levels too (contiguous
+ * ranges of (ky, channel chunk) stages per split, last-arriver reduction in split order: the same bits on every run).
+ * SHOWO_CONV_3TAP_SPLITK=0 sends them to the older kernel. */
+int64_t showo_conv3t_split_launches(void);
 /* fp32 -> (hi, lo) bf16 pair */
 int showo_split_f32_bf16(const float* src, uint16_t* hi, uint16_t* lo, int64_t n, void* stream);
 
@@ -501,7 +525,20 @@ int showo_gn_finalize(const double* part, double* stats, int B, int nblk, void* 
  * ylo (optional): low half for split precision, ylo = bf16(value - float(y)). */
 int showo_gn_apply(const float* x, const double* stats, const float* gamma, const float* beta, uint16_t* y, uint16_t* ylo,
                    int B, int HW, int C, float eps, int do_swish, void* stream);
-/* 3x3 convolution as implicit GEMM on MFMA.  x bf16 NHWC [B,Hin,Win,Cin]; w bf16 [Cout][3][3][Cin];
+/* The apply pass sizes its grid to the tensor: 512 pixels per block on the large levels, fewer on the small ones so that B x blocks
+ * reaches about 1024 (down to one pass of the block).  showo_gn_set_fixed_grid(1) keeps 512 everywhere (the former grid: A/B lever and
+ * reference of tests/test_vq_tail_gpu.py).  The kernel is elementwise given the statistics: same output bits either way. */
+int showo_gn_set_fixed_grid(int on);
+/* Folded finalize.  An image with at most SHOWO_GN_FOLD_MAX partials (the 16^2 ... 64^2 levels) does not need the separate
+ * showo_gn_finalize launch: showo_gn_apply_part takes part[b][k][32][2], k < nblk, and every block sums them in its prologue in
+ * showo_gn_finalize's order (four strided quarters, (q0 + q1) + (q2 + q3), in double), so y / ylo have the bits of the
+ * showo_gn_finalize + showo_gn_apply pair.  showo_gn_stats_lazy is showo_gn_stats that stops after the partial pass when it may:
+ * *pending = the partial count (they lie at stats + B * 64) or 0 when stats holds the final sums (pending == NULL: always final). */
+#define SHOWO_GN_FOLD_MAX 16
+int showo_gn_stats_lazy(const float* x, double* stats, int B, int HW, int C, int* pending, void* stream);
+int showo_gn_apply_part(const float* x, const double* part, int nblk, const float* gamma, const float* beta, uint16_t* y,
+                        uint16_t* ylo, int B, int HW, int C, float eps, int do_swish, void* stream);
+/* 3x3 convolution as implicit GEMM on MFMA. x bf16 NHWC [B,Hin,Win,Cin]; w bf16 [Cout][3][3][Cin];
  * out fp32 NHWC [B,Hout,Wout,Cout] = conv + bias (+ resid).  mode: 0 = stride 1 pad 1;
  * 1 = nearest-2x upsample then stride 1 pad 1 (common_modules.py:36-40); 2 = pad (0,1,0,1) then stride 2
  * (common_modules.py:83-88).  Cin % 64 == 0 (thin inputs are zero-padded to 64 channels); any Cout. */
@@ -824,6 +861,16 @@ void showo_vq_destroy(showo_vq* v);
  * layout (conv: [Cout,Cin,kh,kw]); repacked to channel-last bf16 inside. */
 int showo_vq_load(showo_vq* v, const char* key, const float* src, int64_t n, void* stream);
 int showo_vq_missing(const showo_vq* v);
+/* A/B switches of the low-resolution tail (1 = on, the default; 0 = off; negative = leave unchanged).  attn_batched: the attention block
+ * runs V^T, Q K^T, softmax and P V once for all images (showo_gemm_bf16x3_batched; split precision, B > 1) instead of looping over
+ * them.  gn_fold: GroupNorm applies from <= SHOWO_GN_FOLD_MAX partials (showo_gn_apply_part) without the finalize launch.  The outputs
+ * have the same bits with either setting of those two.  thin_conv: decoder.conv_out (Cout = 3) runs showo_conv3x3_thin_bf16x3 instead of
+ * the MFMA conv (split precision); this one changes the image's low bits.  SHOWO_VQ_ATTN_BATCH=0 / SHOWO_GN_FOLD=0 /
+ * SHOWO_CONV_THIN=0 select 0 at creation. */
+int showo_vq_set_tail(showo_vq* v, int attn_batched, int gn_fold, int thin_conv);
+/* One attention block alone (prefix = "decoder.mid.attn_1" or "encoder.mid.attn_1"), in place on x fp32 channel-last [B, H * W, C]:
+ * x += AttnBlock(x) (common_modules.py:187-211).  Per image the result does not depend on B; tests of the batched form use it. */
+int showo_vq_attn_block(showo_vq* v, const char* prefix, float* x, int B, int H, int W, void* stream);
 /* MAGVITv2.decode_code (modeling_magvitv2.py:429-433): ids int64 [B,h*w] -> image fp32 NCHW [B,3,16h,16w]. */
 int showo_vq_decode_code(showo_vq* v, const int64_t* ids, int B, int h, int w, float* image, void* stream);
 /* MAGVITv2.get_code (modeling_magvitv2.py:423-427): pixels fp32 NCHW [B,3,H,W] -> ids int64 [B,(H/16)*(W/16)];

@@ -149,6 +149,15 @@ _PROTOS = {
     "showo_gn_stats_doubles": [c_i, c_i],
     "showo_gn_finalize": [c_p, c_p, c_i, c_i, c_p],
     "showo_gn_apply": [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_i, c_p],
+    "showo_gn_set_fixed_grid": [c_i],
+    "showo_gn_stats_lazy": [c_p, c_p, c_i, c_i, c_i, c_p, c_p],
+    "showo_gn_apply_part": [c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_i, c_p],
+    "showo_conv3x3_bf16x3_gn_lazy": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p, c_p],
+    "showo_gemm_bf16x3_batched": [c_p, c_p, c_i, c_i64, c_p, c_p, c_i, c_i64, c_p, c_i, c_i64, c_p, c_i, c_i64, c_p, c_i, c_i64,
+                                  c_i, c_i, c_i, c_i, c_p],
+    "showo_vq_set_tail": [c_p, c_i, c_i, c_i],
+    "showo_vq_attn_block": [c_p, C.c_char_p, c_p, c_i, c_i, c_i, c_p],
+    "showo_conv3x3_thin_bf16x3": [c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_p],
     "showo_conv3x3_bf16": [c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p],
     "showo_conv_small_f32": [c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_p],
     "showo_softmax_rows_bf16": [c_p, c_p, c_p, c_i, c_i, c_i, c_f, c_p],
@@ -244,7 +253,7 @@ _PROTOS = {
     "showo_prof_set_stride": [c_i],
     "showo_prof_totals": [c_i, c_p, c_p],
 }
-_I64 = {"showo_gemm_tiled_elems": [c_i, c_i], "showo_conv3t_launches": [], "showo_train_generation": [c_p]}
+_I64 = {"showo_gemm_tiled_elems": [c_i, c_i], "showo_conv3t_launches": [], "showo_conv3t_split_launches": [], "showo_train_generation": [c_p]}
 _VOID = {"showo_engine_destroy": [c_p], "showo_vq_destroy": [c_p], "showo_train_destroy": [c_p], "showo_clip_destroy": [c_p], "showo_projector_destroy": [c_p]}
 EXPORTED_SYMBOLS = sorted(list(_PROTOS) + list(_VOID) + list(_I64) + ["showo_last_error"])
 
@@ -298,6 +307,8 @@ def load():
         fn.argtypes = args
         fn.restype = None
     for name, args in _I64.items():
+        if os.environ.get("SHOWO_LIB_PATH") and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)
         fn.argtypes = args
         fn.restype = c_i64

@@ -45,6 +45,8 @@ struct LinearLoader {
     const bf16_t* Alo;
     const bf16_t* rowp[4];
     int64_t lo_delta;  // element offset from the hi to the lo operand (same layout)
+    int64_t bsA = 0;   // strided batch (GemmArgs::batch): element offset of image z's operand
+    __device__ inline void image(int z) { A += z * bsA; if (Alo) Alo += z * bsA; }
     __device__ inline void setup(int i, int m) {
         int mm = m < M ? m : M - 1;
         rowp[i] = A + (int64_t)mm * lda;
@@ -60,6 +62,7 @@ struct ConvLoader {
     int oy[4], ox[4];
     const bf16_t* img[4];
     int ky, kx, cbase;  // per k-tile (block-uniform)
+    __device__ inline void image(int) {}
     __device__ inline void setup(int i, int m) {
         int mm = m < M ? m : M - 1;
         int hw = c.Hout * c.Wout;
@@ -107,6 +110,16 @@ struct ConvLoader {
 template <int EPI, class Loader, bool SPLIT, bool F16 = false>  // F16: IEEE-half operands (common.h Op16; plain form only)
 __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs g, Loader ld_in) {
     Loader ld = ld_in;
+    if (g.batch > 1) {  // strided batch: block-uniform pointer offsets of image blockIdx.y, then exactly the single launch
+        const int64_t z = blockIdx.y;
+        g.W += z * g.bsW;
+        if (SPLIT) g.Wlo += z * g.bsW;
+        if (EPI == SHOWO_EPI_F32 || EPI == SHOWO_EPI_RESID_F32) g.out = reinterpret_cast<float*>(g.out) + z * g.bsOut;
+        else g.out = reinterpret_cast<bf16_t*>(g.out) + z * g.bsOut;
+        if (g.bias) g.bias += z * g.bsBias;
+        if (g.resid) g.resid += z * g.bsResid;
+        ld.image((int)z);
+    }
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     // plain: [2][128*64] per operand (double-buffered, 64 KiB).  SPLIT: four operand images, SINGLE-buffered (64 KiB, two
     // barriers per k-tile) so that two blocks share a CU and overlap each other's staging and MFMA phases.
@@ -261,7 +274,7 @@ int launch(const GemmArgs& g, const Loader& ld, hipStream_t s) {
         attr_set = true;
     }
     int tilesM = (g.M + BM - 1) / BM, tilesN = (g.N + BN - 1) / BN;
-    kfn<<<dim3(tilesM * tilesN), dim3(256), smem, s>>>(g, ld);
+    kfn<<<dim3(tilesM * tilesN, g.batch > 1 ? g.batch : 1), dim3(256), smem, s>>>(g, ld);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return set_error_hip(e, "gemm launch", __FILE__, __LINE__);
     return 0;
@@ -1225,7 +1238,7 @@ __global__ __launch_bounds__(512) void conv2p_split_kernel(GemmArgs g, ConvArgs 
 // at entry r (TW + 2) + x + kx -- a shifted view, no second fetch: A bytes per k-tile 32 KiB -> (256 + 2 R) / 768 of that (12 KiB),
 // W unchanged (16 KiB): 28 instead of 48 KiB per k-tile.  k order: (ky, channel chunk, kx); weights are addressed by k0 = (3 ky + kx)
 // Cin + cb as before.  modes 0 (stride 1, pad 1) and 1 (nearest 2x upsample + pad 1: the entry's source is (uy >> 1, ux >> 1));
-// the stride-2 form and split-K launches stay on conv2p_split_kernel.  Same wave tiling, fragment layout, swizzle (a function of the
+// the stride-2 form stays on conv2p_split_kernel; split-K launches run contiguous stage ranges here (see the kernel).  Same wave tiling, fragment layout, swizzle (a function of the
 // PHYSICAL LDS row, so 16 consecutive rows from any start are conflict-free) and epilogue as conv2p_split_kernel.
 // Schedule: one barrier per k-tile; the DMA of the next k-tile's weights (and, at kx = 0, of the next stage) is issued before the
 // fragment reads + 48 MFMAs of the current one and waited for at the barrier.
@@ -1253,6 +1266,11 @@ __global__ __launch_bounds__(512) void conv3t_split_kernel(GemmArgs g, ConvArgs 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int tilesM = g.M / CS_AROWS, tilesN = (g.N + CS_WROWS - 1) / CS_WROWS;
     int nwg = tilesM * tilesN, bid = blockIdx.x;
+    // split-K (GemmArgs::splits > 1, the 16 x 16 / 32 x 32 levels): the grid is tiles x splits and block (tile, split) runs a contiguous
+    // range of STAGES (ky, channel chunk) -- see the k loop; the last block of a tile to arrive sums the partials in split order and
+    // runs the epilogue (conv_splitk_exchange, as in conv2p_split_kernel).  No block waits for another.
+    int split = 0;
+    if (g.splits > 1) { split = bid / nwg; bid -= split * nwg; }
     {
         int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, loc = bid >> 3;
         bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + loc;
@@ -1343,13 +1361,22 @@ __global__ __launch_bounds__(512) void conv3t_split_kernel(GemmArgs g, ConvArgs 
     //   kx = 1: W(t + 1) heads the list of kx = 0          -> its A pieces (2 a0) + W(t + 2) + slot 1                  = 2 a0 + 4
     //   kx = 2: the next stage must be complete             -> W(t + 2) only                                             = 2
     // (a0 = 1 + has2).  Weights have two k-tiles to land, activations one to two.  The last stage (no prefetch left) waits for everything.
-    const int cchunks = c.Cin / CS_BK, nstages = 3 * cchunks, nk = 3 * nstages;
+    // This block's stages: [s0, s1) -- all of them, or split `split`'s share of ceil(nstages / splits) (the host leaves no split empty).
+    const int cchunks = c.Cin / CS_BK, nstages = 3 * cchunks;
+    int s0 = 0, s1 = nstages;
+    if (g.splits > 1) {
+        const int per = (nstages + g.splits - 1) / g.splits;
+        s0 = split * per;
+        s1 = min(nstages, s0 + per);
+    }
+    const int nk = 3 * s1;  // end of this block's k-tiles
     const int a0 = has2 ? 2 : 1;
-    dma_w(0, 0);
-    dma_w(1, c.Cin);  // tap (0, 1), channel chunk 0
-    dma_a(0, 0, 0, 0);
-    dma_a(1, 0, 0, 0);
-    if (has2) dma_a(2, 0, 0, 0);
+    int ky = s0 / cchunks, cbi = s0 - ky * cchunks;  // stage s = ky * cchunks + cbi
+    dma_w(0, ky * 3 * c.Cin + cbi * CS_BK);        // tap (ky, 0) of the first stage
+    dma_w(1, (ky * 3 + 1) * c.Cin + cbi * CS_BK);  // tap (ky, 1)
+    dma_a(0, s0 & 1, ky, cbi * CS_BK);
+    dma_a(1, s0 & 1, ky, cbi * CS_BK);
+    if (has2) dma_a(2, s0 & 1, ky, cbi * CS_BK);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     bar_raw_fn();
     // Two phases per k-tile -- [DMA issue + fragment reads + the counted wait] | barrier | [48 MFMAs] | barrier -- with wave group 1
@@ -1357,13 +1384,12 @@ __global__ __launch_bounds__(512) void conv3t_split_kernel(GemmArgs g, ConvArgs 
     // other reads its fragments (conv2p_split_kernel's arrangement).  A wave's reads have returned (lgkmcnt(0)) and its DMA of what the
     // next k-tile needs has landed before it passes the mid barrier, i.e. one full phase before any wave touches that data / that buffer.
     if (grp == 1) bar_raw_fn();
-    int ky = 0, cbi = 0;  // stage s = ky * cchunks + cbi
-    int wb = 0;           // W buffer of k-tile t: t % 3
-    for (int s = 0; s < nstages; ++s) {
+    int wb = 0;  // W buffer of k-tile t: (t - 3 s0) % 3
+    for (int s = s0; s < s1; ++s) {
         const int cb = cbi * CS_BK;
         int nky = ky, ncbi = cbi + 1;
         if (ncbi == cchunks) { ncbi = 0; ++nky; }
-        const bool more = s + 1 < nstages;
+        const bool more = s + 1 < s1;
 #pragma unroll
         for (int kx = 0; kx < 3; ++kx) {
             const int t = s * 3 + kx;
@@ -1418,9 +1444,14 @@ __global__ __launch_bounds__(512) void conv3t_split_kernel(GemmArgs g, ConvArgs 
         ky = nky; cbi = ncbi;
     }
     if (grp == 0) bar_raw_fn();
+    if (g.splits > 1) {
+        __shared__ int s_last;
+        if (!conv_splitk_exchange(g, acc, tn * tilesM + tm, split, &s_last)) return;
+    }
     conv_split_epilogue<EPI>(g, c, acc, smem_raw, m0, n0, tm, arow0, wn, wave, fr, fg, tid);
 }
 
+static std::atomic<long> g_conv3t_split_launches{0};  // of those, launches that split K (showo_conv3t_split_launches)
 static std::atomic<long> g_conv3t_launches{0};  // tests assert that their shapes reached this kernel (showo_conv3t_launches)
 // shapes the 3-tap-reuse kernel serves (everything else: conv2p_split_kernel)
 static bool conv3t_ok(const GemmArgs& g, const ConvArgs& c) {
@@ -1463,7 +1494,16 @@ int launch_conv2p_split(const GemmArgs& g, const ConvArgs& c, hipStream_t s) {
             gemm_splitk_ws(s, (size_t)tiles * S * 16 * 512 * sizeof(float4), &gs.ws, &gs.tick))
             gs.splits = S;  // (no workspace -- first use inside a stream capture: the unsplit launch is always valid)
     }
-    if (gs.splits == 1 && conv3t_ok(g, c)) {
+    // the 3-tap kernel splits K by stages (ky, channel chunk: three k-tiles each): the same split count unless a split would be empty
+    static int split3_on = -1;  // SHOWO_CONV_3TAP_SPLITK=0: split launches stay on conv2p_split_kernel (A/B)
+    if (split3_on < 0) { const char* e = getenv("SHOWO_CONV_3TAP_SPLITK"); split3_on = e ? atoi(e) : 1; }
+    const bool take3 = conv3t_ok(g, c) && (gs.splits == 1 || split3_on);
+    if (take3 && gs.splits > 1) {
+        const int nstages = nk / 3, per = (nstages + gs.splits - 1) / gs.splits;
+        gs.splits = (nstages + per - 1) / per;
+        if (gs.splits > 1) ++g_conv3t_split_launches;
+    }
+    if (take3) {
         static bool attr3_set = false;
         auto k3 = conv3t_split_kernel<EPI>;
         if (!attr3_set) {
@@ -1472,7 +1512,7 @@ int launch_conv2p_split(const GemmArgs& g, const ConvArgs& c, hipStream_t s) {
             attr3_set = true;
         }
         ++g_conv3t_launches;
-        k3<<<dim3(tiles), dim3(512), C3_SMEM, s>>>(gs, c);
+        k3<<<dim3(tiles * gs.splits), dim3(512), C3_SMEM, s>>>(gs, c);
         hipError_t e3 = hipGetLastError();
         if (e3 != hipSuccess) return set_error_hip(e3, "conv3t_split launch", __FILE__, __LINE__);
         return 0;
@@ -1505,8 +1545,36 @@ extern "C" int showo_gemm_bf16x3(const uint16_t* A, const uint16_t* Alo, int lda
     return dispatch_split(g, ld, resid ? SHOWO_EPI_RESID_F32 : SHOWO_EPI_F32, (hipStream_t)stream);
 }
 
+// Strided batch of showo_gemm_bf16x3 on the 128^2 split kernel (the one showo_gemm_bf16x3 runs): grid y = image.
+extern "C" int showo_gemm_bf16x3_batched(const uint16_t* A, const uint16_t* Alo, int lda, int64_t sA, const uint16_t* W, const uint16_t* Wlo,
+                                         int ldw, int64_t sW, const float* bias, int bias_per_row, int64_t sBias, float* out, int ldo,
+                                         int64_t sOut, const float* resid, int ldr, int64_t sResid, int M, int N, int K, int batch,
+                                         void* stream) {
+    if (M <= 0 || N <= 0 || batch <= 0) return 0;
+    if (K <= 0 || (K % BK) != 0) return set_error_msg(1, "gemm x3: K must be a positive multiple of 64");
+    if (!Alo || !Wlo) return set_error_msg(1, "gemm x3: lo operands required");
+    if ((lda % 8) || (ldw % 8) || (((uintptr_t)A) & 15) || (((uintptr_t)W) & 15) || (((uintptr_t)Alo) & 15) || (((uintptr_t)Wlo) & 15))
+        return set_error_msg(1, "gemm x3: operands must be 16B aligned with lda,ldw multiples of 8");
+    if ((sA % 8) || (sW % 8) || sA < 0 || sW < 0 || sOut < 0 || sBias < 0 || sResid < 0)
+        return set_error_msg(1, "gemm x3 batched: operand strides must be non-negative multiples of 8 elements");
+    if (batch > 65535) return set_error_msg(1, "gemm x3 batched: batch <= 65535");
+    GemmArgs g;
+    g.A = A; g.lda = lda; g.W = W; g.ldw = ldw; g.Wlo = Wlo; g.bias = bias; g.bias_per_row = bias_per_row;
+    g.out = out; g.ldo = ldo; g.resid = resid; g.ldr = ldr; g.M = M; g.N = N; g.K = K;
+    g.batch = batch; g.bsW = sW; g.bsOut = sOut; g.bsBias = sBias; g.bsResid = sResid;
+    // (vector or scalar stores write the same values: only every image's alignment decides which)
+    g.vec_out = ((ldo % 4) == 0) && ((((uintptr_t)out) & 15) == 0) && (sOut % 4) == 0;
+    if (resid) g.vec_out = g.vec_out && ((ldr % 4) == 0) && ((((uintptr_t)resid) & 15) == 0) && (sResid % 4) == 0;
+    LinearLoader ld;
+    ld.A = A; ld.lda = lda; ld.M = M; ld.Alo = Alo; ld.bsA = sA;
+    ProfScope prof(PROF_GEMM, 6.0 * M * N * K * batch, (hipStream_t)stream);
+    return dispatch_split(g, ld, resid ? SHOWO_EPI_RESID_F32 : SHOWO_EPI_F32, (hipStream_t)stream);
+}
+
 static int conv3x3_x3_impl(const uint16_t* x, const uint16_t* xlo, const uint16_t* w, const uint16_t* wlo, const float* bias,
-                           const float* resid, float* out, double* stats, int B, int Hin, int Win, int Cin, int Cout, int mode, void* stream) {
+                           const float* resid, float* out, double* stats, int B, int Hin, int Win, int Cin, int Cout, int mode, void* stream,
+                           int* pending = nullptr) {  // pending: the statistics may stay as <= SHOWO_GN_FOLD_MAX partials (showo_gn_apply_part)
+    if (pending) *pending = 0;
     if (B <= 0) return 0;
     if (Cin % 64) return set_error_msg(1, "conv3x3 x3: Cin % 64 == 0 required");
     if (mode < 0 || mode > 2) return set_error_msg(1, "conv3x3 x3: bad mode");
@@ -1553,8 +1621,9 @@ static int conv3x3_x3_impl(const uint16_t* x, const uint16_t* xlo, const uint16_
         }
     }
     if (rc || !stats) return rc;
+    if (fused && pending && HW / CS_AROWS <= SHOWO_GN_FOLD_MAX) { *pending = HW / CS_AROWS; return 0; }
     if (fused) return showo_gn_finalize(stats + (int64_t)B * 64, stats, B, HW / CS_AROWS, stream);
-    return showo_gn_stats(out, stats, B, HW, Cout, stream);
+    return showo_gn_stats_lazy(out, stats, B, HW, Cout, pending, stream);
 }
 
 extern "C" int showo_conv3x3_bf16x3(const uint16_t* x, const uint16_t* xlo, const uint16_t* w, const uint16_t* wlo, const float* bias,
@@ -1574,5 +1643,15 @@ extern "C" int showo_conv3x3_bf16x3_gn(const uint16_t* x, const uint16_t* xlo, c
     return conv3x3_x3_impl(x, xlo, w, wlo, bias, resid, out, stats, B, Hin, Win, Cin, Cout, mode, stream);
 }
 
+extern "C" int showo_conv3x3_bf16x3_gn_lazy(const uint16_t* x, const uint16_t* xlo, const uint16_t* w, const uint16_t* wlo, const float* bias,
+                                            const float* resid, float* out, double* stats, int B, int Hin, int Win, int Cin, int Cout,
+                                            int mode, int* pending, void* stream) {
+    if (!stats) return set_error_msg(1, "conv3x3 x3 gn: stats buffer required");
+    if (Cout % 128) return set_error_msg(1, "conv3x3 x3 gn: Cout must be a multiple of 128 (GroupNorm(32) over channel quads)");
+    return conv3x3_x3_impl(x, xlo, w, wlo, bias, resid, out, stats, B, Hin, Win, Cin, Cout, mode, stream, pending);
+}
+
 // number of launches of the 3-tap-reuse conv kernel (conv3t_split_kernel) so far in this process: tests check their coverage with it
 extern "C" int64_t showo_conv3t_launches(void) { return (int64_t)g_conv3t_launches.load(); }
+// of those, the launches that split K (the 16 x 16 / 32 x 32 levels; SHOWO_CONV_3TAP_SPLITK=0 sends them to conv2p_split_kernel)
+extern "C" int64_t showo_conv3t_split_launches(void) { return (int64_t)g_conv3t_split_launches.load(); }

@@ -57,6 +57,10 @@ struct GemmArgs {
     // host only: the M that the split-K policy is asked about (0 = this launch's own M).  A launch that computes a subset of the rows of
     // another launch keeps that launch's k-partition -- the fp32 summation order of every output element -- this way (gemm_pin_split_m).
     int split_m = 0;
+    // gemm_kernel (the 128^2 kernel) only: strided batch.  batch > 1: the grid's y is the image index z and the image uses W + z * bsW
+    // (hi and lo), out + z * bsOut, bias + z * bsBias, resid + z * bsResid (elements; the loader offsets the activation operand).
+    // Every image runs the tiles of its own (M, N, K) launch: the bits of `batch` separate launches.
+    int batch = 1; int64_t bsW = 0, bsOut = 0, bsBias = 0, bsResid = 0;
 };
 
 constexpr int EPI_QKV = 4;  // internal epilogue code of showo_gemm_qkv_bf16

@@ -10,6 +10,7 @@
 #include "../../include/showo_hip.h"
 #include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <map>
 #include <string>
 #include <vector>
@@ -83,6 +84,11 @@ struct showo_vq {
     bf16_t *aql = nullptr, *akl = nullptr, *avtl = nullptr, *apl = nullptr, *aol = nullptr;
     float* as = nullptr;
     int attn_hw = 0;
+    // A/B switches (showo_vq_set_tail; SHOWO_VQ_ATTN_BATCH=0 / SHOWO_GN_FOLD=0 at creation): the attention block as one strided batch
+    // over the images instead of a loop (split precision), and GroupNorm applying from <= SHOWO_GN_FOLD_MAX partials without the
+    // separate finalize launch.  Same bits either way.
+    // thin_conv: decoder.conv_out on the thin-Cout kernel (showo_conv3x3_thin_bf16x3; SHOWO_CONV_THIN=0); changes the image's low bits
+    bool attn_batched = true, gn_fold = true, thin_conv = true;
     float *zbuf = nullptr, *zbuf2 = nullptr;
 
     template <class T>
@@ -136,6 +142,9 @@ extern "C" int showo_vq_create(const showo_vq_config* c, showo_vq** out) {
     showo_vq* v = new showo_vq();
     v->cfg = *c;
     v->split = c->precision == 1;
+    if (const char* e = getenv("SHOWO_VQ_ATTN_BATCH")) v->attn_batched = atoi(e) != 0;
+    if (const char* e = getenv("SHOWO_GN_FOLD")) v->gn_fold = atoi(e) != 0;
+    if (const char* e = getenv("SHOWO_CONV_THIN")) v->thin_conv = atoi(e) != 0;
     const int ch = c->ch, zc = c->z_channels;
     // ---- encoder tensors (reference modeling_magvitv2.py:62-139)
     v->add_conv("encoder.conv_in", ch, 3, 3);
@@ -206,12 +215,13 @@ extern "C" int showo_vq_create(const showo_vq_config* c, showo_vq** out) {
     v->attn_hw = hw;
     int64_t BP = (int64_t)c->max_batch * hw;
     rc |= v->alloc(&v->aq, BP * max_c); rc |= v->alloc(&v->ak, BP * max_c); rc |= v->alloc(&v->ao, BP * max_c);
-    rc |= v->alloc(&v->avt, (int64_t)max_c * hwp); rc |= v->alloc(&v->ap, (int64_t)hw * hwp);
-    rc |= v->alloc(&v->as, (int64_t)hw * hw);
+    const int64_t MB = c->max_batch;  // the attention scratch holds every image (batched form)
+    rc |= v->alloc(&v->avt, MB * max_c * hwp); rc |= v->alloc(&v->ap, MB * hw * hwp);
+    rc |= v->alloc(&v->as, MB * hw * hw);
     rc |= v->alloc(&v->zbuf, BP * 64); rc |= v->alloc(&v->zbuf2, BP * 64);
     if (v->split) {
         rc |= v->alloc(&v->aql, BP * max_c); rc |= v->alloc(&v->akl, BP * max_c); rc |= v->alloc(&v->aol, BP * max_c);
-        rc |= v->alloc(&v->avtl, (int64_t)max_c * hwp); rc |= v->alloc(&v->apl, (int64_t)hw * hwp);
+        rc |= v->alloc(&v->avtl, MB * max_c * hwp); rc |= v->alloc(&v->apl, MB * hw * hwp);
     }
     if (rc) { showo_vq_destroy(v); return rc; }
     if ((int64_t)max_c * hwp > v->act_elems) { showo_vq_destroy(v); return set_error_msg(5, "vq: workspace too small for the attention block"); }
@@ -223,6 +233,15 @@ extern "C" void showo_vq_destroy(showo_vq* v) {
     if (!v) return;
     for (void* p : v->allocs) hipFree(p);
     delete v;
+}
+
+// 1 = on (default), 0 = the loop over images / the separate finalize launch / conv_out on the MFMA conv, negative = leave unchanged
+extern "C" int showo_vq_set_tail(showo_vq* v, int attn_batched, int gn_fold, int thin_conv) {
+    if (!v) return set_error_msg(1, "vq: null handle");
+    if (attn_batched >= 0) v->attn_batched = attn_batched != 0;
+    if (gn_fold >= 0) v->gn_fold = gn_fold != 0;
+    if (thin_conv >= 0) v->thin_conv = thin_conv != 0;
+    return 0;
 }
 
 extern "C" int showo_vq_missing(const showo_vq* v) {
@@ -271,6 +290,7 @@ struct Ctx {
     // skips the statistics pass.  Cleared when the statistics are consumed or the tensor is rewritten by anything else.
     const float* stats_of = nullptr;
     int stats_hw = 0, stats_c = 0;
+    int stats_pending = 0;  // > 0: the statistics are still that many partials per image (behind the result in v->stats)
 };
 
 // fp32 -> MFMA operand image: bf16, or the (hi, lo) pair in split precision
@@ -282,7 +302,11 @@ int to_operand(Ctx& c, const float* src, bf16_t* hi, bf16_t* lo, int64_t n) {
 int gn(Ctx& c, const float* x, const std::string& name, bf16_t* y, bf16_t* ylo, int HW, int C, int swish) {
     const bool have = c.stats_of == x && c.stats_hw == HW && c.stats_c == C;
     c.stats_of = nullptr;
-    if (!have) TRY(showo_gn_stats(x, c.v->stats, c.B, HW, C, c.s));
+    int pending = have ? c.stats_pending : 0;
+    if (!have) TRY(showo_gn_stats_lazy(x, c.v->stats, c.B, HW, C, c.v->gn_fold ? &pending : nullptr, c.s));
+    if (pending)
+        return showo_gn_apply_part(x, c.v->stats + (int64_t)c.B * 64, pending, c.v->Wf(name), c.v->Bv(name), y, c.v->split ? ylo : nullptr,
+                                   c.B, HW, C, 1e-6f, swish, c.s);
     return showo_gn_apply(x, c.v->stats, c.v->Wf(name), c.v->Bv(name), y, c.v->split ? ylo : nullptr, c.B, HW, C, 1e-6f, swish,
                           c.s);
 }
@@ -293,12 +317,16 @@ int conv3(Ctx& c, const bf16_t* x, const bf16_t* xlo, const std::string& name, c
     showo_vq* v = c.v;
     c.stats_of = nullptr;
     if (v->split && (cout % 128) == 0) {  // every such conv feeds a GroupNorm: its statistics come with it
-        TRY(showo_conv3x3_bf16x3_gn(x, xlo, v->W(name), v->Wl(name), v->Bv(name), resid, out, v->stats, c.B, H, W, cin, cout, mode, c.s));
+        c.stats_pending = 0;
+        TRY(showo_conv3x3_bf16x3_gn_lazy(x, xlo, v->W(name), v->Wl(name), v->Bv(name), resid, out, v->stats, c.B, H, W, cin, cout, mode,
+                                         v->gn_fold ? &c.stats_pending : nullptr, c.s));
         c.stats_of = out;
         c.stats_hw = mode == 1 ? 4 * H * W : mode == 2 ? (H / 2) * (W / 2) : H * W;
         c.stats_c = cout;
         return 0;
     }
+    if (v->split && v->thin_conv && cout <= 4 && mode == 0 && !resid && (cin % 32) == 0 && cin <= 256)
+        return showo_conv3x3_thin_bf16x3(x, xlo, v->W(name), v->Wl(name), v->Bv(name), out, c.B, H, W, cin, cout, c.s);
     if (v->split)
         return showo_conv3x3_bf16x3(x, xlo, v->W(name), v->Wl(name), v->Bv(name), resid, out, c.B, H, W, cin, cout, mode, c.s);
     return showo_conv3x3_bf16(x, v->W(name), v->Bv(name), resid, out, c.B, H, W, cin, cout, mode, c.s);
@@ -346,7 +374,25 @@ int attnblock(Ctx& c, const std::string& p, int C, int H, int W) {
     TRY(gemm32(c, v->b0, v->b0l, C, v->W(p + ".k"), v->Wl(p + ".k"), C, v->Bv(p + ".k"), 0, c.t1, C, nullptr, BP, C, C));
     TRY(to_operand(c, c.t1, v->ak, v->akl, (int64_t)BP * C));
     const float scale = 1.0f / sqrtf((float)C);
-    for (int b = 0; b < c.B; ++b) {
+    const bool batched = v->split && v->attn_batched && c.B > 1 && (int64_t)c.B * C * hwp <= v->act_elems;
+    if (batched) {
+        // every image at once: the products as strided batches (grid y = image; each image runs the tiles of its own launch, so the
+        // bits are the loop's), the re-imaging and the softmax over all B * hw rows -- 7 launches instead of 8 per image
+        const int64_t sx = (int64_t)hw * C, sv = (int64_t)C * hwp, ss = (int64_t)hw * hw, sp = (int64_t)hw * hwp;
+        SHOWO_CHECK_HIP(hipMemsetAsync(c.t1, 0, (size_t)c.B * sv * sizeof(float), c.s));  // key padding columns stay 0
+        if (c.t1 == c.stats_of) c.stats_of = nullptr;
+        TRY(showo_gemm_bf16x3_batched(v->W(p + ".v"), v->Wl(p + ".v"), C, 0, v->b0, v->b0l, C, sx, v->Bv(p + ".v"), 1, 0, c.t1, hwp, sv,
+                                      nullptr, hwp, 0, C, hw, C, c.B, c.s));
+        TRY(to_operand(c, c.t1, v->avt, v->avtl, c.B * sv));
+        TRY(showo_gemm_bf16x3_batched(v->aq, v->aql, C, sx, v->ak, v->akl, C, sx, nullptr, 0, 0, v->as, hw, ss, nullptr, hw, 0, hw, hw, C,
+                                      c.B, c.s));
+        TRY(showo_softmax_rows_bf16(v->as, v->ap, v->apl, BP, hw, hwp, scale, c.s));  // [B][hw][hwp]: the images' rows are contiguous
+        if (c.t2 == c.stats_of) c.stats_of = nullptr;
+        TRY(showo_gemm_bf16x3_batched(v->ap, v->apl, hwp, sp, v->avt, v->avtl, hwp, sv, nullptr, 0, 0, c.t2, C, sx, nullptr, C, 0, hw, C,
+                                      hwp, c.B, c.s));
+        TRY(to_operand(c, c.t2, v->ao, v->aol, (int64_t)BP * C));
+    }
+    for (int b = 0; b < (batched ? 0 : c.B); ++b) {
         const int64_t ob = (int64_t)b * hw * C;
         // v^T[c][p] = sum_ci Wv[c][ci] h[p][ci] + bv[c]  (the GEMM "activation" is the weight matrix here)
         SHOWO_CHECK_HIP(hipMemsetAsync(c.t1, 0, (size_t)C * hwp * sizeof(float), c.s));  // key padding columns stay 0
@@ -372,6 +418,18 @@ int check_vq(showo_vq* v, int B, int H, int W) {
 }
 
 }  // namespace
+
+// The attention block `prefix` ("decoder.mid.attn_1" / "encoder.mid.attn_1") alone, in place on x fp32 [B, H * W, C]: x += attn(norm(x)).
+// The block's arithmetic per image does not depend on B (no launch of it splits K), which the convolutions around it in
+// decode_code / get_code do not promise (their split-K follows the tile count): tests compare batches with single images here.
+extern "C" int showo_vq_attn_block(showo_vq* v, const char* prefix, float* x, int B, int H, int W, void* stream) {
+    if (!v || !prefix || !x) return set_error_msg(1, "vq_attn_block: null argument");
+    TRY(check_vq(v, B, H, W));
+    const std::string p(prefix);
+    if (!v->has(p + ".q.weight")) return set_error_msg(3, "vq_attn_block: unknown attention block");
+    Ctx c{v, (hipStream_t)stream, B, x, v->f1, v->f2};
+    return attnblock(c, p, v->t[p + ".q.weight"].cout, H, W);
+}
 
 extern "C" int showo_vq_decode_code(showo_vq* v, const int64_t* ids, int B, int h, int w, float* image, void* stream) {
     hipStream_t s = (hipStream_t)stream;

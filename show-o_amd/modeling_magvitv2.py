@@ -154,6 +154,20 @@ class MAGVITv2(PretrainedMixin, nn.Module):
         self.max_batch, self.max_res = max_batch, max_res
         self._vq = None
         self._versions = None
+        self._tail = [-1, -1, -1]  # set_tail(): -1 = the library's default
+
+    def set_tail(self, attn_batched=None, gn_fold=None, thin_conv=None):
+        """A/B switches of the native decode tail (showo_vq_set_tail): attn_batched=False runs the attention block as a loop over
+        images, gn_fold=False keeps the separate GroupNorm finalize launch (same output bits either way); thin_conv=False runs
+        decoder.conv_out on the MFMA conv instead of the thin-Cout kernel (same accuracy class, different low bits)."""
+        if attn_batched is not None:
+            self._tail[0] = int(bool(attn_batched))
+        if gn_fold is not None:
+            self._tail[1] = int(bool(gn_fold))
+        if thin_conv is not None:
+            self._tail[2] = int(bool(thin_conv))
+        if self._vq is not None:
+            _lib.call("showo_vq_set_tail", self._vq, *self._tail)
 
     def forward(self, pixel_values, return_loss=False):
         pass  # the reference's forward is empty too (modeling_magvitv2.py:413-414)
@@ -198,6 +212,8 @@ class MAGVITv2(PretrainedMixin, nn.Module):
             h = C.c_void_p()
             _lib.check(lib.showo_vq_create(C.byref(cfg), C.byref(h)), "showo_vq_create")
             self._vq, self._versions = h, {}
+            if hasattr(lib, "showo_vq_set_tail"):  # (absent from an older build loaded through SHOWO_LIB_PATH for an A/B run)
+                _lib.call("showo_vq_set_tail", self._vq, *self._tail)
         for k, v in self.state_dict().items():
             if k.startswith("quantize."):
                 continue
