@@ -12,10 +12,15 @@ synthetic decimal-id tokenizer are used (same kernels, meaningless text).
     python examples/mmu_demo.py --logprobs                                                              # + log-probability of every token
     python examples/mmu_demo.py --questions "What is in the image? *** What colour is it?"              # one prefill of the image prefix,
     python examples/mmu_demo.py --questions "What is in the image? *** What colour is it?" --follow-up  # every question appended to it
+    python examples/mmu_demo.py --questions "q1 *** q2 *** ... (more than 8)" --share-prefix            # all decoded together on wide
+                                                                                                        # slots that read the prefix in place
 
 `--questions` takes the reference's ` *** ` separator (inference_mmu.py:86) and answers all of them from ONE `Showo.mmu_session`: the
 607-row prefix (<|mmu|>, system prompt, <|soi|>, image, <|eoi|>) is prefilled once; each question is appended to its KV cache and the
 session rewinds to the prefix for the next one.  `--follow-up` keeps the conversation instead: question 2 sees question 1 and its answer.
+`--share-prefix` answers all questions in ONE `sess.generate_batch(..., slots=32, share_prefix=True)`: with more than 8 questions they
+decode together on the slots of a wide batch, each slot holding only its question and answer and attending to the prefix in the
+session's own cache (with 8 or fewer it is the plain generate_batch call).
 """
 import argparse
 import os
@@ -52,6 +57,8 @@ def main():
     ap.add_argument("--question", default=None)
     ap.add_argument("--questions", default=None, help="several questions separated by ' *** ', answered from one mmu_session")
     ap.add_argument("--follow-up", action="store_true", help="with --questions: ask each question in the same conversation (no rewind)")
+    ap.add_argument("--share-prefix", action="store_true",
+                    help="with --questions: one generate_batch call on wide slots that share the prefix (slots=32, share_prefix=True)")
     ap.add_argument("--max-new-tokens", type=int, default=100)
     ap.add_argument("--top-k", type=int, default=1)
     ap.add_argument("--temperature", type=float, default=1.0)
@@ -98,6 +105,19 @@ def main():
             prefix = emb[:, :cut + img_emb.shape[1] + 1].contiguous()             # ... up to and including <|eoi|>
             sess = model.mmu_session(input_embeddings=prefix, attention_mask=intervals_for_mmu_vit(prefix, system_prompt_len=len(sys_ids)))
             start = sess.mark()
+            if a.share_prefix:
+                qs = [q.strip() for q in a.questions.split(" *** ")]
+                q_embs = [model.showo.model.embed_tokens(torch.tensor([tok([q])["input_ids"][0]], device="cuda")) for q in qs]
+                outs = sess.generate_batch(input_embeddings=q_embs, max_new_tokens=a.max_new_tokens, top_k=a.top_k, temperature=a.temperature,
+                                           eot_token=tok.eos_token_id, top_p=a.top_p, return_logprobs=a.logprobs, slots=32, share_prefix=True)
+                outs, lpss = outs if a.logprobs else (outs, [None] * len(qs))
+                for q, ans, lps in zip(qs, outs, lpss):
+                    ans = [int(t) for t in ans]
+                    print(f"[{sess.length} rows in the cache] {q!r} -> {len(ans)} tokens:", ans[:24], "..." if len(ans) > 24 else "")
+                    report_logprobs(lps)
+                    if a.tokenizer:
+                        print(tok.decode(ans, skip_special_tokens=True))
+                return
             for q in [q.strip() for q in a.questions.split(" *** ")]:
                 q_emb = model.showo.model.embed_tokens(torch.tensor([tok([q])["input_ids"][0]], device="cuda"))
                 ans = sess.generate(input_embeddings=q_emb, max_new_tokens=a.max_new_tokens, top_k=a.top_k, temperature=a.temperature,

@@ -775,6 +775,47 @@ int showo_engine_batch_slot_ptrs(showo_engine* e, int b, uint16_t** k, uint16_t*
 int showo_engine_batch_fork(showo_engine* e, int b, void* stream);
 int showo_engine_batch_prefill_append(showo_engine* e, int b, const int64_t* ids, const float* embeds, int Ln, float* logits_last,
                                       void* stream);
+/* Shared-prefix slots (opt-in; csrc/attn_shared.hip, DESIGN.md "Shared-prefix slots"): a wide batch whose slots hold only a SUFFIX
+ * cache and read the engine's decode cache [0, P) in place, P = the cache length when the batch begins.  With base = P & ~63, key
+ * k >= P of a slot lives at row / column k - base of its suffix cache (K [heads, cap_s, 64], V^T [heads, 64, cap_s] per layer, cap_s a
+ * multiple of 64); rows below P - base of a suffix cache are dead.  Per layer the step runs two launches in place of the wide step's
+ * attention: the prefix launch (grid heads x 64-key splits of [0, P), one wave each: q prep of all nb slots, S^T = K Q^T and
+ * O^T = V^T P^T on v_mfma_f32_32x32x16_bf16, fp32 partials (m, l, o[64]) per (split, head, slot)) and the suffix + merge launch (grid
+ * heads x nb: the single-query attention over the slot's suffix with the new token's K row / V^T column appended, then the partials
+ * merged in split order by log-sum-exp rescaling).  A slot's row depends only on its own query, the prefix and its own suffix.
+ *
+ * showo_engine_batch_begin_shared: showo_engine_batch_begin_wide whose capacity counts suffix tokens: cap_suffix_tokens >= (P - base) +
+ *   appended rows + new tokens + 1.  Refused (1) without a prefill or when the cache was prefilled under another precision.
+ * showo_engine_batch_attach_append: fills slot b: the Ln rows are appended to the ENGINE'S cache at P by the code of
+ *   showo_engine_prefill_append (logits_last has its bits), K rows / V^T columns [P, P + Ln) are copied into the slot, and the engine's
+ *   cache is rewound to P (also when a step failed).  Replaces the occupant of b, leaves the other slots alone.
+ * Every showo_engine_batch_decode_* entry serves a shared batch; it refuses (1) once the engine's cache is not the one the batch began
+ * on (another prefill, a length other than P, another precision).  showo_engine_batch_slot_ptrs reports the suffix cache and cap_s;
+ * showo_engine_batch_fork / _batch_prefill / _batch_prefill_append refuse a shared batch (1).
+ * showo_engine_batch_shared_state (test hook): P, base and cap_s of the running shared batch (any out pointer may be NULL).
+ *
+ * The kernels alone (test hooks):
+ * showo_attn_decode_shared: one layer's two launches on caller buffers.  qkv [nb, 3 heads 64] bf16 projection rows; k_pre / vt_pre one
+ *   layer of a prefix cache of capacity cap_pre; k_suf / vt_suf [nb][heads][cap_suf][64] / [nb][heads][64][cap_suf]; pre_iv (HOST) the
+ *   two prefix intervals, clipped to [0, P) here; pos_dev int [nb] (device) absolute positions, P <= pos < base + cap_suf; lk_max = an
+ *   upper bound of pos + 1 (0: none); O [nb, heads 64] bf16; ws fp32 of showo_attn_shared_ws_elems(heads, P) elements.  Rows >= nb of
+ *   O and ws are neither read nor written.  Keys >= P of the prefix buffers may hold anything.
+ * showo_attn_shared_ws_elems: returns the element count (not an error code); 0 for bad arguments or a count beyond INT_MAX.
+ * showo_kv_copy_rows: showo_kv_fork for a row range: K rows / V^T columns [r0, r1) of the source go to [r0 - base, r1 - base) of the
+ *   destination (base a multiple of 64, base <= r0 < r1), V^T columns [r1 - base, 64 ceil((r1 - base) / 64)) of the destination are
+ *   zeroed, nothing else is written. */
+int showo_engine_batch_begin_shared(showo_engine* e, int nb, int cap_suffix_tokens);
+int showo_engine_batch_attach_append(showo_engine* e, int b, const int64_t* ids, const float* embeds, int Ln, float* logits_last,
+                                     void* stream);
+int showo_engine_batch_shared_state(const showo_engine* e, int* P, int* base, int* cap_s);
+int showo_attn_decode_shared(const uint16_t* qkv, const float* qln_w, const float* qln_b, const float* kln_w, const float* kln_b,
+                             const float* cosT, const float* sinT, const uint16_t* k_pre, const uint16_t* vt_pre, int cap_pre,
+                             uint16_t* k_suf, uint16_t* vt_suf, int cap_suf, const int32_t* pre_iv, int P, const int* pos_dev, int lk_max,
+                             uint16_t* O, float* ws, int nb, int nH, int rot, float eps, void* stream);
+int showo_attn_shared_ws_elems(int nH, int P);
+int showo_kv_copy_rows(const uint16_t* k_src, const uint16_t* vt_src, int cap_src, int64_t k_lstride_src, int64_t v_lstride_src,
+                       uint16_t* k_dst, uint16_t* vt_dst, int cap_dst, int64_t k_lstride_dst, int64_t v_lstride_dst, int nL, int nH,
+                       int r0, int r1, int base, void* stream);
 /* Next-token draw of the AR decode (modeling_showo.py:220-228): x = logits / temperature; values below the top_k-th largest
  * are dropped (top_k <= 0 or >= V: none); token = multinomial(softmax(x), 1) computed as argmax_i p_i / E_i, E ~ Exp(1):
  * E = exp_noise[step * V + i] when exp_noise != NULL (parity tests inject the reference's draws), else Philox(seed; step, i). */

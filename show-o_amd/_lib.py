@@ -204,6 +204,14 @@ _PROTOS = {
     "showo_engine_batch_slot_ptrs": [c_p, c_i, C.POINTER(c_p), C.POINTER(c_p), C.POINTER(c_i64), C.POINTER(c_i64), C.POINTER(c_i)],
     "showo_engine_batch_fork": [c_p, c_i, c_p],
     "showo_engine_batch_prefill_append": [c_p, c_i, c_p, c_p, c_i, c_p, c_p],
+    # shared-prefix slots (csrc/attn_shared.hip): suffix caches over the engine's decode cache; the two attention launches and the copy alone
+    "showo_engine_batch_begin_shared": [c_p, c_i, c_i],
+    "showo_engine_batch_attach_append": [c_p, c_i, c_p, c_p, c_i, c_p, c_p],
+    "showo_engine_batch_shared_state": [c_p, C.POINTER(c_i), C.POINTER(c_i), C.POINTER(c_i)],
+    "showo_attn_decode_shared": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_i, c_p, c_i, c_p, c_p, c_i, c_i,
+                                 c_i, c_f, c_p],
+    "showo_attn_shared_ws_elems": [c_i, c_i],
+    "showo_kv_copy_rows": [c_p, c_p, c_i, c_i64, c_i64, c_p, c_p, c_i, c_i64, c_i64, c_i, c_i, c_i, c_i, c_i, c_p],
     "showo_clip_create": [c_p, c_p],
     "showo_clip_load": [c_p, C.c_char_p, c_p, c_i64, c_p],
     "showo_clip_missing": [c_p],

@@ -720,14 +720,7 @@ static __device__ __forceinline__ void attn_decode_body(AttnArgs a, DecPrep f, c
         const float cs = f.cosT[(int64_t)pos * f.rot + dl], sn = f.sinT[(int64_t)pos * f.rot + dl];
         __builtin_amdgcn_sched_barrier(0);  // every load of the prologue is issued before the first wait (the scheduler otherwise starts the LayerNorm -- and its wait for the token element -- ahead of the RoPE loads)
         // ln_rope_lane's expressions with the statistics on the VALU-only reductions (same bits) and the RoPE operands in registers
-        const float x0 = Op16<F16>::tof(xin);
-        const float mean = wave_sum_swap(x0) * (1.0f / 64.0f);
-        const float c = x0 - mean;
-        const float var = wave_sum_swap(c * c) * (1.0f / 64.0f);
-        float y = c * (1.0f / sqrtf(var + f.eps)) * lnw + lnb;
-        const int half = f.rot >> 1;
-        const float partner = __shfl_xor(y, half, 64);
-        if (lane < f.rot) y = y * cs + (lane < half ? -partner : partner) * sn;
+        const float y = decode_prep_lane(Op16<F16>::tof(xin), lnw, lnb, f.eps, cs, sn, f.rot, lane);
         if (wave == 0) {
             sq[lane] = Op16<F16>::tof(Op16<F16>::cvt(y * 0.125f));
         } else if (wave == 1) {

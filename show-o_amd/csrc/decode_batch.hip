@@ -13,6 +13,8 @@
 // A wave owns whole output columns and splits K over its lanes EXACTLY like the batch-1 kernels of decode.hip (same lane split, same
 // accumulation order per sequence, same epilogue expressions), so every sequence gets the bits its batch-1 run gets: tokens AND
 // logits of showo_engine_batch_decode_greedy equal NB separate showo_engine_decode_greedy runs (tests/test_decode_batch_gpu.py).
+// A wide batch (decode_wide.hip) runs MFMA skinny GEMMs instead; a shared-prefix batch (attn_shared.hip) is a wide batch whose slots
+// hold only the rows behind the engine's own decode cache and attend to that cache in place.
 // The whole step replays as a hipGraph with the NB positions in device memory (engine.h replay_steps, shared with the batch-1 loop of
 // decode_engine.hip).  The weight images of a layer come from decode_layer_ops (decode.hip), the prefill / append of a slot from
 // engine_prefill_into / engine_append_into (decode_engine.hip); every NB-templated launch goes through dispatch_int below.
@@ -20,6 +22,7 @@
 #include "decode_common.h"
 #include "sample_row.h"
 #include "decode_wide.h"
+#include "attn_shared.h"
 #include <string>
 #include <type_traits>
 
@@ -543,6 +546,15 @@ struct showo_engine::BatchDecode {
     int precision = 0;    // the precision the caches were prefilled under (element type of K / V^T)
     bool wide = false;    // begun by showo_engine_batch_begin_wide: the step runs the MFMA kernels of decode_wide.hip
     showo::WideWs wws;    // their workspace (one per engine: its decode steps are ordered on one stream)
+    // shared-prefix slots (showo_engine_batch_begin_shared; attn_shared.hip): k / vt are SUFFIX caches of `cap` rows, key k >= P of a
+    // slot at row k - base; every length and position of this struct stays absolute
+    bool shared = false;
+    int P = 0, base = 0;     // the engine cache's length when the batch began; P & ~63
+    int64_t epoch = 0;       // its epoch then
+    int pre_iv[4] = {0, 0, 0, 0};  // what every appended or decode row sees of [0, P): the last prefill row's rule at position P - 1
+    float* sws = nullptr;    // the prefix partials (showo::shared_attn_ws_elems)
+    int64_t sws_elems = 0;
+    int abs_cap() const { return shared ? base + cap : cap; }  // first position beyond a slot's cache
 };
 
 namespace showo {
@@ -551,13 +563,29 @@ void engine_batch_free(showo_engine* e) {
 }
 }  // namespace showo
 
-static int batch_begin(showo_engine* e, int nb, int cap_tokens, bool wide) {
+static int batch_begin(showo_engine* e, int nb, int cap_tokens, bool wide, bool shared = false) {
     if (!e) return set_error_msg(1, "engine: null handle");
+    int pre_iv[4] = {0, 0, 0, 0};  // shared: what every row behind P sees of [0, P)
     if (!wide && (nb < 1 || nb > NARROW_B)) return set_error_msg(1, "batch_begin: 1..8 sequences");
     if (wide && (nb < 1 || nb > MAXB)) return set_error_msg(1, "batch_begin_wide: 1..32 sequences");
     if (wide && e->precision != 0) return set_error_msg(1, "batch_begin_wide: the wide decode batch runs at precision 0 (bf16 operands) only");
     if (wide && ((e->H % 32) || (e->F % 32))) return set_error_msg(1, "batch_begin_wide: hidden and ffn must be multiples of 32");
     if (!decode_fused_shapes_ok(e->H, e->F)) return set_error_msg(1, "batch_begin: hidden <= 2048 and ffn <= 8192 (multiples of 8) required");
+    if (shared) {
+        if (e->cache_len <= 0) return set_error_msg(1, "batch_begin_shared: prefill first");
+        if (e->cache_precision != e->precision)
+            return set_error_msg(1, "batch_begin_shared: the KV cache was prefilled under another precision: prefill again");
+        if (cap_tokens < (e->cache_len & 63) + 2) return set_error_msg(5, "batch_begin_shared: no room behind the prefix");
+        // the decode rule at position P - 1 (decode_common.h next_iv): the run that ends at prompt_len, or an empty one, reaches P
+        int* v = pre_iv;
+        for (int i = 0; i < 4; ++i) v[i] = e->last_iv[i];
+        const int L0 = e->prompt_len, P = e->cache_len;
+        if (v[1] == L0 && v[0] < v[1]) v[1] = P;
+        else if (v[3] == L0 && v[2] < v[3]) v[3] = P;
+        else if (!(v[2] < v[3])) { v[2] = L0; v[3] = P; }
+        else if (!(v[0] < v[1])) { v[0] = L0; v[1] = P; }
+        else return set_error_msg(6, "batch_begin_shared: mask row needs more than two intervals");
+    }
     if (nb > e->maxT) return set_error_msg(5, "batch_begin: more sequences than workspace rows");
     int cap = ((cap_tokens + 63) / 64) * 64;
     if (cap_tokens < 2 || cap > ((e->cfg.max_pos + 63) / 64) * 64) return set_error_msg(5, "batch_begin: capacity exceeds max_position_embeddings");
@@ -585,6 +613,23 @@ static int batch_begin(showo_engine* e, int nb, int cap_tokens, bool wide) {
         TRY(e->alloc(&d->last_iv_dev, 4 * MAXB)); TRY(e->alloc(&d->iv_dev, 4 * MAXB));
     }
     if (wide) TRY(showo::wide_ws_reserve(&d->wws, e->H, e->H));
+    if (shared) {
+        const int64_t need_ws = showo::shared_attn_ws_elems(e->nH, e->cache_len);
+        if (need_ws > d->sws_elems) {
+            SHOWO_CHECK_HIP(hipDeviceSynchronize());
+            e->release(&d->sws);
+            d->sws_elems = 0;
+            TRY(e->alloc(&d->sws, need_ws));
+            d->sws_elems = need_ws;
+        }
+    }
+    // nothing above can fail from here on: the batch's fields change together
+    d->shared = shared;
+    if (shared) {
+        d->P = e->cache_len; d->base = e->cache_len & ~63; d->epoch = e->cache_epoch;
+        for (int i = 0; i < 4; ++i) d->pre_iv[i] = pre_iv[i];
+        d->precision = e->precision;
+    }
     d->nb = nb; d->cap = cap; d->wide = wide;
     for (int b = 0; b < MAXB; ++b) { d->prompt_len[b] = 0; d->cache_len[b] = 0; }
     return 0;
@@ -592,12 +637,23 @@ static int batch_begin(showo_engine* e, int nb, int cap_tokens, bool wide) {
 
 extern "C" int showo_engine_batch_begin(showo_engine* e, int nb, int cap_tokens) { return batch_begin(e, nb, cap_tokens, false); }
 extern "C" int showo_engine_batch_begin_wide(showo_engine* e, int nb, int cap_tokens) { return batch_begin(e, nb, cap_tokens, true); }
+extern "C" int showo_engine_batch_begin_shared(showo_engine* e, int nb, int cap_suffix_tokens) {
+    return batch_begin(e, nb, cap_suffix_tokens, true, true);
+}
+extern "C" int showo_engine_batch_shared_state(const showo_engine* e, int* P, int* base, int* cap_s) {
+    if (!e || !e->bd || e->bd->nb == 0 || !e->bd->shared) return set_error_msg(1, "batch_shared_state: showo_engine_batch_begin_shared first");
+    if (P) *P = e->bd->P;
+    if (base) *base = e->bd->base;
+    if (cap_s) *cap_s = e->bd->cap;
+    return 0;
+}
 
 extern "C" int showo_engine_batch_prefill(showo_engine* e, int b, const int64_t* ids, const float* embeds, const float* mask, int L,
                                           float* logits_last, void* stream) {
     if (!e || !e->bd || e->bd->nb == 0) return set_error_msg(1, "batch_prefill: showo_engine_batch_begin first");
     auto* d = e->bd;
     if (b < 0 || b >= d->nb) return set_error_msg(1, "batch_prefill: bad sequence index");
+    if (d->shared) return set_error_msg(1, "batch_prefill: a shared-prefix batch fills its slots with showo_engine_batch_attach_append");
     if (L + 1 > d->cap) return set_error_msg(5, "batch_prefill: prompt exceeds the batch's cache capacity");
     if (showo_engine_missing(e) != 0) return set_error_msg(4, "engine: weights missing (showo_engine_missing() != 0)");
     if (L < 1 || L > e->maxT || L > e->cfg.max_seq || L > e->cfg.max_pos) return set_error_msg(5, "engine: sequence exceeds the configured workspace");
@@ -630,6 +686,7 @@ extern "C" int showo_engine_batch_fork(showo_engine* e, int b, void* stream) {
     if (!e || !e->bd || e->bd->nb == 0) return set_error_msg(1, "batch_fork: showo_engine_batch_begin first");
     auto* d = e->bd;
     if (b < 0 || b >= d->nb) return set_error_msg(1, "batch_fork: bad sequence index");
+    if (d->shared) return set_error_msg(1, "batch_fork: a shared-prefix batch fills its slots with showo_engine_batch_attach_append");
     if (e->cache_len <= 0) return set_error_msg(1, "batch_fork: prefill first");
     if (e->precision == 1) return set_error_msg(1, "batch_fork: the batched decode runs at precision 0, 2 or 3");
     if (e->cache_precision != e->precision) return set_error_msg(1, "batch_fork: the KV cache was prefilled under another precision: prefill again");
@@ -650,6 +707,7 @@ extern "C" int showo_engine_batch_prefill_append(showo_engine* e, int b, const i
     if (!e || !e->bd || e->bd->nb == 0) return set_error_msg(1, "batch_prefill_append: showo_engine_batch_begin first");
     auto* d = e->bd;
     if (b < 0 || b >= d->nb) return set_error_msg(1, "batch_prefill_append: bad sequence index");
+    if (d->shared) return set_error_msg(1, "batch_prefill_append: a shared-prefix batch fills its slots with showo_engine_batch_attach_append");
     if (d->cache_len[b] <= 0) return set_error_msg(1, "batch_prefill_append: the slot has no prefill (showo_engine_batch_prefill / _batch_fork first)");
     if (e->precision == 1) return set_error_msg(1, "batch_prefill_append: the batched decode runs at precision 0, 2 or 3");
     if (d->precision != e->precision) return set_error_msg(1, "batch_prefill_append: the caches were prefilled under another precision: prefill again");
@@ -658,6 +716,48 @@ extern "C" int showo_engine_batch_prefill_append(showo_engine* e, int b, const i
     TRY(showo::engine_append_into(e, ids, embeds, Ln, P, d->last_iv[b], d->prompt_len[b], d->k + b * per_seq, d->vt + b * per_seq, lstride,
                                   lstride, d->cap, logits_last, (hipStream_t)stream, nullptr, nullptr));
     d->cache_len[b] = P + Ln;
+    return 0;
+}
+
+// ---- shared-prefix slots: the slot keeps the rows behind the engine cache's [0, P) only ----------------------------------------------
+namespace {
+// the engine's decode cache is still the one the shared batch began on
+int shared_cache_check(const showo_engine* e, const char* what) {
+    const auto* d = e->bd;
+    if (e->cache_epoch != d->epoch || e->cache_len != d->P || e->cache_precision != e->precision || d->precision != e->precision)
+        return set_error_msg(1, (std::string(what) + ": the engine's decode cache is no longer the one the shared batch began on "
+                                                     "(another prefill, another length or another precision)").c_str());
+    return 0;
+}
+}  // namespace
+
+extern "C" int showo_engine_batch_attach_append(showo_engine* e, int b, const int64_t* ids, const float* embeds, int Ln, float* logits_last,
+                                                void* stream) {
+    if (!e || !e->bd || e->bd->nb == 0 || !e->bd->shared) return set_error_msg(1, "batch_attach_append: showo_engine_batch_begin_shared first");
+    auto* d = e->bd;
+    if (b < 0 || b >= d->nb) return set_error_msg(1, "batch_attach_append: bad sequence index");
+    if (e->precision != 0) return set_error_msg(1, "batch_attach_append: a shared-prefix batch runs at precision 0 (bf16 operands) only");
+    TRY(shared_cache_check(e, "batch_attach_append"));
+    const int P = d->P;
+    if (Ln < 1 || P - d->base + Ln + 1 > d->cap) return set_error_msg(5, "batch_attach_append: the rows exceed the batch's suffix capacity");
+    const showo::KVDest kv = showo::kv_decode_cache(e);
+    // showo_engine_prefill_append's call on the engine's own cache, whose length stays P on the books
+    int rc = showo::engine_append_into(e, ids, embeds, Ln, P, e->last_iv, e->prompt_len, kv.k, kv.vt, kv.k_lstride, kv.v_lstride, kv.Lcap,
+                                       logits_last, (hipStream_t)stream, kv.k_lo, kv.vt_lo);
+    if (!rc) {
+        const int64_t per_seq = (int64_t)e->nH * d->cap * 64, lstride = (int64_t)d->nb * per_seq;
+        rc = showo_kv_copy_rows(kv.k, kv.vt, kv.Lcap, kv.k_lstride, kv.v_lstride, d->k + b * per_seq, d->vt + b * per_seq, d->cap, lstride,
+                                lstride, e->nL, e->nH, P, P + Ln, d->base, stream);
+    }
+    // rewind to P whatever happened: the V^T columns the rows (or a part of them) wrote are zero again up to the end of their last tile
+    e->cache_len = P + Ln < kv.Lcap ? P + Ln : kv.Lcap;
+    const int rc2 = showo_engine_cache_rewind(e, P, stream);
+    e->cache_len = P;
+    if (rc) return rc;
+    if (rc2) return rc2;
+    d->prompt_len[b] = e->prompt_len;
+    d->cache_len[b] = P + Ln;
+    for (int i = 0; i < 4; ++i) d->last_iv[b][i] = e->last_iv[i];
     return 0;
 }
 
@@ -673,6 +773,7 @@ int batch_decode_checks(showo_engine* e, const char* what) {
     const int op = e->precision == 2 ? SHOWO_OP_F16 : SHOWO_OP_BF16;
     if ((op == SHOWO_OP_F16) != e->img_f16) return fail(4, "the weight images hold the other 16-bit type: upload the weights again");
     if (d->precision != e->precision) return fail(1, "the caches were prefilled under another precision: prefill again");
+    if (d->shared) TRY(shared_cache_check(e, what));
     if (op && (!e->wlm_lo || !e->lo_loaded.count("showo.lm_head.weight")))
         return fail(4, "(precision 2) the lm_head's low half is missing: upload the weights again");
     for (int b = 0; b < d->nb; ++b) {
@@ -700,6 +801,16 @@ int batch_step_layers(showo_engine* e, int op, bool co, int lk_max, float* logit
         const OutGemvBArgs o{e->x, w.Wd, e->attn, w.bd, H, H, w.W2, e->ffn, w.b2, F, F, H, d->y2, w.sd, w.s2};
         if (d->wide) {  // ln_gemmW -> attention (heads x nb blocks) -> out_gemmW: the MFMA step of decode_wide.hip
             TRY(showo::ln_gemmW(nb, a, d->wws, s));
+            if (d->shared) {  // the prefix launch over the engine's cache + the suffix / merge launch over the slots (attn_shared.hip)
+                const showo::KVDest kv = showo::kv_decode_cache(e);
+                showo::SharedAttnArgs sa{e->qkv, l.qln_w, l.qln_b, l.kln_w, l.kln_b, e->cosT, e->sinT, kv.k + li * kv.k_lstride,
+                                         kv.vt + li * kv.v_lstride, kv.Lcap, d->k + li * lstride, d->vt + li * lstride, d->cap,
+                                         d->pre_iv[0], d->pre_iv[1], d->pre_iv[2], d->pre_iv[3], d->P, d->base, d->pos_dev, lk_max,
+                                         e->attn, d->sws, nb, nH, e->cfg.rotary_dim, e->cfg.ln_eps};
+                TRY(showo::attn_decode_shared(sa, s));
+                TRY(showo::out_gemmW(nb, o, d->wws, s));
+                continue;
+            }
             TRY(showo::attn_decode_fused_batch(e->qkv, l.qln_w, l.qln_b, l.kln_w, l.kln_b, e->cosT, e->sinT, d->k + li * lstride,
                                                d->vt + li * lstride, d->iv_dev, e->attn, nb, nH, e->cfg.rotary_dim, e->cfg.ln_eps,
                                                d->pos_dev, lk_max, d->cap, d->cap, s, 0));
@@ -768,7 +879,7 @@ extern "C" int showo_engine_batch_decode_greedy(showo_engine* e, int64_t* tok, i
     int P0[MAXB];
     for (int b = 0; b < nb; ++b) {
         P0[b] = d->cache_len[b];
-        if (P0[b] + n_steps > d->cap || P0[b] + n_steps > e->cfg.max_pos) return set_error_msg(5, "batch_decode_greedy: cache full");
+        if (P0[b] + n_steps > d->abs_cap() || P0[b] + n_steps > e->cfg.max_pos) return set_error_msg(5, "batch_decode_greedy: cache full");
         lk_max = lk_max > P0[b] + n_steps ? lk_max : P0[b] + n_steps;
     }
     SHOWO_CHECK_HIP(hipMemcpyAsync(d->pos_dev, P0, sizeof(int) * nb, hipMemcpyHostToDevice, s));
@@ -810,7 +921,7 @@ static int batch_decode_sample(showo_engine* e, int64_t* tok, int n_steps, int64
     TRY(batch_decode_checks(e, "batch_decode_sample"));
     const int op = e->precision == 2 ? SHOWO_OP_F16 : SHOWO_OP_BF16;
     // positions stay below lim: the cache capacity and the rotary tables (max_position_embeddings)
-    const int lim = d->cap < e->cfg.max_pos ? d->cap : e->cfg.max_pos;
+    const int lim = d->abs_cap() < e->cfg.max_pos ? d->abs_cap() : e->cfg.max_pos;
     int lk_max = 0;
     int P0[MAXB], pos0[MAXB];
     SlotDraw sd[MAXB];

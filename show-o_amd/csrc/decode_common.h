@@ -5,6 +5,21 @@
 namespace showo {
 
 // mask row of the token at position P (the batched decode seams, showo_mask_append_rows): the last prompt row extended by the columns [L0, P] (modeling_showo.py:203-217)
+// q / k LayerNorm(64) + partial RoPE of one head row of a NEW token, lane = dimension: the statistics on the VALU-only reductions
+// (the bits of wave_sum), the RoPE operands (cs, sn: the lane's entries of the position's table row) in registers.  The ONE copy of
+// these expressions: the fused single-query attention (attention.hip attn_decode_body) and both launches of the shared-prefix
+// attention (attn_shared.hip) call it, so a query row has the same bits wherever it is prepared.
+static __device__ __forceinline__ float decode_prep_lane(float x0, float lnw, float lnb, float eps, float cs, float sn, int rot, int lane) {
+    const float mean = wave_sum_swap(x0) * (1.0f / 64.0f);
+    const float c = x0 - mean;
+    const float var = wave_sum_swap(c * c) * (1.0f / 64.0f);
+    float y = c * (1.0f / sqrtf(var + eps)) * lnw + lnb;
+    const int half = rot >> 1;
+    const float partner = __shfl_xor(y, half, 64);
+    if (lane < rot) y = y * cs + (lane < half ? -partner : partner) * sn;
+    return y;
+}
+
 static __device__ __forceinline__ void next_iv(const int32_t* last_iv, int L0, int P, int32_t* iv) {
     int a = last_iv[0], b = last_iv[1], c = last_iv[2], d = last_iv[3];
     if (b == L0 && a < b) b = P + 1;

@@ -1191,23 +1191,26 @@ def _singles(single, n, return_logprobs):
     return ([o[0] for o in outs], [o[1] for o in outs]) if return_logprobs else outs
 
 
-def _batch_begin(eng, slots, capacity, wide=False):
-    """open a decode batch of `slots` KV caches of `capacity` rows (showo_engine_batch_begin / _begin_wide).  False: the batch's common
+def _batch_begin(eng, slots, capacity, wide=False, shared=False):
+    """open a decode batch of `slots` KV caches of `capacity` rows (showo_engine_batch_begin / _begin_wide; `shared`: _begin_shared,
+    whose slots are suffix caches over the engine's decode cache and whose capacity counts suffix rows).  False: the batch's common
     capacity (longest prompt + max_new_tokens) does not fit the engine (max_position_embeddings, the single-block decode attention) --
     the caller then makes n sequential calls, which fail only if a sequence actually reaches the limit before <eot>"""
     try:
-        _lib.call("showo_engine_batch_begin_wide" if wide else "showo_engine_batch_begin", eng, slots, capacity)
+        _lib.call("showo_engine_batch_begin_shared" if shared else "showo_engine_batch_begin_wide" if wide else "showo_engine_batch_begin",
+                  eng, slots, capacity)
     except RuntimeError:
         return False
     return True
 
 
-def _run_on_slots(eng, n, wide, capacity, slot_engine, max_new_tokens, eot_token, want_lp):
-    """n requests on the slots of a decode batch (`wide`: the slot count of a wide one, else up to 8): begin, `slot_engine(slots)` as the
-    engine side of _mmu_batch_schedule, the schedule.  The int token lists in request order, want_lp: (token lists, log-probability
-    tensors); None when the batch does not fit the engine (nothing but the begin has happened then)."""
+def _run_on_slots(eng, n, wide, capacity, slot_engine, max_new_tokens, eot_token, want_lp, shared=False):
+    """n requests on the slots of a decode batch (`wide`: the slot count of a wide one, else up to 8; `shared`: a wide one of suffix
+    caches, `capacity` in suffix rows): begin, `slot_engine(slots)` as the engine side of _mmu_batch_schedule, the schedule.  The int
+    token lists in request order, want_lp: (token lists, log-probability tensors); None when the batch does not fit the engine (nothing
+    but the begin has happened then)."""
     slots = wide if wide else _mmu_batch_slots(n)
-    if not _batch_begin(eng, slots, capacity, bool(wide)):
+    if not _batch_begin(eng, slots, capacity, bool(wide), bool(wide) and shared):
         return None
     se = slot_engine(slots)
     out = _mmu_batch_schedule(se, n, slots, max_new_tokens, eot_token)
@@ -1319,16 +1322,29 @@ Showo._mmu_generate_batch_greedy = _mmu_generate_batch_greedy
 
 
 # ---- mmu sessions: one prefill of the question-invariant prefix, questions appended to its KV cache ("mmu sessions") -------
+def _shared_suffix_capacity(length, lens, max_new_tokens):
+    """rows a slot of a shared-prefix batch needs behind the prefix [0, length): the dead rows below the prefix's last 64-row tile
+    boundary, the longest request, the new tokens and the row an idle slot keeps rewriting"""
+    return (length - (length & ~63)) + max(lens) + max_new_tokens + 1
+
+
 class _SessionSlotEngine(_MmuSlotEngine):
     """engine side of _mmu_batch_schedule for MmuSession.generate_batch: a slot is filled by a fork of the session's cache plus an
-    append of the request's rows instead of a prefill of a whole prompt"""
+    append of the request's rows instead of a prefill of a whole prompt; `share_prefix`: by showo_engine_batch_attach_append -- the
+    rows are appended to the session's own cache, copied into the slot's suffix cache, and the session's cache is rewound"""
 
-    def __init__(self, model, eng, rows, lens, slots, temps, top_ks, seeds, noises, eot_token, dev, top_ps=None, want_lp=False):
+    def __init__(self, model, eng, rows, lens, slots, temps, top_ks, seeds, noises, eot_token, dev, top_ps=None, want_lp=False,
+                 share_prefix=False):
         super().__init__(model, eng, None, None, None, lens, slots, temps, top_ks, seeds, noises, eot_token, dev, top_ps, want_lp)
         self.rows = rows
+        self.share_prefix = share_prefix
 
     def fill(self, s, r):
         ids, emb = self.rows[r]
+        if self.share_prefix:
+            _lib.call("showo_engine_batch_attach_append", self.eng, s, _lib.ptr(ids), _lib.ptr(emb), self.lens[r], _lib.ptr(self.logits[s]),
+                      _lib.stream())
+            return
         _lib.call("showo_engine_batch_fork", self.eng, s, _lib.stream())
         _lib.call("showo_engine_batch_prefill_append", self.eng, s, _lib.ptr(ids), _lib.ptr(emb), self.lens[r], _lib.ptr(self.logits[s]),
                   _lib.stream())
@@ -1410,15 +1426,18 @@ class _SessionEngine:
         return lp, rk
 
     def run_batch(self, length, rows, lens, max_new_tokens, temps, top_ks, seeds, noises, eot_token, top_ps=None, return_logprobs=False,
-                  slots=None):
+                  slots=None, share_prefix=False):
         """n continuations of the cache [0, length) on the slots of a decode batch; None when the batch does not fit the engine;
-        return_logprobs: (token lists, log-probability tensors); slots: the slot count of a wide batch (_mmu_wide_slots)"""
+        return_logprobs: (token lists, log-probability tensors); slots: the slot count of a wide batch (_mmu_wide_slots);
+        share_prefix (with slots): the slots are suffix caches that read [0, length) in the session's cache"""
+        shared = bool(share_prefix and slots)
+
         def slot_engine(slots):
             return _SessionSlotEngine(self.model, self.eng, rows, lens, slots, temps, top_ks, seeds, noises, eot_token, self.dev, top_ps,
-                                      want_lp=return_logprobs)
+                                      want_lp=return_logprobs, share_prefix=shared)
 
-        return _run_on_slots(self.eng, len(rows), slots, length + max(lens) + max_new_tokens + 1, slot_engine, max_new_tokens, eot_token,
-                             return_logprobs)
+        capacity = _shared_suffix_capacity(length, lens, max_new_tokens) if shared else length + max(lens) + max_new_tokens + 1
+        return _run_on_slots(self.eng, len(rows), slots, capacity, slot_engine, max_new_tokens, eot_token, return_logprobs, shared=shared)
 
 
 class _SessionRecompute:
@@ -1628,7 +1647,7 @@ class MmuSession:
 
     @torch.no_grad()
     def generate_batch(self, idx=None, input_embeddings=None, max_new_tokens=100, temperature=1.0, top_k=None, eot_token=None,
-                       generator=None, _exp_noise=None, top_p=None, return_logprobs=False, slots=None):
+                       generator=None, _exp_noise=None, top_p=None, return_logprobs=False, slots=None, share_prefix=False):
         """n continuations of the CURRENT state: `idx` / `input_embeddings` is a list of n row blocks ([1, Ln_i] ids or [1, Ln_i, H]
         embeddings), `temperature` / `top_k` / `top_p` scalars or lists, `_exp_noise` None or a list.  result[i] is what `generate(<block i>)`
         followed by a rewind returns when those calls are made in order (same seeds from `generator`); the session is left unchanged.
@@ -1636,10 +1655,21 @@ class MmuSession:
         `return_logprobs=True`: `(tokens, logprobs)`, logprobs a list of n fp32 device tensors.
         `slots=S` (an int in 9..32, precision 0; else ValueError): n > 8 continuations run on min(S, n) slots of a WIDE decode batch
         (`Showo.mmu_generate_batch` states its contract: deterministic, independent of S / n / slot / neighbours, bf16-class and not
-        the batch-1 bits); n <= 8 is the call without `slots`."""
+        the batch-1 bits); n <= 8 is the call without `slots`.
+        `share_prefix=True` (needs `slots=S` and precision 0; else ValueError): the slots of that wide batch keep only the rows BEHIND
+        the session's cache and attend to [0, length) in place (showo_engine_batch_begin_shared, csrc/attn_shared.hip): no fork copy,
+        a quarter of the slot memory, the prefix read once per head and step.  Contract: deterministic run to run; a request's tokens
+        and log-probabilities do not depend on S, n, its slot, the request order or its neighbours; the first token of every request
+        comes from logits bit-equal to `generate`'s; later tokens are bf16-class and NOT the bits of the forked wide path (P is
+        rounded relative to its key segment's max, not the row's, and the fp32 sums are split); the session, including its cache
+        bits, is unchanged afterwards.  n <= 8 is the call without `slots` / `share_prefix`."""
         self._check()
         seqs = idx if idx is not None else input_embeddings
         n = len(seqs)
+        if share_prefix and slots is None:
+            raise ValueError("share_prefix needs slots=S (the slots of a wide decode batch share the prefix)")
+        if share_prefix and int(getattr(self.model, "_precision", 0)) != 0:
+            raise ValueError("share_prefix needs precision 0 (bf16 operands)")
         wide = _mmu_wide_slots(slots, n, getattr(self.model, "_precision", 0))
         temps, top_ks, top_ps, noises, _ = _per_request(n, temperature, top_k, top_p, _exp_noise)
 
@@ -1674,6 +1704,8 @@ class MmuSession:
             nucleus["return_logprobs"] = True
         if wide:
             nucleus["slots"] = wide
+            if share_prefix:
+                nucleus["share_prefix"] = True
         out = self._be.run_batch(self.length, rows, lens, max_new_tokens, temps, top_ks, seeds, noises, eot_token, **nucleus)
         if out is None:  # the batch's common capacity does not fit the engine: the sequential calls, drawing the same seeds again
             if gen_state is not None:

@@ -13,7 +13,14 @@ every figure is the median of >= 5 wall-clock intervals taken between device syn
 
 The baseline is the full-prompt path of the same build in the same process.  Writes profiles/mmu_prefix_bench.json.
 
-  python tools/mmu_prefix_bench.py [--reps 5] [--new 100] [--out profiles/mmu_prefix_bench.json]"""
+  python tools/mmu_prefix_bench.py [--reps 5] [--new 100] [--out profiles/mmu_prefix_bench.json]
+  python tools/mmu_prefix_bench.py --share-prefix [--reps 7]   # shared-prefix slots (share_prefix=True, csrc/attn_shared.hip): n = 32 / 64
+                                               # questions about one image on 32 wide slots, greedy and top_k=5; legs alternating in
+                                               # this process: sess.generate_batch(slots=32) forked, the same call with share_prefix=True,
+                                               # mmu_generate_batch(slots=32) on full prompts (behind them: it replaces the decode cache);
+                                               # tokens/s of the whole call, one decode step
+                                               # by the 100-vs-36-token difference, token agreement forked / shared -> profiles/shared_prefix_bench.json
+  python tools/mmu_prefix_bench.py --profile-shared 32   # one shared greedy n = S call of 17 tokens, twice, for a kernel trace"""
 import argparse
 import ctypes as C
 import json
@@ -77,12 +84,82 @@ def ints(rows):
     return [[int(t) for t in r] for r in rows]
 
 
+def shared_legs(reps, new, short, out, ns=(32, 64), S=32):
+    """forked / shared / full-prompt legs at n questions about one image on S wide slots; see the module docstring"""
+    pkg, model, prefix, pmask, questions, fulls, fmask = build(max(ns))
+    sess = model.mmu_session(input_embeddings=prefix, attention_mask=pmask)
+    arch = model.arch
+    nL, nH = arch["num_hidden_layers"], arch["num_attention_heads"]
+    base = P & ~63
+    res = {"shape": f"cfg4: prefix {P} rows, questions of {LQ} rows, {new} new tokens, {S} wide slots, full-size seeded weights",
+           "reps": reps, "unit": "tokens/s of the whole call (appends / prefills included), median of reps; step_ms: (t(new) - t(short)) / "
+                                 f"(new - short) per n / {S}-slot round", "short": short,
+           "from_shapes": {"slot_cache_bytes_forked": 4 * nL * nH * 64 * ((P + LQ + new + 1 + 63) // 64 * 64),
+                           "slot_cache_bytes_shared": 4 * nL * nH * 64 * ((P - base + LQ + new + 1 + 63) // 64 * 64),
+                           "fork_copy_bytes_each_way_per_request": 4 * nL * nH * 64 * P,
+                           "shared_copy_bytes_each_way_per_request": 4 * nL * nH * 64 * LQ}}
+    for mode, kw in (("greedy", dict(top_k=1)), ("topk5", dict(top_k=5, temperature=0.7))):
+        for n in ns:
+            def legs(nt):
+                gen = lambda: torch.Generator(device="cuda").manual_seed(11)
+                return {"forked": lambda: sess.generate_batch(input_embeddings=questions[:n], max_new_tokens=nt, generator=gen(), slots=S, **kw),
+                        "shared": lambda: sess.generate_batch(input_embeddings=questions[:n], max_new_tokens=nt, generator=gen(), slots=S,
+                                                              share_prefix=True, **kw)}
+            r = alternate(legs(new), reps)
+            r_short = alternate(legs(short), reps)
+            row = {}
+            for k in ("forked", "shared"):
+                row[k] = {"seconds": r[k][0], "tokens_per_s": n * new / r[k][0],
+                          "step_ms": 1e3 * (r[k][0] - r_short[k][0]) / (new - short) / ((n + S - 1) // S)}
+            a_, b_ = ints(r["forked"][1]), ints(r["shared"][1])
+            row["requests_with_equal_tokens"] = sum(x == y for x, y in zip(a_, b_))
+            row["common_prefix_tokens_mean"] = sum(next((i for i, (u, v) in enumerate(zip(x, y)) if u != v), len(x)) for x, y in zip(a_, b_)) / n
+            row["shared_over_forked"] = row["shared"]["tokens_per_s"] / row["forked"]["tokens_per_s"]
+            res[f"{mode}_n{n}"] = row
+            print(mode, n, row, file=sys.stderr, flush=True)
+    # the full-prompt leg replaces the engine's decode cache, which would make the session stale: it runs BEHIND the session legs, on its
+    # own (its long and short calls alternating with each other), not in their alternation -- the result says so
+    res["full_prompts_leg"] = "measured behind the alternating session legs in the same process, not alternating with them"
+    for mode, kw in (("greedy", dict(top_k=1)), ("topk5", dict(top_k=5, temperature=0.7))):
+        for n in ns:
+            gen = lambda: torch.Generator(device="cuda").manual_seed(11)
+
+            def full(nt):
+                return lambda: model.mmu_generate_batch(input_embeddings=fulls[:n], attention_mask=[fmask] * n, max_new_tokens=nt,
+                                                        generator=gen(), slots=S, **kw)
+            r = alternate({"long": full(new), "short": full(short)}, reps)
+            t, ts = r["long"][0], r["short"][0]
+            res[f"{mode}_n{n}"]["full_prompts"] = {"seconds": t, "tokens_per_s": n * new / t,
+                                                   "step_ms": 1e3 * (t - ts) / (new - short) / ((n + S - 1) // S)}
+            print(mode, n, "full prompts", res[f"{mode}_n{n}"]["full_prompts"], file=sys.stderr, flush=True)
+    os.makedirs(os.path.dirname(out), exist_ok=True)
+    with open(out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--reps", type=int, default=None)
     ap.add_argument("--new", type=int, default=100)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mmu_prefix_bench.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--share-prefix", action="store_true", help="measure shared-prefix slots against forked slots and full prompts")
+    ap.add_argument("--profile-shared", type=int, default=None, help="one shared greedy call of 17 tokens on this many slots, twice")
     a = ap.parse_args()
+    if a.profile_shared is not None:
+        S = a.profile_shared
+        pkg, model, prefix, pmask, questions, fulls, fmask = build(S)
+        sess = model.mmu_session(input_embeddings=prefix, attention_mask=pmask)
+        for _ in range(2):
+            sess.generate_batch(input_embeddings=questions, max_new_tokens=17, top_k=1, slots=S, share_prefix=True)
+        torch.cuda.synchronize()
+        print(json.dumps({"profiled": f"sess.generate_batch n={S} greedy slots={S} share_prefix=True, 17 tokens, twice"}))
+        return
+    if a.share_prefix:
+        shared_legs(a.reps or 7, a.new, 36, a.out or os.path.join(ROOT, "profiles", "shared_prefix_bench.json"))
+        return
+    a.reps = a.reps or 5
+    a.out = a.out or os.path.join(ROOT, "profiles", "mmu_prefix_bench.json")
     reps = max(5, a.reps)
     pkg, model, prefix, pmask, questions, fulls, fmask = build(8)
     L = pkg._lib
