@@ -64,6 +64,11 @@ def main():
     ap.add_argument("--temperature", type=float, default=1.0)
     ap.add_argument("--top-p", type=float, default=None, help="nucleus sampling behind the top-k filter (needs --top-k other than 1; 0: no top-k)")
     ap.add_argument("--logprobs", action="store_true", help="also report every answer token's log-probability (return_logprobs=True)")
+    ap.add_argument("--repetition-penalty", type=float, default=None,
+                    help="penalise the tokens of the prompt's text ids and of the answer so far (Hugging Face's rule; 1: none)")
+    ap.add_argument("--ban", default=None, help="comma-separated token ids (or, with --tokenizer, words) that must not be produced")
+    ap.add_argument("--allow", default=None,
+                    help="comma-separated token ids (or words) the answer is confined to, e.g. 'yes,no'; <eos> stays allowed")
     ap.add_argument("--seed", type=int, default=0)
     a = ap.parse_args()
     torch.manual_seed(a.seed)
@@ -75,6 +80,15 @@ def main():
     else:
         tok = synthetic.SyntheticTokenizer()
         system, question = synthetic.random_text(rs, SYSTEM_PROMPT_LEN), a.question or synthetic.random_text(rs, 24)
+
+    def token_set(arg):
+        """the ids of a --ban / --allow list: integers as they are, words through the tokenizer (every piece of the word)"""
+        out = []
+        for item in arg.split(","):
+            item = item.strip()
+            out += [int(item)] if item.lstrip("-").isdigit() else [int(t) for t in tok([item])["input_ids"][0]]
+        return out
+
     uni = UniversalPrompting(tok, max_text_len=128, special_tokens=synthetic.SPECIAL_TOKENS, ignore_id=-100, cond_dropout_prob=0.1)
     if a.showo:
         model = showo_amd.Showo.from_pretrained(a.showo, max_batch=1, max_seq=1024)
@@ -96,6 +110,14 @@ def main():
     q_ids = tok([question])["input_ids"][0]
     sp = uni.sptids_dict
     ids = torch.tensor([[int(sp['<|mmu|>'])] + sys_ids + [int(sp['<|soi|>']), int(sp['<|eoi|>'])] + q_ids], device="cuda")
+    # logit adjustment (on the device, in front of every pick): only the keywords that were given are passed on
+    adjust = {}
+    if a.repetition_penalty is not None:
+        adjust.update(repetition_penalty=a.repetition_penalty, repetition_context=ids[0])  # the prompt is embeddings: name its text ids
+    if a.ban:
+        adjust["banned_tokens"] = token_set(a.ban)
+    if a.allow:
+        adjust["allowed_tokens"] = token_set(a.allow) + ([int(tok.eos_token_id)] if tok.eos_token_id is not None else [])
     with torch.no_grad():
         img_emb = model.mm_projector(tower(pixels[None]))                    # [1, 576, 2048]
         txt = model.showo.model.embed_tokens(ids)
@@ -109,7 +131,8 @@ def main():
                 qs = [q.strip() for q in a.questions.split(" *** ")]
                 q_embs = [model.showo.model.embed_tokens(torch.tensor([tok([q])["input_ids"][0]], device="cuda")) for q in qs]
                 outs = sess.generate_batch(input_embeddings=q_embs, max_new_tokens=a.max_new_tokens, top_k=a.top_k, temperature=a.temperature,
-                                           eot_token=tok.eos_token_id, top_p=a.top_p, return_logprobs=a.logprobs, slots=32, share_prefix=True)
+                                           eot_token=tok.eos_token_id, top_p=a.top_p, return_logprobs=a.logprobs, slots=32, share_prefix=True,
+                                           **adjust)
                 outs, lpss = outs if a.logprobs else (outs, [None] * len(qs))
                 for q, ans, lps in zip(qs, outs, lpss):
                     ans = [int(t) for t in ans]
@@ -121,7 +144,7 @@ def main():
             for q in [q.strip() for q in a.questions.split(" *** ")]:
                 q_emb = model.showo.model.embed_tokens(torch.tensor([tok([q])["input_ids"][0]], device="cuda"))
                 ans = sess.generate(input_embeddings=q_emb, max_new_tokens=a.max_new_tokens, top_k=a.top_k, temperature=a.temperature,
-                                    eot_token=tok.eos_token_id, top_p=a.top_p, return_logprobs=a.logprobs)
+                                    eot_token=tok.eos_token_id, top_p=a.top_p, return_logprobs=a.logprobs, **adjust)
                 ans, lps = ans if a.logprobs else (ans, None)
                 ans = [int(t) for t in ans]
                 print(f"[{sess.length} rows in the cache] {q!r} -> {len(ans)} tokens:", ans[:24], "..." if len(ans) > 24 else "")
@@ -133,7 +156,8 @@ def main():
             return
         mask = intervals_for_mmu_vit(emb, system_prompt_len=len(sys_ids))     # per-row intervals, no [1,1,L,L] tensor
         toks = model.mmu_generate(input_embeddings=emb, attention_mask=mask, max_new_tokens=a.max_new_tokens, top_k=a.top_k,
-                                  temperature=a.temperature, eot_token=tok.eos_token_id, top_p=a.top_p, return_logprobs=a.logprobs)
+                                  temperature=a.temperature, eot_token=tok.eos_token_id, top_p=a.top_p, return_logprobs=a.logprobs,
+                                  **adjust)
     toks, lps = toks if a.logprobs else (toks, None)
     out = [int(t) for t in toks]
     print(f"prompt of {emb.shape[1]} embeddings -> {len(out)} tokens:", out[:24], "..." if len(out) > 24 else "")

@@ -885,6 +885,47 @@ int showo_engine_score(showo_engine* e, const int64_t* ids, const float* embeds,
                        const int64_t* targets, int n, int chunk_rows, float* logprob, int32_t* rank, void* stream);
 int showo_engine_prefill_append_score(showo_engine* e, const int64_t* ids, int Ln, const float* logits_prev, float* logprob, int32_t* rank,
                                       float* logits_last, void* stream);
+/* Logit adjustment: repetition penalty and logit bias in front of the pick, on the device (csrc/logit_adjust.hip).
+ * For one fp32 logits row x[0, V), a token set S, a penalty theta (finite, > 0) and an optional fp32 bias row beta[0, V):
+ *   r_i = x_i                                  i not in S
+ *   r_i = x_i * theta  if x_i < 0,  else  x_i / theta     i in S   (fp32 multiply; fp32 IEEE division)
+ *   y_i = r_i + beta_i                         (no bias row: y_i = r_i)
+ * Hugging Face's RepetitionPenaltyLogitsProcessor followed by a sequence bias, both ahead of temperature / top-k / top-p, which the
+ * picks apply to y exactly as they apply them to x.  -0.0 and 0.0 count as "not < 0"; -inf stays -inf; beta_i = -inf bans token i
+ * (the callers refuse +inf and NaN in beta).  theta == 1 without a bias row is a bit copy.  y goes to a second row: x is never
+ * overwritten, and log-probabilities stay the log-softmax of x.  The work is elementwise, so equal rows give equal bits at every
+ * row alignment, row count and from every caller below.
+ * The set is a bitmap (part of this ABI): uint32 words [rows, seen_ld], seen_ld >= ceil(V / 32); token i is bit i & 31 of word
+ * i >> 5 of its row; bits at positions >= V of the last word are never set.  The caller owns it (and clears it).
+ * showo_seen_mark: sets the bits of ids int64 [n] (device) in ONE bitmap row; ids < 0 or >= V are ignored (the -1 of an idle slot's
+ * output row may be passed in); n == 0 launches nothing.
+ * showo_logits_adjust: rows logits + r * ld -> out + r * ld_out (ld, ld_out >= V; 4-byte aligned), r < nrows, one launch per 32
+ * rows.  mark: NULL, or int64 [nrows] (device): row r treats mark[r] as a member of its set and ORs its bit into the bitmap
+ * (atomically; the output does not depend on when that lands); a mark outside [0, V) means none.  penalty: HOST float [nrows].
+ * bias: NULL, or a HOST array of nrows device pointers (fp32 [V] rows), NULL entries allowed.  active: NULL, or int32 [nrows]
+ * (device): a row whose entry is 0 is neither marked nor written.  Error 1, before any launch: out overlapping logits, a penalty
+ * that is not finite or not > 0, seen_ld too small.  nrows == 0 launches nothing.
+ * showo_engine_decode_sample_adj / showo_engine_batch_decode_sample_adj: showo_engine_decode_sample_lp / _batch_decode_sample_lp
+ * (logprobs may be NULL, the batched top_p may be NULL) with one adjust launch per step, inside the captured step, between the
+ * lm_head and the pick: it reads logits_ws, marks the token the step FED (*tok; tok[b] of the slots that are still decoding -- an
+ * idle or stopped slot is skipped) and writes adj_ws fp32 [nb, V] (device), which the pick reads.  The log-probability launch keeps
+ * reading logits_ws: log-probabilities are those of the RAW logits.  seen: bitmap [nb, seen_ld] (nb = 1 for the batch-1 form);
+ * penalty HOST float [nb]; bias NULL or HOST [nb] of device rows, NULL entries allowed; all fixed for the call.  The caller marks
+ * what the set starts with (showo_seen_mark) and adjusts the prefill logits for the first token (showo_logits_adjust).  With an
+ * adjustment the batch-1 greedy step (top_k == 1) takes showo_argmax_f32 on adj_ws and the separate store / increment launches
+ * instead of the fused token seam.  A row with theta == 1 and no bias draws the bits of the call without. */
+int showo_seen_mark(uint32_t* seen_row, int V, const int64_t* ids, int n, void* stream);
+int showo_logits_adjust(const float* logits, int64_t ld, int nrows, int V, uint32_t* seen, int64_t seen_ld, const int64_t* mark,
+                        const float* penalty, const float* const* bias, const int32_t* active, float* out, int64_t ld_out, void* stream);
+int showo_engine_decode_sample_adj(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws, int top_k,
+                                   float top_p, float temperature, const float* exp_noise, uint64_t seed, int step0, float* logprobs,
+                                   int32_t* ranks, uint32_t* seen, int64_t seen_ld, const float* penalty, const float* const* bias,
+                                   float* adj_ws, int use_graph, void* stream);
+int showo_engine_batch_decode_sample_adj(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws,
+                                         const int* top_k, const float* top_p, const float* temperature, const uint64_t* seed,
+                                         const int* draw0, const float* const* exp_noise, const int* budget, int64_t eot, int* produced,
+                                         float* logprobs, int32_t* ranks, uint32_t* seen, int64_t seen_ld, const float* penalty,
+                                         const float* const* bias, float* adj_ws, int use_graph, void* stream);
 /* greedy/top-k=1 pick on device: out int64[1] = argmax(logits) (first maximal index, like torch.topk/multinomial on a one-hot). */
 int showo_argmax_f32(const float* x, int n, int64_t* out, void* stream);
 

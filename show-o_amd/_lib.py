@@ -239,6 +239,13 @@ _PROTOS = {
     "showo_engine_batch_decode_sample_lp": [c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_i, c_p],
     "showo_engine_score": [c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_i, c_i, c_p, c_p, c_p],
     "showo_engine_prefill_append_score": [c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p],
+    # logit adjustment (csrc/logit_adjust.hip): the bitmap of seen tokens, the stand-alone adjust, and the _lp decode loops with one
+    # adjust launch per step (seen, seen_ld, host penalty[nb], host bias[nb] of device rows, adj_ws in front of use_graph)
+    "showo_seen_mark": [c_p, c_i, c_p, c_i, c_p],
+    "showo_logits_adjust": [c_p, c_i64, c_i, c_i, c_p, c_i64, c_p, c_p, c_p, c_p, c_p, c_i64, c_p],
+    "showo_engine_decode_sample_adj": [c_p, c_p, c_i, c_p, c_p, c_i, c_f, c_f, c_p, c_u64, c_i, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_i, c_p],
+    "showo_engine_batch_decode_sample_adj": [c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p,
+                                             c_p, c_p, c_i, c_p],
     # wide decode batches (csrc/decode_wide.hip): the two MFMA kernels alone
     "showo_decode_wide_ln_gemm": [c_p, c_p, c_p, c_f, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_p],
     "showo_decode_wide_out_gemm": [c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_p],

@@ -23,6 +23,8 @@
 #include "sample_row.h"
 #include "decode_wide.h"
 #include "attn_shared.h"
+#include "logit_adjust.h"
+#include <cstddef>
 #include <string>
 #include <type_traits>
 
@@ -347,6 +349,8 @@ struct SlotDraw {
     int active;    // 0: stopped (budget spent or <eot> emitted) or idle from the start
     float top_p;   // >= 1: no nucleus filter (sample_topk_row); 0 < top_p < 1: sample_topk_topp_row
 };
+static_assert(sizeof(SlotDraw) % sizeof(int) == 0 && offsetof(SlotDraw, active) % sizeof(int) == 0,
+              "the adjust launch reads SlotDraw.active as a strided int array");
 
 // Row of slot b for its next step: the embedding of its token while it decodes; zeros once it is idle (a fixed, finite row, so the
 // idle slot's residual row stays bounded while the other slots keep decoding).
@@ -908,10 +912,13 @@ extern "C" int showo_engine_batch_decode_greedy(showo_engine* e, int64_t* tok, i
 // emits at most budget[b] tokens, stopping early after `eot`; a stopped or idle slot keeps decoding a fixed row in place so that the
 // captured step stays the same for every slot.  Its cache length advances by what it produced.
 // top_p == NULL: no slot filters (showo_engine_batch_decode_sample); else host float [nb], per slot >= 1 (off) or in (0, 1).
+// adj != NULL (showo_engine_batch_decode_sample_adj): one adjust launch for all nb slots between the layers and the seam reads
+// logits_ws, marks tok[b] of the slots whose SlotDraw.active is set (an idle slot is skipped) and writes adj->ws, which the seam reads
+// instead; logprob_slots_kernel keeps reading logits_ws.  The <= 8 slots, the wide slots and the shared-prefix slots share this seam.
 static int batch_decode_sample(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws, const int* top_k,
                                const float* top_p, const float* temperature, const uint64_t* seed, const int* draw0,
                                const float* const* exp_noise, const int* budget, int64_t eot, int* produced, int use_graph, void* stream,
-                               float* lps = nullptr, int32_t* ranks = nullptr) {
+                               float* lps = nullptr, int32_t* ranks = nullptr, const showo::LogitAdjust* adj = nullptr) {
     hipStream_t s = (hipStream_t)stream;
     if (!e || !e->bd || e->bd->nb == 0) return set_error_msg(1, "batch_decode_sample: showo_engine_batch_begin + _batch_prefill first");
     auto* d = e->bd;
@@ -919,6 +926,10 @@ static int batch_decode_sample(showo_engine* e, int64_t* tok, int n_steps, int64
     if (!tok || !out_tokens || !logits_ws || n_steps < 1 || !top_k || !temperature || !seed || !draw0 || !budget || !produced)
         return set_error_msg(1, "batch_decode_sample: bad arguments");
     TRY(batch_decode_checks(e, "batch_decode_sample"));
+    if (adj) {
+        if (!adj->ws || adj->ws == logits_ws) return set_error_msg(1, "batch_decode_sample_adj: needs an adj_ws [nb, V] of its own");
+        TRY(showo::logits_adjust_check(nb, V, adj->seen, adj->seen_ld, adj->penalty, "batch_decode_sample_adj"));
+    }
     const int op = e->precision == 2 ? SHOWO_OP_F16 : SHOWO_OP_BF16;
     // positions stay below lim: the cache capacity and the rotary tables (max_position_embeddings)
     const int lim = d->abs_cap() < e->cfg.max_pos ? d->abs_cap() : e->cfg.max_pos;
@@ -962,11 +973,18 @@ static int batch_decode_sample(showo_engine* e, int64_t* tok, int n_steps, int64
     TRY(batch_use_co(e, &co));
     auto one = [&]() -> int {
         TRY(batch_step_layers(e, op, co, lk_max, logits_ws, s));
+        const float* pick = logits_ws;
+        if (adj) {
+            const int* active = reinterpret_cast<const int*>(reinterpret_cast<const char*>(d->slots_dev) + offsetof(SlotDraw, active));
+            TRY(showo::logits_adjust_launch(logits_ws, V, nb, V, adj->seen, adj->seen_ld, tok, adj->penalty, adj->bias, active,
+                                            (int)(sizeof(SlotDraw) / sizeof(int)), adj->ws, V, s));
+            pick = adj->ws;
+        }
         if (nucleus)
-            sample_seam_rows_kernel<true><<<dim3(nb), dim3(1024), 0, s>>>(logits_ws, V, eot, tok, out_tokens, n_steps, d->pos_dev, lim,
+            sample_seam_rows_kernel<true><<<dim3(nb), dim3(1024), 0, s>>>(pick, V, eot, tok, out_tokens, n_steps, d->pos_dev, lim,
                                                                          d->slots_dev, e->embed, e->x, H, d->last_iv_dev, d->L0_dev, d->iv_dev);
         else
-            sample_seam_rows_kernel<false><<<dim3(nb), dim3(1024), 0, s>>>(logits_ws, V, eot, tok, out_tokens, n_steps, d->pos_dev, lim,
+            sample_seam_rows_kernel<false><<<dim3(nb), dim3(1024), 0, s>>>(pick, V, eot, tok, out_tokens, n_steps, d->pos_dev, lim,
                                                                           d->slots_dev, e->embed, e->x, H, d->last_iv_dev, d->L0_dev, d->iv_dev);
         if (lps) logprob_slots_kernel<<<dim3(nb), dim3(1024), 0, s>>>(logits_ws, V, out_tokens, n_steps, d->slots_dev, lps, ranks);
         SHOWO_CHECK_HIP(hipGetLastError());
@@ -1007,4 +1025,16 @@ extern "C" int showo_engine_batch_decode_sample_lp(showo_engine* e, int64_t* tok
                                                    int* produced, float* logprobs, int32_t* ranks, int use_graph, void* stream) {
     return batch_decode_sample(e, tok, n_steps, out_tokens, logits_ws, top_k, top_p, temperature, seed, draw0, exp_noise, budget, eot,
                                produced, use_graph, stream, logprobs, logprobs ? ranks : nullptr);
+}
+
+// showo_engine_batch_decode_sample_lp with the logit adjustment in front of the seam (include/showo_hip.h, "Logit adjustment")
+extern "C" int showo_engine_batch_decode_sample_adj(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws,
+                                                    const int* top_k, const float* top_p, const float* temperature, const uint64_t* seed,
+                                                    const int* draw0, const float* const* exp_noise, const int* budget, int64_t eot,
+                                                    int* produced, float* logprobs, int32_t* ranks, uint32_t* seen, int64_t seen_ld,
+                                                    const float* penalty, const float* const* bias, float* adj_ws, int use_graph,
+                                                    void* stream) {
+    const showo::LogitAdjust adj{seen, seen_ld, penalty, bias, adj_ws};
+    return batch_decode_sample(e, tok, n_steps, out_tokens, logits_ws, top_k, top_p, temperature, seed, draw0, exp_noise, budget, eot,
+                               produced, use_graph, stream, logprobs, logprobs ? ranks : nullptr, &adj);
 }

@@ -6,6 +6,7 @@
 // modeling_showo.py:203-217).  The layers and the head are the engine's (engine.hip run_layers / head_rows; a one-token step takes the
 // fused launches of decode.hip); engine_prefill_into / engine_append_into also fill the slots of a decode batch (decode_batch.hip).
 #include "engine.h"
+#include "logit_adjust.h"
 
 using namespace showo;
 
@@ -257,9 +258,12 @@ extern "C" int showo_engine_cache_ptrs(showo_engine* e, uint16_t** k, uint16_t**
 // in front of the draw (showo_sample_topk_topp), top_p >= 1 is the launch of a call without it.
 // lps != NULL (showo_engine_decode_sample_lp): one more launch per step, behind the token boundary, scores the token the step stored
 // against the step's row in logits_ws (sample_row.h logprob_row) -> lps / ranks [n_steps]; NULL: no launch, the loop of a call without.
+// adj != NULL (showo_engine_decode_sample_adj): one adjust launch behind the head reads logits_ws, marks *tok -- the token this step fed,
+// the newest member of the set -- and writes adj->ws, which the pick reads; the log-prob launch keeps reading logits_ws.  The greedy
+// form then leaves the fused token seam for the arg-max on adj->ws and the separate store / increment launches.  NULL: nothing changes.
 static int decode_loop(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws, int top_k, float top_p,
                        float temperature, const float* exp_noise, uint64_t seed, int step0, int use_graph, void* stream,
-                       float* lps = nullptr, int32_t* ranks = nullptr) {
+                       float* lps = nullptr, int32_t* ranks = nullptr, const showo::LogitAdjust* adj = nullptr) {
     hipStream_t s = (hipStream_t)stream;
     if (!e || e->cache_len <= 0) return set_error_msg(1, "decode_greedy: prefill first");
     if (!tok || !out_tokens || !logits_ws || n_steps < 1) return set_error_msg(1, "decode_greedy: bad arguments");
@@ -288,7 +292,7 @@ static int decode_loop(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_
     // [layers, lm_head, arg-max partials, boundary] and only the first step embeds its token up front.  SHOWO_DECODE_TOKSEAM=0: the
     // five separate launches.
     static const int tokseam = env_flag("SHOWO_DECODE_TOKSEAM", 1);
-    const bool seam_tok = tokseam && top_k == 1 && e->V >= 16384;
+    const bool seam_tok = tokseam && top_k == 1 && e->V >= 16384 && !adj;
     auto pre = [&]() -> int {
         TRY(showo_embed_f32(tok, e->embed, e->x, 1, e->H, e->V, s));
         decode_iv_kernel<<<1, 64, 0, s>>>(e->last_iv_dev, e->prompt_len, e->pos_dev, e->iv1);
@@ -307,10 +311,16 @@ static int decode_loop(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_
                                          e->prompt_len, e->iv1, s));
             return score();
         }
-        if (top_k == 1) TRY(showo_argmax_f32(logits_ws, e->V, tok, s));
-        else if (top_p >= 1.f) TRY(showo::sample_topk_launch(logits_ws, e->V, top_k, temperature, exp_noise, (int64_t)e->V, seed, step0, e->pos_dev, P0,
+        const float* pick = logits_ws;
+        if (adj) {
+            TRY(showo::logits_adjust_launch(logits_ws, e->V, 1, e->V, adj->seen, adj->seen_ld, tok, adj->penalty, adj->bias, nullptr, 0, adj->ws,
+                                            e->V, s));
+            pick = adj->ws;
+        }
+        if (top_k == 1) TRY(showo_argmax_f32(pick, e->V, tok, s));
+        else if (top_p >= 1.f) TRY(showo::sample_topk_launch(pick, e->V, top_k, temperature, exp_noise, (int64_t)e->V, seed, step0, e->pos_dev, P0,
                                                              tok, s));
-        else TRY(showo::sample_topk_topp_launch(logits_ws, e->V, top_k, top_p, temperature, exp_noise, (int64_t)e->V, seed, step0,
+        else TRY(showo::sample_topk_topp_launch(pick, e->V, top_k, top_p, temperature, exp_noise, (int64_t)e->V, seed, step0,
                                                 e->pos_dev, P0, tok, s));
         store_token_kernel<<<1, 64, 0, s>>>(tok, out_tokens, e->pos_dev, P0);
         TRY(showo::sampler_step_inc(e->pos_dev, s));
@@ -352,4 +362,18 @@ extern "C" int showo_engine_decode_sample_lp(showo_engine* e, int64_t* tok, int 
     if (!(top_p > 0.f)) return set_error_msg(1, "decode_sample_lp: top_p must be > 0 (>= 1: no nucleus filter)");
     return decode_loop(e, tok, n_steps, out_tokens, logits_ws, top_k, top_p, temperature, exp_noise, seed, step0, use_graph, stream,
                        logprobs, logprobs ? ranks : nullptr);
+}
+
+// showo_engine_decode_sample_lp with the logit adjustment in front of the pick (include/showo_hip.h, "Logit adjustment")
+extern "C" int showo_engine_decode_sample_adj(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws, int top_k,
+                                              float top_p, float temperature, const float* exp_noise, uint64_t seed, int step0,
+                                              float* logprobs, int32_t* ranks, uint32_t* seen, int64_t seen_ld, const float* penalty,
+                                              const float* const* bias, float* adj_ws, int use_graph, void* stream) {
+    if (!(temperature > 0.f)) return set_error_msg(1, "decode_sample_adj: temperature must be > 0");
+    if (!(top_p > 0.f)) return set_error_msg(1, "decode_sample_adj: top_p must be > 0 (>= 1: no nucleus filter)");
+    if (!e || !adj_ws || adj_ws == logits_ws) return set_error_msg(1, "decode_sample_adj: needs an adj_ws [V] of its own");
+    TRY(showo::logits_adjust_check(1, e->V, seen, seen_ld, penalty, "decode_sample_adj"));
+    const showo::LogitAdjust adj{seen, seen_ld, penalty, bias, adj_ws};
+    return decode_loop(e, tok, n_steps, out_tokens, logits_ws, top_k, top_p, temperature, exp_noise, seed, step0, use_graph, stream,
+                       logprobs, logprobs ? ranks : nullptr, &adj);
 }

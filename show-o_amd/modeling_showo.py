@@ -10,6 +10,8 @@ PyTorch fallback: without a GPU or without the built library every compute entry
 """
 import collections
 import contextlib
+import math
+import numbers
 import types
 
 import torch
@@ -829,14 +831,30 @@ class Showo(PretrainedMixin, nn.Module):
     # ---- Showo.mmu_generate (reference models/modeling_showo.py:183-240) -----------------------------------
     @torch.no_grad()
     def mmu_generate(self, idx=None, input_embeddings=None, attention_mask=None, max_new_tokens=100, temperature=1.0,
-                     top_k=None, eot_token=None, generator=None, _exp_noise=None, top_p=None, return_logprobs=False):
+                     top_k=None, eot_token=None, generator=None, _exp_noise=None, top_p=None, return_logprobs=False,
+                     repetition_penalty=None, repetition_context=None, logit_bias=None, allowed_tokens=None, banned_tokens=None):
         """reference signature + `generator` (seeds the on-device Philox stream of the multinomial draws; default: torch's
         global generator), `_exp_noise` fp32 [max_new_tokens, vocab] (parity tests inject the reference's Exp(1) draws) and `top_p`
         (nucleus sampling on the device behind the top-k filter, the reference's top_k_top_p_filtering: a token stays iff the mass of
         the strictly more probable candidates is <= top_p; None or >= 1: off, <= 0: ValueError; top_k == 1 stays the arg-max).
         `return_logprobs=True` returns `(tokens, logprobs)`: logprobs fp32 [len(tokens)] on the device, entry j the log-softmax of the
         RAW logits (temperature 1, no filter) at token j -- one more launch per decode step (showo_engine_decode_sample_lp); the
-        tokens are those of the call without it."""
+        tokens are those of the call without it.
+
+        Logit adjustment ("Logit adjustment"; all None: exactly the calls above, no bit changes), applied on the device in
+        front of the pick, in Hugging Face's order (repetition penalty, then bias, then temperature / top-k / top-p):
+        `repetition_penalty` theta (finite, > 0): a token of the set S has its logit x replaced by x * theta if x < 0, else x / theta.
+        S is per call: it starts as the ids of `repetition_context` (a tensor or list of ids; None: empty) and every token this call
+        produces joins it as it is fed back; nothing persists across calls.  Hugging Face's set is the whole `input_ids`, which
+        an `input_embeddings` prompt does not have: pass `repetition_context=idx[0]` for that behaviour.
+        `logit_bias` ({id: float} or an fp32 [vocab] tensor; -inf bans, +inf / NaN: ValueError) is added to the penalised logits;
+        `banned_tokens` puts -inf on the listed ids, `allowed_tokens` puts -inf everywhere else -- if it leaves out `eot_token` the
+        call runs to `max_new_tokens`.  A row without a finite token, ids outside the vocabulary, theta <= 0 / NaN / inf: ValueError
+        before the engine is touched.  `return_logprobs` stays the log-softmax of the RAW logits, adjusted or not."""
+        adj_kw = {k_: v for k_, v in zip(_ADJUST_KEYS, (repetition_penalty, repetition_context, logit_bias, allowed_tokens, banned_tokens))
+                  if v is not None}
+        adjust = _adjust_of(self.vocab_size, **adj_kw) if adj_kw else None
+        adj_kw = {} if adjust is None else {"adjust": adjust}  # (None: the calls below are those of a call without the keywords)
         # greedy (top_k == 1) is the reference caller's setting (inference_mmu.py:81): multinomial of a one-hot = arg-max
         greedy, k, noise, seed, p = _draw_params(self, max_new_tokens, temperature, top_k, top_p, generator, _exp_noise)
         eng = self.engine()
@@ -846,7 +864,8 @@ class Showo(PretrainedMixin, nn.Module):
         if int(getattr(self, "_precision", 0)) == 1 and (getattr(self, "precise_recompute", False) or
                                                          not _lib.load().showo_engine_precise_fast(eng)):
             return self._mmu_generate_recompute(idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token,
-                                                greedy, None if greedy else (k, seed, noise), top_p=p, return_logprobs=return_logprobs)
+                                                greedy, None if greedy else (k, seed, noise), top_p=p, return_logprobs=return_logprobs,
+                                                **adj_kw)
         if input_embeddings is not None:
             idx = None
         if (idx if idx is not None else input_embeddings).shape[0] != 1:
@@ -855,7 +874,8 @@ class Showo(PretrainedMixin, nn.Module):
         tok = torch.empty((1,), dtype=torch.int64, device=dev)
         # (an IntervalMask, prompting_utils.intervals_for_mmu / _mmu_vit: no [1,1,L,L] tensor at all)
         _prefill(eng, *_prompt_args(self, eng, idx, input_embeddings, attention_mask), logits)
-        out = _decode_batch1(self, eng, logits, tok, max_new_tokens, (greedy, k, p, temperature, noise, seed), eot_token, return_logprobs)
+        out = _decode_batch1(self, eng, logits, tok, max_new_tokens, (greedy, k, p, temperature, noise, seed), eot_token, return_logprobs,
+                             **adj_kw)
         toks, lps = out if return_logprobs else (out, None)
         toks = [torch.tensor(t, device=dev) for t in toks]
         return (toks, lps) if return_logprobs else toks
@@ -870,6 +890,158 @@ def _nucleus_p(top_p):
     if not p > 0:
         raise ValueError("top_p must be > 0 (>= 1 or None: no nucleus filter)")
     return None if p >= 1 else p
+
+
+# ---- logit adjustment: repetition penalty, logit bias, allowed / banned tokens ("Logit adjustment") ----------------------------
+class _Adjust:
+    """one request's logit adjustment: `theta` (the repetition penalty, 1.0: none), `bias` (None or the dense fp32 [V] row on the CPU:
+    logit_bias, allowed_tokens and banned_tokens combined) and `context` (the ids the set of seen tokens starts with)"""
+    __slots__ = ("theta", "bias", "context")
+
+    def __init__(self, theta, bias, context):
+        self.theta, self.bias, self.context = theta, bias, context
+
+
+def _token_ids(V, ids, what):
+    """`ids` (None, a tensor, any iterable of ints) as a list of ints inside [0, V); ValueError for anything else"""
+    if ids is None:
+        return []
+    if isinstance(ids, torch.Tensor):
+        ids = ids.detach().reshape(-1).tolist()
+    out = []
+    for t in ids:
+        if isinstance(t, bool) or not isinstance(t, numbers.Integral):
+            raise ValueError(f"{what}: token ids must be integers, got {t!r}")
+        if not 0 <= int(t) < V:
+            raise ValueError(f"{what}: token id {int(t)} outside [0, {V})")
+        out.append(int(t))
+    return out
+
+
+def _bias_row(V, logit_bias=None, allowed_tokens=None, banned_tokens=None):
+    """the dense fp32 [V] bias row (CPU) of one request, or None when it would change nothing: `logit_bias` ({id: float} or an fp32
+    [V] tensor), -inf everywhere outside `allowed_tokens`, -inf on `banned_tokens`.  ValueError: ids out of range, +inf or NaN in the
+    bias, a row that leaves no finite token."""
+    if logit_bias is None and allowed_tokens is None and banned_tokens is None:
+        return None
+    if isinstance(logit_bias, torch.Tensor):
+        if logit_bias.numel() != V:
+            raise ValueError(f"logit_bias: a tensor must hold vocab_size = {V} values")
+        row = logit_bias.detach().to(torch.float32).cpu().reshape(-1).clone()
+    else:
+        row = torch.zeros((V,), dtype=torch.float32)
+        for t, v in (dict(logit_bias).items() if logit_bias is not None else ()):
+            row[_token_ids(V, [t], "logit_bias")[0]] = float(v)
+    if bool(torch.isnan(row).any()) or bool((row == float("inf")).any()):
+        raise ValueError("logit_bias: +inf and NaN are refused (-inf bans a token)")
+    if allowed_tokens is not None:
+        keep = torch.zeros((V,), dtype=torch.bool)
+        keep[torch.tensor(_token_ids(V, allowed_tokens, "allowed_tokens"), dtype=torch.int64)] = True
+        row[~keep] = float("-inf")
+    if banned_tokens is not None:
+        row[torch.tensor(_token_ids(V, banned_tokens, "banned_tokens"), dtype=torch.int64)] = float("-inf")
+    if not bool(torch.isfinite(row).any()):
+        raise ValueError("logit_bias / allowed_tokens / banned_tokens leave no finite token")
+    return row if bool((row != 0).any()) else None
+
+
+def _adjust_of(V, repetition_penalty=None, repetition_context=None, logit_bias=None, allowed_tokens=None, banned_tokens=None):
+    """the _Adjust of one request, or None when the keywords change nothing (all None, or a penalty of 1 without a bias row): such a
+    request takes exactly the calls of one without the keywords.  ValueError for a penalty <= 0, NaN or inf and for what _bias_row
+    and _token_ids refuse -- before anything touches the engine."""
+    theta = 1.0 if repetition_penalty is None else float(repetition_penalty)
+    if not (theta > 0 and math.isfinite(theta)):
+        raise ValueError("repetition_penalty must be finite and > 0 (1: none)")
+    context = _token_ids(V, repetition_context, "repetition_context")
+    row = _bias_row(V, logit_bias, allowed_tokens, banned_tokens)
+    if theta == 1.0 and row is None:
+        return None
+    return _Adjust(theta, row, context)
+
+
+_ADJUST_KEYS = ("repetition_penalty", "repetition_context", "logit_bias", "allowed_tokens", "banned_tokens")
+
+
+def _adjust_per_request(n, V, repetition_penalty=None, repetition_context=None, logit_bias=None, allowed_tokens=None, banned_tokens=None):
+    """(adjusts, kws) of a batch call, the convention of _per_request: every keyword is one value shared by all n requests or a
+    list / tuple of n per-request values.  A penalty or bias list is always per request; an id keyword (context, allowed, banned) is per
+    request when it is a list / tuple whose entries are None or id collections themselves, else one shared collection of ids.
+    adjusts: None when no request adjusts, else n entries (None | _Adjust), ONE _Adjust (one dense row) per distinct request;
+    kws[b]: the keywords of the single call of request b."""
+    groups = (list, tuple, set, frozenset, range, torch.Tensor)
+
+    def spread(v, ids):
+        per = isinstance(v, (list, tuple)) and (not ids or (len(v) > 0 and all(t is None or isinstance(t, groups) for t in v)))
+        if per and len(v) != n:
+            raise ValueError("repetition_penalty / repetition_context / logit_bias / allowed_tokens / banned_tokens lists need one entry per "
+                             "sequence")
+        return list(v) if per else [v] * n
+
+    cols = [spread(v, ids) for v, ids in ((repetition_penalty, False), (repetition_context, True), (logit_bias, False),
+                                          (allowed_tokens, True), (banned_tokens, True))]
+    made, adjusts, kws = {}, [], []
+    for b in range(n):
+        vals = [c[b] for c in cols]
+        key = (None if vals[0] is None else float(vals[0]),) + tuple(id(v) for v in vals[1:])
+        if key not in made:
+            made[key] = _adjust_of(V, *vals)
+        adjusts.append(made[key])
+        kws.append({k: v for k, v in zip(_ADJUST_KEYS, vals) if v is not None})
+    return (None if all(a is None for a in adjusts) else adjusts), kws
+
+
+class _AdjustState:
+    """device side of the adjustment of `rows` logits rows (one decode slot each): the bitmap of seen tokens [rows, ceil(V / 32)], the
+    adjusted rows [rows, V] the picks read, and the bias rows, uploaded once per distinct request.  Nothing here outlives the call."""
+
+    def __init__(self, V, rows, dev):
+        self.V, self.W, self.dev = V, (V + 31) // 32, dev
+        self.seen = torch.zeros((rows, self.W), dtype=torch.int32, device=dev)
+        self.ws = torch.empty((rows, V), dtype=torch.float32, device=dev)
+        self.adj = [None] * rows  # the _Adjust of the request each row serves (None: unadjusted)
+        self._bias = {}
+
+    def bias(self, a):
+        if a is None or a.bias is None:
+            return None
+        if id(a) not in self._bias:
+            self._bias[id(a)] = a.bias.to(self.dev).contiguous()
+        return self._bias[id(a)]
+
+    def seed(self, s, a):
+        """row s serves a new request: a cleared bitmap row, re-seeded with the request's context ids"""
+        self.seen[s].zero_()
+        self.adj[s] = a
+        if a is not None and a.context:
+            ids = torch.tensor(a.context, dtype=torch.int64, device=self.dev)
+            _lib.call("showo_seen_mark", _lib.ptr(self.seen[s]), self.V, _lib.ptr(ids), len(a.context), _lib.stream())
+
+    def mark(self, s, tok):
+        """the one-element int64 device view `tok` joins row s's set"""
+        _lib.call("showo_seen_mark", _lib.ptr(self.seen[s]), self.V, _lib.ptr(tok), 1, _lib.stream())
+
+    def host_args(self):
+        """(penalty, bias) host arrays with one entry per row, as the C entries take them (keep them alive over the call)"""
+        import ctypes as C
+        n = len(self.adj)
+        pen = (C.c_float * n)(*[1.0 if a is None else a.theta for a in self.adj])
+        rows = (C.c_void_p * n)(*[_lib.ptr(self.bias(a)) for a in self.adj])
+        return pen, rows
+
+    def adjust(self, s, logits):
+        """the stand-alone launch on one row: logits fp32 [V] -> the adjusted row of slot s (a view of self.ws), nothing marked"""
+        import ctypes as C
+        pen, rows = self.host_args()
+        _lib.call("showo_logits_adjust", _lib.ptr(logits), self.V, 1, self.V, _lib.ptr(self.seen[s]), self.W, None,
+                  C.c_void_p(C.addressof(pen) + C.sizeof(C.c_float) * s), C.c_void_p(C.addressof(rows) + C.sizeof(C.c_void_p) * s), None,
+                  _lib.ptr(self.ws[s]), self.V, _lib.stream())
+        return self.ws[s]
+
+    def loop_args(self):
+        """the adjustment arguments of showo_engine_decode_sample_adj / _batch_decode_sample_adj, and what must stay alive over the call"""
+        import ctypes as C
+        pen, rows = self.host_args()
+        return (_lib.ptr(self.seen), self.W, C.cast(pen, C.c_void_p), C.cast(rows, C.c_void_p), _lib.ptr(self.ws)), (pen, rows)
 
 
 def _draw_seed(generator):
@@ -953,26 +1125,34 @@ def _logprob_of(logits, V, tok):
 _GREEDY_DRAW = (True, 1, None, 1.0, None, 0)  # a draw (greedy, k, p, temperature, noise, seed) that is the arg-max
 
 
-def _first_token(logits, V, tok, draw, want_lp=False):
+def _first_token(logits, V, tok, draw, want_lp=False, pick=None):
     """launch the pick of a sequence's first token from its prefill logits into the one-element view `tok`: the arg-max, or draw 0 of
     `draw` (logits / temperature -> top-k filter -> softmax -> multinomial, reference :220-228, one kernel).  want_lp: also launch its
-    log-probability and return it (fp32 [1]).  Nothing is read back: the caller decides when to synchronise."""
+    log-probability and return it (fp32 [1]).  Nothing is read back: the caller decides when to synchronise.  `pick`: the adjusted
+    row the pick reads instead (_AdjustState.adjust); the log-probability stays that of the raw `logits`."""
     greedy, k, p, temperature, noise, seed = draw
+    row = logits if pick is None else pick
     if greedy:
-        _lib.call("showo_argmax_f32", _lib.ptr(logits), V, _lib.ptr(tok), _lib.stream())
+        _lib.call("showo_argmax_f32", _lib.ptr(row), V, _lib.ptr(tok), _lib.stream())
     else:
-        _sample_call(logits, V, k, p, temperature, noise, seed, 0, tok)
+        _sample_call(row, V, k, p, temperature, noise, seed, 0, tok)
     return _logprob_of(logits, V, tok) if want_lp else None
 
 
-def _decode_batch1(model, eng, logits, tok, max_new_tokens, draw, eot_token, want_lp):
+def _decode_batch1(model, eng, logits, tok, max_new_tokens, draw, eot_token, want_lp, adjust=None):
     """One sequence behind its prefill (`logits`: its last row's): the int tokens, cut behind <eot>; want_lp: (tokens, their
     log-probabilities fp32 [len(tokens)]).  logits / temperature does not change the arg-max for temperature > 0 and top_k=1 makes the
     reference's multinomial a deterministic arg-max.  The first token comes from the prefill logits; the continuation
     runs in chunks of `chunk` steps entirely on the device (embed -> 24 layers on the KV cache -> lm_head -> pick), one hipGraph
-    replay per step, and the host looks at the tokens (for <eot>) once per chunk."""
+    replay per step, and the host looks at the tokens (for <eot>) once per chunk.
+    `adjust` (an _Adjust): the first token is picked from the adjusted prefill logits (the stand-alone launch, the context ids marked)
+    and every chunk runs on showo_engine_decode_sample_adj, whose steps mark the token they feed; None: the calls of a call without."""
     greedy, k, p, temperature, noise, seed = draw
-    lps = [_first_token(logits, model.vocab_size, tok, draw, want_lp)]
+    st = None
+    if adjust is not None:
+        st = _AdjustState(model.vocab_size, 1, tok.device)
+        st.seed(0, adjust)
+    lps = [_first_token(logits, model.vocab_size, tok, draw, want_lp, None if st is None else st.adjust(0, logits))]
 
     def done(result):
         return (result, torch.cat(lps)[:len(result)]) if want_lp else result
@@ -989,7 +1169,13 @@ def _decode_batch1(model, eng, logits, tok, max_new_tokens, draw, eot_token, wan
             lps.append(torch.empty((n,), dtype=torch.float32, device=tok.device))
         head = (eng, _lib.ptr(tok), n, _lib.ptr(outc), _lib.ptr(logits))
         with _graph_stream_of(model):
-            if want_lp:  # one entry: it takes the greedy step for top_k == 1 and the plain top-k draw for top_p >= 1
+            if st is not None:
+                args, keep = st.loop_args()
+                _lib.call("showo_engine_decode_sample_adj", *head, k, 1.0 if (greedy or p is None) else p,
+                          1.0 if greedy else float(temperature), _lib.ptr(noise), seed, step0, _lib.ptr(lps[-1]) if want_lp else None, None,
+                          *args, use_graph, _lib.stream())
+                del keep
+            elif want_lp:  # one entry: it takes the greedy step for top_k == 1 and the plain top-k draw for top_p >= 1
                 _lib.call("showo_engine_decode_sample_lp", *head, k, 1.0 if (greedy or p is None) else p,
                           1.0 if greedy else float(temperature), _lib.ptr(noise), seed, step0, _lib.ptr(lps[-1]), None, use_graph, _lib.stream())
             elif greedy:
@@ -1084,8 +1270,13 @@ class _MmuSlotEngine:
     """engine side of _mmu_batch_schedule: `slots` KV caches of showo_engine_batch_*, one request per slot"""
 
     def __init__(self, model, eng, idx, input_embeddings, masks, lens, slots, temps, top_ks, seeds, noises, eot_token, dev, top_ps=None,
-                 want_lp=False):
+                 want_lp=False, adjusts=None):
         self.model, self.eng, self.idx, self.emb, self.masks, self.lens = model, eng, idx, input_embeddings, masks, lens
+        # adjusts: None, or per request None | _Adjust -- every decode call then goes through showo_engine_batch_decode_sample_adj (an
+        # unadjusted request's slot runs with penalty 1 and no bias row: a bit copy of its logits); a slot's bitmap row is cleared and
+        # re-seeded with its request's context whenever the scheduler refills it
+        self.adjusts = adjusts
+        self.adj = None if adjusts is None else _AdjustState(model.vocab_size, slots, dev)
         # want_lp: every decode call goes through showo_engine_batch_decode_sample_lp; lps[r] collects request r's log-probabilities
         self.lps = {} if want_lp else None
         self.slots, self.temps, self.top_ks, self.seeds, self.noises = slots, temps, top_ks, seeds, noises
@@ -1111,7 +1302,12 @@ class _MmuSlotEngine:
         """request r's first token, drawn from self.logits[s]"""
         k = self.top_ks[r]
         draw = (k == 1, 0 if k is None else int(k), self.top_ps[r], self.temps[r], self.noises[r], self.seeds[r])
-        lp = _first_token(self.logits[s], self.model.vocab_size, self.tok[s:s + 1], draw, self.lps is not None)
+        pick = None
+        if self.adj is not None:
+            self.adj.seed(s, self.adjusts[r])
+            if self.adjusts[r] is not None:
+                pick = self.adj.adjust(s, self.logits[s])
+        lp = _first_token(self.logits[s], self.model.vocab_size, self.tok[s:s + 1], draw, self.lps is not None, pick)
         self.occ[s] = r
         if self.lps is not None:
             self.lps[r] = [lp]
@@ -1127,7 +1323,7 @@ class _MmuSlotEngine:
         for s in range(S):
             # a slot no request ever took (first tokens that were <eot> ended their sequences before they needed one) still has to hold
             # a prefill for the batched step: it idles on a copy of request 0
-            if self.occ[s] is None and self.lps is not None:
+            if self.occ[s] is None and (self.lps is not None or self.adj is not None):
                 self.fill(s, 0)
                 self.occ[s] = 0
         occ = [r if budget[s] > 0 else None for s, r in enumerate(self.occ)]
@@ -1143,7 +1339,13 @@ class _MmuSlotEngine:
         out = torch.empty((S, m), dtype=torch.int64, device=self.dev)
         lp = None if self.lps is None else torch.empty((S, m), dtype=torch.float32, device=self.dev)
         with _graph_stream_of(self.model):
-            if lp is not None:
+            if self.adj is not None:
+                args, keep = self.adj.loop_args()
+                _lib.call("showo_engine_batch_decode_sample_adj", self.eng, _lib.ptr(self.tok), m, _lib.ptr(out), _lib.ptr(self.logits),
+                          *(C.cast(a, C.c_void_p) for a in (a_k, a_p, a_t, a_s, a_d, a_n, a_b)), self.eot, C.cast(prod, C.c_void_p),
+                          _lib.ptr(lp), None, *args, self.use_graph, _lib.stream())
+                del keep
+            elif lp is not None:
                 _lib.call("showo_engine_batch_decode_sample_lp", self.eng, _lib.ptr(self.tok), m, _lib.ptr(out), _lib.ptr(self.logits),
                           *(C.cast(a, C.c_void_p) for a in (a_k, a_p, a_t, a_s, a_d, a_n, a_b)), self.eot, C.cast(prod, C.c_void_p),
                           _lib.ptr(lp), None, self.use_graph, _lib.stream())
@@ -1219,7 +1421,8 @@ def _run_on_slots(eng, n, wide, capacity, slot_engine, max_new_tokens, eot_token
 
 @torch.no_grad()
 def mmu_generate_batch(self, idx=None, input_embeddings=None, attention_mask=None, max_new_tokens=100, temperature=1.0, top_k=None,
-                       eot_token=None, generator=None, _exp_noise=None, top_p=None, return_logprobs=False, slots=None):
+                       eot_token=None, generator=None, _exp_noise=None, top_p=None, return_logprobs=False, slots=None,
+                       repetition_penalty=None, repetition_context=None, logit_bias=None, allowed_tokens=None, banned_tokens=None):
     """n independent `mmu_generate` calls served together (BASELINE cfg4: "batch=4 images"; the reference's mmu_generate is batch-1 and
     inference_mmu.py:87-177 walks the images one by one).  `idx` / `input_embeddings` / `attention_mask` are LISTS (one entry per
     sequence, each what a single `mmu_generate` call takes: [1, L_b] ids or [1, L_b, H] embeddings, its own mask or IntervalMask);
@@ -1240,21 +1443,32 @@ def mmu_generate_batch(self, idx=None, input_embeddings=None, attention_mask=Non
     16 slots per instruction instead of one dot2 chain per slot).  Contract of a wide call: results are deterministic run to run; a
     request's tokens and log-probabilities do not depend on S, on n, on the slot it lands in or on what the other slots hold (an MFMA
     output column reads only its own sequence, the K order is fixed); they are NOT promised to equal the batch-1 bits -- same bf16
-    rounding points, another fp32 summation order, so a near-tie may resolve differently.  With n <= 8 the call is the one without `slots`."""
+    rounding points, another fp32 summation order, so a near-tie may resolve differently.  With n <= 8 the call is the one without `slots`.
+
+    `repetition_penalty` / `repetition_context` / `logit_bias` / `allowed_tokens` / `banned_tokens` (`mmu_generate` states them): each is
+    one value shared by all n requests or a list of n per-request values (an id keyword is per request when its entries are None or id
+    collections themselves); one dense bias row is built per distinct request.  Any adjusted request puts the whole batch on the slots
+    of showo_engine_batch_decode_sample_adj (one adjust launch per step for all slots; an unadjusted request's slot gets a bit copy of
+    its logits, so its tokens are those of a batch without); every slot keeps its own set, cleared and re-seeded when it is refilled.
+    All None, or penalty 1 without a bias: exactly the calls of a batch without the keywords."""
     seqs = idx if idx is not None else input_embeddings
     n = len(seqs)
     wide = _mmu_wide_slots(slots, n, getattr(self, "_precision", 0))
     temps, top_ks, top_ps, noises, masks = _per_request(n, temperature, top_k, top_p, _exp_noise, attention_mask)
+    adjusts, adj_kws = None, [{}] * n
+    if any(v is not None for v in (repetition_penalty, repetition_context, logit_bias, allowed_tokens, banned_tokens)):
+        adjusts, adj_kws = _adjust_per_request(n, self.vocab_size, repetition_penalty, repetition_context, logit_bias, allowed_tokens,
+                                               banned_tokens)
 
     def single(b):
         return self.mmu_generate(idx=None if idx is None else idx[b], input_embeddings=None if input_embeddings is None else input_embeddings[b],
                                  attention_mask=masks[b], max_new_tokens=max_new_tokens, temperature=temps[b], top_k=top_ks[b],
                                  eot_token=eot_token, generator=generator, _exp_noise=noises[b], top_p=top_ps[b],
-                                 **({"return_logprobs": True} if return_logprobs else {}))
+                                 **({"return_logprobs": True} if return_logprobs else {}), **adj_kws[b])
 
     if int(getattr(self, "_precision", 0)) == 1 or n < 2:
         return _singles(single, n, return_logprobs)
-    if n <= _MMU_BATCH_MAX and all(k == 1 for k in top_ks) and not return_logprobs:
+    if n <= _MMU_BATCH_MAX and all(k == 1 for k in top_ks) and not return_logprobs and adjusts is None:
         return self._mmu_generate_batch_greedy(idx, input_embeddings, masks, max_new_tokens, eot_token, single)
     for b in range(n):
         if seqs[b].shape[0] != 1:
@@ -1266,7 +1480,8 @@ def mmu_generate_batch(self, idx=None, input_embeddings=None, attention_mask=Non
 
     def slot_engine(slots):  # (the seeds are drawn behind a begin that succeeded: the sequential calls draw their own)
         return _MmuSlotEngine(self, eng, idx, input_embeddings, masks, lens, slots, temps, top_ks, _mmu_batch_seeds(top_ks, generator),
-                              _batch_noises(top_ks, noises, dev), eot_token, dev, top_ps, want_lp=return_logprobs)
+                              _batch_noises(top_ks, noises, dev), eot_token, dev, top_ps, want_lp=return_logprobs,
+                              **({} if adjusts is None else {"adjusts": adjusts}))
 
     out = _run_on_slots(eng, n, wide, max(lens) + max_new_tokens + 1, slot_engine, max_new_tokens, eot_token, return_logprobs)
     if out is None:
@@ -1334,8 +1549,8 @@ class _SessionSlotEngine(_MmuSlotEngine):
     rows are appended to the session's own cache, copied into the slot's suffix cache, and the session's cache is rewound"""
 
     def __init__(self, model, eng, rows, lens, slots, temps, top_ks, seeds, noises, eot_token, dev, top_ps=None, want_lp=False,
-                 share_prefix=False):
-        super().__init__(model, eng, None, None, None, lens, slots, temps, top_ks, seeds, noises, eot_token, dev, top_ps, want_lp)
+                 share_prefix=False, adjusts=None):
+        super().__init__(model, eng, None, None, None, lens, slots, temps, top_ks, seeds, noises, eot_token, dev, top_ps, want_lp, adjusts)
         self.rows = rows
         self.share_prefix = share_prefix
 
@@ -1408,11 +1623,11 @@ class _SessionEngine:
         past an <eot>)"""
         self.rewind(length + len(toks) - 1)
 
-    def run(self, max_new_tokens, greedy, k, temperature, noise, seed, eot_token, top_p=None, return_logprobs=False):
+    def run(self, max_new_tokens, greedy, k, temperature, noise, seed, eot_token, top_p=None, return_logprobs=False, adjust=None):
         """Showo.mmu_generate behind its prefill: the first token from the current logits, the rest from the device loop in chunks;
-        return_logprobs: (tokens, their log-probabilities fp32 [len(tokens)])"""
+        return_logprobs: (tokens, their log-probabilities fp32 [len(tokens)]); adjust: the call's _Adjust"""
         return _decode_batch1(self.model, self.eng, self.logits, self.tok, max_new_tokens, (greedy, k, top_p, temperature, noise, seed),
-                              eot_token, return_logprobs)
+                              eot_token, return_logprobs, adjust)
 
     def score(self, ids, Ln, use_prefix_logits):
         """log-probabilities / ranks [Ln] of the rows ids [1, Ln] appended to the cache (showo_engine_prefill_append_score): row j from
@@ -1426,7 +1641,7 @@ class _SessionEngine:
         return lp, rk
 
     def run_batch(self, length, rows, lens, max_new_tokens, temps, top_ks, seeds, noises, eot_token, top_ps=None, return_logprobs=False,
-                  slots=None, share_prefix=False):
+                  slots=None, share_prefix=False, adjusts=None):
         """n continuations of the cache [0, length) on the slots of a decode batch; None when the batch does not fit the engine;
         return_logprobs: (token lists, log-probability tensors); slots: the slot count of a wide batch (_mmu_wide_slots);
         share_prefix (with slots): the slots are suffix caches that read [0, length) in the session's cache"""
@@ -1434,7 +1649,7 @@ class _SessionEngine:
 
         def slot_engine(slots):
             return _SessionSlotEngine(self.model, self.eng, rows, lens, slots, temps, top_ks, seeds, noises, eot_token, self.dev, top_ps,
-                                      want_lp=return_logprobs, share_prefix=shared)
+                                      want_lp=return_logprobs, share_prefix=shared, adjusts=adjusts)
 
         capacity = _shared_suffix_capacity(length, lens, max_new_tokens) if shared else length + max(lens) + max_new_tokens + 1
         return _run_on_slots(self.eng, len(rows), slots, capacity, slot_engine, max_new_tokens, eot_token, return_logprobs, shared=shared)
@@ -1483,9 +1698,10 @@ class _SessionRecompute:
         if len(toks) > 1:
             self.append(torch.tensor([toks[:-1]], dtype=torch.int64, device=self.dev), None, len(toks) - 1)
 
-    def run(self, max_new_tokens, greedy, k, temperature, noise, seed, eot_token, top_p=None, return_logprobs=False):
+    def run(self, max_new_tokens, greedy, k, temperature, noise, seed, eot_token, top_p=None, return_logprobs=False, adjust=None):
         out = self.model._mmu_generate_recompute(None, self.emb, self.mask, max_new_tokens, temperature, 1 if greedy else k, eot_token,
-                                                 greedy, None if greedy else (k, seed, noise), top_p=top_p, return_logprobs=return_logprobs)
+                                                 greedy, None if greedy else (k, seed, noise), top_p=top_p, return_logprobs=return_logprobs,
+                                                 **({} if adjust is None else {"adjust": adjust}))
         if return_logprobs:
             return [int(t) for t in out[0]], out[1]
         return [int(t) for t in out]
@@ -1581,11 +1797,17 @@ class MmuSession:
 
     @torch.no_grad()
     def generate(self, idx=None, input_embeddings=None, max_new_tokens=100, temperature=1.0, top_k=None, eot_token=None, generator=None,
-                 _exp_noise=None, top_p=None, return_logprobs=False):
+                 _exp_noise=None, top_p=None, return_logprobs=False, repetition_penalty=None, repetition_context=None, logit_bias=None,
+                 allowed_tokens=None, banned_tokens=None):
         """Append the rows (ids [1, Ln] or embeddings [1, Ln, H]; none: continue where the last call stopped), then decode like
         `mmu_generate`: same return type, `eot_token` cut, greedy pick for top_k == 1 and sampled draws (`top_p`: nucleus).  Afterwards the cache holds the
         prefix, the rows and the answer up to its last token but one; the last token is pending and is fed first by the next call.
-        `return_logprobs=True`: `(tokens, logprobs)` as `mmu_generate` returns them."""
+        `return_logprobs=True`: `(tokens, logprobs)` as `mmu_generate` returns them.
+        `repetition_penalty` / `repetition_context` / `logit_bias` / `allowed_tokens` / `banned_tokens`: as `mmu_generate` takes them.  The
+        set of seen tokens belongs to THIS call (the context ids, then the tokens it produces): it does not live in the session, `mark`
+        / `rewind` and the cache do not know it, and an identical call from the same state gives identical tokens."""
+        adj_vals = (repetition_penalty, repetition_context, logit_bias, allowed_tokens, banned_tokens)
+        adjust = _adjust_of(self.model.vocab_size, *adj_vals) if any(v is not None for v in adj_vals) else None
         self._check()
         ids, emb, Ln = self._rows(idx, input_embeddings)
         if Ln == 0 and self.length != self.prefix_length:
@@ -1594,6 +1816,8 @@ class MmuSession:
         nucleus = {} if p is None else {"top_p": p}  # an engine stand-in without the keyword still serves every call without top_p
         if return_logprobs:
             nucleus["return_logprobs"] = True
+        if adjust is not None:
+            nucleus["adjust"] = adjust
         lps = None
         start = self.length
         try:
@@ -1647,7 +1871,8 @@ class MmuSession:
 
     @torch.no_grad()
     def generate_batch(self, idx=None, input_embeddings=None, max_new_tokens=100, temperature=1.0, top_k=None, eot_token=None,
-                       generator=None, _exp_noise=None, top_p=None, return_logprobs=False, slots=None, share_prefix=False):
+                       generator=None, _exp_noise=None, top_p=None, return_logprobs=False, slots=None, share_prefix=False,
+                       repetition_penalty=None, repetition_context=None, logit_bias=None, allowed_tokens=None, banned_tokens=None):
         """n continuations of the CURRENT state: `idx` / `input_embeddings` is a list of n row blocks ([1, Ln_i] ids or [1, Ln_i, H]
         embeddings), `temperature` / `top_k` / `top_p` scalars or lists, `_exp_noise` None or a list.  result[i] is what `generate(<block i>)`
         followed by a rewind returns when those calls are made in order (same seeds from `generator`); the session is left unchanged.
@@ -1662,10 +1887,16 @@ class MmuSession:
         and log-probabilities do not depend on S, n, its slot, the request order or its neighbours; the first token of every request
         comes from logits bit-equal to `generate`'s; later tokens are bf16-class and NOT the bits of the forked wide path (P is
         rounded relative to its key segment's max, not the row's, and the fp32 sums are split); the session, including its cache
-        bits, is unchanged afterwards.  n <= 8 is the call without `slots` / `share_prefix`."""
-        self._check()
+        bits, is unchanged afterwards.  n <= 8 is the call without `slots` / `share_prefix`.
+        `repetition_penalty` / `repetition_context` / `logit_bias` / `allowed_tokens` / `banned_tokens`: shared values or per-request lists
+        as `Showo.mmu_generate_batch` takes them; every request has its own set of seen tokens, none of it stays in the session."""
         seqs = idx if idx is not None else input_embeddings
         n = len(seqs)
+        adjusts, adj_kws = None, [{}] * n
+        if any(v is not None for v in (repetition_penalty, repetition_context, logit_bias, allowed_tokens, banned_tokens)):
+            adjusts, adj_kws = _adjust_per_request(n, self.model.vocab_size, repetition_penalty, repetition_context, logit_bias,
+                                                   allowed_tokens, banned_tokens)
+        self._check()
         if share_prefix and slots is None:
             raise ValueError("share_prefix needs slots=S (the slots of a wide decode batch share the prefix)")
         if share_prefix and int(getattr(self.model, "_precision", 0)) != 0:
@@ -1679,7 +1910,7 @@ class MmuSession:
                 return self.generate(idx=None if idx is None else idx[b], input_embeddings=None if input_embeddings is None else input_embeddings[b],
                                      max_new_tokens=max_new_tokens, temperature=temps[b], top_k=top_ks[b], eot_token=eot_token,
                                      generator=generator, _exp_noise=noises[b], top_p=top_ps[b],
-                                     **({"return_logprobs": True} if return_logprobs else {}))
+                                     **({"return_logprobs": True} if return_logprobs else {}), **adj_kws[b])
             finally:
                 self.rewind(mark)
 
@@ -1706,6 +1937,8 @@ class MmuSession:
             nucleus["slots"] = wide
             if share_prefix:
                 nucleus["share_prefix"] = True
+        if adjusts is not None:
+            nucleus["adjusts"] = adjusts
         out = self._be.run_batch(self.length, rows, lens, max_new_tokens, temps, top_ks, seeds, noises, eot_token, **nucleus)
         if out is None:  # the batch's common capacity does not fit the engine: the sequential calls, drawing the same seeds again
             if gen_state is not None:
@@ -1767,10 +2000,11 @@ def _grow_mask(mask, L, Ln):
 
 
 def _mmu_generate_recompute(self, idx, input_embeddings, attention_mask, max_new_tokens, temperature, top_k, eot_token, greedy, sampling,
-                            top_p=None, return_logprobs=False):
+                            top_p=None, return_logprobs=False, adjust=None):
     """Accuracy mode (`set_precision(1)`): the reference's OWN algorithm (models/modeling_showo.py:190-240) -- no KV cache, the whole
     sequence is run again for every token on the grown mask (new column hidden from the old rows, new row = last row + itself,
-    :203-217) -- on the fp32-class engine path.  O(tokens x forward): a parity mode, not a serving mode."""
+    :203-217) -- on the fp32-class engine path.  O(tokens x forward): a parity mode, not a serving mode.
+    `adjust` (an _Adjust): every step's pick reads the row the stand-alone showo_logits_adjust writes, and the picked token is marked."""
     eng = self.engine()
     dev = idx.device if idx is not None else input_embeddings.device
     if (input_embeddings if input_embeddings is not None else idx).shape[0] != 1:
@@ -1785,15 +2019,22 @@ def _mmu_generate_recompute(self, idx, input_embeddings, attention_mask, max_new
     logits = torch.empty((self.vocab_size,), dtype=torch.float32, device=dev)
     tok = torch.empty((1,), dtype=torch.int64, device=dev)
     result, lps = [], []
+    st = None
+    if adjust is not None:
+        st = _AdjustState(self.vocab_size, 1, dev)
+        st.seed(0, adjust)
     for step in range(max_new_tokens):
         row.fill_(L - 1)
         _lib.call("showo_engine_forward_rows", eng, None, _lib.ptr(emb), _lib.ptr(mask), 1, L, _lib.ptr(row), 1, 0, self.vocab_size,
                   _lib.ptr(logits), _lib.stream())
+        pick = logits if st is None else st.adjust(0, logits)
         if greedy:
-            _lib.call("showo_argmax_f32", _lib.ptr(logits), self.vocab_size, _lib.ptr(tok), _lib.stream())
+            _lib.call("showo_argmax_f32", _lib.ptr(pick), self.vocab_size, _lib.ptr(tok), _lib.stream())
         else:
             k, seed, noise = sampling
-            _sample_call(logits, self.vocab_size, k, top_p, temperature, noise, seed, step, tok)
+            _sample_call(pick, self.vocab_size, k, top_p, temperature, noise, seed, step, tok)
+        if st is not None:
+            st.mark(0, tok)
         if return_logprobs:
             lps.append(_logprob_of(logits, self.vocab_size, tok))
         t = int(tok.item())

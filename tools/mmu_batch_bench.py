@@ -16,6 +16,10 @@ against the sequential calls' (same generator seed).
                                                # `slots`, alternating in this process, n = 16 / 32 / 64, greedy and top_k=5: medians over
                                                # --reps calls, and the time of one decode step; writes profiles/wide_decode_bench.json
   python tools/mmu_batch_bench.py --profile-wide 32   # one wide greedy n = S call of 17 tokens, for a kernel trace of the wide step
+  python tools/mmu_batch_bench.py --repetition-penalty 1.2   # cost of the logit adjustment (csrc/logit_adjust.hip): every leg with and
+                                               # without repetition_penalty, alternating in this process, at batch 1 and n = 4 / 16,
+                                               # greedy and top_k=5, and (with --slots 32) on 32 wide slots at n = 32: medians over
+                                               # --reps calls; writes profiles/logit_adjust_bench.json
 
 The slot count for n > 8 is set through modeling_showo._MMU_BATCH_SLOTS for this run only."""
 import argparse
@@ -146,6 +150,52 @@ def logprob_legs(model, embs, masks, reps):
     return res
 
 
+def penalty_legs(model, embs, masks, theta, reps, wide_slots=None):
+    """tokens/s of every leg without and with repetition_penalty=theta, measured alternately (off, on, off, on, ...) so that both see the
+    same clocks; per leg the median and the min / max of `reps` whole calls after one warm-up call each.  eot_token is None, so both
+    legs emit the same number of tokens (the tokens themselves differ: that is the feature).  per_token_us: the difference of the
+    median call times over the tokens of the call.  What "on" adds per decode step: one adjust launch for all slots; the batch-1 greedy
+    leg (reported on its own as n1_greedy) ALSO trades the fused token seam for arg-max + store + increment launches, the top-k 5 legs
+    keep their token boundary, so n1_topk5 is the launch alone; at n = 4 the greedy "on" leg trades the all-greedy loop for the slot
+    scheduler's as return_logprobs does.  wide_slots: one more pair of legs at n = 32 on that many wide slots."""
+    gen = lambda: torch.Generator(device="cuda").manual_seed(7)  # noqa: E731
+
+    def call(n, kw):
+        if n == 1:
+            return lambda: model.mmu_generate(input_embeddings=embs[0], attention_mask=masks[0], max_new_tokens=NEW, generator=gen(), **kw)
+        return lambda: model.mmu_generate_batch(input_embeddings=embs[:n], attention_mask=masks[:n], max_new_tokens=NEW, generator=gen(), **kw)
+
+    def once(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    res = {"shape": "cfg4: 631-embedding w_clip_vit prompts, 100 new tokens each, full-size seeded weights",
+           "unit": "tokens/s (whole call)", "reps": reps, "repetition_penalty": theta}
+    shapes = [(1, {}), (4, {}), (16, {})] + ([(32, {"slots": wide_slots})] if wide_slots else [])
+    for n, extra in shapes:
+        for name, kw in (("greedy", GREEDY), ("topk5_t0.7", SAMPLED)):
+            kw = dict(kw, **extra)
+            legs = {"off": call(n, kw), "on": call(n, dict(kw, repetition_penalty=theta))}
+            for fn in legs.values():
+                fn()  # warm-up
+            times = {k: [] for k in legs}
+            for _ in range(reps):
+                for k, fn in legs.items():
+                    times[k].append(once(fn))
+            row = {}
+            for k, ts in times.items():
+                rate = sorted(n * NEW / t for t in ts)
+                row[k] = {"median": float(np.median(rate)), "min": rate[0], "max": rate[-1]}
+            row["adjust_overhead_percent"] = 100.0 * (row["off"]["median"] / row["on"]["median"] - 1.0)
+            row["per_token_us"] = 1e6 * (float(np.median(times["on"])) - float(np.median(times["off"]))) / (n * NEW)
+            res[f"n{n}_{name}" + (f"_slots{wide_slots}" if extra else "")] = row
+            print(f"n={n} {name}: {row}", file=sys.stderr, flush=True)
+    return res
+
+
 def wide_legs(model, embs, masks, slot_counts, reps):
     """tokens/s of mmu_generate_batch without `slots` (the baseline: 8 slots of the dot2 kernels) and with slots=S for every S, measured
     alternately (None, S1, S2, None, ...) so that all legs see the same clocks; per leg the median and min / max of `reps` whole calls
@@ -214,7 +264,18 @@ def main():
     ap.add_argument("--out", default=None, help="also write the JSON of --top-p / --logprobs to this file")
     ap.add_argument("--slots", default=None, help="comma-separated wide slot counts (9..32) to measure against the call without `slots`")
     ap.add_argument("--profile-wide", type=int, default=None, help="one wide greedy call of 17 tokens on this many slots, for a kernel trace")
+    ap.add_argument("--repetition-penalty", type=float, default=None,
+                    help="measure repetition_penalty=THETA against the same legs without it (with --slots S: also n = 32 on S wide slots)")
     a = ap.parse_args()
+    if a.repetition_penalty is not None:
+        wide = int(a.slots.split(",")[0]) if a.slots else None
+        pkg, model, embs, masks = build(32 if wide else 16)
+        res = penalty_legs(model, embs, masks, a.repetition_penalty, a.reps, wide)
+        out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "logit_adjust_bench.json")
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1)
+        print(json.dumps(res))
+        return
     if a.profile_wide is not None:
         S = a.profile_wide
         pkg, model, embs, masks = build(S)
