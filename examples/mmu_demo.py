@@ -69,6 +69,9 @@ def main():
     ap.add_argument("--ban", default=None, help="comma-separated token ids (or, with --tokenizer, words) that must not be produced")
     ap.add_argument("--allow", default=None,
                     help="comma-separated token ids (or words) the answer is confined to, e.g. 'yes,no'; <eos> stays allowed")
+    ap.add_argument("--num-beams", type=int, default=None, help="beam search with this many beams (2..8; greedy settings otherwise)")
+    ap.add_argument("--length-penalty", type=float, default=1.0, help="with --num-beams: a hypothesis scores sum of log-probs / len ** this")
+    ap.add_argument("--early-stopping", action="store_true", help="with --num-beams: stop once as many hypotheses are finished")
     ap.add_argument("--seed", type=int, default=0)
     a = ap.parse_args()
     torch.manual_seed(a.seed)
@@ -118,6 +121,8 @@ def main():
         adjust["banned_tokens"] = token_set(a.ban)
     if a.allow:
         adjust["allowed_tokens"] = token_set(a.allow) + ([int(tok.eos_token_id)] if tok.eos_token_id is not None else [])
+    if a.num_beams is not None:  # (beam search on the device; it takes the greedy settings and no adjustment)
+        adjust.update(num_beams=a.num_beams, length_penalty=a.length_penalty, early_stopping=a.early_stopping)
     with torch.no_grad():
         img_emb = model.mm_projector(tower(pixels[None]))                    # [1, 576, 2048]
         txt = model.showo.model.embed_tokens(ids)

@@ -926,6 +926,57 @@ int showo_engine_batch_decode_sample_adj(showo_engine* e, int64_t* tok, int n_st
                                          const int* draw0, const float* const* exp_noise, const int* budget, int64_t eot, int* produced,
                                          float* logprobs, int32_t* ranks, uint32_t* seen, int64_t seen_ld, const float* penalty,
                                          const float* const* bias, float* adj_ws, int use_graph, void* stream);
+/* Beam search (csrc/beam.hip; DESIGN.md, "Beam search"): Hugging Face beam search for one prompt, do_sample=False, no processors,
+ * B = number of beams = the slots of a regular batch, every slot a showo_engine_batch_fork of the engine's cache.
+ * A candidate (beam b, token i) of a step scores cum[b] + lp(b, i), lp the log-softmax of the RAW logits (showo_logprob_rows' value
+ * and bits).  The 2B best over all B x V are taken in the order (score descending, beam ascending, token ascending) and walked in that
+ * order: an <eot> candidate of rank < B becomes a finished hypothesis with final = score / len ** length_penalty (len = generated
+ * tokens, the <eot> included), one of rank >= B is dropped; every other candidate becomes the next live beam until B are filled.  The B
+ * best hypotheses are kept (a new one beats the worst only strictly).  Done: B are finished and (early_stopping, or worst final >=
+ * best live score / len ** length_penalty).  At max_new tokens without done the B live beams join the table (len = max_new).
+ *
+ * showo_beam_select (the selection alone; test hook): logits fp32 rows logits + b * ld (any 4-byte alignment), b < nb, cum fp32 [nb]
+ *   -> norm fp32 [nb, 2] = (row max mx, logS = logf(S 2^-40), S the integer sum of showo_logprob_rows) and cand [2B] records
+ *   { float score; int32 beam; int32 token; } in the order above, score = cum[b] + ((x - mx) - logS) in exactly this fp32 order: given
+ *   norm, the scores and the selection are a pure function of the input bits at every row alignment.  1 <= nb, B <= 8, 2B <= V < 2^24.
+ *   A -inf logit scores -inf.  A row with NaN or +inf (or of -inf alone) gets logS = NaN and the candidates (NaN, token -1), which
+ *   rank behind every other row's.  ws: fp32 [nb, 2B, 2] (the per-row survivors).  Two launches: one 1024-thread block per row (the
+ *   normaliser, then the picks from per-thread bests: a block reduction per pick), one 128-thread merge block.
+ * showo_kv_permute_rows (the parent copy alone; test hook): k_slots / vt_slots are DEVICE tables of B slot pointers ([layers] of
+ *   [heads][cap][64] K and [heads][64][cap] V^T with the given layer strides, elements).  Beam c takes K rows / V^T columns [r0, r1) of
+ *   beam parent[c], for every c with parent[c] != c (an index outside [0, B) counts as c).  parent int32 [B] and r1 int32 [1] are read
+ *   from DEVICE memory by the launches (r1 is clipped to r0 + span and cap).  A gather launch copies slot parent[c] -> stage[c], a
+ *   scatter launch stage[c] -> slot c, so every map is served.  Whole 16-byte chunks move: of V^T also the columns [8 floor(r0 / 8), r0)
+ *   -- precondition: below r0 all beams hold identical bits -- and [r1, 8 ceil(r1 / 8)), beyond the live length; nothing else is
+ *   written.  stage_k / stage_vt: showo_kv_permute_stage_elems(layers, heads, B, span) 16-bit elements each (returns the count, not
+ *   an error code; 0 for bad arguments), B layers heads 64 (8 ceil(span / 8) + 8).
+ * showo_engine_batch_beam_begin: starts a search of at most max_new tokens on the running batch and takes its first step, on
+ *   logits_row fp32 [V] (the prefill's / append's last row): the 2B best tokens of that row with cumulative score 0; no cache row moves.
+ *   state: int32 [64 + max_new + 1] (device, 8-byte aligned), written here: word 0 generated length t, 1 done, 2 finished hypotheses,
+ *   3 worst final (fp32), 4 max_new, 5 B, 8.. cum fp32 [8], 16.. the last parent map [8], 32.. int64 [8] the tokens the beams feed next,
+ *   64 + len the fp32 divisor (float)pow(len, length_penalty).  Trace (device, [max_new, B], row t - 1 = the live beams after t tokens):
+ *   tr_parent / tr_token int32, tr_cum / tr_lp fp32 (lp of that token).  hyp (device): [B] records { int32 step, beam, kind; float final;
+ *   int32 len; float sumlp; int32 order; float lp (of its last token) } sorted best first; kind 0 ended on <eot>: its tokens are those of live beam `beam` of
+ *   trace row step - 1 (none for step 0) plus <eot>; kind 1 is live beam `beam` of row `step`.  Token sequences are rebuilt from the
+ *   back-pointers.  eot < 0: nothing finishes early.
+ *   Refused before anything changes: a wide or shared batch (1), slots of unequal length (1), what showo_engine_batch_decode_greedy
+ *   refuses, V < 2B (1), a non-finite length_penalty (1), cache length + max_new - 1 beyond the capacity (5).
+ * showo_engine_batch_decode_beam: the next min(n_steps, max_new - t) steps, each batch_step_layers -> select -> seam -> permute pair
+ *   over [cache length at begin, position + 1), one captured step replayed on `stream`.  Once done is set the remaining steps of the
+ *   call idle (zero rows, frozen positions, no table changes), and a call on a finished search runs nothing.  The caller reads done and
+ *   the tables once per call.  logits_ws fp32 [B, V].  The same state / trace / hyp pointers as at begin; precisions 0, 2 and 3. */
+int showo_beam_select(const float* logits, int64_t ld, int nb, int V, const float* cum, int B, float* norm, void* cand, float* ws,
+                      void* stream);
+int64_t showo_kv_permute_stage_elems(int nL, int nH, int B, int span);
+int showo_kv_permute_rows(uint16_t* const* k_slots, uint16_t* const* vt_slots, int cap, int64_t k_lstride, int64_t v_lstride, int nL, int nH,
+                          int B, const int32_t* parent, int r0, const int32_t* r1, uint16_t* stage_k, uint16_t* stage_vt, int span,
+                          void* stream);
+int showo_engine_batch_beam_begin(showo_engine* e, int32_t* state, int max_new, const float* logits_row, int64_t eot, float length_penalty,
+                                  int early_stopping, int32_t* tr_parent, int32_t* tr_token, float* tr_cum, float* tr_lp, void* hyp,
+                                  void* stream);
+int showo_engine_batch_decode_beam(showo_engine* e, int32_t* state, int n_steps, int64_t eot, float length_penalty, int early_stopping,
+                                   float* logits_ws, int32_t* tr_parent, int32_t* tr_token, float* tr_cum, float* tr_lp, void* hyp,
+                                   int use_graph, void* stream);
 /* greedy/top-k=1 pick on device: out int64[1] = argmax(logits) (first maximal index, like torch.topk/multinomial on a one-hot). */
 int showo_argmax_f32(const float* x, int n, int64_t* out, void* stream);
 

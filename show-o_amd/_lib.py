@@ -246,6 +246,11 @@ _PROTOS = {
     "showo_engine_decode_sample_adj": [c_p, c_p, c_i, c_p, c_p, c_i, c_f, c_f, c_p, c_u64, c_i, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_i, c_p],
     "showo_engine_batch_decode_sample_adj": [c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p,
                                              c_p, c_p, c_i, c_p],
+    # beam search (csrc/beam.hip): the selection and the parent copy alone, and the batched loop (state, ..., trace x 4, hyp)
+    "showo_beam_select": [c_p, c_i64, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p],
+    "showo_kv_permute_rows": [c_p, c_p, c_i, c_i64, c_i64, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_i, c_p],
+    "showo_engine_batch_beam_begin": [c_p, c_p, c_i, c_p, c_i64, c_f, c_i, c_p, c_p, c_p, c_p, c_p, c_p],
+    "showo_engine_batch_decode_beam": [c_p, c_p, c_i, c_i64, c_f, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p],
     # wide decode batches (csrc/decode_wide.hip): the two MFMA kernels alone
     "showo_decode_wide_ln_gemm": [c_p, c_p, c_p, c_f, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_p],
     "showo_decode_wide_out_gemm": [c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_p],
@@ -268,7 +273,7 @@ _PROTOS = {
     "showo_prof_set_stride": [c_i],
     "showo_prof_totals": [c_i, c_p, c_p],
 }
-_I64 = {"showo_gemm_tiled_elems": [c_i, c_i], "showo_conv3t_launches": [], "showo_conv3t_split_launches": [], "showo_train_generation": [c_p]}
+_I64 = {"showo_kv_permute_stage_elems": [c_i, c_i, c_i, c_i], "showo_gemm_tiled_elems": [c_i, c_i],"showo_conv3t_launches": [], "showo_conv3t_split_launches": [], "showo_train_generation": [c_p]}
 _VOID = {"showo_engine_destroy": [c_p], "showo_vq_destroy": [c_p], "showo_train_destroy": [c_p], "showo_clip_destroy": [c_p], "showo_projector_destroy": [c_p]}
 EXPORTED_SYMBOLS = sorted(list(_PROTOS) + list(_VOID) + list(_I64) + ["showo_last_error"])
 

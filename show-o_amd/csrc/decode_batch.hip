@@ -24,7 +24,10 @@
 #include "decode_wide.h"
 #include "attn_shared.h"
 #include "logit_adjust.h"
+#include "beam.h"
+#include <cmath>
 #include <cstddef>
+#include <cstring>
 #include <string>
 #include <type_traits>
 
@@ -352,19 +355,7 @@ struct SlotDraw {
 static_assert(sizeof(SlotDraw) % sizeof(int) == 0 && offsetof(SlotDraw, active) % sizeof(int) == 0,
               "the adjust launch reads SlotDraw.active as a strided int array");
 
-// Row of slot b for its next step: the embedding of its token while it decodes; zeros once it is idle (a fixed, finite row, so the
-// idle slot's residual row stays bounded while the other slots keep decoding).
-__device__ __forceinline__ void slot_embed_row(int64_t id, bool active, const float* __restrict__ table, float* __restrict__ xr, int H, int V,
-                                               int tid, int nthr) {
-    if (!active) {
-        for (int i = tid; i < H; i += nthr) xr[i] = 0.f;
-    } else if (id < 0 || id >= V) {
-        for (int i = tid; i < H; i += nthr) xr[i] = __builtin_nanf("");
-    } else {
-        const float* src = table + id * H;
-        for (int i = tid; i < H; i += nthr) xr[i] = src[i];
-    }
-}
+// (slot_embed_row, the row of slot b for its next step: decode_common.h)
 __global__ __launch_bounds__(256) void slot_embed_kernel(const int64_t* __restrict__ tok, const SlotDraw* __restrict__ sd,
                                                          const float* __restrict__ table, float* __restrict__ x, int H, int V) {
     const int b = blockIdx.x;
@@ -559,6 +550,15 @@ struct showo_engine::BatchDecode {
     float* sws = nullptr;    // the prefix partials (showo::shared_attn_ws_elems)
     int64_t sws_elems = 0;
     int abs_cap() const { return shared ? base + cap : cap; }  // first position beyond a slot's cache
+    // beam search (showo_engine_batch_beam_begin / _batch_decode_beam; beam.hip): the selection's buffers, the slots' pointer tables and
+    // the staging buffer of the parent copies, sized for rows [beam_P0, beam_P0 + beam_span)
+    float *beam_norm = nullptr, *beam_ws = nullptr;
+    showo::BeamCand* beam_cand = nullptr;
+    uint16_t **beam_ktab = nullptr, **beam_vtab = nullptr;
+    bf16_t *beam_stage_k = nullptr, *beam_stage_vt = nullptr;
+    int64_t beam_stage_elems = 0;
+    int beam_P0 = 0, beam_span = 0;
+    const int32_t* beam_state = nullptr;  // the state block of the running search (nullptr: none)
 };
 
 namespace showo {
@@ -635,6 +635,7 @@ static int batch_begin(showo_engine* e, int nb, int cap_tokens, bool wide, bool 
         d->precision = e->precision;
     }
     d->nb = nb; d->cap = cap; d->wide = wide;
+    d->beam_state = nullptr;  // (a search does not outlive its batch)
     for (int b = 0; b < MAXB; ++b) { d->prompt_len[b] = 0; d->cache_len[b] = 0; }
     return 0;
 }
@@ -1037,4 +1038,149 @@ extern "C" int showo_engine_batch_decode_sample_adj(showo_engine* e, int64_t* to
     const showo::LogitAdjust adj{seen, seen_ld, penalty, bias, adj_ws};
     return batch_decode_sample(e, tok, n_steps, out_tokens, logits_ws, top_k, top_p, temperature, seed, draw0, exp_noise, budget, eot,
                                produced, use_graph, stream, logprobs, logprobs ? ranks : nullptr, &adj);
+}
+
+// ---- beam search (include/showo_hip.h, "Beam search") -----------------------------------------------------------------------
+namespace {
+// a regular batch whose slots all hold caches of one length (forks of the engine's cache): *P = that length
+int beam_checks(showo_engine* e, const char* what, int* P) {
+    auto* d = e->bd;
+    auto fail = [&](int code, const char* msg) { return set_error_msg(code, (std::string(what) + ": " + msg).c_str()); };
+    if (d->wide || d->shared) return fail(1, "beams run on a regular batch (showo_engine_batch_begin), not on a wide or shared-prefix one");
+    if (e->V < 2 * d->nb) return fail(1, "the vocabulary must hold 2 x beams tokens");
+    TRY(batch_decode_checks(e, what));
+    for (int b = 1; b < d->nb; ++b)
+        if (d->cache_len[b] != d->cache_len[0] || d->prompt_len[b] != d->prompt_len[0])
+            return fail(1, "the slots hold caches of unequal length (fork every slot from one cache)");
+    *P = d->cache_len[0];
+    return 0;
+}
+
+int beam_upload_positions(showo_engine* e, int P, hipStream_t s) {
+    auto* d = e->bd;
+    int P0[NARROW_B];
+    for (int b = 0; b < d->nb; ++b) P0[b] = P;
+    SHOWO_CHECK_HIP(hipMemcpyAsync(d->pos_dev, P0, sizeof(int) * d->nb, hipMemcpyHostToDevice, s));
+    SHOWO_CHECK_HIP(hipMemcpyAsync(d->L0_dev, d->prompt_len, sizeof(int) * d->nb, hipMemcpyHostToDevice, s));
+    SHOWO_CHECK_HIP(hipMemcpyAsync(d->last_iv_dev, d->last_iv, sizeof(int32_t) * 4 * d->nb, hipMemcpyHostToDevice, s));
+    SHOWO_CHECK_HIP(hipStreamSynchronize(s));  // P0 is a host temporary of this call
+    return 0;
+}
+
+showo::BeamSeamArgs beam_seam_args(showo_engine* e, const float* logits, int32_t* state, int64_t eot, int early, int first, int lim,
+                                   int32_t* tr_parent, int32_t* tr_token, float* tr_cum, float* tr_lp, void* hyp) {
+    auto* d = e->bd;
+    return showo::BeamSeamArgs{logits, e->V, e->V, d->beam_norm, d->beam_cand, d->nb, eot, early, first, state, tr_parent, tr_token, tr_cum,
+                               tr_lp, reinterpret_cast<showo::BeamHyp*>(hyp), d->pos_dev, lim, e->embed, e->x, e->H, d->last_iv_dev,
+                               d->L0_dev, d->iv_dev};
+}
+}  // namespace
+
+extern "C" int showo_engine_batch_beam_begin(showo_engine* e, int32_t* state, int max_new, const float* logits_row, int64_t eot,
+                                             float length_penalty, int early_stopping, int32_t* tr_parent, int32_t* tr_token, float* tr_cum,
+                                             float* tr_lp, void* hyp, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!e || !e->bd || e->bd->nb == 0) return set_error_msg(1, "batch_beam_begin: showo_engine_batch_begin + _batch_fork first");
+    auto* d = e->bd;
+    if (!state || !logits_row || !tr_parent || !tr_token || !tr_cum || !tr_lp || !hyp || max_new < 1 || !std::isfinite(length_penalty) ||
+        ((uintptr_t)state & 7))
+        return set_error_msg(1, "batch_beam_begin: bad arguments");
+    int P = 0;
+    TRY(beam_checks(e, "batch_beam_begin", &P));
+    const int nb = d->nb, V = e->V;
+    const int lim = d->abs_cap() < e->cfg.max_pos ? d->abs_cap() : e->cfg.max_pos;
+    if (P + max_new - 1 > lim) return set_error_msg(5, "batch_beam_begin: cache full");
+    if (!d->beam_norm) {
+        TRY(e->alloc(&d->beam_norm, 2 * showo::BEAM_MAX));
+        TRY(e->alloc(&d->beam_ws, 4 * showo::BEAM_MAX * showo::BEAM_MAX));
+        TRY(e->alloc(&d->beam_cand, 2 * showo::BEAM_MAX));
+        TRY(e->alloc(&d->beam_ktab, showo::BEAM_MAX));
+        TRY(e->alloc(&d->beam_vtab, showo::BEAM_MAX));
+    }
+    const int64_t need = (int64_t)nb * e->nL * e->nH * 64 * showo::kv_permute_pitch(max_new);
+    if (need > d->beam_stage_elems) {
+        SHOWO_CHECK_HIP(hipDeviceSynchronize());
+        e->release(&d->beam_stage_k);
+        e->release(&d->beam_stage_vt);
+        d->beam_stage_elems = 0;
+        TRY(e->alloc(&d->beam_stage_k, need));
+        TRY(e->alloc(&d->beam_stage_vt, need));
+        d->beam_stage_elems = need;
+    }
+    d->beam_state = nullptr;
+    std::vector<int32_t> hd(showo::BEAM_STATE_HEAD + max_new + 1, 0);
+    auto bits = [](float f) { int32_t i; memcpy(&i, &f, 4); return i; };
+    hd[showo::BS_WORST] = bits(-INFINITY);
+    hd[showo::BS_MAXNEW] = max_new;
+    hd[showo::BS_B] = nb;
+    for (int b = 0; b < showo::BEAM_MAX; ++b) hd[showo::BS_PARENT + b] = b;
+    for (int len = 1; len <= max_new; ++len) hd[showo::BEAM_STATE_HEAD + len] = bits((float)std::pow((double)len, (double)length_penalty));
+    const int64_t per_seq = (int64_t)e->nH * d->cap * 64;
+    uint16_t *kt[showo::BEAM_MAX], *vt[showo::BEAM_MAX];
+    for (int b = 0; b < showo::BEAM_MAX; ++b) {
+        kt[b] = reinterpret_cast<uint16_t*>(d->k + (b < nb ? b : 0) * per_seq);
+        vt[b] = reinterpret_cast<uint16_t*>(d->vt + (b < nb ? b : 0) * per_seq);
+    }
+    SHOWO_CHECK_HIP(hipMemcpyAsync(state, hd.data(), hd.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    SHOWO_CHECK_HIP(hipMemcpyAsync(d->beam_ktab, kt, sizeof(kt), hipMemcpyHostToDevice, s));
+    SHOWO_CHECK_HIP(hipMemcpyAsync(d->beam_vtab, vt, sizeof(vt), hipMemcpyHostToDevice, s));
+    TRY(beam_upload_positions(e, P, s));  // (synchronises: hd, kt and vt are host temporaries)
+    // the first step: the 2B best tokens of the prefill's one row, cumulative score 0
+    TRY(showo::beam_select_launch(logits_row, V, 1, V, reinterpret_cast<const float*>(state + showo::BS_CUM), nb, d->beam_norm, d->beam_cand,
+                                  d->beam_ws, s));
+    TRY(showo::beam_seam_launch(beam_seam_args(e, logits_row, state, eot, early_stopping != 0, 1, lim, tr_parent, tr_token, tr_cum, tr_lp, hyp),
+                                s));
+    d->beam_state = state;
+    d->beam_P0 = P;
+    d->beam_span = max_new;
+    return 0;
+}
+
+extern "C" int showo_engine_batch_decode_beam(showo_engine* e, int32_t* state, int n_steps, int64_t eot, float length_penalty,
+                                              int early_stopping, float* logits_ws, int32_t* tr_parent, int32_t* tr_token, float* tr_cum,
+                                              float* tr_lp, void* hyp, int use_graph, void* stream) {
+    hipStream_t s = (hipStream_t)stream;
+    if (!e || !e->bd || e->bd->nb == 0) return set_error_msg(1, "batch_decode_beam: showo_engine_batch_begin + _batch_fork first");
+    auto* d = e->bd;
+    if (!state || !logits_ws || !tr_parent || !tr_token || !tr_cum || !tr_lp || !hyp || n_steps < 1 || !std::isfinite(length_penalty))
+        return set_error_msg(1, "batch_decode_beam: bad arguments");
+    if (d->beam_state != state) return set_error_msg(1, "batch_decode_beam: showo_engine_batch_beam_begin on this state block first");
+    int P = 0;
+    TRY(beam_checks(e, "batch_decode_beam", &P));
+    const int nb = d->nb, H = e->H, V = e->V;
+    int32_t hd[showo::BEAM_STATE_HEAD];
+    SHOWO_CHECK_HIP(hipMemcpyAsync(hd, state, sizeof(hd), hipMemcpyDeviceToHost, s));
+    SHOWO_CHECK_HIP(hipStreamSynchronize(s));
+    const int t0 = hd[showo::BS_T], max_new = hd[showo::BS_MAXNEW];
+    if (hd[showo::BS_B] != nb || max_new != d->beam_span || t0 < 1 || t0 > max_new || P != d->beam_P0 + t0 - 1)
+        return set_error_msg(1, "batch_decode_beam: the state block does not belong to the batch as it stands");
+    if (hd[showo::BS_DONE] || t0 >= max_new) return 0;  // the search is over: nothing to run
+    const int n = n_steps < max_new - t0 ? n_steps : max_new - t0;
+    const int lim = d->abs_cap() < e->cfg.max_pos ? d->abs_cap() : e->cfg.max_pos;
+    if (P + n > lim) return set_error_msg(5, "batch_decode_beam: cache full");
+    const int lk_max = P + n + 1 < lim ? P + n + 1 : lim;
+    const int op = e->precision == 2 ? SHOWO_OP_F16 : SHOWO_OP_BF16;
+    TRY(beam_upload_positions(e, P, s));
+    TRY(showo_embed_f32(reinterpret_cast<const int64_t*>(state + showo::BS_TOK), e->embed, e->x, nb, H, V, s));
+    batch_iv_kernel<<<1, 64, 0, s>>>(d->last_iv_dev, d->L0_dev, d->pos_dev, d->iv_dev, nb);
+    SHOWO_CHECK_HIP(hipGetLastError());
+    bool co = false;
+    TRY(batch_use_co(e, &co));
+    const int64_t lstride = (int64_t)nb * e->nH * d->cap * 64;
+    const showo::BeamSeamArgs sa = beam_seam_args(e, logits_ws, state, eot, early_stopping != 0, 0, lim, tr_parent, tr_token, tr_cum, tr_lp, hyp);
+    auto one = [&]() -> int {
+        TRY(batch_step_layers(e, op, co, lk_max, logits_ws, s));
+        TRY(showo::beam_select_launch(logits_ws, V, nb, V, reinterpret_cast<const float*>(state + showo::BS_CUM), nb, d->beam_norm,
+                                      d->beam_cand, d->beam_ws, s));
+        TRY(showo::beam_seam_launch(sa, s));
+        // every new beam inherits rows [P0, position) of its parent (the seam has advanced the positions; idle: the identity map)
+        return showo_kv_permute_rows(d->beam_ktab, d->beam_vtab, d->cap, lstride, lstride, e->nL, e->nH, nb, state + showo::BS_PARENT,
+                                     d->beam_P0, d->pos_dev, reinterpret_cast<uint16_t*>(d->beam_stage_k),
+                                     reinterpret_cast<uint16_t*>(d->beam_stage_vt), d->beam_span, s);
+    };
+    TRY(showo::replay_steps(one, n, use_graph != 0, s));
+    SHOWO_CHECK_HIP(hipMemcpyAsync(hd, state, sizeof(hd), hipMemcpyDeviceToHost, s));
+    SHOWO_CHECK_HIP(hipStreamSynchronize(s));
+    for (int b = 0; b < nb; ++b) d->cache_len[b] = P + (hd[showo::BS_T] - t0);
+    return 0;
 }

@@ -29,6 +29,20 @@ static __device__ __forceinline__ void next_iv(const int32_t* last_iv, int L0, i
     iv[0] = a; iv[1] = b; iv[2] = c; iv[3] = d;
 }
 
+// Row of slot b for its next step (the batched sampled seam and the beam seam): the embedding of its token while it decodes; zeros
+// once it is idle (a fixed, finite row, so the idle slot's residual row stays bounded while the other slots keep decoding).
+static __device__ __forceinline__ void slot_embed_row(int64_t id, bool active, const float* __restrict__ table, float* __restrict__ xr, int H,
+                                                      int V, int tid, int nthr) {
+    if (!active) {
+        for (int i = tid; i < H; i += nthr) xr[i] = 0.f;
+    } else if (id < 0 || id >= V) {
+        for (int i = tid; i < H; i += nthr) xr[i] = __builtin_nanf("");
+    } else {
+        const float* src = table + id * H;
+        for (int i = tid; i < H; i += nthr) xr[i] = src[i];
+    }
+}
+
 static __device__ __forceinline__ void load4(const bf16_t* row, int k0, int K, uint4 (&wv)[4]) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) {

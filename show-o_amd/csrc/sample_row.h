@@ -348,18 +348,37 @@ __device__ __forceinline__ void row_for_each_1024(const float* __restrict__ row,
     if (tid < V - tail0) f(row[tail0 + tid]);
 }
 
-__device__ __forceinline__ RowLogprob logprob_row(const float* __restrict__ row, int V, int64_t target, RowLogprobSmem& sm) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    RowLogprob r{0.f, -1};
-    if (target < 0 || target >= V) {  // block-uniform
-        r.lp = target < 0 ? 0.f : __builtin_nanf("");
-        r.rank = -1;
-        return r;
+// The same walk with the element's index: f(v, i) for every i in [0, V)
+template <class F>
+__device__ __forceinline__ void row_for_each_idx_1024(const float* __restrict__ row, int V, F&& f) {
+    const int tid = threadIdx.x;
+    int head = (int)(((16u - (unsigned)((uintptr_t)row & 15u)) & 15u) >> 2);
+    if (head > V) head = V;
+    const int n4 = (V - head) >> 2, tail0 = head + 4 * n4;
+    if (tid < head) f(row[tid], tid);
+    const float4* __restrict__ q = reinterpret_cast<const float4*>(row + head);
+    for (int i = tid; i < n4; i += 1024) {
+        const float4 v = q[i];
+        const int at = head + 4 * i;
+        f(v.x, at); f(v.y, at + 1); f(v.z, at + 2); f(v.w, at + 3);
     }
-    const float xt = row[target];
+    if (tid < V - tail0) f(row[tail0 + tid], tail0 + tid);
+}
+
+// The normaliser of a row's log-softmax, shared by logprob_row and the beam selection (beam.hip): mx = max(x) and the integer sum
+// S = sum_i (uint64)(expf(x_i - mx) * 2^40) (0 for a row whose max is not finite); count = sum_i count_of(x_i), an int the first pass
+// adds up on the way (logprob_row: the rank).  mx and count are valid in every thread, S in thread 0.
+struct RowNorm {
+    float mx;
+    int count;
+    unsigned long long S;
+};
+template <class C>
+__device__ __forceinline__ RowNorm row_norm_1024(const float* __restrict__ row, int V, RowLogprobSmem& sm, C&& count_of) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     float mx = -INFINITY;
     int above = 0;
-    row_for_each_1024(row, V, [&](float v) { mx = fmaxf(mx, v); above += v > xt; });
+    row_for_each_1024(row, V, [&](float v) { mx = fmaxf(mx, v); above += count_of(v); });
     mx = wave_max(mx);
     for (int o = 32; o > 0; o >>= 1) above += __shfl_xor(above, o, 64);
     if (lane == 0) { sm.red_f[wave] = mx; sm.red_i[wave] = above; }
@@ -373,13 +392,28 @@ __device__ __forceinline__ RowLogprob logprob_row(const float* __restrict__ row,
     for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
     if (lane == 0) sm.red_w[wave] = acc;
     __syncthreads();
-    if (tid == 0) {
-        unsigned long long S = 0ull;
-        for (int w = 0; w < 16; ++w) S += sm.red_w[w];
-        r.lp = S ? (xt - mx) - logf((float)((double)S * (1.0 / 1099511627776.0))) : __builtin_nanf("");
-        r.rank = above;
-    }
+    RowNorm n{mx, above, 0ull};
+    if (tid == 0)
+        for (int w = 0; w < 16; ++w) n.S += sm.red_w[w];
     __syncthreads();  // the caller may reuse sm
+    return n;
+}
+// log S of a RowNorm with S != 0, as logprob_row subtracts it
+__device__ __forceinline__ float row_norm_logS(unsigned long long S) { return logf((float)((double)S * (1.0 / 1099511627776.0))); }
+
+__device__ __forceinline__ RowLogprob logprob_row(const float* __restrict__ row, int V, int64_t target, RowLogprobSmem& sm) {
+    RowLogprob r{0.f, -1};
+    if (target < 0 || target >= V) {  // block-uniform
+        r.lp = target < 0 ? 0.f : __builtin_nanf("");
+        r.rank = -1;
+        return r;
+    }
+    const float xt = row[target];
+    const RowNorm n = row_norm_1024(row, V, sm, [&](float v) { return (int)(v > xt); });
+    if (threadIdx.x == 0) {
+        r.lp = n.S ? (xt - n.mx) - row_norm_logS(n.S) : __builtin_nanf("");
+        r.rank = n.count;
+    }
     return r;
 }
 

@@ -832,7 +832,8 @@ class Showo(PretrainedMixin, nn.Module):
     @torch.no_grad()
     def mmu_generate(self, idx=None, input_embeddings=None, attention_mask=None, max_new_tokens=100, temperature=1.0,
                      top_k=None, eot_token=None, generator=None, _exp_noise=None, top_p=None, return_logprobs=False,
-                     repetition_penalty=None, repetition_context=None, logit_bias=None, allowed_tokens=None, banned_tokens=None):
+                     repetition_penalty=None, repetition_context=None, logit_bias=None, allowed_tokens=None, banned_tokens=None,
+                     num_beams=None, length_penalty=1.0, early_stopping=False, num_return_sequences=1, return_beam_scores=False):
         """reference signature + `generator` (seeds the on-device Philox stream of the multinomial draws; default: torch's
         global generator), `_exp_noise` fp32 [max_new_tokens, vocab] (parity tests inject the reference's Exp(1) draws) and `top_p`
         (nucleus sampling on the device behind the top-k filter, the reference's top_k_top_p_filtering: a token stays iff the mass of
@@ -850,9 +851,29 @@ class Showo(PretrainedMixin, nn.Module):
         `logit_bias` ({id: float} or an fp32 [vocab] tensor; -inf bans, +inf / NaN: ValueError) is added to the penalised logits;
         `banned_tokens` puts -inf on the listed ids, `allowed_tokens` puts -inf everywhere else -- if it leaves out `eot_token` the
         call runs to `max_new_tokens`.  A row without a finite token, ids outside the vocabulary, theta <= 0 / NaN / inf: ValueError
-        before the engine is touched.  `return_logprobs` stays the log-softmax of the RAW logits, adjusted or not."""
+        before the engine is touched.  `return_logprobs` stays the log-softmax of the RAW logits, adjusted or not.
+
+        Beam search ("Beam search"; `num_beams` None or 1: exactly the calls above, no bit changes): `num_beams` 2..8 runs
+        Hugging Face's beam search (do_sample=False, no processors) on the device, the beams as the slots of a decode batch forked
+        from the prompt's cache.  A hypothesis that ends on `eot_token` scores sum of log-probabilities / len ** `length_penalty`;
+        `early_stopping` (a bool) stops once `num_beams` hypotheses are finished.  The best hypothesis comes back in the return type
+        above (it includes its `eot_token`); `num_return_sequences` > 1 returns a list of them, best first;
+        `return_logprobs=True` adds the per-token log-probabilities of each, `return_beam_scores=True` their final scores (fp32
+        [num_return_sequences], last).  Beams take top_k None / 1 only, and no `top_p`, `temperature` != 1, `generator`, noise or
+        logit-adjustment keyword; precision 1 has no beams: ValueError before the engine is touched."""
         adj_kw = {k_: v for k_, v in zip(_ADJUST_KEYS, (repetition_penalty, repetition_context, logit_bias, allowed_tokens, banned_tokens))
                   if v is not None}
+        beams = _beam_request(self, num_beams, length_penalty, early_stopping, num_return_sequences, return_beam_scores, max_new_tokens,
+                              temperature, top_k, top_p, generator, _exp_noise, bool(adj_kw))
+        if beams is not None:
+            if (idx if input_embeddings is None else input_embeddings).shape[0] != 1:
+                raise ValueError("mmu_generate has batch-1 semantics (reference modeling_showo.py:204,229)")
+            eng = self.engine()
+            dev = idx.device if input_embeddings is None else input_embeddings.device
+            logits = torch.empty((self.vocab_size,), dtype=torch.float32, device=dev)
+            L = _prefill(eng, *_prompt_args(self, eng, None if input_embeddings is not None else idx, input_embeddings, attention_mask), logits)
+            hyps = _beam_search(self, eng, logits, L, beams, max_new_tokens, eot_token, float(length_penalty), early_stopping, dev)
+            return _beam_result(hyps, num_return_sequences, return_logprobs, return_beam_scores, dev)
         adjust = _adjust_of(self.vocab_size, **adj_kw) if adj_kw else None
         adj_kw = {} if adjust is None else {"adjust": adjust}  # (None: the calls below are those of a call without the keywords)
         # greedy (top_k == 1) is the reference caller's setting (inference_mmu.py:81): multinomial of a one-hot = arg-max
@@ -1191,6 +1212,122 @@ def _decode_batch1(model, eng, logits, tok, max_new_tokens, draw, eot_token, wan
                 return done(result)
         remaining -= n
     return done(result)
+
+
+# ---- beam search ("Beam search") ----------------------------------------------------------------------------------------------
+_BEAM_MAX = 8         # beams: the slots of a regular decode batch
+_BEAM_STATE_HEAD = 64  # words of a state block in front of its length-penalty table (csrc/beam.h)
+_BEAM_CHUNK = 16      # steps per showo_engine_batch_decode_beam call (`model.beam_chunk` overrides it)
+
+
+def _beam_request(model, num_beams, length_penalty, early_stopping, num_return_sequences, return_beam_scores, max_new_tokens, temperature,
+                  top_k, top_p, generator, noise, adjusted):
+    """the beam keywords of mmu_generate / MmuSession.generate, checked before the engine is touched: None for `num_beams` None or 1
+    (the call is the one without the keywords), else the number of beams 2..8.  ValueError: num_beams outside 1..8,
+    num_return_sequences outside 1..num_beams, a non-finite length_penalty, an early_stopping that is not a bool ("never" is not
+    served), return_beam_scores without beams; with beams: top_k other than None / 1, any top_p, temperature != 1, a generator or
+    noise, a logit-adjustment keyword, max_new_tokens < 1, precision 1."""
+    B = 1 if num_beams is None else num_beams
+    if isinstance(B, bool) or not isinstance(B, int) or not 1 <= B <= _BEAM_MAX:
+        raise ValueError(f"num_beams must be an int in 1..{_BEAM_MAX}")
+    n = num_return_sequences
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= B:
+        raise ValueError("num_return_sequences must be an int in 1..num_beams")
+    if isinstance(length_penalty, bool) or not isinstance(length_penalty, (int, float)) or not math.isfinite(length_penalty):
+        raise ValueError("length_penalty must be a finite number")
+    if not isinstance(early_stopping, bool):
+        raise ValueError('early_stopping must be a bool (early_stopping="never" is not served)')
+    if B == 1:
+        if return_beam_scores:
+            raise ValueError("return_beam_scores needs num_beams >= 2")
+        return None
+    if top_k not in (None, 1):
+        raise ValueError("beam search takes top_k None or 1 (beam sampling is not served)")
+    if top_p is not None or temperature != 1 or generator is not None or noise is not None:
+        raise ValueError("beam search takes no top_p, temperature != 1, generator or noise (beam sampling is not served)")
+    if adjusted:
+        raise ValueError("beam search takes no logit-adjustment keyword (logits processors with beams are not served)")
+    if max_new_tokens < 1:
+        raise ValueError("max_new_tokens must be >= 1")
+    if int(getattr(model, "_precision", 0)) == 1:
+        raise ValueError("beam search runs at precision 0, 2 or 3 (the batched decode step)")
+    return B
+
+
+def _beam_hypotheses(n_hyp, tr_parent, tr_token, tr_lp, hyp, eot_token):
+    """the finished hypotheses of a search, best first, rebuilt on the host from the back-pointers: dicts with `tokens` (ints, the
+    <eot> included), `final`, `sumlp`, `len` and `lps` (fp32 numpy, one per token).  tr_* [T, B] and hyp int32 [B, 8] as numpy."""
+    import numpy as np
+    out = []
+    for rec in hyp[:n_hyp]:
+        step, beam, kind, length = int(rec[0]), int(rec[1]), int(rec[2]), int(rec[4])
+        f = rec.view(np.float32)
+        toks, lps = [], []
+        s, b = (step - 1, beam) if kind == 0 else (step, beam)
+        while s >= 0:
+            toks.append(int(tr_token[s, b]))
+            lps.append(tr_lp[s, b])
+            b = int(tr_parent[s, b])
+            s -= 1
+        toks.reverse()
+        lps.reverse()
+        if kind == 0:
+            toks.append(int(eot_token))
+            lps.append(f[7])
+        assert len(toks) == length
+        out.append({"tokens": toks, "final": float(f[3]), "sumlp": float(f[5]), "len": length, "lps": np.array(lps, dtype=np.float32),
+                    "step": step, "beam": beam, "kind": kind})
+    return out
+
+
+def _beam_search(model, eng, logits, length, B, max_new_tokens, eot_token, length_penalty, early_stopping, dev, trace=None):
+    """Beam search behind a prefill or append (`logits`: its last row's; `length`: rows in the engine's decode cache): a batch of B
+    slots, each a fork of that cache, showo_engine_batch_beam_begin for the first step and showo_engine_batch_decode_beam in chunks;
+    the host reads the done flag once per chunk and the tables once at the end.  The engine's own cache is left as it is.  Returns
+    _beam_hypotheses' list (B entries).  `trace`: a dict that receives the raw device tables (tests)."""
+    V, T = model.vocab_size, int(max_new_tokens)
+    if not _batch_begin(eng, B, length + T + 1):
+        raise RuntimeError("beam search: prompt + max_new_tokens does not fit the engine's decode batch (max_position_embeddings, "
+                           "the single-block decode attention)")
+    for b in range(B):
+        _lib.call("showo_engine_batch_fork", eng, b, _lib.stream())
+    state = torch.zeros((_BEAM_STATE_HEAD + T + 1,), dtype=torch.int32, device=dev)
+    tr_parent, tr_token = (torch.zeros((T, B), dtype=torch.int32, device=dev) for _ in range(2))
+    tr_cum, tr_lp = (torch.zeros((T, B), dtype=torch.float32, device=dev) for _ in range(2))
+    hyp = torch.zeros((B, 8), dtype=torch.int32, device=dev)
+    ws = torch.empty((B, V), dtype=torch.float32, device=dev)
+    eot = -1 if eot_token is None else int(eot_token)
+    tail = (_lib.ptr(tr_parent), _lib.ptr(tr_token), _lib.ptr(tr_cum), _lib.ptr(tr_lp), _lib.ptr(hyp))
+    _lib.call("showo_engine_batch_beam_begin", eng, _lib.ptr(state), T, _lib.ptr(logits), eot, length_penalty, int(early_stopping), *tail,
+              _lib.stream())
+    use_graph, chunk = int(getattr(model, "decode_graph", 1)), int(getattr(model, "beam_chunk", _BEAM_CHUNK))
+    while True:
+        t, done = state[:2].tolist()
+        if done or t >= T:
+            break
+        with _graph_stream_of(model):
+            _lib.call("showo_engine_batch_decode_beam", eng, _lib.ptr(state), min(chunk, T - t), eot, length_penalty, int(early_stopping),
+                      _lib.ptr(ws), *tail, use_graph, _lib.stream())
+    head = state[:_BEAM_STATE_HEAD].cpu().numpy()
+    tables = [x.cpu().numpy() for x in (tr_parent, tr_token, tr_cum, tr_lp, hyp)]
+    if trace is not None:
+        trace.update(state=head, parent=tables[0], token=tables[1], cum=tables[2], lp=tables[3], hyp=tables[4])
+    return _beam_hypotheses(int(head[2]), tables[0], tables[1], tables[3], tables[4], eot_token)
+
+
+def _beam_result(hyps, num_return_sequences, return_logprobs, return_beam_scores, dev):
+    """what a beam call returns: the best hypothesis' token list (num_return_sequences > 1: a list of them, best first), then, if
+    asked for, the per-token log-probabilities (fp32 tensors, likewise) and the final scores (fp32 [num_return_sequences])"""
+    hyps = hyps[:num_return_sequences]
+    toks = [[torch.tensor(t, device=dev) for t in h["tokens"]] for h in hyps]
+    lps = [torch.from_numpy(h["lps"]).to(dev) for h in hyps]
+    one = num_return_sequences == 1
+    out = [toks[0] if one else toks]
+    if return_logprobs:
+        out.append(lps[0] if one else lps)
+    if return_beam_scores:
+        out.append(torch.tensor([h["final"] for h in hyps], dtype=torch.float32, device=dev))
+    return out[0] if len(out) == 1 else tuple(out)
 
 
 # Slot scheduler of mmu_generate_batch (n >= 2 sequences at precision 0 / 2 beyond the all-greedy 2..8 case).  Slot count for more
@@ -1629,6 +1766,11 @@ class _SessionEngine:
         return _decode_batch1(self.model, self.eng, self.logits, self.tok, max_new_tokens, (greedy, k, top_p, temperature, noise, seed),
                               eot_token, return_logprobs, adjust)
 
+    def run_beam(self, length, B, max_new_tokens, eot_token, length_penalty, early_stopping):
+        """beam search behind the current logits on B forks of the cache [0, length): _beam_search's hypotheses, best first.  The
+        session's own cache is only read."""
+        return _beam_search(self.model, self.eng, self.logits, length, B, max_new_tokens, eot_token, length_penalty, early_stopping, self.dev)
+
     def score(self, ids, Ln, use_prefix_logits):
         """log-probabilities / ranks [Ln] of the rows ids [1, Ln] appended to the cache (showo_engine_prefill_append_score): row j from
         the logits of row j - 1, row 0 from the prefill's logits (use_prefix_logits) or NaN / -1.  The rows stay in the cache: the
@@ -1798,21 +1940,32 @@ class MmuSession:
     @torch.no_grad()
     def generate(self, idx=None, input_embeddings=None, max_new_tokens=100, temperature=1.0, top_k=None, eot_token=None, generator=None,
                  _exp_noise=None, top_p=None, return_logprobs=False, repetition_penalty=None, repetition_context=None, logit_bias=None,
-                 allowed_tokens=None, banned_tokens=None):
+                 allowed_tokens=None, banned_tokens=None, num_beams=None, length_penalty=1.0, early_stopping=False,
+                 num_return_sequences=1, return_beam_scores=False):
         """Append the rows (ids [1, Ln] or embeddings [1, Ln, H]; none: continue where the last call stopped), then decode like
         `mmu_generate`: same return type, `eot_token` cut, greedy pick for top_k == 1 and sampled draws (`top_p`: nucleus).  Afterwards the cache holds the
         prefix, the rows and the answer up to its last token but one; the last token is pending and is fed first by the next call.
         `return_logprobs=True`: `(tokens, logprobs)` as `mmu_generate` returns them.
         `repetition_penalty` / `repetition_context` / `logit_bias` / `allowed_tokens` / `banned_tokens`: as `mmu_generate` takes them.  The
         set of seen tokens belongs to THIS call (the context ids, then the tokens it produces): it does not live in the session, `mark`
-        / `rewind` and the cache do not know it, and an identical call from the same state gives identical tokens."""
+        / `rewind` and the cache do not know it, and an identical call from the same state gives identical tokens.
+        `num_beams` / `length_penalty` / `early_stopping` / `num_return_sequences` / `return_beam_scores`: as `mmu_generate` takes them
+        (None or 1: the call without them).  The search runs on forks of the cache and leaves the session's rows as they are; afterwards
+        the BEST hypothesis is the answer: its tokens but the last are appended with one showo_engine_prefill_append of ids and its
+        last token is pending, the state shape a greedy `generate` leaves.  These answer rows carry the bits of the append path, not
+        those of the decode steps that scored them (both are the rows of the same tokens; a follow-up turn reads the appended ones)."""
         adj_vals = (repetition_penalty, repetition_context, logit_bias, allowed_tokens, banned_tokens)
+        beams = _beam_request(self.model, num_beams, length_penalty, early_stopping, num_return_sequences, return_beam_scores, max_new_tokens,
+                              temperature, top_k, top_p, generator, _exp_noise, any(v is not None for v in adj_vals))
+        if beams is not None and not hasattr(self._be, "run_beam"):
+            raise ValueError("beam search needs the KV-cached engine (precision 0, 2 or 3)")
         adjust = _adjust_of(self.model.vocab_size, *adj_vals) if any(v is not None for v in adj_vals) else None
         self._check()
         ids, emb, Ln = self._rows(idx, input_embeddings)
         if Ln == 0 and self.length != self.prefix_length:
             raise ValueError("generate: no rows and no pending token to continue from")
-        greedy, k, noise, seed, p = self._draw_args(max_new_tokens, temperature, top_k, generator, _exp_noise, top_p)
+        # (a beam call draws nothing: no seed is taken from the generator)
+        greedy, k, noise, seed, p = self._draw_args(max_new_tokens, temperature, 1 if beams is not None else top_k, generator, _exp_noise, top_p)
         nucleus = {} if p is None else {"top_p": p}  # an engine stand-in without the keyword still serves every call without top_p
         if return_logprobs:
             nucleus["return_logprobs"] = True
@@ -1826,10 +1979,17 @@ class MmuSession:
                 self.length += Ln
             else:
                 self._be.use_prefix_logits()
-            toks = self._be.run(max_new_tokens, greedy, k, temperature, noise, seed, eot_token, **nucleus)
-            if return_logprobs:
-                toks, lps = toks
-            self._be.settle(self.length, toks)
+            if beams is not None:
+                hyps = self._be.run_beam(self.length, beams, max_new_tokens, eot_token, float(length_penalty), early_stopping)
+                toks = hyps[0]["tokens"]
+                if len(toks) > 1:
+                    fed = torch.tensor([toks[:-1]], dtype=torch.int64, device=self._be.dev)
+                    self._be.append(fed, None, len(toks) - 1)
+            else:
+                toks = self._be.run(max_new_tokens, greedy, k, temperature, noise, seed, eot_token, **nucleus)
+                if return_logprobs:
+                    toks, lps = toks
+                self._be.settle(self.length, toks)
         except BaseException:
             # a call that fails midway (a full cache inside the decode loop) leaves the session where it was: the rows it wrote are
             # dropped; if even that fails, _check finds the cache out of step on the next call
@@ -1839,6 +1999,8 @@ class MmuSession:
             raise
         self.length += len(toks) - 1
         self._pending = toks[-1]
+        if beams is not None:
+            return _beam_result(hyps, num_return_sequences, return_logprobs, return_beam_scores, self._be.dev)
         out = [torch.tensor(t, device=self._be.dev) for t in toks]
         return (out, lps) if return_logprobs else out
 

@@ -20,6 +20,10 @@ against the sequential calls' (same generator seed).
                                                # without repetition_penalty, alternating in this process, at batch 1 and n = 4 / 16,
                                                # greedy and top_k=5, and (with --slots 32) on 32 wide slots at n = 32: medians over
                                                # --reps calls; writes profiles/logit_adjust_bench.json
+  python tools/mmu_batch_bench.py --num-beams 4,8   # beam search (csrc/beam.hip) against mmu_generate_batch of as many greedy
+                                               # sequences, alternating in this process: tokens/s of the best hypothesis, ms per step
+                                               # of both legs and their difference; writes profiles/beam_bench.json
+  python tools/mmu_batch_bench.py --profile-beam 4   # one beam call of 17 tokens, twice, for a kernel trace of the beam step
 
 The slot count for n > 8 is set through modeling_showo._MMU_BATCH_SLOTS for this run only."""
 import argparse
@@ -255,9 +259,51 @@ def wide_legs(model, embs, masks, slot_counts, reps):
     return res
 
 
+def beam_legs(model, embs, masks, B, reps):
+    """Beam search with B beams against mmu_generate_batch of n = B greedy sequences (the same weight stream per step without the
+    selection, the seam and the parent copies), measured alternately in this process at two lengths (SHORT and NEW new tokens): per
+    leg the medians of `reps` whole calls, tokens/s of the best hypothesis, and the time of one step as the difference of the two
+    lengths' medians over the difference in steps (prefill, forks and the first pick drop out).  eot_token=None: every call runs to its
+    length."""
+    SHORT = 20
+
+    def once(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    def beam(T):
+        return lambda: model.mmu_generate(input_embeddings=embs[0], attention_mask=masks[0], max_new_tokens=T, num_beams=B)
+
+    def greedy(T):
+        return lambda: model.mmu_generate_batch(input_embeddings=embs[:B], attention_mask=masks[:B], max_new_tokens=T, top_k=1)
+
+    legs = {"beam_short": beam(SHORT), "greedy_short": greedy(SHORT), "beam": beam(NEW), "greedy": greedy(NEW)}
+    for fn in legs.values():
+        fn()  # warm-up
+    times = {k: [] for k in legs}
+    for _ in range(reps):
+        for k, fn in legs.items():
+            times[k].append(once(fn))
+    med = {k: float(np.median(v)) for k, v in times.items()}
+    step = {k: 1e3 * (med[k] - med[k + "_short"]) / (NEW - SHORT) for k in ("beam", "greedy")}
+    res = {"shape": "cfg4: 631-embedding w_clip_vit prompts, full-size seeded weights", "num_beams": B, "new_tokens": NEW, "reps": reps,
+           "call_ms": {k: 1e3 * v for k, v in med.items()},
+           "call_ms_min_max": {k: [1e3 * min(v), 1e3 * max(v)] for k, v in times.items()},
+           "best_hypothesis_tokens_per_s": NEW / med["beam"], "greedy_batch_tokens_per_s": B * NEW / med["greedy"],
+           "step_ms": step, "step_ms_added_by_beams": step["beam"] - step["greedy"]}
+    print(f"num_beams={B}: {res}", file=sys.stderr, flush=True)
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--profile", action="store_true")
+    ap.add_argument("--num-beams", default=None, help="comma-separated beam counts (2..8): beam search against mmu_generate_batch of as many "
+                                                      "greedy sequences, alternating in this process; writes profiles/beam_bench.json")
+    ap.add_argument("--profile-beam", type=int, default=None, help="one beam call of 17 tokens with this many beams, twice, for a kernel trace")
     ap.add_argument("--top-p", type=float, default=None, help="measure nucleus sampling against the same sampled leg without it")
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--logprobs", action="store_true", help="measure return_logprobs=True against the same legs without it")
@@ -267,6 +313,21 @@ def main():
     ap.add_argument("--repetition-penalty", type=float, default=None,
                     help="measure repetition_penalty=THETA against the same legs without it (with --slots S: also n = 32 on S wide slots)")
     a = ap.parse_args()
+    if a.profile_beam is not None:
+        pkg, model, embs, masks = build(1)
+        for _ in range(2):
+            model.mmu_generate(input_embeddings=embs[0], attention_mask=masks[0], max_new_tokens=17, num_beams=a.profile_beam)
+        torch.cuda.synchronize()
+        print(json.dumps({"profiled": f"mmu_generate num_beams={a.profile_beam}, 17 tokens, twice"}))
+        return
+    if a.num_beams is not None:
+        pkg, model, embs, masks = build(8)
+        res = {f"num_beams_{B}": beam_legs(model, embs, masks, B, a.reps) for B in (int(t) for t in a.num_beams.split(","))}
+        out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "beam_bench.json")
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1)
+        print(json.dumps(res))
+        return
     if a.repetition_penalty is not None:
         wide = int(a.slots.split(",")[0]) if a.slots else None
         pkg, model, embs, masks = build(32 if wide else 16)
