@@ -710,6 +710,24 @@ int showo_decode_wide_ln_gemm(const float* x, const float* lnw, const float* lnb
                               int ld1, int nb, void* stream);
 int showo_decode_wide_out_gemm(float* x, const uint16_t* Wd, const uint16_t* attn, const float* bd, int K0, const uint16_t* W2,
                                const uint16_t* ffn, const float* b2, int K1, int N, int nb, void* stream);
+/* The dot2 GEMV kernels of the default decode step alone (test hooks; tests/test_decode_narrow_kernels_gpu.py).  Each call validates
+ * (nonzero return and a message, nothing launched) and then runs the launcher the engine runs.  op: SHOWO_OP_BF16 / SHOWO_OP_F16, the
+ * type of every 16-bit operand and output.  s0 / s1 != NULL: W0 / W1 are int8 row-major with one fp32 scale per row (bf16 activations,
+ * every K a multiple of 16).  Weights, activations, x, lnw and lnb of ln_gemv must be 16-byte aligned.
+ *   ln_gemv:  kernel 0 = ln_gemv2_kernel (nb = 1; ld0 / ld1 not read), 1 = ln_gemvB_kernel (nb = 1..8).  h = LayerNorm(x [nb, H]) as op
+ *             values; out0 [nb, ld0] = op(W0 h + b0) or (outf given instead) outf [nb, ld0] = fp32(W0 h + b0); out1 [nb, ld1] =
+ *             op(gelu_new(W1 h + b1)) (N1 = 0: absent).  H % 8 == 0, H <= 2048.  W0lo != NULL (kernel 1, bf16, outf, N1 = 0): the
+ *             split head, W0 / W0lo the (hi, lo) bf16 halves of the weight rows.
+ *   out_gemv: kernel 0 = out_gemv2_kernel (nb = 1; lda0 / lda1 not read), mode 0: x [N] = (x + (W0 a0 + b0)) + (W1 a1 + b1); mode 1:
+ *             y2 [N] = W1 a1 + b1; mode 2: x = (x + (W0 a0 + b0)) + y2.  kernel 1 = out_gemvB_kernel (mode 0, nb = 1..8; x [nb, N],
+ *             a0 [nb, lda0], a1 [nb, lda1]).  kernel 2 = out_dense_y2B_kernel (mode 2, nb = 2..4; y2 [nb, N]).  K0 % 8 == 0 <= 2048,
+ *             K1 % 8 == 0 <= 8192; the half a mode does not use is not read. */
+int showo_decode_narrow_ln_gemv(int kernel, int nb, int op, const float* x, const float* lnw, const float* lnb, float eps, int H,
+                                const void* W0, const uint16_t* W0lo, const float* s0, const float* b0, uint16_t* out0, float* outf, int N0,
+                                int ld0, const void* W1, const float* s1, const float* b1, uint16_t* out1, int N1, int ld1, void* stream);
+int showo_decode_narrow_out_gemv(int kernel, int nb, int mode, int op, float* x, const void* W0, const uint16_t* a0, const float* s0,
+                                 const float* b0, int K0, int lda0, const void* W1, const uint16_t* a1, const float* s1, const float* b1,
+                                 int K1, int lda1, int N, float* y2, void* stream);
 int showo_engine_batch_prefill(showo_engine* e, int b, const int64_t* ids, const float* embeds, const float* mask, int L,
                                float* logits_last, void* stream);
 int showo_engine_batch_decode_greedy(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws, int use_graph,

@@ -254,6 +254,9 @@ _PROTOS = {
     # wide decode batches (csrc/decode_wide.hip): the two MFMA kernels alone
     "showo_decode_wide_ln_gemm": [c_p, c_p, c_p, c_f, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_p],
     "showo_decode_wide_out_gemm": [c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_p, c_i, c_i, c_i, c_p],
+    "showo_decode_narrow_ln_gemv": [c_i, c_i, c_i, c_p, c_p, c_p, c_f, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i,
+                                    c_i, c_p],
+    "showo_decode_narrow_out_gemv": [c_i, c_i, c_i, c_i, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_p, c_p],
     "showo_vq_create": [c_p, C.POINTER(c_p)],
     "showo_vq_load": [c_p, C.c_char_p, c_p, c_i64, c_p],
     "showo_vq_missing": [c_p],

@@ -46,7 +46,9 @@ constexpr int NARROW_B = 8;  // the dot2 kernels of this file serve 1..8
 // F16: weights and 16-bit activations are IEEE half (precision 2; common.h Op16).  HEAD3 (precision 2's lm_head, fp32 logits only): the
 // normalised row is kept as a (hi, lo) bf16 pair and the weights come as (hi, lo) bf16 rows (W0, W0lo): acc = hi.hi + lo.hi + hi.lo in
 // ONE chain per sequence -- the split-bf16 product of engine.hip head_rows_precise_fast without its 3 H image (2 x 240 MB instead of
-// 719 MB per token step) and without a separate LayerNorm launch.
+// 719 MB per token step) and without a separate LayerNorm launch.  The bits of that 3 H GEMV where H is a multiple of 2048 (Phi-1.5's
+// width: its three segments then start on chunk boundaries and a lane's chain visits them in this order); at any other H the same
+// 3 H products reach the lanes' chains in another grouping (tests/test_decode_batch_gpu.py, the H 576 geometry).
 // Q8 (precision 3): int8 weight rows, converted exactly to bf16 ONCE per weight for all NB sequences, and tot * scale[n] in front of the
 // epilogue (decode_common.h): per sequence the arithmetic of ln_gemv2_kernel's int8 instance.
 template <int NB, bool REG, bool F16 = false, bool HEAD3 = false, bool Q8 = false>
@@ -1183,4 +1185,69 @@ extern "C" int showo_engine_batch_decode_beam(showo_engine* e, int32_t* state, i
     SHOWO_CHECK_HIP(hipStreamSynchronize(s));
     for (int b = 0; b < nb; ++b) d->cache_len[b] = P + (hd[showo::BS_T] - t0);
     return 0;
+}
+
+// ---- test hooks: the dot2 GEMV kernels alone (tests/test_decode_narrow_kernels_gpu.py) ---------------------------------------------
+// Each hook checks everything the engine guarantees its own launches (shapes of decode_fused_shapes_ok, the int8 forms' % 16 rule, the
+// slot range, 16-byte operand alignment) and refuses before any launch; then it calls the launcher the engine calls.
+static bool hook_al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+
+extern "C" int showo_decode_narrow_ln_gemv(int kernel, int nb, int op, const float* x, const float* lnw, const float* lnb, float eps, int H,
+                                           const void* W0, const uint16_t* W0lo, const float* s0, const float* b0, uint16_t* out0,
+                                           float* outf, int N0, int ld0, const void* W1, const float* s1, const float* b1, uint16_t* out1,
+                                           int N1, int ld1, void* stream) {
+    const char* who = "showo_decode_narrow_ln_gemv";
+    auto bad = [&](const char* what) { return set_error_msg(1, (std::string(who) + ": " + what).c_str()); };
+    if (kernel != 0 && kernel != 1) return bad("kernel is 0 (ln_gemv2, one row) or 1 (ln_gemvB)");
+    if (op != SHOWO_OP_BF16 && op != SHOWO_OP_F16) return bad("op must be SHOWO_OP_BF16 or SHOWO_OP_F16");
+    if (kernel == 0 ? nb != 1 : (nb < 1 || nb > NARROW_B)) return bad("nb is 1 for ln_gemv2 and 1..8 for ln_gemvB");
+    if (!x || !lnw || !lnb || !W0 || !b0 || (!out0) == (!outf)) return bad("x, lnw, lnb, W0, b0 and exactly one of out0 / outf required");
+    if (N0 < 1 || N1 < 0 || ld0 < N0 || (N1 > 0 && (!W1 || !b1 || !out1 || ld1 < N1))) return bad("N0 >= 1, ld >= N, and W1 / b1 / out1 with N1 > 0");
+    if (H < 8 || H > 2048 || (H % 8)) return bad("H must be a multiple of 8 in 8..2048");
+    if ((s1 && !s0) || (s0 && (op || W0lo || (N1 > 0 && !s1) || (H % 16))))
+        return bad("int8 weights take bf16 activations, a scale per matrix, no split head and H % 16 == 0");
+    if (W0lo && (kernel != 1 || !outf || N1 > 0 || op)) return bad("the split head is ln_gemvB with bf16 halves, fp32 logits and no second matrix");
+    if (!hook_al16(x) || !hook_al16(lnw) || !hook_al16(lnb) || !hook_al16(W0) || !hook_al16(W0lo) || (N1 > 0 && !hook_al16(W1)))
+        return bad("x, lnw, lnb and the weight matrices must be 16-byte aligned");
+    LnGemvBArgs g{x, lnw, lnb, eps, H, reinterpret_cast<const bf16_t*>(W0), b0, outf ? nullptr : out0, outf, N0, ld0,
+                  N1 > 0 ? reinterpret_cast<const bf16_t*>(W1) : nullptr, N1 > 0 ? b1 : nullptr, N1 > 0 ? out1 : nullptr, N1, ld1};
+    g.W0lo = W0lo;
+    g.s0 = s0;
+    g.s1 = N1 > 0 ? s1 : nullptr;
+    if (kernel == 0) return showo::decode_ln_gemv2(g, (hipStream_t)stream, op);
+    return ln_gemvB(nb, g, (hipStream_t)stream, op, W0lo != nullptr);
+}
+
+extern "C" int showo_decode_narrow_out_gemv(int kernel, int nb, int mode, int op, float* x, const void* W0, const uint16_t* a0, const float* s0,
+                                            const float* b0, int K0, int lda0, const void* W1, const uint16_t* a1, const float* s1,
+                                            const float* b1, int K1, int lda1, int N, float* y2, void* stream) {
+    const char* who = "showo_decode_narrow_out_gemv";
+    auto bad = [&](const char* what) { return set_error_msg(1, (std::string(who) + ": " + what).c_str()); };
+    if (kernel < 0 || kernel > 2) return bad("kernel is 0 (out_gemv2, one row), 1 (out_gemvB) or 2 (out_dense_y2B)");
+    if (op != SHOWO_OP_BF16 && op != SHOWO_OP_F16) return bad("op must be SHOWO_OP_BF16 or SHOWO_OP_F16");
+    if (mode < 0 || mode > 2 || (kernel == 1 && mode != 0) || (kernel == 2 && mode != 2))
+        return bad("mode 0..2 for out_gemv2, 0 for out_gemvB, 2 for out_dense_y2B");
+    if (kernel == 0 ? nb != 1 : kernel == 1 ? (nb < 1 || nb > NARROW_B) : (nb < 2 || nb > 4))
+        return bad("nb is 1 for out_gemv2, 1..8 for out_gemvB and 2..4 for out_dense_y2B");
+    const bool use0 = mode != 1, use1 = mode != 2;  // the dense half / the fc2 half
+    if (N < 1 || (use0 && (!x || !W0 || !a0 || !b0)) || (use1 && (!W1 || !a1 || !b1)) || (mode && !y2))
+        return bad("N >= 1, x / W0 / a0 / b0 (modes 0, 2), W1 / a1 / b1 (modes 0, 1) and y2 (modes 1, 2) required");
+    if (use0 && (K0 < 8 || K0 > 2048 || (K0 % 8) || lda0 < K0 || (lda0 % 8))) return bad("K0 must be a multiple of 8 in 8..2048, lda0 % 8 == 0 >= K0");
+    if (use1 && (K1 < 8 || K1 > 8192 || (K1 % 8) || lda1 < K1 || (lda1 % 8))) return bad("K1 must be a multiple of 8 in 8..8192, lda1 % 8 == 0 >= K1");
+    const bool q8 = (use0 && s0) || (use1 && s1);
+    if (q8 && (op || (use0 && (!s0 || (K0 % 16))) || (use1 && (!s1 || (K1 % 16)))))
+        return bad("int8 weights take bf16 activations, a scale per matrix and K % 16 == 0");
+    if ((use0 && (!hook_al16(W0) || !hook_al16(a0))) || (use1 && (!hook_al16(W1) || !hook_al16(a1))))
+        return bad("weights and activations must be 16-byte aligned");
+    const bf16_t* w0 = use0 ? reinterpret_cast<const bf16_t*>(W0) : nullptr;
+    const bf16_t* w1 = use1 ? reinterpret_cast<const bf16_t*>(W1) : nullptr;
+    const int k0 = use0 ? K0 : 0, k1 = use1 ? K1 : 0;
+    if (kernel == 0) {
+        const OutGemvArgs g{x, w0, use0 ? a0 : nullptr, b0, k0, w1, use1 ? a1 : nullptr, b1, k1, N, y2, use0 ? s0 : nullptr, use1 ? s1 : nullptr};
+        return showo::decode_out_gemv2(g, (hipStream_t)stream, mode, op);
+    }
+    const OutGemvBArgs g{x, w0, use0 ? a0 : nullptr, b0, k0, lda0, w1, use1 ? a1 : nullptr, b1, k1, lda1, N, y2, use0 ? s0 : nullptr,
+                         use1 ? s1 : nullptr};
+    if (kernel == 1) return out_gemvB(nb, g, (hipStream_t)stream, op);
+    return out_dense_y2B(nb, g, (hipStream_t)stream, op);
 }

@@ -100,7 +100,13 @@ BAD = (dict(num_beams=0), dict(num_beams=9), dict(num_beams=-2), dict(num_beams=
        dict(return_beam_scores=True), dict(num_beams=1, return_beam_scores=True))
 
 
-@pytest.mark.parametrize("kw", BAD, ids=lambda kw: ",".join(f"{k}={v if not torch.is_tensor(v) else 'T'}" for k, v in kw.items()))
+def _kw_id(kw):
+    """a test id that is the same in every process: a tensor is 'T', a generator 'G' (its repr holds its address)"""
+    show = lambda v: "T" if torch.is_tensor(v) else "G" if isinstance(v, torch.Generator) else v
+    return ",".join(f"{k}={show(v)}" for k, v in kw.items())
+
+
+@pytest.mark.parametrize("kw", BAD, ids=_kw_id)
 def test_bad_beam_keywords_are_value_errors_before_the_engine_is_touched(kw):
     S = util.pkg().Showo
     ids = torch.tensor([[1, 2, 3]])

@@ -110,3 +110,97 @@ def test_batch_decode_logits_are_the_bits_of_the_batch1_run(precision):
         L.call("showo_engine_batch_decode_greedy", eng, L.ptr(tok), 4096, L.ptr(big), L.ptr(lgs), 0, L.stream())
     with pytest.raises(RuntimeError):
         L.call("showo_engine_batch_begin", eng, 9, 64)
+
+
+# ---- a geometry between the tiny and the full-size one ------------------------------------------------------------------------------
+# hidden 576 (9 heads): a weight row ends inside sub-span u = 1 (lanes 0..7); ffn 4672 = 2 * 2048 + 576: a third chunk that ends there
+# too, so the out kernels run at C = 1 + 3 = 4 chunks.  (showo_engine_create takes hidden and ffn in multiples of 64 only: 4672 is the
+# nearest such ffn that, like 4624, ends inside a sub-span; 4608 would end on a sub-span boundary.)
+MID = dict(util.Wt.TINY, hidden=576, heads=9, ffn=4672)
+
+
+def _mid_model(precision=0):
+    d = util.Wt.ShowoDims(**MID)
+    sd = util.Wt.make_showo_state(d, seed=11)
+    m = util.build_showo(d, sd)
+    m.set_precision(precision)
+    return d, sd, m
+
+
+def _mid_impl_runs(precision, impls):
+    """logits after a prefill and after each of 4 decode steps, per showo_decode_set_impl setting"""
+    g = util.golden("showo_tiny_mmu.npz")
+    d, _, m = _mid_model(precision)
+    L = util.lib()
+    eng = m.engine()
+    ids = dev(g["ids"]).to(torch.int64).contiguous()
+    mask = dev(g["mask"]).float().reshape(1, 1, ids.shape[1], ids.shape[1]).contiguous()
+    runs = []
+    try:
+        for impl in impls:
+            L.call("showo_decode_set_impl", impl)
+            logits = torch.empty((d.vocab,), dtype=torch.float32, device="cuda")
+            L.call("showo_engine_prefill", eng, L.ptr(ids), None, L.ptr(mask), ids.shape[1], L.ptr(logits), L.stream())
+            torch.cuda.synchronize()
+            seq = [(-1, logits.clone())]
+            for _ in range(4):
+                tok = logits.argmax().reshape(1).to(torch.int64)
+                L.call("showo_engine_decode_step", eng, L.ptr(tok), None, L.ptr(logits), L.stream())
+                torch.cuda.synchronize()
+                seq.append((int(tok), logits.clone()))
+            runs.append(seq)
+    finally:
+        L.call("showo_decode_set_impl", 0)
+    return runs
+
+
+def test_mid_geometry_decode_layer_forms_equal_bits():
+    """showo_decode_set_impl 1 (general seven-launch layer), 2 (plain chain) and 0 (default) give the same logits bits over a prefill and 4
+    decode steps at H 576 / F 4672"""
+    for a, b, c in zip(*_mid_impl_runs(0, (1, 2, 0))):
+        assert a[0] == b[0] == c[0]
+        assert torch.isfinite(c[1]).all()
+        assert torch.equal(a[1], b[1]) and torch.equal(a[1], c[1]), (float((a[1] - c[1]).abs().max()), float((a[1] - b[1]).abs().max()))
+
+
+def test_mid_geometry_fp16_decode_layer_forms():
+    """precision 2 at the same geometry: the plain chain and the default layer agree bit for bit.  The general layer (impl 1) is NOT held
+    to their bits here: its lm_head is the GEMV over the [hi | lo | hi] x [Whi | Whi | Wlo] image of 3 H columns, whose lane split
+    (k' -> lane (k' % 512) / 8) puts the segments' products into the lanes' chains in ln_gemvB_kernel<.., HEAD3>'s grouping only where
+    H is a multiple of 2048, Phi-1.5's width (tests/test_modules_gpu.py holds the three forms to equal bits there).  At H = 576 the
+    same 3 H products are summed in another grouping: measured on an MI355X, the logits differ by at most 2.4e-7 (one fp32 ulp at their
+    size); the figure is printed, the split head's values are bounded in tests/test_decode_narrow_kernels_gpu.py."""
+    runs = _mid_impl_runs(2, (1, 2, 0))
+    worst = 0.0
+    for a, b, c in zip(*runs):
+        assert torch.isfinite(a[1]).all() and torch.isfinite(c[1]).all()
+        assert b[0] == c[0] and torch.equal(b[1], c[1]), float((b[1] - c[1]).abs().max())
+        worst = max(worst, float((a[1] - c[1]).abs().max()))
+    print(f"[parity] H 576 / F 4672 precision 2: general layer vs fused layer, worst |logit difference| over prefill + 4 steps {worst:.3e}")
+
+
+@pytest.mark.parametrize("n", [3, 5, 8])
+def test_mid_geometry_mmu_generate_batch_equals_n_single_calls(n):
+    g = util.golden("showo_tiny_mmu.npz")
+    d, _, m = _mid_model()
+    ids = _prompts(d, g, n)
+    masks = [O.mask_mmu(t, d.eoi_id).cuda() for t in ids]
+    ids = [t.cuda() for t in ids]
+    single = [[int(t) for t in m.mmu_generate(ids[b], attention_mask=masks[b], max_new_tokens=12, top_k=1)] for b in range(n)]
+    for graph in (0, 1):
+        m.decode_graph = graph
+        got = m.mmu_generate_batch(idx=ids, attention_mask=masks, max_new_tokens=12, top_k=1)
+        assert [[int(t) for t in r] for r in got] == single, graph
+
+
+def test_mid_geometry_int8_kernels_give_the_bits_of_the_bf16_kernels_on_pow2_scaled_weights():
+    """precision 3 at H 576 / F 4672 with power-of-two scales against the bf16 kernels on q * s: batch-1 (default layer, plain chain,
+    general layer) and 2 / 3 / 4 / 8 slots, eager and graph (tests/test_int8_decode_gpu.py _bit_exact_case)"""
+    from test_int8_decode_gpu import _bit_exact_case
+    g = util.golden("showo_tiny_mmu.npz")
+    d = util.Wt.ShowoDims(**MID)
+    sd = util.Wt.make_showo_state(d, seed=11)
+    ids = dev(g["ids"]).to(torch.int64).contiguous()
+    mask = dev(g["mask"]).float().reshape(1, 1, ids.shape[1], ids.shape[1]).contiguous()
+    batch = [(t.cuda().contiguous(), O.mask_mmu(t, d.eoi_id).cuda().float().contiguous()) for t in _prompts(d, g, 8)]
+    _bit_exact_case(d, sd, ids, mask, 128, (0, 2, 1), batch)

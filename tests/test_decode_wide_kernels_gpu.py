@@ -72,7 +72,8 @@ def _out_gemm(c, x, attn, ffn, K0, K1, N, nb):
 
 
 # (2048, 8192, 48): two column groups only, the second half empty -- the K split over waves and blocks is still exercised
-@pytest.mark.parametrize("shape", [(128, 256, 128), (2048, 8192, 2048), (2048, 8192, 48)])
+# (576, 2080) and (1536, 4640): K ends inside a 512-element span / a 2048-element chunk, within the kernel's K % 32 rule
+@pytest.mark.parametrize("shape", [(128, 256, 128), (576, 2080, 128), (1536, 4640, 128), (2048, 8192, 2048), (2048, 8192, 48)])
 @pytest.mark.parametrize("nb", NBS)
 def test_out_gemm_is_exact_on_integer_operands(nb, shape):
     K0, K1, N = shape
@@ -117,7 +118,7 @@ def _check_one_hot(H, N, nb):
 
 
 @pytest.mark.parametrize("N", [439, 642])
-@pytest.mark.parametrize("H", [128, 2048])
+@pytest.mark.parametrize("H", [128, 576, 2048])
 @pytest.mark.parametrize("nb", NBS)
 def test_ln_gemm_one_hot_rows_return_the_layernorm_bits(nb, H, N):
     _check_one_hot(H, N, nb)
