@@ -1,5 +1,5 @@
-// Internal layout of the transformer engine and the functions its files share (engine.hip, decode.hip, decode_engine.hip,
-// decode_batch.hip, train_engine.hip), each declared once; hipGraph capture / replay helpers at the end.
+// Internal layout of the transformer engine and the functions its files share (engine.hip, t2i_engine.hip, decode.hip,
+// decode_engine.hip, decode_batch.hip, train_engine.hip), each declared once; hipGraph capture / replay helpers at the end.
 #pragma once
 #include "common.h"
 #include "../../include/showo_hip.h"
@@ -97,10 +97,14 @@ int attn_decode_fused_batch(const bf16_t* qkv, const float* qw, const float* qb,
 // the layers of one batch-1 decode step (decode.hip): per layer LN + qkv / fc1 GEMV -> attention (co: with the fc2 role) -> dense / fc2
 // GEMV + both residual adds.  The caller (run_layers, engine.hip) has decided that the fused step applies.
 int decode_layers_b1(::showo_engine* e, int op, const KVDest& kv, const int32_t* iv, int pos0, bool co, hipStream_t s);
-// engine.hip, for the KV-cached decode (decode_engine.hip, decode_batch.hip)
+// engine.hip, for the KV-cached decode (decode_engine.hip, decode_batch.hip) and t2i generation (t2i_engine.hip)
 int run_layers(::showo_engine* e, int B, int L, int pos0, const KVDest& kv, const int32_t* iv, const int32_t* flag, const float* dense,
                hipStream_t s);
 int head_rows(::showo_engine* e, const int32_t* rows, int nrows, int col0, int ncols, float* logits, hipStream_t s);
+KVDest kv_workspace(::showo_engine* e, int L);         // the per-call K / V^T workspace as a destination
+int fused_sync(::showo_engine* e, hipStream_t s);      // derived weight images, rebuilt where stale; never inside a capture
+int precise_sync(::showo_engine* e, hipStream_t s);
+int head3_sync(::showo_engine* e, hipStream_t s);
 int embed_in(::showo_engine* e, const int64_t* ids, const float* embeds, int T, hipStream_t s);
 int check_ready(::showo_engine* e, int B, int L);
 bool precise_fast_ok(const ::showo_engine* e);
@@ -180,10 +184,6 @@ struct showo_engine {
     float* x = nullptr;
     bf16_t *h = nullptr, *qkv = nullptr, *Q = nullptr, *K = nullptr, *Vt = nullptr, *attn = nullptr, *ffn = nullptr, *hf = nullptr;
     int32_t *iv = nullptr, *flag = nullptr, *rows = nullptr;
-    // t2i state
-    int64_t *ids_all = nullptr, *cur = nullptr, *sampled = nullptr;
-    float *sel = nullptr, *row_logits = nullptr;
-    int64_t row_logits_cap = 0;
     // decode (KV cache) state: per-layer caches, capacity cap tokens
     bf16_t *kcache = nullptr, *vtcache = nullptr;
     int cache_cap = 0, cache_len = 0, prompt_len = 0;
@@ -192,11 +192,6 @@ struct showo_engine {
     int last_iv[4] = {0, 0, 0, 0};
     int32_t* iv1 = nullptr;
     int64_t* tok1 = nullptr;
-    // t2i prefix reuse: per-layer K / V^T of the whole batch (text rows are written once, image rows every step)
-    bf16_t *tk = nullptr, *tvt = nullptr;
-    int64_t tk_cap = 0, tvt_cap = 0;
-    int64_t* ids_act = nullptr;
-    int32_t *iv_act = nullptr, *rows_act = nullptr, *pfx_flag = nullptr;
     // caller-provided visibility intervals (showo_engine_use_intervals): used when a call passes no dense mask
     const int32_t* ext_iv = nullptr;
     const int32_t* ext_flag = nullptr;
@@ -205,32 +200,6 @@ struct showo_engine {
     int32_t* last_iv_dev = nullptr;
     // second stream for the two independent branches of a Phi block (attention branch | fc1): see run_layers
     float* y2 = nullptr;  // forked decode layer: fc2 + b2 of the current layer
-    // hipGraph replay of the denoise step: instantiated graphs of one active-rows step are cached (small LRU), keyed by everything
-    // BAKED into their launches: shapes, scalars, and every pointer that is neither engine-owned-and-fixed nor refreshed per call.
-    // With prefix reuse the captured step reads its visibility intervals from the engine's own gathered copy (iv_act, rewritten by
-    // every call), so the caller's mask / interval pointers are NOT part of the key: a caller that builds a fresh, equal mask tensor
-    // per batch (reference inference_t2i.py:290-318) replays the same graph.  Without reuse the step reads the caller's intervals /
-    // dense mask directly and their pointers stay in the key.
-    struct T2IGraphKey {
-        int B, nseq, L, N, prefix, steps, id_offset, codebook, reuse, cfg, has_iv;
-        int64_t mask_id;
-        float guidance;
-        int prec;
-        const void* p[13];
-    };
-    struct T2IGraphEntry {
-        T2IGraphKey key;
-        hipGraphExec_t exec;
-        uint64_t last_use;
-    };
-    static constexpr int T2I_GRAPH_SLOTS = 6;  // full / ragged last batch x CFG on / off x reuse on / off never thrash
-    std::vector<T2IGraphEntry> t2i_graphs;
-    uint64_t t2i_tick = 0;
-    // deferred prefix check of t2i_generate: the device flag lands in pinned host memory behind an event; the host looks at it only
-    // after every step of the call is queued (no pipeline bubble), and repeats the call without prefix reuse in the (never yet seen)
-    // case that a text row can see an image column
-    int32_t* pfx_host = nullptr;
-    hipEvent_t ev_pfx = nullptr;
     // accuracy mode (showo_engine_set_precision): 0 = bf16 operands (default, the timed path), 1 = split-bf16 GEMMs + fp32 attention.
     // lo_loaded: GEMM weights whose low halves are current (cleared when somebody rewrites the hi images behind the loader's back).
     // precision 2 (round 6): IEEE-half ("fp16") operands on the same kernels -- the layer weight images (wqkv / w1 / wd / w2 and the fused
@@ -256,8 +225,7 @@ struct showo_engine {
     // [attn_hi | ffn_hi | attn_lo | ffn_lo], low halves of Q / K / V^T and of the KV caches
     bool px3_valid = false;
     bf16_t *wlm3 = nullptr, *p_h3 = nullptr, *p_hf3 = nullptr, *p_act = nullptr, *p_Qlo = nullptr, *p_Klo = nullptr, *p_Vtlo = nullptr;
-    bf16_t *kcache_lo = nullptr, *vtcache_lo = nullptr, *tk_lo = nullptr, *tvt_lo = nullptr;
-    int64_t tk_lo_cap = 0, tvt_lo_cap = 0;
+    bf16_t *kcache_lo = nullptr, *vtcache_lo = nullptr;
     bf16_t* wtmp3 = nullptr;
     // batched AR decode (decode_batch.hip: showo_engine_batch_begin / _batch_prefill / _batch_decode_greedy)
     struct BatchDecode;
@@ -268,13 +236,53 @@ struct showo_engine {
     int64_t score_rows = 0;
     int32_t* score_iota = nullptr;
     float* collect = nullptr;  // parity hook (showo_engine_set_collect)
-    int t2i_captures = 0;  // how often a denoise step was captured (tests: a second identical call must not capture again)
-    int t2i_step0[4] = {0, 0, 0, 0};  // last t2i_generate call: sequences / rows trimmed / rows run in step 0, host wait in us (showo_engine_t2i_step0)
-    float* t2i_logits0 = nullptr;     // test hooks (showo_engine_t2i_debug): step-0 logits go here; NaN-fill the K cache per call
-    bool t2i_poison = false;
-    int* step_dev = nullptr;
-    float* sched_dev = nullptr;
-    int sched_cap = 0;
+    // ---- t2i generation (t2i_engine.hip): everything that lives across showo_engine_t2i_generate calls
+    struct T2I {
+        int64_t *ids_all = nullptr, *cur = nullptr, *sampled = nullptr;
+        float *sel = nullptr, *row_logits = nullptr;
+        int64_t row_logits_cap = 0;
+        // prefix reuse: per-layer K / V^T of the whole batch (text rows are written once, image rows every step); the low halves in
+        // accuracy mode on the production kernels; ids / intervals / head rows of the active rows
+        bf16_t *tk = nullptr, *tvt = nullptr, *tk_lo = nullptr, *tvt_lo = nullptr;
+        int64_t tk_cap = 0, tvt_cap = 0, tk_lo_cap = 0, tvt_lo_cap = 0;
+        int64_t* ids_act = nullptr;
+        int32_t *iv_act = nullptr, *rows_act = nullptr, *pfx_flag = nullptr;
+        // deferred prefix check: the device flag lands in pinned host memory behind an event; the host looks at it only after every
+        // step of the call is queued (no pipeline bubble), and repeats the call without prefix reuse in the (never yet seen) case
+        // that a text row can see an image column
+        int32_t* pfx_host = nullptr;
+        hipEvent_t ev_pfx = nullptr;
+        // step index | pad | seed and the per-step schedule, read on the device by a replayed step
+        int* step_dev = nullptr;
+        float* sched_dev = nullptr;
+        int sched_cap = 0;
+        // hipGraph replay of the denoise step: instantiated graphs of one active-rows step are cached (small LRU), keyed by everything
+        // BAKED into their launches: shapes, scalars, and every pointer that is neither engine-owned-and-fixed nor refreshed per call.
+        // With prefix reuse the captured step reads its visibility intervals from the engine's own gathered copy (iv_act, rewritten by
+        // every call), so the caller's mask / interval pointers are NOT part of the key: a caller that builds a fresh, equal mask tensor
+        // per batch (reference inference_t2i.py:290-318) replays the same graph.  Without reuse the step reads the caller's intervals /
+        // dense mask directly and their pointers stay in the key.
+        struct GraphKey {
+            int B, nseq, L, N, prefix, steps, id_offset, codebook, reuse, cfg, has_iv;
+            int64_t mask_id;
+            float guidance;
+            int prec;
+            const void* p[13];
+        };
+        struct GraphEntry {
+            GraphKey key;
+            hipGraphExec_t exec;
+            uint64_t last_use;
+        };
+        static constexpr int T2I_GRAPH_SLOTS = 6;  // full / ragged last batch x CFG on / off x reuse on / off never thrash
+        std::vector<GraphEntry> graphs;
+        uint64_t tick = 0;
+        int captures = 0;  // how often a denoise step was captured (tests: a second identical call must not capture again)
+        int step0[4] = {0, 0, 0, 0};  // last t2i_generate call: sequences / rows trimmed / rows run in step 0, host wait in us (showo_engine_t2i_step0)
+        float* logits0 = nullptr;     // test hooks (showo_engine_t2i_debug): step-0 logits go here; NaN-fill the K cache per call
+        bool poison = false;
+    };
+    T2I t2i;
 
     // hipFree a buffer obtained from alloc() and forget it (buffers that are re-sized during the engine's life)
     template <class T>

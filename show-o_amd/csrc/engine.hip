@@ -1,6 +1,6 @@
 // Show-o transformer engine: packed bf16 weights + workspaces resident in HBM, whole-module entry points.
 // Replaces (reference): PhiForCausalLM/PhiModel forward (models/phi.py:953-1183), Showo.forward without
-// labels (models/modeling_showo.py:76-79), Showo.t2i_generate (models/modeling_showo.py:104-181) and the
+// labels (models/modeling_showo.py:76-79), the layer stack and head under Showo.t2i_generate (its host side is t2i_engine.hip) and the
 // layer stack and head under the incremental form of Showo.mmu_generate (models/modeling_showo.py:183-240; its KV cache
 // and token loop are in decode_engine.hip, the launches of a one-token step in decode.hip).
 //
@@ -15,7 +15,6 @@
 #include "engine.h"
 #include "decode_common.h"
 #include <algorithm>
-#include <chrono>
 #include <cstdio>
 #include <vector>
 #include <cstring>
@@ -24,164 +23,6 @@
 #include <vector>
 
 using namespace showo;
-
-namespace {
-
-__global__ void init_cur_kernel(const int64_t* ids, int ld, int img_start, int64_t mask_id, int64_t offset, int64_t* cur, int N,
-                                int total) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    int b = i / N, n = i - b * N;
-    int64_t v = ids[(int64_t)b * ld + img_start + n];
-    cur[i] = (v == mask_id) ? mask_id : v - offset;
-}
-// uncond rows = uncond prefix (first `prefix` tokens) + cond tokens from `prefix` on (modeling_showo.py:137-138)
-__global__ void build_ids_kernel(const int64_t* cond, const int64_t* uncond, int64_t* all, int B, int L, int prefix) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= B * L) return;
-    int b = i / L, l = i - b * L;
-    int64_t c = cond[i];
-    all[i] = c;
-    if (uncond) all[(int64_t)(B + b) * L + l] = (l < prefix) ? uncond[i] : c;
-}
-__global__ void rows_index_kernel(int32_t* rows, int nseq, int L, int img_start, int N) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nseq * N) return;
-    int b = i / N, n = i - b * N;
-    rows[i] = b * L + img_start + n;
-}
-// ---- t2i prefix reuse: rows [0, prefix) of every sequence (pads + text; causal, never see an image column) are step-invariant
-__global__ void gather_ids_kernel(const int64_t* __restrict__ all, int64_t* __restrict__ act, int nseq, int L, int prefix) {
-    const int La = L - prefix;
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nseq * La) return;
-    int b = i / La, j = i - b * La;
-    act[i] = all[(int64_t)b * L + prefix + j];
-}
-__global__ void gather_iv_kernel(const int32_t* __restrict__ iv, int32_t* __restrict__ act, int nseq, int L, int prefix) {
-    const int La = L - prefix;
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nseq * La) return;
-    int b = i / La, j = i - b * La;
-    reinterpret_cast<int4*>(act)[i] = reinterpret_cast<const int4*>(iv)[(int64_t)b * L + prefix + j];
-}
-// out |= 1 if a prefix row can see a column >= prefix (then the prefix is not step-invariant), out |= 2 if *mask_flag is set
-__global__ void prefix_check_kernel(const int32_t* __restrict__ iv, const int32_t* __restrict__ mask_flag, int32_t* __restrict__ out,
-                                    int nseq, int L, int prefix) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i == 0 && mask_flag && *mask_flag) atomicOr(out, 2);
-    if (i >= nseq * prefix) return;
-    int b = i / prefix, r = i - b * prefix;
-    const int4 v = reinterpret_cast<const int4*>(iv)[(int64_t)b * L + r];
-    int hi = 0;
-    if (v.x < v.y) hi = max(hi, v.y);
-    if (v.z < v.w) hi = max(hi, v.w);
-    if (hi > prefix) atomicOr(out, 1);
-}
-// ---- t2i reduced step 0: which rows of the full step does the result need?  One block per sequence b.
-//   p_b = the largest p <= prefix such that no row r >= p of the sequence sees a column < p (rows [p_b, L) are closed under "sees"; both
-//         intervals of a row count).  With left padding that is the pad count: text and image rows never see a pad column.
-//   out[2] / out[3] = max over the sequences [0, first] / (first, nseq) of prefix - p_b  (the uniform trim is the smallest p_b)
-//   out[1] |= 1  when an unconditional sequence first+1 .. nseq-1 differs from sequence `first` in an id or an interval row (first > 0:
-//                CFG call), or when the mask is not an interval mask (then also p = 0)
-// (out[0] belongs to prefix_check_kernel; all four ints are zeroed before the two launches.)
-__global__ void step0_plan_kernel(const int64_t* __restrict__ ids, const int32_t* __restrict__ iv, const int32_t* __restrict__ mask_flag,
-                                  int32_t* __restrict__ out, int first, int nseq, int L, int prefix) {
-    __shared__ int s_min[256];
-    __shared__ int s_best;
-    const int b = blockIdx.x, t = threadIdx.x;
-    const int4* row = reinterpret_cast<const int4*>(iv) + (int64_t)b * L;
-    auto lo_of = [&](int r) {  // first column row r sees (INT_MAX: none)
-        const int4 v = row[r];
-        int lo = 0x7fffffff;
-        if (v.x < v.y) lo = min(lo, v.x);
-        if (v.z < v.w) lo = min(lo, v.z);
-        return lo;
-    };
-    const int chunk = (L + 255) / 256, r0 = min(L, t * chunk), r1 = min(L, r0 + chunk);
-    int m = 0x7fffffff;
-    for (int r = r0; r < r1; ++r) m = min(m, lo_of(r));
-    s_min[t] = m;
-    if (t == 0) s_best = 0;
-    __syncthreads();
-    m = 0x7fffffff;  // min over the rows behind this thread's chunk
-    for (int j = t + 1; j < 256; ++j) m = min(m, s_min[j]);
-    for (int r = r1 - 1; r >= r0; --r) {
-        m = min(m, lo_of(r));
-        if (r <= prefix && m >= r) { atomicMax(&s_best, r); break; }
-    }
-    __syncthreads();
-    if (t == 0) {
-        atomicMax(out + (b <= first ? 2 : 3), prefix - s_best);
-        if (b == 0 && mask_flag && *mask_flag) { atomicOr(out + 1, 1); atomicMax(out + 2, prefix); }
-    }
-    if (first > 0 && b > first) {
-        const int64_t *ia = ids + (int64_t)first * L, *ib = ids + (int64_t)b * L;
-        const int4* ra = reinterpret_cast<const int4*>(iv) + (int64_t)first * L;
-        bool diff = false;
-        for (int r = t; r < L; r += 256) {
-            const int4 u = ra[r], v = row[r];
-            diff |= ia[r] != ib[r] || u.x != v.x || u.y != v.y || u.z != v.z || u.w != v.w;
-        }
-        if (diff) atomicOr(out + 1, 1);
-    }
-}
-// interval rows [p, L) of the first nseq sequences with every interval cut to columns >= p.  A no-op for the rows that are closed under
-// "sees" at p; a pad row of a sequence with more than p pads would otherwise read cache rows < p, which the reduced step 0 never writes.
-// Such a row then computes something else than in the full step, but nothing that is used can see it (it lies before its sequence's p_b).
-__global__ void gather_iv_cut_kernel(const int32_t* __restrict__ iv, int32_t* __restrict__ act, int nseq, int L, int p) {
-    const int La = L - p;
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nseq * La) return;
-    int b = i / La, j = i - b * La;
-    int4 v = reinterpret_cast<const int4*>(iv)[(int64_t)b * L + p + j];
-    v.x = max(v.x, p); v.z = max(v.z, p);
-    reinterpret_cast<int4*>(act)[i] = v;
-}
-// Copies `len` units at `off` of every (layer, inner) chunk of one sequence to the same place of the next `ndst` sequences:
-// chunk (li, h) starts at base + li * lstride + h * istride, sequences are seq_stride apart.  T = uint4 wherever the layout allows.
-template <class T>
-__global__ void bcast_seq_kernel(T* __restrict__ base, int64_t lstride, int inner, int64_t istride, int64_t off, int len, int64_t seq_stride,
-                                 int ndst, int64_t total) {
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const int64_t o = i / len, li = o / inner;
-    T* src = base + li * lstride + (o - li * inner) * istride + off + (i - o * len);
-    const T v = *src;
-    for (int d = 1; d <= ndst; ++d) src[d * seq_stride] = v;
-}
-// per-call constants of the graph-replayed denoise loop, passed BY VALUE as kernel arguments (no host staging buffer to keep alive,
-// no stream synchronisation): sched[0..n) = mask_len_f | temperature per step, hdr = step index | pad | seed lo | seed hi
-struct SchedArgs { float v[512]; int hdr[4]; int n; };
-__global__ void sched_upload_kernel(SchedArgs a, float* __restrict__ sched, int* __restrict__ hdr) {
-    for (int i = threadIdx.x; i < a.n; i += blockDim.x) sched[i] = a.v[i];
-    if (threadIdx.x < 4) hdr[threadIdx.x] = a.hdr[threadIdx.x];
-}
-__global__ void copy_i64_kernel(const int64_t* s, int64_t* d, int n) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) d[i] = s[i];
-}
-
-}  // namespace
-
-// bcast_seq_kernel in the widest unit that every stride, offset and length (given in elements of E) is a multiple of
-template <class E>
-static int bcast_seq(E* base, int64_t lstride, int n_layers, int inner, int64_t istride, int64_t off, int64_t len, int64_t seq_stride, int ndst,
-                     hipStream_t s) {
-    if (ndst <= 0 || len <= 0) return 0;
-    constexpr int W = 16 / (int)sizeof(E);
-    const bool wide = !(lstride % W) && !(istride % W) && !(off % W) && !(len % W) && !(seq_stride % W) && !((uintptr_t)base & 15);
-    const int64_t u = wide ? W : 1, total = (int64_t)n_layers * inner * (len / u);
-    if (len / u >= ((int64_t)1 << 31) || (total + 255) / 256 >= ((int64_t)1 << 31)) return set_error_msg(5, "t2i: broadcast too large");
-    const dim3 grid((unsigned)((total + 255) / 256));
-    if (wide)
-        bcast_seq_kernel<uint4><<<grid, dim3(256), 0, s>>>(reinterpret_cast<uint4*>(base), lstride / W, inner, istride / W, off / W, (int)(len / W),
-                                                           seq_stride / W, ndst, total);
-    else
-        bcast_seq_kernel<E><<<grid, dim3(256), 0, s>>>(base, lstride, inner, istride, off, (int)len, seq_stride, ndst, total);
-    SHOWO_CHECK_HIP(hipGetLastError());
-    return 0;
-}
 
 extern "C" int showo_engine_create(const showo_engine_config* c, showo_engine** out) {
     if (!c || !out) return set_error_msg(1, "engine_create: null argument");
@@ -216,7 +57,7 @@ extern "C" int showo_engine_create(const showo_engine_config* c, showo_engine** 
     rc |= e->alloc(&e->Vt, (int64_t)c->max_batch * H * Lp);
     rc |= e->alloc(&e->attn, T * H); rc |= e->alloc(&e->ffn, T * F); rc |= e->alloc(&e->hf, (T + 64) * H);  // + 64 rows: the trainer's lm_head weight gradient reads hf up to the next multiple of 64 rows
     rc |= e->alloc(&e->iv, T * 4); rc |= e->alloc(&e->flag, 4); rc |= e->alloc(&e->rows, T);
-    rc |= e->alloc(&e->ids_all, T); rc |= e->alloc(&e->cur, T); rc |= e->alloc(&e->sampled, T); rc |= e->alloc(&e->sel, T);
+    rc |= e->alloc(&e->t2i.ids_all, T); rc |= e->alloc(&e->t2i.cur, T); rc |= e->alloc(&e->t2i.sampled, T); rc |= e->alloc(&e->t2i.sel, T);
     rc |= e->alloc(&e->iv1, 4); rc |= e->alloc(&e->tok1, 1);
     if (rc) { showo_engine_destroy(e); return rc; }
     hipMemset(e->Vt, 0, (size_t)c->max_batch * H * Lp * sizeof(bf16_t));
@@ -228,10 +69,10 @@ extern "C" int showo_engine_create(const showo_engine_config* c, showo_engine** 
 
 extern "C" void showo_engine_destroy(showo_engine* e) {
     if (!e) return;
-    for (auto& ge : e->t2i_graphs)
+    for (auto& ge : e->t2i.graphs)
         if (ge.exec) hipGraphExecDestroy(ge.exec);
-    if (e->ev_pfx) hipEventDestroy(e->ev_pfx);
-    if (e->pfx_host) hipHostFree(e->pfx_host);
+    if (e->t2i.ev_pfx) hipEventDestroy(e->t2i.ev_pfx);
+    if (e->t2i.pfx_host) hipHostFree(e->t2i.pfx_host);
     showo::engine_batch_free(e);
     for (void* p : e->allocs) hipFree(p);
     delete e;
@@ -242,23 +83,6 @@ extern "C" void showo_engine_destroy(showo_engine* e) {
 extern "C" int showo_engine_set_collect(showo_engine* e, float* buf) {
     if (!e) return set_error_msg(1, "engine: null handle");
     e->collect = buf;
-    return 0;
-}
-
-extern "C" int showo_engine_t2i_captures(const showo_engine* e) { return e ? e->t2i_captures : -1; }
-// what step 0 of the last showo_engine_t2i_generate call ran: sequences, leading rows trimmed, rows (= out[0] * (L - out[1])), and the
-// host time in microseconds spent waiting for that decision
-extern "C" int showo_engine_t2i_step0(const showo_engine* e, int* out) {
-    if (!e || !out) return set_error_msg(1, "engine: null argument");
-    for (int i = 0; i < 4; ++i) out[i] = e->t2i_step0[i];
-    return 0;
-}
-// test hooks of t2i_generate.  logits0 (device, fp32 [nseq * N, codebook], or null): receives the logit rows of step 0.  poison_kv: the
-// batch-wide K cache is filled with NaN bit patterns at the start of every call (rows that no step writes must never reach a result).
-extern "C" int showo_engine_t2i_debug(showo_engine* e, float* logits0, int poison_kv) {
-    if (!e) return set_error_msg(1, "engine: null handle");
-    e->t2i_logits0 = logits0;
-    e->t2i_poison = poison_kv != 0;
     return 0;
 }
 
@@ -497,7 +321,7 @@ static bool w_tiled_enabled() {
 // Weight images of the two fused projections, rebuilt for every block whose wqkv / wd / w1 / w2 / bd / b2 changed since they were built:
 //   wd2  = [Wd | W2] ([H, H + F], K-concatenated) for showo_gemm_kcat_bf16, bd2 = bd + b2;
 //   wq1t = tiled copy of [Wqkv ; W1] (showo_gemm_tile_weight) -- with SHOWO_W_TILED (default) wd2 is stored tiled as well
-static int fused_sync(showo_engine* e, hipStream_t s) {
+int showo::fused_sync(showo_engine* e, hipStream_t s) {
     if (!showo::engine_fused_stale(e)) return 0;
     const int H = e->H, F = e->F;
     const bool tiled = w_tiled_enabled();
@@ -532,7 +356,7 @@ static bool fused_layer_enabled() {
 }
 
 // ---- the 24-layer stack.  K / V^T go to a KVDest (engine.h): the per-call workspace here, or a per-layer cache.
-static KVDest kv_workspace(showo_engine* e, int L) { return KVDest{e->K, e->Vt, 0, 0, L, ((L + 63) / 64) * 64, e->p_Klo, e->p_Vtlo}; }
+KVDest showo::kv_workspace(showo_engine* e, int L) { return KVDest{e->K, e->Vt, 0, 0, L, ((L + 63) / 64) * 64, e->p_Klo, e->p_Vtlo}; }
 namespace showo { int g_decode_impl = 0; }
 static int g_decode_chain = 0;  // 1: the fused layer as a plain three-launch chain (no co-scheduled fc2 role)
 extern "C" int showo_decode_set_impl(int impl) {
@@ -782,9 +606,8 @@ static int head_rows_precise(showo_engine* e, const int32_t* rows, int nrows, in
                              logits, ncols, nullptr, 0, nrows, ncols, e->H, s);
 }
 
-static int fused_sync(showo_engine* e, hipStream_t s);
 // [hi | hi | lo] rows of the lm_head (precision 1 and 2: the head is a split-bf16 product in both); never inside a capture
-static int head3_sync(showo_engine* e, hipStream_t s) {
+int showo::head3_sync(showo_engine* e, hipStream_t s) {
     if (e->head3_valid) return 0;
     if (!e->wlm3 || !e->wlm_lo || !e->lo_loaded.count("showo.lm_head.weight"))
         return set_error_msg(4, "engine: the low half of the lm_head is missing or stale (the weights were loaded before "
@@ -797,7 +620,7 @@ static int head3_sync(showo_engine* e, hipStream_t s) {
     return 0;
 }
 // K-concatenated split images of every GEMM weight (see "accuracy mode" above), rebuilt after any weight load; never inside a capture
-static int precise_sync(showo_engine* e, hipStream_t s) {
+int showo::precise_sync(showo_engine* e, hipStream_t s) {
     if (e->px3_valid) return 0;
     TRY(precise_check(e));
     TRY(fused_sync(e, s));  // bd2 = bd + b2
@@ -1044,277 +867,6 @@ extern "C" int showo_engine_forward_rows(showo_engine* e, const int64_t* ids, co
     if (nrows > e->maxT) return set_error_msg(5, "engine: too many rows");
     TRY(hidden(e, ids, embeds, mask, B, L, s));
     return head_rows(e, rows, nrows, col0, ncols, logits, s);
-}
-
-extern "C" int showo_engine_t2i_generate(showo_engine* e, int64_t* ids_cond, int64_t* ids_uncond, const float* mask, int B,
-                                         int L, int N, int text_len, int64_t mask_id, int id_offset, int codebook,
-                                         float guidance, int steps, const float* mask_len_host, const float* temps_host,
-                                         uint64_t seed, const float* exp_noise, const float* uniform, int use_graph,
-                                         int64_t* sampled_out, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    const bool cfg = (ids_uncond != nullptr) && guidance > 0.f;  // modeling_showo.py:136
-    const int nseq = cfg ? 2 * B : B;
-    TRY(check_ready(e, nseq, L));
-    if (N + 2 > L || steps < 1 || !mask_len_host || !temps_host) return set_error_msg(1, "t2i: bad arguments");
-    if (id_offset + codebook > e->V) return set_error_msg(1, "t2i: codebook slice exceeds the vocabulary");
-    const int img_start = L - (N + 1);  // input_ids[:, -(N+1):-1]
-    const int nrows = nseq * N;
-    if ((int64_t)nrows * codebook > e->row_logits_cap) {
-        e->row_logits_cap = (int64_t)nrows * codebook;
-        TRY(e->alloc(&e->row_logits, e->row_logits_cap));
-    }
-    const int thr = 256;
-    const int32_t *iv = nullptr, *flag = nullptr;
-    if (mask) {
-        TRY(showo_mask_compress(mask, e->iv, e->flag, nseq, L, L, s));  // the mask is step-invariant: compress once
-        iv = e->iv; flag = e->flag;
-    } else if (e->ext_iv) {
-        iv = e->ext_iv; flag = e->ext_flag;
-    }
-    // ---- prefix reuse.  Rows [0, prefix) of every sequence (pads + text, prefix = position of <soi>) are causal: they never see
-    // an image column, and their ids never change, so their hidden states -- hence their K / V in every layer -- are the same
-    // in all steps.  Step 0 runs the whole sequence and leaves K / V^T of every layer in a batch-wide cache; the later steps run
-    // only the rows [prefix, L) (soi, image tokens, eoi: 258 of 387 at 256x256) against the cached text keys.  Exact up to the
-    // grouping of rows into tiles (same arithmetic per row); checked on the device: interval masks only, no prefix row may see
-    // a column >= prefix.  use_graph bit 1 disables it.
-    // The check is DEFERRED: its flag travels to pinned host memory behind an event and is read after every step of the call has
-    // been queued (the GPU never waits for the host); in the case that it fires the call is repeated without reuse -- ids_cond /
-    // sampled_out are only written at the very end, so nothing of the optimistic attempt is visible to the caller.
-    const int prefix = text_len + 1;
-    const int La = L - prefix;
-    const int LpC = ((L + 63) / 64) * 64;
-    const bool pfast = e->precision == 1 && precise_fast_ok(e);
-    const bool reuse_ok = (e->precision == 0 || e->precision == 2 || e->precision == 3 || pfast) && !(use_graph & 2) && steps > 1 && prefix >= 1 && La >= N + 1 && nseq * La >= 1;
-    hipStreamCaptureStatus cs0 = hipStreamCaptureStatusNone;
-    hipStreamIsCapturing(s, &cs0);
-    if (cs0 != hipStreamCaptureStatusNone) return set_error_msg(7, "t2i_generate: the call captures its own graph; do not call it inside a stream capture");
-    TRY(fused_sync(e, s));  // weight images of the fused launches: rebuilt here (never inside a capture), so cached graphs stay valid
-    if (pfast) TRY(precise_sync(e, s));
-    if (e->precision == 2) TRY(head3_sync(e, s));
-    if (reuse_ok && !e->pfx_flag) {
-        TRY(e->alloc(&e->pfx_flag, 4));
-        SHOWO_CHECK_HIP(hipHostMalloc((void**)&e->pfx_host, 64, hipHostMallocDefault));
-        SHOWO_CHECK_HIP(hipEventCreateWithFlags(&e->ev_pfx, hipEventDisableTiming));
-    }
-    e->t2i_step0[0] = nseq; e->t2i_step0[1] = 0; e->t2i_step0[2] = nseq * L; e->t2i_step0[3] = 0;
-    for (int attempt = 0; attempt < 2; ++attempt) {
-    const bool reuse = reuse_ok && attempt == 0;
-    bool check_pending = false;
-    // ---- reduced step 0 (use_graph bit 2 disables it).  Step 0 only has to leave the prefix K / V^T in the cache and produce the image
-    // rows' logits.  (a) Leading rows that no later row can see (left pads) feed nothing: rows [p0, L) are run, p0 the smallest of the
-    // sequences' own trims (the pad rows that a sequence has beyond p0 run with their intervals cut at p0: nothing that is used sees
-    // them).  (b) In a pure t2i CFG call the unconditional sequences are ONE sequence (empty prompt, all-mask image part): it is run once
-    // and its prefix K / V^T and logit rows are copied to the other B - 1.  Both are decided on the device from the ids and intervals of
-    // THIS call; grid sizes depend on the answer, so the host waits for it here, once, before the first launch of step 0.
-    const bool red = reuse && iv && !(use_graph & 4);
-    int nseq0 = nseq, p0 = 0;
-    bool shared = false;
-    build_ids_kernel<<<dim3((B * L + thr - 1) / thr), dim3(thr), 0, s>>>(ids_cond, cfg ? ids_uncond : nullptr, e->ids_all, B, L,
-                                                                       text_len + 1);
-    init_cur_kernel<<<dim3((B * N + thr - 1) / thr), dim3(thr), 0, s>>>(ids_cond, L, img_start, mask_id, id_offset, e->cur, N, B * N);
-    rows_index_kernel<<<dim3((nrows + thr - 1) / thr), dim3(thr), 0, s>>>(e->rows, nseq, L, img_start, N);
-    SHOWO_CHECK_HIP(hipGetLastError());
-    if (reuse && iv) {
-        SHOWO_CHECK_HIP(hipMemsetAsync(e->pfx_flag, 0, 4 * sizeof(int32_t), s));
-        prefix_check_kernel<<<dim3((nseq * prefix + thr - 1) / thr), dim3(thr), 0, s>>>(iv, flag, e->pfx_flag, nseq, L, prefix);
-        if (red) step0_plan_kernel<<<dim3(nseq), dim3(256), 0, s>>>(e->ids_all, iv, flag, e->pfx_flag, cfg ? B : 0, nseq, L, prefix);
-        SHOWO_CHECK_HIP(hipMemcpyAsync(e->pfx_host, e->pfx_flag, 4 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-        SHOWO_CHECK_HIP(hipEventRecord(e->ev_pfx, s));
-        check_pending = true;
-    }
-    if (red) {
-        const auto t0 = std::chrono::steady_clock::now();
-        SHOWO_CHECK_HIP(hipEventSynchronize(e->ev_pfx));
-        e->t2i_step0[3] += (int)std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
-        const volatile int32_t* h = e->pfx_host;
-        if (h[0]) continue;  // the prefix check, read in the same wait: repeat without reuse (and without the optimistic attempt)
-        check_pending = false;
-        shared = cfg && B > 1 && !h[1];
-        const int trim_short = shared ? h[2] : std::max(h[2], h[3]);
-        p0 = std::min(std::max(prefix - trim_short, 0), prefix);
-        nseq0 = shared ? B + 1 : nseq;
-    }
-    const bool reduced = shared || p0 > 0;
-    if (reuse) { e->t2i_step0[0] = nseq0; e->t2i_step0[1] = p0; e->t2i_step0[2] = nseq0 * (L - p0); }
-    KVDest kvc = kv_workspace(e, L);
-    if (reuse) {
-        const int64_t kn = (int64_t)e->nL * nseq * e->nH * L * 64, vn = (int64_t)e->nL * nseq * e->nH * 64 * LpC;
-        if (kn > e->tk_cap) { TRY(e->alloc(&e->tk, kn)); e->tk_cap = kn; }
-        if (vn > e->tvt_cap) { TRY(e->alloc(&e->tvt, vn)); e->tvt_cap = vn; }
-        SHOWO_CHECK_HIP(hipMemsetAsync(e->tvt, 0, (size_t)vn * sizeof(bf16_t), s));  // pad key columns must stay finite
-        // (iv_act / rows_act: the active rows of the later steps, and behind them those of the reduced step 0)
-        if (!e->ids_act) { TRY(e->alloc(&e->ids_act, e->maxT)); TRY(e->alloc(&e->iv_act, e->maxT * 8)); TRY(e->alloc(&e->rows_act, e->maxT * 2)); }
-        if (e->t2i_poison) SHOWO_CHECK_HIP(hipMemsetAsync(e->tk, 0xff, (size_t)kn * sizeof(bf16_t), s));
-        if (pfast) {
-            if (kn > e->tk_lo_cap) { TRY(e->alloc(&e->tk_lo, kn)); e->tk_lo_cap = kn; }
-            if (vn > e->tvt_lo_cap) { TRY(e->alloc(&e->tvt_lo, vn)); e->tvt_lo_cap = vn; }
-            SHOWO_CHECK_HIP(hipMemsetAsync(e->tvt_lo, 0, (size_t)vn * sizeof(bf16_t), s));
-            if (e->t2i_poison) SHOWO_CHECK_HIP(hipMemsetAsync(e->tk_lo, 0xff, (size_t)kn * sizeof(bf16_t), s));
-        }
-        kvc = KVDest{e->tk, e->tvt, (int64_t)nseq * e->nH * L * 64, (int64_t)nseq * e->nH * 64 * LpC, L, LpC, pfast ? e->tk_lo : nullptr,
-                     pfast ? e->tvt_lo : nullptr};
-        if (iv) gather_iv_kernel<<<dim3((nseq * La + thr - 1) / thr), dim3(thr), 0, s>>>(iv, e->iv_act, nseq, L, prefix);
-        rows_index_kernel<<<dim3((nrows + thr - 1) / thr), dim3(thr), 0, s>>>(e->rows_act, nseq, La, img_start - prefix, N);
-        if (reduced) {
-            gather_iv_cut_kernel<<<dim3((nseq0 * (L - p0) + thr - 1) / thr), dim3(thr), 0, s>>>(iv, e->iv_act + e->maxT * 4, nseq0, L, p0);
-            rows_index_kernel<<<dim3((nseq0 * N + thr - 1) / thr), dim3(thr), 0, s>>>(e->rows_act + e->maxT, nseq0, L - p0, img_start - p0, N);
-        }
-        SHOWO_CHECK_HIP(hipGetLastError());
-    }
-    bool first_step = true;
-    // one denoise step (modeling_showo.py:135-179).  step < 0: the step index / schedule constants are read on the device.
-    // full: run every row (always in step 0); otherwise only the rows [prefix, L) against the cached prefix keys.
-    auto denoise_step = [&](int step, bool full) -> int {
-        if (full && reduced) {
-            // rows [p0, L) of the sequences 0 .. nseq0 - 1 through the machinery of the later steps; K / V^T go to their true positions in
-            // the batch-wide cache (cache rows < p0 are never written and never visible: the attention kernel selects masked scores away,
-            // V^T there is zero).  Every GEMM keeps the k-partition of the full-shape launch it replaces (gemm_pin_split_m).
-            const int L0 = L - p0;
-            gather_ids_kernel<<<dim3((nseq0 * L0 + thr - 1) / thr), dim3(thr), 0, s>>>(e->ids_all, e->ids_act, nseq0, L, p0);
-            TRY(showo_embed_f32(e->ids_act, e->embed, e->x, nseq0 * L0, e->H, e->V, s));
-            showo::gemm_pin_split_m(nseq * L);
-            int rc = run_layers(e, nseq0, L0, p0, kvc, e->iv_act + e->maxT * 4, nullptr, nullptr, s);
-            showo::gemm_pin_split_m(nseq * N);
-            if (!rc) rc = head_rows(e, e->rows_act + e->maxT, nseq0 * N, id_offset, codebook, e->row_logits, s);
-            showo::gemm_pin_split_m(0);
-            TRY(rc);
-            if (shared) {
-                // the one unconditional sequence (index B) stands for all B: its prefix K rows [p0, prefix) and V^T columns (widened to
-                // 16-byte units: columns < p0 are zero on both sides, columns >= prefix are rewritten by every later step) of every
-                // layer, and its logit rows
-                const int64_t ks = (int64_t)e->nH * L * 64, vs = (int64_t)e->nH * 64 * LpC;
-                const int c0 = p0 & ~7, c1 = std::min(LpC, (prefix + 7) & ~7);
-                for (int half = 0; half < (pfast ? 2 : 1); ++half) {
-                    TRY(bcast_seq(half ? kvc.k_lo : kvc.k, kvc.k_lstride, e->nL, e->nH, (int64_t)L * 64, B * ks + (int64_t)p0 * 64,
-                                  (int64_t)(prefix - p0) * 64, ks, B - 1, s));
-                    TRY(bcast_seq(half ? kvc.vt_lo : kvc.vt, kvc.v_lstride, e->nL, e->nH * 64, (int64_t)LpC, B * vs + c0, (int64_t)(c1 - c0), vs, B - 1, s));
-                }
-                TRY(bcast_seq(e->row_logits, 0, 1, 1, 0, (int64_t)B * N * codebook, (int64_t)N * codebook, (int64_t)N * codebook, B - 1, s));
-            }
-        } else if (full) {
-            TRY(showo_embed_f32(e->ids_all, e->embed, e->x, nseq * L, e->H, e->V, s));
-            TRY(run_layers(e, nseq, L, 0, kvc, iv, flag, mask, s));
-            TRY(head_rows(e, e->rows, nrows, id_offset, codebook, e->row_logits, s));
-        } else {
-            gather_ids_kernel<<<dim3((nseq * La + thr - 1) / thr), dim3(thr), 0, s>>>(e->ids_all, e->ids_act, nseq, L, prefix);
-            TRY(showo_embed_f32(e->ids_act, e->embed, e->x, nseq * La, e->H, e->V, s));
-            // like the reduced step 0, the active-rows launches sum K in the order of the full-shape launches they stand for: with fewer
-            // than 16 sequences the residual GEMM splits K and the count follows M, and the text rows in the cache (step 0) and the path
-            // without reuse were summed in the full shape's order.  (Baked into the captured launches; a no-op where neither shape splits.)
-            showo::gemm_pin_split_m(nseq * L);
-            const int rc = run_layers(e, nseq, La, prefix, kvc, iv ? e->iv_act : nullptr, nullptr, nullptr, s);
-            showo::gemm_pin_split_m(0);
-            TRY(rc);
-            TRY(head_rows(e, e->rows_act, nrows, id_offset, codebook, e->row_logits, s));
-        }
-        if (first_step && e->t2i_logits0)
-            SHOWO_CHECK_HIP(hipMemcpyAsync(e->t2i_logits0, e->row_logits, (size_t)nrows * codebook * sizeof(float), hipMemcpyDeviceToDevice, s));
-        first_step = false;
-        const float* lu = cfg ? e->row_logits + (int64_t)B * N * codebook : nullptr;
-        const bool dev = step < 0;  // device-step mode: noise offsets are applied inside the kernels
-        TRY(showo_cfg_softmax_sample(e->row_logits, lu, codebook, guidance, e->cur, mask_id,
-                                     exp_noise ? exp_noise + (dev ? 0 : (int64_t)step * B * N * codebook) : nullptr, seed,
-                                     (uint32_t)(dev ? 0 : step), e->sampled, e->sel, B, N, codebook, s));
-        TRY(showo_mask_by_topk(e->sel, e->sampled, e->cur, e->ids_all, cfg ? e->ids_all + (int64_t)B * L : nullptr, L, img_start,
-                               mask_id, id_offset, dev ? 0.f : mask_len_host[step], dev ? 0.f : temps_host[step],
-                               uniform ? uniform + (dev ? 0 : (int64_t)step * B * N) : nullptr, seed, (uint32_t)(dev ? 0 : step), nullptr,
-                               B, N, s));
-        return 0;
-    };
-    // hipGraph path (the default of Showo.t2i_generate): ONE denoise step -- every row from <soi> on, ~80 kernels -- is captured with
-    // everything that changes from step to step or call to call in device memory (step index, schedule constants, seed, the gathered
-    // visibility intervals) and the instantiated graph is CACHED on the engine (LRU of T2I_GRAPH_SLOTS), keyed by every launch
-    // argument baked into it; later calls with the same key replay it without capturing again and without a host synchronisation.
-    // The eager steps before a capture (2 with prefix reuse: the full step 0 and one active-rows step) launch every kernel variant
-    // once (first-use attributes, GEMM tile tuning) outside the capture; step 0 always runs eagerly.  Not combined with per-launch
-    // event timing.
-    const int n_eager = reuse ? 2 : 1;
-    // A registered range-check counter forces the eager path: its launches (and the caller's counter pointer) must not be baked into a
-    // cached graph that later plain calls replay, and a replayed cached graph would skip them.
-    const bool graph = (use_graph & 1) && steps > n_eager && !showo::g_prof_on_query() && (e->precision == 0 || e->precision == 2 || e->precision == 3 || pfast) &&
-                       !(e->range_count && e->precision == 2);
-    if (!graph) {
-        for (int step = 0; step < steps; ++step) TRY(denoise_step(step, step == 0 || !reuse));
-    } else {
-        if (!e->step_dev) { TRY(e->alloc(&e->step_dev, 4)); }
-        if (e->sched_cap < 2 * steps) {
-            // (re)allocation changes a pointer baked into cached graphs: they are keyed on it (p[8]) and simply miss afterwards
-            TRY(e->alloc(&e->sched_dev, 2 * (steps > 256 ? steps : 256))); e->sched_cap = 2 * (steps > 256 ? steps : 256);
-        }
-        if (2 * steps <= 512) {
-            SchedArgs a;
-            for (int i = 0; i < steps; ++i) { a.v[i] = mask_len_host[i]; a.v[steps + i] = temps_host[i]; }
-            a.hdr[0] = 0; a.hdr[1] = 0; a.hdr[2] = (int)(uint32_t)(seed & 0xffffffffu); a.hdr[3] = (int)(uint32_t)(seed >> 32);
-            a.n = 2 * steps;
-            sched_upload_kernel<<<1, 256, 0, s>>>(a, e->sched_dev, e->step_dev);
-            SHOWO_CHECK_HIP(hipGetLastError());
-        } else {
-            std::vector<float> sched(2 * steps);
-            for (int i = 0; i < steps; ++i) { sched[i] = mask_len_host[i]; sched[steps + i] = temps_host[i]; }
-            const int hdr[4] = {0, 0, (int)(uint32_t)(seed & 0xffffffffu), (int)(uint32_t)(seed >> 32)};  // step index | pad | seed
-            SHOWO_CHECK_HIP(hipMemcpyAsync(e->sched_dev, sched.data(), sizeof(float) * 2 * steps, hipMemcpyHostToDevice, s));
-            SHOWO_CHECK_HIP(hipMemcpyAsync(e->step_dev, hdr, sizeof(hdr), hipMemcpyHostToDevice, s));
-            SHOWO_CHECK_HIP(hipStreamSynchronize(s));  // `sched` / `hdr` are host temporaries
-        }
-        showo::sampler_set_device_step(e->step_dev, e->sched_dev, steps);
-        showo_engine::T2IGraphKey key;
-        memset(&key, 0, sizeof(key));  // padding bytes take part in the memcmp below
-        key.B = B; key.nseq = nseq; key.L = L; key.N = N; key.prefix = prefix; key.steps = steps; key.id_offset = id_offset;
-        key.codebook = codebook; key.reuse = reuse ? 1 : 0; key.cfg = cfg ? 1 : 0; key.has_iv = iv ? 1 : 0;
-        key.mask_id = mask_id; key.guidance = guidance; key.prec = e->precision;
-        key.p[11] = (reuse && pfast) ? e->tk_lo : nullptr; key.p[12] = (reuse && pfast) ? e->tvt_lo : nullptr;
-        if (!reuse) { key.p[0] = iv; key.p[1] = flag; key.p[2] = mask; }  // with reuse the captured step reads e->iv_act only
-        key.p[3] = exp_noise; key.p[4] = uniform; key.p[5] = e->row_logits;
-        key.p[6] = reuse ? e->tk : nullptr; key.p[7] = reuse ? e->tvt : nullptr; key.p[8] = e->sched_dev; key.p[9] = e->step_dev; key.p[10] = s;
-        showo_engine::T2IGraphEntry* ent = nullptr;
-        for (auto& ge : e->t2i_graphs)
-            if (memcmp(&key, &ge.key, sizeof(key)) == 0) { ent = &ge; break; }
-        const bool hit = ent != nullptr;
-        int rc = 0;
-        const int first_replay = hit ? 1 : n_eager;
-        for (int i = 0; i < first_replay && !rc; ++i) {
-            rc = denoise_step(-1, i == 0 || !reuse);
-            if (!rc) rc = showo::sampler_step_inc(e->step_dev, s);
-        }
-        if (!rc && !hit) {
-            hipGraphExec_t exec = nullptr;
-            rc = showo::capture_step(s, [&]() -> int {
-                const int rs = denoise_step(-1, !reuse);
-                return rs ? rs : showo::sampler_step_inc(e->step_dev, s);
-            }, &exec);
-            if (!rc) {
-                if ((int)e->t2i_graphs.size() >= showo_engine::T2I_GRAPH_SLOTS) {  // evict the least recently used graph
-                    size_t lru = 0;
-                    for (size_t i = 1; i < e->t2i_graphs.size(); ++i)
-                        if (e->t2i_graphs[i].last_use < e->t2i_graphs[lru].last_use) lru = i;
-                    // the evicted graph may still be executing a previous call's replays on another stream
-                    hipDeviceSynchronize();
-                    hipGraphExecDestroy(e->t2i_graphs[lru].exec);
-                    e->t2i_graphs.erase(e->t2i_graphs.begin() + lru);
-                }
-                e->t2i_graphs.push_back(showo_engine::T2IGraphEntry{key, exec, 0});
-                ent = &e->t2i_graphs.back();
-                e->t2i_captures++;
-            }
-        }
-        if (!rc) ent->last_use = ++e->t2i_tick;
-        for (int step = first_replay; !rc && step < steps; ++step) {
-            hipError_t he = hipGraphLaunch(ent->exec, s);
-            if (he != hipSuccess) rc = set_error_hip(he, "hipGraphLaunch", __FILE__, __LINE__);
-        }
-        showo::sampler_set_device_step(nullptr, nullptr, 0);
-        if (rc) return rc;
-    }
-    if (check_pending) {
-        SHOWO_CHECK_HIP(hipEventSynchronize(e->ev_pfx));  // recorded before the first step: long since complete
-        if (*(volatile int32_t*)e->pfx_host) continue;  // a text row sees an image column (or the mask is not an interval mask): repeat without reuse
-    }
-    break;
-    }  // attempt
-    copy_i64_kernel<<<dim3((B * L + thr - 1) / thr), dim3(thr), 0, s>>>(e->ids_all, ids_cond, B * L);  // in-place update like the reference
-    copy_i64_kernel<<<dim3((B * N + thr - 1) / thr), dim3(thr), 0, s>>>(e->sampled, sampled_out, B * N);
-    SHOWO_CHECK_HIP(hipGetLastError());
-    return 0;
 }
 
 // Visibility intervals built on the device (showo_mask_predict_next / _mmu / _mmu_vit) instead of a dense mask: the next

@@ -935,21 +935,22 @@ def test_full_size_t2i_generate_is_reproducible_and_graph_equals_eager():
     assert torch.equal(again, outs[0])  # back on bf16 images: the first run's tokens
 
 
-def test_t2i_graph_cache_survives_fresh_masks_ragged_batches_and_cfg_changes():
-    """VERDICT r2 #8 / ADVICE r2: the reference caller builds a NEW mask tensor for every batch (inference_t2i.py:290-318).  The cached
-    hipGraph of the denoise step is keyed on what is baked into its launches, not on the caller's mask pointer: equal masks in fresh
-    tensors replay the same graph (captures stays 1); a ragged last batch and a call without CFG get their own graphs WITHOUT
-    evicting the first (small LRU), and each key keeps producing the tokens of the eager loop (B and the cfg flag are in the key)."""
-    P = util.pkg()
-    d, sd = util.tiny_state()
-    m = util.build_showo(d, sd, max_batch=16, max_seq=64)
-    eng = m.engine()
-    caps = lambda: util.lib().load().showo_engine_t2i_captures(eng)
-    cfg = util.gen_config(d)
-    N, T = d.num_vq_tokens, d.max_text_len + 1
-    rs = np.random.RandomState(8)
+class _TinyT2I:
+    """the tiny model behind max_batch=16, max_seq=64 and the calls the graph-cache tests make on it: random left-padded prompts with
+    their unconditional twins, a NEW mask tensor per call, seeded t2i_generate"""
 
-    def batch(B):
+    def __init__(self):
+        self.d, sd = util.tiny_state()
+        self.m = util.build_showo(self.d, sd, max_batch=16, max_seq=64)
+        self.cfg = util.gen_config(self.d)
+        self.rs = np.random.RandomState(8)
+
+    def caps(self):
+        return util.lib().load().showo_engine_t2i_captures(self.m.engine())
+
+    def batch(self, B):
+        d, rs = self.d, self.rs
+        N, T = d.num_vq_tokens, d.max_text_len + 1
         rows_c, rows_u = [], []
         for _ in range(B):
             k = int(rs.randint(3, T))
@@ -958,14 +959,24 @@ def test_t2i_graph_cache_survives_fresh_masks_ragged_batches_and_cfg_changes():
             rows_u.append([d.pad_id] * (T - 3) + [d.t2i_id, 250, 250] + [d.soi_id] + [d.mask_token_id] * N + [d.eoi_id])
         return torch.tensor(rows_c).cuda(), torch.tensor(rows_u).cuda()
 
-    def fresh_mask(ic, iu):
+    def fresh_mask(self, ic, iu):
+        d = self.d
         both = torch.cat([ic, iu]) if iu is not None else ic
         return O.mask_t2i(both.cpu(), d.pad_id, d.soi_id, d.eoi_id).cuda().clone()  # a new tensor every time, like the reference
 
-    def run(ic, iu, w, seed, **kw):
+    def run(self, ic, iu, w, seed, timesteps=6, **kw):
         gen = torch.Generator(device="cuda").manual_seed(seed)
-        return m.t2i_generate(input_ids=ic.clone(), uncond_input_ids=iu, attention_mask=fresh_mask(ic, iu if w > 0 else None), timesteps=6,
-                              guidance_scale=w, generator=gen, config=cfg, **kw)
+        return self.m.t2i_generate(input_ids=ic.clone(), uncond_input_ids=iu, attention_mask=self.fresh_mask(ic, iu if w > 0 else None),
+                                   timesteps=timesteps, guidance_scale=w, generator=gen, config=self.cfg, **kw)
+
+
+def test_t2i_graph_cache_survives_fresh_masks_ragged_batches_and_cfg_changes():
+    """VERDICT r2 #8 / ADVICE r2: the reference caller builds a NEW mask tensor for every batch (inference_t2i.py:290-318).  The cached
+    hipGraph of the denoise step is keyed on what is baked into its launches, not on the caller's mask pointer: equal masks in fresh
+    tensors replay the same graph (captures stays 1); a ragged last batch and a call without CFG get their own graphs WITHOUT
+    evicting the first (small LRU), and each key keeps producing the tokens of the eager loop (B and the cfg flag are in the key)."""
+    t = _TinyT2I()
+    m, cfg, caps, batch, run = t.m, t.cfg, t.caps, t.batch, t.run
 
     ic4, iu4 = batch(4)
     keep = [torch.empty(1 << 20, device="cuda") for _ in range(3)]  # perturb the caching allocator between calls
@@ -994,6 +1005,41 @@ def test_t2i_graph_cache_survives_fresh_masks_ragged_batches_and_cfg_changes():
     f2 = m.t2i_generate(input_ids=ic4.clone(), uncond_input_ids=iu4, attention_mask=full_vis.clone(), timesteps=6, guidance_scale=2.0,
                         generator=gen, config=cfg, use_graph=0, reuse_prefix=False)
     assert torch.equal(f1, f2)
+
+
+def test_t2i_graph_cache_evicts_the_least_recently_used_graph_and_a_hit_refreshes_its_key():
+    """The LRU of instantiated denoise-step graphs (6 slots): seven calls that differ only in the step count (part of the key) capture
+    seven graphs, the seventh evicting the first.  A repeat of the newest key replays; a repeat of the oldest captures again; and the
+    newest key, touched in between, survives that capture (the eviction takes the least recently USED entry, not the oldest insert).
+    Every graphed call gives the tokens of the eager loop under the same seed."""
+    t = _TinyT2I()
+    ic, iu = t.batch(2)
+    eager = {n: t.run(ic, iu, 2.0, 20 + n, timesteps=n, use_graph=0) for n in range(3, 10)}
+    assert t.caps() == 0
+
+    def graphed(n, want_caps):
+        out = t.run(ic, iu, 2.0, 20 + n, timesteps=n)
+        assert t.caps() == want_caps, (n, t.caps(), want_caps)
+        assert torch.equal(out, eager[n]), n
+
+    for i, n in enumerate(range(3, 10)):
+        graphed(n, i + 1)       # 1, 2, ..., 7 captures; the seventh evicts timesteps=3
+    graphed(9, 7)               # the newest key: cached
+    graphed(3, 8)               # the oldest key was evicted: exactly one new capture (which evicts timesteps=4, not 9)
+    graphed(9, 8)               # touched before the re-capture: still cached
+
+
+def test_t2i_schedule_upload_by_kernel_argument_and_by_copy_give_the_eager_tokens():
+    """The per-step schedule reaches the device as kernel arguments while 2 * steps <= 512 floats fit them, else through a host copy and
+    a synchronise: timesteps=256 is the last call on the first side, 257 the first on the second.  Each equals its eager run token
+    for token and captures exactly once."""
+    t = _TinyT2I()
+    ic, iu = t.batch(2)
+    for k, n in enumerate((257, 256)):
+        got = t.run(ic, iu, 2.0, 31, timesteps=n)
+        assert t.caps() == k + 1, (n, t.caps())
+        assert torch.equal(got, t.run(ic, iu, 2.0, 31, timesteps=n, use_graph=0)), n
+        assert t.caps() == k + 1
 
 
 def test_forward_edge_sizes_empty_batch_and_maximum_positions():
