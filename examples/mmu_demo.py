@@ -69,6 +69,11 @@ def main():
     ap.add_argument("--ban", default=None, help="comma-separated token ids (or, with --tokenizer, words) that must not be produced")
     ap.add_argument("--allow", default=None,
                     help="comma-separated token ids (or words) the answer is confined to, e.g. 'yes,no'; <eos> stays allowed")
+    ap.add_argument("--no-repeat-ngram", type=int, default=None, help="no n-gram of this size may occur twice (1..16; no_repeat_ngram_size)")
+    ap.add_argument("--min-new-tokens", type=int, default=None, help="<eos> is held back until the answer has this many tokens")
+    ap.add_argument("--bad-words", default=None,
+                    help="token-id sequences that must never be completed: ids separated by spaces, sequences by ';', e.g. '13 198;50256'")
+    ap.add_argument("--stop", default=None, help="token-id sequences that end the answer, in the format of --bad-words, e.g. '198 198;13'")
     ap.add_argument("--num-beams", type=int, default=None, help="beam search with this many beams (2..8; greedy settings otherwise)")
     ap.add_argument("--length-penalty", type=float, default=1.0, help="with --num-beams: a hypothesis scores sum of log-probs / len ** this")
     ap.add_argument("--early-stopping", action="store_true", help="with --num-beams: stop once as many hypotheses are finished")
@@ -121,6 +126,16 @@ def main():
         adjust["banned_tokens"] = token_set(a.ban)
     if a.allow:
         adjust["allowed_tokens"] = token_set(a.allow) + ([int(tok.eos_token_id)] if tok.eos_token_id is not None else [])
+    # sequence rules (the history is `repetition_context`, then the answer so far): only what was given is passed on
+    id_seqs = lambda arg: [[int(t) for t in seq.split()] for seq in arg.split(";") if seq.strip()]
+    if a.no_repeat_ngram is not None:
+        adjust["no_repeat_ngram_size"] = a.no_repeat_ngram
+    if a.min_new_tokens is not None:
+        adjust["min_new_tokens"] = a.min_new_tokens
+    if a.bad_words:
+        adjust["bad_words_ids"] = id_seqs(a.bad_words)
+    if a.stop:
+        adjust["stop_sequences"] = id_seqs(a.stop)
     if a.num_beams is not None:  # (beam search on the device; it takes the greedy settings and no adjustment)
         adjust.update(num_beams=a.num_beams, length_penalty=a.length_penalty, early_stopping=a.early_stopping)
     with torch.no_grad():

@@ -944,6 +944,55 @@ int showo_engine_batch_decode_sample_adj(showo_engine* e, int64_t* tok, int n_st
                                          const int* draw0, const float* const* exp_noise, const int* budget, int64_t eot, int* produced,
                                          float* logprobs, int32_t* ranks, uint32_t* seen, int64_t seen_ld, const float* penalty,
                                          const float* const* bias, float* adj_ws, int use_graph, void* stream);
+/* Sequence rules: no-repeat n-grams, multi-token bad words and a minimum length in front of the pick, on the device
+ * (csrc/seq_rules.hip; DESIGN.md, "Sequence rules").  Per row, the history h[0, len) is a list of token ids in device memory: the
+ * request's context ids (ctx_len of them), then every token the call has fed.  A token w is banned for the pick of a row if
+ *   n-gram      n = ngram >= 1: some j, 0 <= j <= len - n, has h[j .. j+n-2] == h[len-n+1 .. len-1] (n - 1 tokens) and w == h[j+n-1]
+ *               (Hugging Face's NoRepeatNGramLogitsProcessor on h; n == 1 bans every token of h), or
+ *   bad word    a sequence s of the row's table with m = |s| >= 2 and len >= m - 1 has h[len-m+1 .. len-1] == s[0 .. m-2] and
+ *               w == s[m-1] (NoBadWordsLogitsProcessor, without its skip of a prefix that is the whole input), or
+ *   min length  w == eot and len - ctx_len < min_new (MinNewTokensLengthLogitsProcessor).
+ * A banned token's fp32 entry becomes -inf (0xFF800000); every other entry keeps its bits.  Ids are compared as plain integers; an
+ * id outside [0, V), in the history or in a table, is never stored to: no store lands outside [row, row + V).
+ * struct showo_seq_rules, part of this ABI and fixed for a call: hist int32 [nrows, hist_ld] and hist_len int32 [nrows] on the device, owned
+ * by the caller (which seeds them with the context); ngram (0: off, at most 16), ctx_len, min_new: HOST int32 [nrows]; eot (< 0: no
+ * minimum-length rule); bad: NULL, or a HOST array of nrows device pointers to bad-word tables, NULL entries allowed.
+ * Bad-word table (flat int32, device): t[0] = S, the number of sequences; t[1 .. S+1] = S + 1 offsets, off[0] = 0, non-decreasing;
+ * t[S+2 ..] = the tokens: sequence i is tokens[off[i], off[i+1]).  Sequences shorter than 2 are skipped (a single id is a bias of
+ * -inf).  The kernel walks any S and any length; the table is trusted as the bitmap of the adjustment is.
+ * Limits: ngram <= 16, hist_ld in [1, 2^31); nothing else (rows go 32 to a launch).  Beyond them: error 1 before any launch.
+ * showo_seq_ban: works in place on the fp32 rows rows + r * ld (ld >= V, 4-byte aligned), r < nrows.  mark: NULL, or int64 [nrows]
+ * (device): a mark in [0, V) is the newest member of row r's history -- the rules see hist[r][0, len0) ++ [mark[r]] -- and is stored
+ * (hist[r][len0] = mark[r], hist_len[r] = len0 + 1) if len0 < hist_ld; a full row stores nothing and nothing is read or written
+ * beyond hist_ld; a mark outside [0, V) (the -1 of an idle slot) means none.  active: NULL, or int32 [nrows] (device): a row whose
+ * entry is 0 is neither appended to nor written.  A row left without a finite entry is picked from as the picks do today: the
+ * arg-max returns token 0 and the sampled draw sees NaN probabilities (the callers do not guard it).
+ * showo_engine_decode_sample_seq / showo_engine_batch_decode_sample_seq: the _adj entries with `rules` in front of use_graph: one
+ * ban launch per step directly behind the adjust launch, on adj_ws, marking the token the step FED with the activity the adjust
+ * launch uses; a request without penalty or bias passes penalty 1 and no bias row (the adjust launch is then a bit copy).  The
+ * batched entry bans the <eot> of rules->eot, which the caller sets to its `eot`. */
+typedef struct showo_seq_rules {
+    int32_t* hist;
+    int64_t hist_ld;
+    int32_t* hist_len;
+    const int32_t* ngram;
+    const int32_t* ctx_len;
+    const int32_t* min_new;
+    int64_t eot;
+    const int32_t* const* bad;
+} showo_seq_rules;
+int showo_seq_ban(float* rows, int64_t ld, int nrows, int V, const showo_seq_rules* rules, const int64_t* mark, const int32_t* active,
+                  void* stream);
+int showo_engine_decode_sample_seq(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws, int top_k,
+                                   float top_p, float temperature, const float* exp_noise, uint64_t seed, int step0, float* logprobs,
+                                   int32_t* ranks, uint32_t* seen, int64_t seen_ld, const float* penalty, const float* const* bias,
+                                   float* adj_ws, const showo_seq_rules* rules, int use_graph, void* stream);
+int showo_engine_batch_decode_sample_seq(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws,
+                                         const int* top_k, const float* top_p, const float* temperature, const uint64_t* seed,
+                                         const int* draw0, const float* const* exp_noise, const int* budget, int64_t eot, int* produced,
+                                         float* logprobs, int32_t* ranks, uint32_t* seen, int64_t seen_ld, const float* penalty,
+                                         const float* const* bias, float* adj_ws, const showo_seq_rules* rules, int use_graph,
+                                         void* stream);
 /* Beam search (csrc/beam.hip; DESIGN.md, "Beam search"): Hugging Face beam search for one prompt, do_sample=False, no processors,
  * B = number of beams = the slots of a regular batch, every slot a showo_engine_batch_fork of the engine's cache.
  * A candidate (beam b, token i) of a step scores cum[b] + lp(b, i), lp the log-softmax of the RAW logits (showo_logprob_rows' value

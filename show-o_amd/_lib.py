@@ -246,6 +246,13 @@ _PROTOS = {
     "showo_engine_decode_sample_adj": [c_p, c_p, c_i, c_p, c_p, c_i, c_f, c_f, c_p, c_u64, c_i, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_i, c_p],
     "showo_engine_batch_decode_sample_adj": [c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p,
                                              c_p, c_p, c_i, c_p],
+    # sequence rules (csrc/seq_rules.hip): the stand-alone ban on fp32 rows, and the _adj decode loops with one ban launch behind the
+    # adjust launch (a showo_seq_rules pointer, the SeqRules structure below, in front of use_graph)
+    "showo_seq_ban": [c_p, c_i64, c_i, c_i, c_p, c_p, c_p, c_p],
+    "showo_engine_decode_sample_seq": [c_p, c_p, c_i, c_p, c_p, c_i, c_f, c_f, c_p, c_u64, c_i, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_i,
+                                       c_p],
+    "showo_engine_batch_decode_sample_seq": [c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64, c_p,
+                                             c_p, c_p, c_p, c_i, c_p],
     # beam search (csrc/beam.hip): the selection and the parent copy alone, and the batched loop (state, ..., trace x 4, hyp)
     "showo_beam_select": [c_p, c_i64, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_p],
     "showo_kv_permute_rows": [c_p, c_p, c_i, c_i64, c_i64, c_i, c_i, c_i, c_p, c_i, c_p, c_p, c_p, c_i, c_p],
@@ -287,6 +294,12 @@ class EngineConfig(C.Structure):
     _fields_ = [("hidden", c_i), ("layers", c_i), ("heads", c_i), ("ffn", c_i), ("vocab", c_i),
                 ("rotary_dim", c_i), ("max_pos", c_i), ("ln_eps", c_f), ("rope_theta", c_f),
                 ("max_batch", c_i), ("max_seq", c_i)]
+
+
+class SeqRules(C.Structure):
+    """showo_seq_rules (include/showo_hip.h, "Sequence rules"): device history and lengths, host arrays with one entry per row"""
+    _fields_ = [("hist", c_p), ("hist_ld", c_i64), ("hist_len", c_p), ("ngram", c_p), ("ctx_len", c_p), ("min_new", c_p), ("eot", c_i64),
+                ("bad", c_p)]
 
 
 class VQConfig(C.Structure):

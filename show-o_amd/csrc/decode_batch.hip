@@ -24,6 +24,7 @@
 #include "decode_wide.h"
 #include "attn_shared.h"
 #include "logit_adjust.h"
+#include "seq_rules.h"
 #include "beam.h"
 #include <cmath>
 #include <cstddef>
@@ -918,10 +919,13 @@ extern "C" int showo_engine_batch_decode_greedy(showo_engine* e, int64_t* tok, i
 // adj != NULL (showo_engine_batch_decode_sample_adj): one adjust launch for all nb slots between the layers and the seam reads
 // logits_ws, marks tok[b] of the slots whose SlotDraw.active is set (an idle slot is skipped) and writes adj->ws, which the seam reads
 // instead; logprob_slots_kernel keeps reading logits_ws.  The <= 8 slots, the wide slots and the shared-prefix slots share this seam.
+// seq != NULL (showo_engine_batch_decode_sample_seq; needs adj): one ban launch for all nb slots directly behind the adjust launch
+// works on adj->ws in place and appends tok[b] of the active slots to their device histories (seq_rules.hip).
 static int batch_decode_sample(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws, const int* top_k,
                                const float* top_p, const float* temperature, const uint64_t* seed, const int* draw0,
                                const float* const* exp_noise, const int* budget, int64_t eot, int* produced, int use_graph, void* stream,
-                               float* lps = nullptr, int32_t* ranks = nullptr, const showo::LogitAdjust* adj = nullptr) {
+                               float* lps = nullptr, int32_t* ranks = nullptr, const showo::LogitAdjust* adj = nullptr,
+                               const showo_seq_rules* seq = nullptr) {
     hipStream_t s = (hipStream_t)stream;
     if (!e || !e->bd || e->bd->nb == 0) return set_error_msg(1, "batch_decode_sample: showo_engine_batch_begin + _batch_prefill first");
     auto* d = e->bd;
@@ -932,6 +936,9 @@ static int batch_decode_sample(showo_engine* e, int64_t* tok, int n_steps, int64
     if (adj) {
         if (!adj->ws || adj->ws == logits_ws) return set_error_msg(1, "batch_decode_sample_adj: needs an adj_ws [nb, V] of its own");
         TRY(showo::logits_adjust_check(nb, V, adj->seen, adj->seen_ld, adj->penalty, "batch_decode_sample_adj"));
+        if (seq) TRY(showo::seq_rules_check(nb, seq, "batch_decode_sample_seq"));
+    } else if (seq) {
+        return set_error_msg(1, "batch_decode_sample_seq: the rules work on the adjusted rows");
     }
     const int op = e->precision == 2 ? SHOWO_OP_F16 : SHOWO_OP_BF16;
     // positions stay below lim: the cache capacity and the rotary tables (max_position_embeddings)
@@ -981,6 +988,7 @@ static int batch_decode_sample(showo_engine* e, int64_t* tok, int n_steps, int64
             const int* active = reinterpret_cast<const int*>(reinterpret_cast<const char*>(d->slots_dev) + offsetof(SlotDraw, active));
             TRY(showo::logits_adjust_launch(logits_ws, V, nb, V, adj->seen, adj->seen_ld, tok, adj->penalty, adj->bias, active,
                                             (int)(sizeof(SlotDraw) / sizeof(int)), adj->ws, V, s));
+            if (seq) TRY(showo::seq_ban_launch(adj->ws, V, nb, V, seq, tok, active, (int)(sizeof(SlotDraw) / sizeof(int)), s));
             pick = adj->ws;
         }
         if (nucleus)
@@ -1040,6 +1048,19 @@ extern "C" int showo_engine_batch_decode_sample_adj(showo_engine* e, int64_t* to
     const showo::LogitAdjust adj{seen, seen_ld, penalty, bias, adj_ws};
     return batch_decode_sample(e, tok, n_steps, out_tokens, logits_ws, top_k, top_p, temperature, seed, draw0, exp_noise, budget, eot,
                                produced, use_graph, stream, logprobs, logprobs ? ranks : nullptr, &adj);
+}
+
+// showo_engine_batch_decode_sample_adj with the sequence rules behind the adjustment (include/showo_hip.h, "Sequence rules")
+extern "C" int showo_engine_batch_decode_sample_seq(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws,
+                                                    const int* top_k, const float* top_p, const float* temperature, const uint64_t* seed,
+                                                    const int* draw0, const float* const* exp_noise, const int* budget, int64_t eot,
+                                                    int* produced, float* logprobs, int32_t* ranks, uint32_t* seen, int64_t seen_ld,
+                                                    const float* penalty, const float* const* bias, float* adj_ws,
+                                                    const showo_seq_rules* rules, int use_graph, void* stream) {
+    if (!rules) return set_error_msg(1, "batch_decode_sample_seq: bad arguments");
+    const showo::LogitAdjust adj{seen, seen_ld, penalty, bias, adj_ws};
+    return batch_decode_sample(e, tok, n_steps, out_tokens, logits_ws, top_k, top_p, temperature, seed, draw0, exp_noise, budget, eot,
+                               produced, use_graph, stream, logprobs, logprobs ? ranks : nullptr, &adj, rules);
 }
 
 // ---- beam search (include/showo_hip.h, "Beam search") -----------------------------------------------------------------------

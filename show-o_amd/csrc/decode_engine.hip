@@ -7,6 +7,7 @@
 // fused launches of decode.hip); engine_prefill_into / engine_append_into also fill the slots of a decode batch (decode_batch.hip).
 #include "engine.h"
 #include "logit_adjust.h"
+#include "seq_rules.h"
 
 using namespace showo;
 
@@ -261,9 +262,12 @@ extern "C" int showo_engine_cache_ptrs(showo_engine* e, uint16_t** k, uint16_t**
 // adj != NULL (showo_engine_decode_sample_adj): one adjust launch behind the head reads logits_ws, marks *tok -- the token this step fed,
 // the newest member of the set -- and writes adj->ws, which the pick reads; the log-prob launch keeps reading logits_ws.  The greedy
 // form then leaves the fused token seam for the arg-max on adj->ws and the separate store / increment launches.  NULL: nothing changes.
+// seq != NULL (showo_engine_decode_sample_seq; needs adj): one ban launch directly behind the adjust launch works on adj->ws in place
+// and appends *tok to the device history (seq_rules.hip).
 static int decode_loop(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws, int top_k, float top_p,
                        float temperature, const float* exp_noise, uint64_t seed, int step0, int use_graph, void* stream,
-                       float* lps = nullptr, int32_t* ranks = nullptr, const showo::LogitAdjust* adj = nullptr) {
+                       float* lps = nullptr, int32_t* ranks = nullptr, const showo::LogitAdjust* adj = nullptr,
+                       const showo_seq_rules* seq = nullptr) {
     hipStream_t s = (hipStream_t)stream;
     if (!e || e->cache_len <= 0) return set_error_msg(1, "decode_greedy: prefill first");
     if (!tok || !out_tokens || !logits_ws || n_steps < 1) return set_error_msg(1, "decode_greedy: bad arguments");
@@ -315,6 +319,7 @@ static int decode_loop(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_
         if (adj) {
             TRY(showo::logits_adjust_launch(logits_ws, e->V, 1, e->V, adj->seen, adj->seen_ld, tok, adj->penalty, adj->bias, nullptr, 0, adj->ws,
                                             e->V, s));
+            if (seq) TRY(showo::seq_ban_launch(adj->ws, e->V, 1, e->V, seq, tok, nullptr, 0, s));
             pick = adj->ws;
         }
         if (top_k == 1) TRY(showo_argmax_f32(pick, e->V, tok, s));
@@ -376,4 +381,20 @@ extern "C" int showo_engine_decode_sample_adj(showo_engine* e, int64_t* tok, int
     const showo::LogitAdjust adj{seen, seen_ld, penalty, bias, adj_ws};
     return decode_loop(e, tok, n_steps, out_tokens, logits_ws, top_k, top_p, temperature, exp_noise, seed, step0, use_graph, stream,
                        logprobs, logprobs ? ranks : nullptr, &adj);
+}
+
+// showo_engine_decode_sample_adj with the sequence rules behind the adjustment (include/showo_hip.h, "Sequence rules")
+extern "C" int showo_engine_decode_sample_seq(showo_engine* e, int64_t* tok, int n_steps, int64_t* out_tokens, float* logits_ws, int top_k,
+                                              float top_p, float temperature, const float* exp_noise, uint64_t seed, int step0,
+                                              float* logprobs, int32_t* ranks, uint32_t* seen, int64_t seen_ld, const float* penalty,
+                                              const float* const* bias, float* adj_ws, const showo_seq_rules* rules, int use_graph,
+                                              void* stream) {
+    if (!(temperature > 0.f)) return set_error_msg(1, "decode_sample_seq: temperature must be > 0");
+    if (!(top_p > 0.f)) return set_error_msg(1, "decode_sample_seq: top_p must be > 0 (>= 1: no nucleus filter)");
+    if (!e || !adj_ws || adj_ws == logits_ws) return set_error_msg(1, "decode_sample_seq: needs an adj_ws [V] of its own");
+    TRY(showo::logits_adjust_check(1, e->V, seen, seen_ld, penalty, "decode_sample_seq"));
+    TRY(showo::seq_rules_check(1, rules, "decode_sample_seq"));
+    const showo::LogitAdjust adj{seen, seen_ld, penalty, bias, adj_ws};
+    return decode_loop(e, tok, n_steps, out_tokens, logits_ws, top_k, top_p, temperature, exp_noise, seed, step0, use_graph, stream,
+                       logprobs, logprobs ? ranks : nullptr, &adj, rules);
 }

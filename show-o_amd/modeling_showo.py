@@ -833,7 +833,8 @@ class Showo(PretrainedMixin, nn.Module):
     def mmu_generate(self, idx=None, input_embeddings=None, attention_mask=None, max_new_tokens=100, temperature=1.0,
                      top_k=None, eot_token=None, generator=None, _exp_noise=None, top_p=None, return_logprobs=False,
                      repetition_penalty=None, repetition_context=None, logit_bias=None, allowed_tokens=None, banned_tokens=None,
-                     num_beams=None, length_penalty=1.0, early_stopping=False, num_return_sequences=1, return_beam_scores=False):
+                     num_beams=None, length_penalty=1.0, early_stopping=False, num_return_sequences=1, return_beam_scores=False,
+                     no_repeat_ngram_size=None, bad_words_ids=None, min_new_tokens=None, stop_sequences=None):
         """reference signature + `generator` (seeds the on-device Philox stream of the multinomial draws; default: torch's
         global generator), `_exp_noise` fp32 [max_new_tokens, vocab] (parity tests inject the reference's Exp(1) draws) and `top_p`
         (nucleus sampling on the device behind the top-k filter, the reference's top_k_top_p_filtering: a token stays iff the mass of
@@ -853,6 +854,17 @@ class Showo(PretrainedMixin, nn.Module):
         call runs to `max_new_tokens`.  A row without a finite token, ids outside the vocabulary, theta <= 0 / NaN / inf: ValueError
         before the engine is touched.  `return_logprobs` stays the log-softmax of the RAW logits, adjusted or not.
 
+        Sequence rules ("Sequence rules"; all None: exactly the calls above, no bit changes).  The history of a call is the ids
+        of `repetition_context` followed by every token the call has produced.  `no_repeat_ngram_size` n (an int in 1..16): no n-gram of
+        the history may occur twice (Hugging Face's NoRepeatNGramLogitsProcessor); `bad_words_ids` (a list of id sequences): a sequence
+        is never completed (NoBadWordsLogitsProcessor; a one-token sequence is a banned token); `min_new_tokens` m (needs `eot_token`):
+        `eot_token` is banned while fewer than m tokens have been produced; all three put -inf on the banned tokens on the device,
+        behind the repetition penalty and the bias and in front of temperature / top-k / top-p.  `stop_sequences` (a list of id
+        sequences): the answer ends behind the first position at which the produced tokens end with one of them (it is part of the
+        answer, as <eot> is; whichever of <eot>, a stop sequence and max_new_tokens comes first wins).  Nothing persists across calls.
+        An empty sequence, ids outside the vocabulary, n outside 1..16, min_new_tokens < 0 or without eot_token, any of the four with
+        beams: ValueError before the engine is touched.
+
         Beam search ("Beam search"; `num_beams` None or 1: exactly the calls above, no bit changes): `num_beams` 2..8 runs
         Hugging Face's beam search (do_sample=False, no processors) on the device, the beams as the slots of a decode batch forked
         from the prompt's cache.  A hypothesis that ends on `eot_token` scores sum of log-probabilities / len ** `length_penalty`;
@@ -863,6 +875,7 @@ class Showo(PretrainedMixin, nn.Module):
         logit-adjustment keyword; precision 1 has no beams: ValueError before the engine is touched."""
         adj_kw = {k_: v for k_, v in zip(_ADJUST_KEYS, (repetition_penalty, repetition_context, logit_bias, allowed_tokens, banned_tokens))
                   if v is not None}
+        adj_kw.update({k_: v for k_, v in zip(_SEQ_KEYS, (no_repeat_ngram_size, bad_words_ids, min_new_tokens, stop_sequences)) if v is not None})
         beams = _beam_request(self, num_beams, length_penalty, early_stopping, num_return_sequences, return_beam_scores, max_new_tokens,
                               temperature, top_k, top_p, generator, _exp_noise, bool(adj_kw))
         if beams is not None:
@@ -874,7 +887,7 @@ class Showo(PretrainedMixin, nn.Module):
             L = _prefill(eng, *_prompt_args(self, eng, None if input_embeddings is not None else idx, input_embeddings, attention_mask), logits)
             hyps = _beam_search(self, eng, logits, L, beams, max_new_tokens, eot_token, float(length_penalty), early_stopping, dev)
             return _beam_result(hyps, num_return_sequences, return_logprobs, return_beam_scores, dev)
-        adjust = _adjust_of(self.vocab_size, **adj_kw) if adj_kw else None
+        adjust = _adjust_of(self.vocab_size, eot_token=eot_token, **adj_kw) if adj_kw else None
         adj_kw = {} if adjust is None else {"adjust": adjust}  # (None: the calls below are those of a call without the keywords)
         # greedy (top_k == 1) is the reference caller's setting (inference_mmu.py:81): multinomial of a one-hot = arg-max
         greedy, k, noise, seed, p = _draw_params(self, max_new_tokens, temperature, top_k, top_p, generator, _exp_noise)
@@ -917,10 +930,10 @@ def _nucleus_p(top_p):
 class _Adjust:
     """one request's logit adjustment: `theta` (the repetition penalty, 1.0: none), `bias` (None or the dense fp32 [V] row on the CPU:
     logit_bias, allowed_tokens and banned_tokens combined) and `context` (the ids the set of seen tokens starts with)"""
-    __slots__ = ("theta", "bias", "context")
+    __slots__ = ("theta", "bias", "context", "rules")
 
-    def __init__(self, theta, bias, context):
-        self.theta, self.bias, self.context = theta, bias, context
+    def __init__(self, theta, bias, context, rules=None):
+        self.theta, self.bias, self.context, self.rules = theta, bias, context, rules  # rules: None or the request's _SeqRules
 
 
 def _token_ids(V, ids, what):
@@ -966,61 +979,213 @@ def _bias_row(V, logit_bias=None, allowed_tokens=None, banned_tokens=None):
     return row if bool((row != 0).any()) else None
 
 
-def _adjust_of(V, repetition_penalty=None, repetition_context=None, logit_bias=None, allowed_tokens=None, banned_tokens=None):
-    """the _Adjust of one request, or None when the keywords change nothing (all None, or a penalty of 1 without a bias row): such a
-    request takes exactly the calls of one without the keywords.  ValueError for a penalty <= 0, NaN or inf and for what _bias_row
-    and _token_ids refuse -- before anything touches the engine."""
+def _adjust_of(V, repetition_penalty=None, repetition_context=None, logit_bias=None, allowed_tokens=None, banned_tokens=None,
+               no_repeat_ngram_size=None, bad_words_ids=None, min_new_tokens=None, stop_sequences=None, eot_token=None):
+    """the _Adjust of one request, or None when the keywords change nothing (all None, or a penalty of 1 without a bias row and no
+    sequence rule): such a request takes exactly the calls of one without the keywords.  ValueError for a penalty <= 0, NaN or inf and
+    for what _bias_row, _token_ids and _seq_rules_of refuse -- before anything touches the engine.  A request with sequence rules
+    alone is a penalty of 1 without a bias row: its adjust launch is a bit copy."""
     theta = 1.0 if repetition_penalty is None else float(repetition_penalty)
     if not (theta > 0 and math.isfinite(theta)):
         raise ValueError("repetition_penalty must be finite and > 0 (1: none)")
     context = _token_ids(V, repetition_context, "repetition_context")
+    rules, single = _seq_rules_of(V, no_repeat_ngram_size, bad_words_ids, min_new_tokens, stop_sequences, eot_token)
+    if single:  # bad words of one token are banned tokens: they live in the bias row
+        banned_tokens = _token_ids(V, banned_tokens, "banned_tokens") + single
     row = _bias_row(V, logit_bias, allowed_tokens, banned_tokens)
-    if theta == 1.0 and row is None:
+    if theta == 1.0 and row is None and rules is None:
         return None
-    return _Adjust(theta, row, context)
+    return _Adjust(theta, row, context, rules)
 
 
 _ADJUST_KEYS = ("repetition_penalty", "repetition_context", "logit_bias", "allowed_tokens", "banned_tokens")
+_SEQ_KEYS = ("no_repeat_ngram_size", "bad_words_ids", "min_new_tokens", "stop_sequences")
+
+# ---- sequence rules: no-repeat n-grams, multi-token bad words, minimum length, stop sequences (DESIGN.md, "Sequence rules") ---------------
+_SEQ_NGRAM_MAX = 16     # csrc/seq_rules.h SEQ_NGRAM_MAX
+_SEQ_BAD_MAX = 1024     # bad-word sequences per request (the kernel walks any number: this bounds the table a request may upload)
+_SEQ_BAD_LEN_MAX = 64   # tokens per bad-word sequence
+_SEQ_STOP_MAX = 256     # stop sequences per request, each of at most _SEQ_BAD_LEN_MAX tokens (host work)
 
 
-def _adjust_per_request(n, V, repetition_penalty=None, repetition_context=None, logit_bias=None, allowed_tokens=None, banned_tokens=None):
+class _SeqRules:
+    """one request's sequence rules: `ngram` (0: off), `bad` (the bad-word sequences of two tokens and more, tuples of ints), `min_new`
+    (0: off) and `stops` (the stop sequences, host work).  `table`: the flat int32 bad-word table of include/showo_hip.h (CPU) or None."""
+    __slots__ = ("ngram", "bad", "min_new", "stops", "table")
+
+    def __init__(self, ngram, bad, min_new, stops):
+        self.ngram, self.bad, self.min_new, self.stops = ngram, bad, min_new, stops
+        self.table = None
+        if bad:
+            off = [0]
+            for q in bad:
+                off.append(off[-1] + len(q))
+            self.table = torch.tensor([len(bad)] + off + [t for q in bad for t in q], dtype=torch.int32)
+
+    @property
+    def device(self):
+        """the request has a rule the device computes (stop sequences alone are host work)"""
+        return bool(self.ngram or self.bad or self.min_new)
+
+
+def _token_seqs(V, seqs, what, limit):
+    """`seqs` (a list / tuple of id collections, or a 2-D tensor) as a list of tuples of ints inside [0, V); ValueError for an empty
+    sequence, ids outside the vocabulary, more than `limit` sequences or more than _SEQ_BAD_LEN_MAX tokens in one"""
+    if isinstance(seqs, torch.Tensor):
+        if seqs.dim() != 2:
+            raise ValueError(f"{what}: a tensor must be 2-D (one sequence per row)")
+        seqs = seqs.tolist()
+    if not isinstance(seqs, (list, tuple)):
+        raise ValueError(f"{what}: a list of token-id sequences")
+    if len(seqs) > limit:
+        raise ValueError(f"{what}: at most {limit} sequences")
+    out = []
+    for q in seqs:
+        if not isinstance(q, (list, tuple, torch.Tensor)):
+            raise ValueError(f"{what}: every entry is a sequence of token ids, got {q!r}")
+        ids = _token_ids(V, q, what)
+        if not ids:
+            raise ValueError(f"{what}: an empty sequence")
+        if len(ids) > _SEQ_BAD_LEN_MAX:
+            raise ValueError(f"{what}: at most {_SEQ_BAD_LEN_MAX} tokens per sequence")
+        out.append(tuple(ids))
+    return out
+
+
+def _seq_rules_of(V, no_repeat_ngram_size=None, bad_words_ids=None, min_new_tokens=None, stop_sequences=None, eot_token=None):
+    """(the _SeqRules of one request or None when the keywords change nothing, the ids of its one-token bad words).  ValueError: a
+    no_repeat_ngram_size that is not an int in 1.._SEQ_NGRAM_MAX, an empty or over-long sequence, ids outside the vocabulary, a
+    min_new_tokens that is not an int >= 0 or comes without an eot_token."""
+    n = 0
+    if no_repeat_ngram_size is not None:
+        n = no_repeat_ngram_size
+        if isinstance(n, bool) or not isinstance(n, numbers.Integral) or not 1 <= int(n) <= _SEQ_NGRAM_MAX:
+            raise ValueError(f"no_repeat_ngram_size must be an int in 1..{_SEQ_NGRAM_MAX}")
+        n = int(n)
+    m = 0
+    if min_new_tokens is not None:
+        m = min_new_tokens
+        if isinstance(m, bool) or not isinstance(m, numbers.Integral) or int(m) < 0:
+            raise ValueError("min_new_tokens must be an int >= 0")
+        if eot_token is None:
+            raise ValueError("min_new_tokens needs an eot_token (it is the token the rule holds back)")
+        m = int(m)
+    bad = [] if bad_words_ids is None else _token_seqs(V, bad_words_ids, "bad_words_ids", _SEQ_BAD_MAX)
+    stops = [] if stop_sequences is None else _token_seqs(V, stop_sequences, "stop_sequences", _SEQ_STOP_MAX)
+    single = [q[0] for q in bad if len(q) == 1]
+    bad = [q for q in bad if len(q) > 1]
+    if not (n or m or bad or stops):
+        return None, single
+    return _SeqRules(n, bad, m, stops), single
+
+
+def _stop_len(tokens, stops, eot_token, start=0):
+    """the length of the answer `tokens` cut behind the first position i >= start at which it ends: tokens[i] is the eot_token, or
+    tokens[:i + 1] ends with one of the stop sequences (a match may begin in front of `start`); None when it does not end"""
+    for i in range(start, len(tokens)):
+        if eot_token is not None and tokens[i] == eot_token:
+            return i + 1
+        for q in stops or ():
+            if len(q) <= i + 1 and tuple(tokens[i + 1 - len(q):i + 1]) == tuple(q):
+                return i + 1
+    return None
+
+
+def _adjust_per_request(n, V, repetition_penalty=None, repetition_context=None, logit_bias=None, allowed_tokens=None, banned_tokens=None,
+                        no_repeat_ngram_size=None, bad_words_ids=None, min_new_tokens=None, stop_sequences=None, eot_token=None):
     """(adjusts, kws) of a batch call, the convention of _per_request: every keyword is one value shared by all n requests or a
-    list / tuple of n per-request values.  A penalty or bias list is always per request; an id keyword (context, allowed, banned) is per
-    request when it is a list / tuple whose entries are None or id collections themselves, else one shared collection of ids.
+    list / tuple of n per-request values.  A penalty, bias, no_repeat_ngram_size or min_new_tokens list is always per request; an id
+    keyword (context, allowed, banned) is per request when it is a list / tuple whose entries are None or id collections themselves,
+    else one shared collection of ids; a sequence keyword (bad_words_ids, stop_sequences) is per request when its entries are None or
+    lists of sequences themselves, else one shared list of sequences.
     adjusts: None when no request adjusts, else n entries (None | _Adjust), ONE _Adjust (one dense row) per distinct request;
     kws[b]: the keywords of the single call of request b."""
     groups = (list, tuple, set, frozenset, range, torch.Tensor)
 
-    def spread(v, ids):
-        per = isinstance(v, (list, tuple)) and (not ids or (len(v) > 0 and all(t is None or isinstance(t, groups) for t in v)))
+    def nested(t):  # a list of sequences, not a sequence of ids
+        if isinstance(t, torch.Tensor):
+            return t.dim() == 2
+        return isinstance(t, (list, tuple)) and all(isinstance(q, (list, tuple, torch.Tensor)) for q in t)
+
+    def spread(v, kind):
+        per = isinstance(v, (list, tuple)) and (kind == 0 or (len(v) > 0 and all(
+            t is None or (isinstance(t, groups) if kind == 1 else nested(t)) for t in v)))
         if per and len(v) != n:
-            raise ValueError("repetition_penalty / repetition_context / logit_bias / allowed_tokens / banned_tokens lists need one entry per "
-                             "sequence")
+            raise ValueError("repetition_penalty / repetition_context / logit_bias / allowed_tokens / banned_tokens / no_repeat_ngram_size / "
+                             "bad_words_ids / min_new_tokens / stop_sequences lists need one entry per sequence")
         return list(v) if per else [v] * n
 
-    cols = [spread(v, ids) for v, ids in ((repetition_penalty, False), (repetition_context, True), (logit_bias, False),
-                                          (allowed_tokens, True), (banned_tokens, True))]
+    cols = [spread(v, kind) for v, kind in ((repetition_penalty, 0), (repetition_context, 1), (logit_bias, 0), (allowed_tokens, 1),
+                                            (banned_tokens, 1), (no_repeat_ngram_size, 0), (bad_words_ids, 2), (min_new_tokens, 0),
+                                            (stop_sequences, 2))]
     made, adjusts, kws = {}, [], []
     for b in range(n):
         vals = [c[b] for c in cols]
-        key = (None if vals[0] is None else float(vals[0]),) + tuple(id(v) for v in vals[1:])
+        key = (None if vals[0] is None else float(vals[0]),) + tuple(v if isinstance(v, int) else id(v) for v in vals[1:])
         if key not in made:
-            made[key] = _adjust_of(V, *vals)
+            made[key] = _adjust_of(V, *vals, eot_token=eot_token)
         adjusts.append(made[key])
-        kws.append({k: v for k, v in zip(_ADJUST_KEYS, vals) if v is not None})
+        kws.append({k: v for k, v in zip(_ADJUST_KEYS + _SEQ_KEYS, vals) if v is not None})
     return (None if all(a is None for a in adjusts) else adjusts), kws
+
+
+def _hist_ld(adjusts, max_new_tokens):
+    """columns of the device history a call needs: the longest context plus max_new_tokens; None when no request has a device rule"""
+    ruled = [a for a in adjusts if a is not None and a.rules is not None and a.rules.device]
+    return max(len(a.context) for a in ruled) + max(int(max_new_tokens), 1) if ruled else None
 
 
 class _AdjustState:
     """device side of the adjustment of `rows` logits rows (one decode slot each): the bitmap of seen tokens [rows, ceil(V / 32)], the
-    adjusted rows [rows, V] the picks read, and the bias rows, uploaded once per distinct request.  Nothing here outlives the call."""
+    adjusted rows [rows, V] the picks read, and the bias rows, uploaded once per distinct request.  `hist_ld` (not None: some request
+    has a sequence rule the device computes): also the token histories int32 [rows, hist_ld] with their lengths [rows], seeded with the
+    context when a row is (re)filled, and the bad-word tables, uploaded once per distinct request; `eot`: the token the minimum-length
+    rule holds back.  Nothing here outlives the call."""
 
-    def __init__(self, V, rows, dev):
+    def __init__(self, V, rows, dev, hist_ld=None, eot=None):
         self.V, self.W, self.dev = V, (V + 31) // 32, dev
         self.seen = torch.zeros((rows, self.W), dtype=torch.int32, device=dev)
         self.ws = torch.empty((rows, V), dtype=torch.float32, device=dev)
         self.adj = [None] * rows  # the _Adjust of the request each row serves (None: unadjusted)
         self._bias = {}
+        self.ruled = hist_ld is not None
+        if self.ruled:
+            self.hist_ld, self.eot = int(hist_ld), -1 if eot is None else int(eot)
+            self.hist = torch.zeros((rows, self.hist_ld), dtype=torch.int32, device=dev)
+            self.hist_len = torch.zeros((rows,), dtype=torch.int32, device=dev)
+            self._bad = {}
+
+    def bad(self, a):
+        if a is None or a.rules is None or a.rules.table is None:
+            return None
+        if id(a) not in self._bad:
+            self._bad[id(a)] = a.rules.table.to(self.dev).contiguous()
+        return self._bad[id(a)]
+
+    def rules_args(self, s=None):
+        """(pointer to the showo_seq_rules of all rows, or of row s alone; what must stay alive over the call)"""
+        import ctypes as C
+        rows = list(range(len(self.adj))) if s is None else [s]
+        rl = [None if self.adj[r] is None or self.adj[r].rules is None or not self.adj[r].rules.device else self.adj[r].rules for r in rows]
+        n = len(rows)
+        ngram = (C.c_int32 * n)(*[0 if q is None else q.ngram for q in rl])
+        ctx = (C.c_int32 * n)(*[0 if q is None else len(self.adj[r].context) for r, q in zip(rows, rl)])  # (what seed() put there)
+        mnew = (C.c_int32 * n)(*[0 if q is None else q.min_new for q in rl])
+        bad = (C.c_void_p * n)(*[_lib.ptr(self.bad(self.adj[r])) for r in rows])
+        r0 = rows[0]
+        from ._lib import SeqRules
+        st = SeqRules(_lib.ptr(self.hist[r0]), self.hist_ld, _lib.ptr(self.hist_len[r0:]), C.cast(ngram, C.c_void_p),
+                           C.cast(ctx, C.c_void_p), C.cast(mnew, C.c_void_p), self.eot, C.cast(bad, C.c_void_p))
+        return C.c_void_p(C.addressof(st)), (st, ngram, ctx, mnew, bad)
+
+    def ban(self, s, mark=None):
+        """the stand-alone ban on the adjusted row of slot s, in place; mark: None, or the one-element int64 device view of the token
+        that joins row s's history in front of the rules"""
+        if not self.ruled or self.adj[s] is None or self.adj[s].rules is None or not self.adj[s].rules.device:
+            return
+        args, keep = self.rules_args(s)
+        _lib.call("showo_seq_ban", _lib.ptr(self.ws[s]), self.V, 1, self.V, args, _lib.ptr(mark), None, _lib.stream())
+        del keep
 
     def bias(self, a):
         if a is None or a.bias is None:
@@ -1036,6 +1201,11 @@ class _AdjustState:
         if a is not None and a.context:
             ids = torch.tensor(a.context, dtype=torch.int64, device=self.dev)
             _lib.call("showo_seen_mark", _lib.ptr(self.seen[s]), self.V, _lib.ptr(ids), len(a.context), _lib.stream())
+        if self.ruled:  # the history starts as the context (only a request with a device rule reads it)
+            c = len(a.context) if a is not None and a.rules is not None and a.rules.device else 0
+            if c:
+                self.hist[s, :c].copy_(torch.tensor(a.context, dtype=torch.int32))
+            self.hist_len[s:s + 1].fill_(c)
 
     def mark(self, s, tok):
         """the one-element int64 device view `tok` joins row s's set"""
@@ -1062,7 +1232,15 @@ class _AdjustState:
         """the adjustment arguments of showo_engine_decode_sample_adj / _batch_decode_sample_adj, and what must stay alive over the call"""
         import ctypes as C
         pen, rows = self.host_args()
-        return (_lib.ptr(self.seen), self.W, C.cast(pen, C.c_void_p), C.cast(rows, C.c_void_p), _lib.ptr(self.ws)), (pen, rows)
+        args, keep = (_lib.ptr(self.seen), self.W, C.cast(pen, C.c_void_p), C.cast(rows, C.c_void_p), _lib.ptr(self.ws)), (pen, rows)
+        if self.ruled:  # the _seq entries: the rules behind adj_ws
+            q, keep_q = self.rules_args()
+            args, keep = args + (q,), keep + keep_q
+        return args, keep
+
+    def entry(self, adj_name):
+        """the loop entry: `adj_name` (an _adj entry), or its _seq form when some request has a device rule"""
+        return adj_name[:-4] + "_seq" if self.ruled else adj_name
 
 
 def _draw_seed(generator):
@@ -1167,19 +1345,24 @@ def _decode_batch1(model, eng, logits, tok, max_new_tokens, draw, eot_token, wan
     runs in chunks of `chunk` steps entirely on the device (embed -> 24 layers on the KV cache -> lm_head -> pick), one hipGraph
     replay per step, and the host looks at the tokens (for <eot>) once per chunk.
     `adjust` (an _Adjust): the first token is picked from the adjusted prefill logits (the stand-alone launch, the context ids marked)
-    and every chunk runs on showo_engine_decode_sample_adj, whose steps mark the token they feed; None: the calls of a call without."""
+    and every chunk runs on showo_engine_decode_sample_adj, whose steps mark the token they feed; None: the calls of a call without.
+    With sequence rules the device computes (adjust.rules) the first token also takes the stand-alone ban on the history = context and
+    the chunks run on showo_engine_decode_sample_seq; stop sequences cut the answer where the host looks at the tokens, as <eot> does."""
     greedy, k, p, temperature, noise, seed = draw
-    st = None
+    st, pick, stops = None, None, None
     if adjust is not None:
-        st = _AdjustState(model.vocab_size, 1, tok.device)
+        st = _AdjustState(model.vocab_size, 1, tok.device, _hist_ld([adjust], max_new_tokens), eot_token)
         st.seed(0, adjust)
-    lps = [_first_token(logits, model.vocab_size, tok, draw, want_lp, None if st is None else st.adjust(0, logits))]
+        pick = st.adjust(0, logits)
+        st.ban(0)  # (sequence rules: the history is the context, nothing marked)
+        stops = adjust.rules.stops if adjust.rules is not None else None
+    lps = [_first_token(logits, model.vocab_size, tok, draw, want_lp, pick)]
 
     def done(result):
         return (result, torch.cat(lps)[:len(result)]) if want_lp else result
 
     result = [int(tok.item())]
-    if (eot_token is not None and result[0] == eot_token) or max_new_tokens <= 1:
+    if (eot_token is not None and result[0] == eot_token) or max_new_tokens <= 1 or (stops and _stop_len(result, stops, None) is not None):
         return done(result[:max_new_tokens])
     use_graph, chunk = int(getattr(model, "decode_graph", 1)), 16
     remaining = max_new_tokens - 1
@@ -1192,7 +1375,7 @@ def _decode_batch1(model, eng, logits, tok, max_new_tokens, draw, eot_token, wan
         with _graph_stream_of(model):
             if st is not None:
                 args, keep = st.loop_args()
-                _lib.call("showo_engine_decode_sample_adj", *head, k, 1.0 if (greedy or p is None) else p,
+                _lib.call(st.entry("showo_engine_decode_sample_adj"), *head, k, 1.0 if (greedy or p is None) else p,
                           1.0 if greedy else float(temperature), _lib.ptr(noise), seed, step0, _lib.ptr(lps[-1]) if want_lp else None, None,
                           *args, use_graph, _lib.stream())
                 del keep
@@ -1208,7 +1391,7 @@ def _decode_batch1(model, eng, logits, tok, max_new_tokens, draw, eot_token, wan
                           _lib.stream())
         for t in outc.tolist():
             result.append(t)
-            if eot_token is not None and t == eot_token:
+            if (eot_token is not None and t == eot_token) or (stops and _stop_len(result, stops, None, len(result) - 1) is not None):
                 return done(result)
         remaining -= n
     return done(result)
@@ -1369,14 +1552,24 @@ def _mmu_batch_seeds(top_ks, generator):
     return seeds
 
 
-def _mmu_batch_schedule(eng, n, slots, max_new_tokens, eot_token, chunk=_MMU_BATCH_CHUNK):
+def _mmu_batch_schedule(eng, n, slots, max_new_tokens, eot_token, chunk=_MMU_BATCH_CHUNK, stops=None):
     """Serve requests 0..n-1 on `slots` decode slots; returns their token lists in input order.
 
     `eng` is the engine side: `prefill(slot, r)` puts request r into a free slot and returns its first token (drawn from the prefill
     logits); `decode(m, budget, draw0)` runs m steps of every slot -- slot s emits at most budget[s] tokens (0: idle) with draw indices
     draw0[s], draw0[s] + 1, ..., stopping early after <eot> -- and returns (rows, produced): the tokens of each slot and how many it
-    emitted.  Free slots are refilled in slot order with the pending requests in input order, at chunk boundaries."""
+    emitted.  Free slots are refilled in slot order with the pending requests in input order, at chunk boundaries.
+    `stops`: None, or per request None | its stop sequences (lists of ids): the answer ends behind the first position at which it ends
+    with one of them -- the match may straddle chunks; the slot is retired at the chunk boundary, the tokens behind the match dropped."""
     results = [None] * n
+
+    def stopped(r, start):
+        """cut request r's answer behind the first stop match that ends at or behind position `start`; True when there was one"""
+        cut = None if stops is None or not stops[r] else _stop_len(results[r], stops[r], None, start)
+        if cut is not None:
+            del results[r][cut:]
+        return cut is not None
+
     pending = list(range(n))[::-1]
     occupant = [None] * slots
     remaining = [0] * slots
@@ -1386,7 +1579,7 @@ def _mmu_batch_schedule(eng, n, slots, max_new_tokens, eot_token, chunk=_MMU_BAT
                 r = pending.pop()
                 first = eng.prefill(s, r)
                 results[r] = [first][:max_new_tokens]
-                if not ((eot_token is not None and first == eot_token) or max_new_tokens <= 1):
+                if not ((eot_token is not None and first == eot_token) or max_new_tokens <= 1 or stopped(r, 0)):
                     occupant[s], remaining[s] = r, max_new_tokens - 1
         live = [s for s in range(slots) if occupant[s] is not None]
         if not live:
@@ -1397,9 +1590,10 @@ def _mmu_batch_schedule(eng, n, slots, max_new_tokens, eot_token, chunk=_MMU_BAT
         rows, produced = eng.decode(m, budget, draw0)
         for s in live:
             toks = list(rows[s][:produced[s]])
+            had = len(results[occupant[s]])
             results[occupant[s]].extend(toks)
             remaining[s] -= produced[s]
-            if remaining[s] <= 0 or (eot_token is not None and toks and toks[-1] == eot_token):
+            if stopped(occupant[s], had) or remaining[s] <= 0 or (eot_token is not None and toks and toks[-1] == eot_token):
                 occupant[s] = None
 
 
@@ -1407,13 +1601,18 @@ class _MmuSlotEngine:
     """engine side of _mmu_batch_schedule: `slots` KV caches of showo_engine_batch_*, one request per slot"""
 
     def __init__(self, model, eng, idx, input_embeddings, masks, lens, slots, temps, top_ks, seeds, noises, eot_token, dev, top_ps=None,
-                 want_lp=False, adjusts=None):
+                 want_lp=False, adjusts=None, max_new_tokens=0):
         self.model, self.eng, self.idx, self.emb, self.masks, self.lens = model, eng, idx, input_embeddings, masks, lens
         # adjusts: None, or per request None | _Adjust -- every decode call then goes through showo_engine_batch_decode_sample_adj (an
         # unadjusted request's slot runs with penalty 1 and no bias row: a bit copy of its logits); a slot's bitmap row is cleared and
         # re-seeded with its request's context whenever the scheduler refills it
+        # sequence rules travel in the _Adjust: with a device rule in the batch every decode call is the _seq entry (one ban launch
+        # behind the adjust launch; a slot's history is re-seeded with its request's context); stop sequences are the scheduler's
         self.adjusts = adjusts
-        self.adj = None if adjusts is None else _AdjustState(model.vocab_size, slots, dev)
+        self.adj = None if adjusts is None else _AdjustState(model.vocab_size, slots, dev, _hist_ld(adjusts, max_new_tokens), eot_token)
+        self.stops = None
+        if adjusts is not None and any(a is not None and a.rules is not None and a.rules.stops for a in adjusts):
+            self.stops = [a.rules.stops if a is not None and a.rules is not None else None for a in adjusts]
         # want_lp: every decode call goes through showo_engine_batch_decode_sample_lp; lps[r] collects request r's log-probabilities
         self.lps = {} if want_lp else None
         self.slots, self.temps, self.top_ks, self.seeds, self.noises = slots, temps, top_ks, seeds, noises
@@ -1444,6 +1643,7 @@ class _MmuSlotEngine:
             self.adj.seed(s, self.adjusts[r])
             if self.adjusts[r] is not None:
                 pick = self.adj.adjust(s, self.logits[s])
+                self.adj.ban(s)
         lp = _first_token(self.logits[s], self.model.vocab_size, self.tok[s:s + 1], draw, self.lps is not None, pick)
         self.occ[s] = r
         if self.lps is not None:
@@ -1478,7 +1678,7 @@ class _MmuSlotEngine:
         with _graph_stream_of(self.model):
             if self.adj is not None:
                 args, keep = self.adj.loop_args()
-                _lib.call("showo_engine_batch_decode_sample_adj", self.eng, _lib.ptr(self.tok), m, _lib.ptr(out), _lib.ptr(self.logits),
+                _lib.call(self.adj.entry("showo_engine_batch_decode_sample_adj"), self.eng, _lib.ptr(self.tok), m, _lib.ptr(out), _lib.ptr(self.logits),
                           *(C.cast(a, C.c_void_p) for a in (a_k, a_p, a_t, a_s, a_d, a_n, a_b)), self.eot, C.cast(prod, C.c_void_p),
                           _lib.ptr(lp), None, *args, self.use_graph, _lib.stream())
                 del keep
@@ -1552,14 +1752,16 @@ def _run_on_slots(eng, n, wide, capacity, slot_engine, max_new_tokens, eot_token
     if not _batch_begin(eng, slots, capacity, bool(wide), bool(wide) and shared):
         return None
     se = slot_engine(slots)
-    out = _mmu_batch_schedule(se, n, slots, max_new_tokens, eot_token)
+    stops = getattr(se, "stops", None)
+    out = _mmu_batch_schedule(se, n, slots, max_new_tokens, eot_token, **({} if stops is None else {"stops": stops}))
     return (out, [se.logprobs(b, len(out[b])) for b in range(n)]) if want_lp else out
 
 
 @torch.no_grad()
 def mmu_generate_batch(self, idx=None, input_embeddings=None, attention_mask=None, max_new_tokens=100, temperature=1.0, top_k=None,
                        eot_token=None, generator=None, _exp_noise=None, top_p=None, return_logprobs=False, slots=None,
-                       repetition_penalty=None, repetition_context=None, logit_bias=None, allowed_tokens=None, banned_tokens=None):
+                       repetition_penalty=None, repetition_context=None, logit_bias=None, allowed_tokens=None, banned_tokens=None,
+                       no_repeat_ngram_size=None, bad_words_ids=None, min_new_tokens=None, stop_sequences=None):
     """n independent `mmu_generate` calls served together (BASELINE cfg4: "batch=4 images"; the reference's mmu_generate is batch-1 and
     inference_mmu.py:87-177 walks the images one by one).  `idx` / `input_embeddings` / `attention_mask` are LISTS (one entry per
     sequence, each what a single `mmu_generate` call takes: [1, L_b] ids or [1, L_b, H] embeddings, its own mask or IntervalMask);
@@ -1587,15 +1789,23 @@ def mmu_generate_batch(self, idx=None, input_embeddings=None, attention_mask=Non
     collections themselves); one dense bias row is built per distinct request.  Any adjusted request puts the whole batch on the slots
     of showo_engine_batch_decode_sample_adj (one adjust launch per step for all slots; an unadjusted request's slot gets a bit copy of
     its logits, so its tokens are those of a batch without); every slot keeps its own set, cleared and re-seeded when it is refilled.
-    All None, or penalty 1 without a bias: exactly the calls of a batch without the keywords."""
+    All None, or penalty 1 without a bias: exactly the calls of a batch without the keywords.
+
+    `no_repeat_ngram_size` / `bad_words_ids` / `min_new_tokens` / `stop_sequences` (`mmu_generate` states them): one value shared by all n
+    requests or a list of n per-request values (a sequence keyword is per request when its entries are None or lists of sequences
+    themselves).  Any request with one of them puts the whole batch on the slot scheduler, as an adjustment does; with a rule the
+    device computes the slots run on showo_engine_batch_decode_sample_seq (one ban launch per step behind the adjust launch; every slot
+    keeps its own token history, re-seeded with the context when it is refilled); a request without rules gets the tokens of a batch
+    without the keywords.  A stop sequence retires its slot at the next chunk boundary.  All None: exactly the calls of today."""
     seqs = idx if idx is not None else input_embeddings
     n = len(seqs)
     wide = _mmu_wide_slots(slots, n, getattr(self, "_precision", 0))
     temps, top_ks, top_ps, noises, masks = _per_request(n, temperature, top_k, top_p, _exp_noise, attention_mask)
     adjusts, adj_kws = None, [{}] * n
-    if any(v is not None for v in (repetition_penalty, repetition_context, logit_bias, allowed_tokens, banned_tokens)):
+    if any(v is not None for v in (repetition_penalty, repetition_context, logit_bias, allowed_tokens, banned_tokens, no_repeat_ngram_size,
+                                   bad_words_ids, min_new_tokens, stop_sequences)):
         adjusts, adj_kws = _adjust_per_request(n, self.vocab_size, repetition_penalty, repetition_context, logit_bias, allowed_tokens,
-                                               banned_tokens)
+                                               banned_tokens, no_repeat_ngram_size, bad_words_ids, min_new_tokens, stop_sequences, eot_token)
 
     def single(b):
         return self.mmu_generate(idx=None if idx is None else idx[b], input_embeddings=None if input_embeddings is None else input_embeddings[b],
@@ -1618,7 +1828,7 @@ def mmu_generate_batch(self, idx=None, input_embeddings=None, attention_mask=Non
     def slot_engine(slots):  # (the seeds are drawn behind a begin that succeeded: the sequential calls draw their own)
         return _MmuSlotEngine(self, eng, idx, input_embeddings, masks, lens, slots, temps, top_ks, _mmu_batch_seeds(top_ks, generator),
                               _batch_noises(top_ks, noises, dev), eot_token, dev, top_ps, want_lp=return_logprobs,
-                              **({} if adjusts is None else {"adjusts": adjusts}))
+                              **({} if adjusts is None else {"adjusts": adjusts, "max_new_tokens": max_new_tokens}))
 
     out = _run_on_slots(eng, n, wide, max(lens) + max_new_tokens + 1, slot_engine, max_new_tokens, eot_token, return_logprobs)
     if out is None:
@@ -1686,8 +1896,9 @@ class _SessionSlotEngine(_MmuSlotEngine):
     rows are appended to the session's own cache, copied into the slot's suffix cache, and the session's cache is rewound"""
 
     def __init__(self, model, eng, rows, lens, slots, temps, top_ks, seeds, noises, eot_token, dev, top_ps=None, want_lp=False,
-                 share_prefix=False, adjusts=None):
-        super().__init__(model, eng, None, None, None, lens, slots, temps, top_ks, seeds, noises, eot_token, dev, top_ps, want_lp, adjusts)
+                 share_prefix=False, adjusts=None, max_new_tokens=0):
+        super().__init__(model, eng, None, None, None, lens, slots, temps, top_ks, seeds, noises, eot_token, dev, top_ps, want_lp, adjusts,
+                         max_new_tokens)
         self.rows = rows
         self.share_prefix = share_prefix
 
@@ -1791,7 +2002,7 @@ class _SessionEngine:
 
         def slot_engine(slots):
             return _SessionSlotEngine(self.model, self.eng, rows, lens, slots, temps, top_ks, seeds, noises, eot_token, self.dev, top_ps,
-                                      want_lp=return_logprobs, share_prefix=shared, adjusts=adjusts)
+                                      want_lp=return_logprobs, share_prefix=shared, adjusts=adjusts, max_new_tokens=max_new_tokens)
 
         capacity = _shared_suffix_capacity(length, lens, max_new_tokens) if shared else length + max(lens) + max_new_tokens + 1
         return _run_on_slots(self.eng, len(rows), slots, capacity, slot_engine, max_new_tokens, eot_token, return_logprobs, shared=shared)
@@ -1941,7 +2152,8 @@ class MmuSession:
     def generate(self, idx=None, input_embeddings=None, max_new_tokens=100, temperature=1.0, top_k=None, eot_token=None, generator=None,
                  _exp_noise=None, top_p=None, return_logprobs=False, repetition_penalty=None, repetition_context=None, logit_bias=None,
                  allowed_tokens=None, banned_tokens=None, num_beams=None, length_penalty=1.0, early_stopping=False,
-                 num_return_sequences=1, return_beam_scores=False):
+                 num_return_sequences=1, return_beam_scores=False, no_repeat_ngram_size=None, bad_words_ids=None, min_new_tokens=None,
+                 stop_sequences=None):
         """Append the rows (ids [1, Ln] or embeddings [1, Ln, H]; none: continue where the last call stopped), then decode like
         `mmu_generate`: same return type, `eot_token` cut, greedy pick for top_k == 1 and sampled draws (`top_p`: nucleus).  Afterwards the cache holds the
         prefix, the rows and the answer up to its last token but one; the last token is pending and is fed first by the next call.
@@ -1949,17 +2161,20 @@ class MmuSession:
         `repetition_penalty` / `repetition_context` / `logit_bias` / `allowed_tokens` / `banned_tokens`: as `mmu_generate` takes them.  The
         set of seen tokens belongs to THIS call (the context ids, then the tokens it produces): it does not live in the session, `mark`
         / `rewind` and the cache do not know it, and an identical call from the same state gives identical tokens.
+        `no_repeat_ngram_size` / `bad_words_ids` / `min_new_tokens` / `stop_sequences`: as `mmu_generate` takes them.  The token history
+        belongs to THIS call as the set does; the session settles on an answer cut by a stop sequence as it does behind an <eot>.
         `num_beams` / `length_penalty` / `early_stopping` / `num_return_sequences` / `return_beam_scores`: as `mmu_generate` takes them
         (None or 1: the call without them).  The search runs on forks of the cache and leaves the session's rows as they are; afterwards
         the BEST hypothesis is the answer: its tokens but the last are appended with one showo_engine_prefill_append of ids and its
         last token is pending, the state shape a greedy `generate` leaves.  These answer rows carry the bits of the append path, not
         those of the decode steps that scored them (both are the rows of the same tokens; a follow-up turn reads the appended ones)."""
-        adj_vals = (repetition_penalty, repetition_context, logit_bias, allowed_tokens, banned_tokens)
+        adj_vals = (repetition_penalty, repetition_context, logit_bias, allowed_tokens, banned_tokens, no_repeat_ngram_size, bad_words_ids,
+                    min_new_tokens, stop_sequences)
         beams = _beam_request(self.model, num_beams, length_penalty, early_stopping, num_return_sequences, return_beam_scores, max_new_tokens,
                               temperature, top_k, top_p, generator, _exp_noise, any(v is not None for v in adj_vals))
         if beams is not None and not hasattr(self._be, "run_beam"):
             raise ValueError("beam search needs the KV-cached engine (precision 0, 2 or 3)")
-        adjust = _adjust_of(self.model.vocab_size, *adj_vals) if any(v is not None for v in adj_vals) else None
+        adjust = _adjust_of(self.model.vocab_size, *adj_vals, eot_token=eot_token) if any(v is not None for v in adj_vals) else None
         self._check()
         ids, emb, Ln = self._rows(idx, input_embeddings)
         if Ln == 0 and self.length != self.prefix_length:
@@ -2034,7 +2249,8 @@ class MmuSession:
     @torch.no_grad()
     def generate_batch(self, idx=None, input_embeddings=None, max_new_tokens=100, temperature=1.0, top_k=None, eot_token=None,
                        generator=None, _exp_noise=None, top_p=None, return_logprobs=False, slots=None, share_prefix=False,
-                       repetition_penalty=None, repetition_context=None, logit_bias=None, allowed_tokens=None, banned_tokens=None):
+                       repetition_penalty=None, repetition_context=None, logit_bias=None, allowed_tokens=None, banned_tokens=None,
+                       no_repeat_ngram_size=None, bad_words_ids=None, min_new_tokens=None, stop_sequences=None):
         """n continuations of the CURRENT state: `idx` / `input_embeddings` is a list of n row blocks ([1, Ln_i] ids or [1, Ln_i, H]
         embeddings), `temperature` / `top_k` / `top_p` scalars or lists, `_exp_noise` None or a list.  result[i] is what `generate(<block i>)`
         followed by a rewind returns when those calls are made in order (same seeds from `generator`); the session is left unchanged.
@@ -2051,13 +2267,17 @@ class MmuSession:
         rounded relative to its key segment's max, not the row's, and the fp32 sums are split); the session, including its cache
         bits, is unchanged afterwards.  n <= 8 is the call without `slots` / `share_prefix`.
         `repetition_penalty` / `repetition_context` / `logit_bias` / `allowed_tokens` / `banned_tokens`: shared values or per-request lists
-        as `Showo.mmu_generate_batch` takes them; every request has its own set of seen tokens, none of it stays in the session."""
+        as `Showo.mmu_generate_batch` takes them; every request has its own set of seen tokens, none of it stays in the session.
+        `no_repeat_ngram_size` / `bad_words_ids` / `min_new_tokens` / `stop_sequences`: shared values or per-request lists as
+        `Showo.mmu_generate_batch` takes them; every request has its own token history, none of it stays in the session."""
         seqs = idx if idx is not None else input_embeddings
         n = len(seqs)
         adjusts, adj_kws = None, [{}] * n
-        if any(v is not None for v in (repetition_penalty, repetition_context, logit_bias, allowed_tokens, banned_tokens)):
+        if any(v is not None for v in (repetition_penalty, repetition_context, logit_bias, allowed_tokens, banned_tokens, no_repeat_ngram_size,
+                                       bad_words_ids, min_new_tokens, stop_sequences)):
             adjusts, adj_kws = _adjust_per_request(n, self.model.vocab_size, repetition_penalty, repetition_context, logit_bias,
-                                                   allowed_tokens, banned_tokens)
+                                                   allowed_tokens, banned_tokens, no_repeat_ngram_size, bad_words_ids, min_new_tokens,
+                                                   stop_sequences, eot_token)
         self._check()
         if share_prefix and slots is None:
             raise ValueError("share_prefix needs slots=S (the slots of a wide decode batch share the prefix)")
@@ -2181,15 +2401,18 @@ def _mmu_generate_recompute(self, idx, input_embeddings, attention_mask, max_new
     logits = torch.empty((self.vocab_size,), dtype=torch.float32, device=dev)
     tok = torch.empty((1,), dtype=torch.int64, device=dev)
     result, lps = [], []
-    st = None
+    st, stops, ints = None, None, []
     if adjust is not None:
-        st = _AdjustState(self.vocab_size, 1, dev)
+        st = _AdjustState(self.vocab_size, 1, dev, _hist_ld([adjust], max_new_tokens), eot_token)
         st.seed(0, adjust)
+        stops = adjust.rules.stops if adjust.rules is not None else None
     for step in range(max_new_tokens):
         row.fill_(L - 1)
         _lib.call("showo_engine_forward_rows", eng, None, _lib.ptr(emb), _lib.ptr(mask), 1, L, _lib.ptr(row), 1, 0, self.vocab_size,
                   _lib.ptr(logits), _lib.stream())
         pick = logits if st is None else st.adjust(0, logits)
+        if st is not None:  # (sequence rules: the stand-alone ban; the token of the last step joins the history in front of it)
+            st.ban(0, tok if step else None)
         if greedy:
             _lib.call("showo_argmax_f32", _lib.ptr(pick), self.vocab_size, _lib.ptr(tok), _lib.stream())
         else:
@@ -2201,7 +2424,8 @@ def _mmu_generate_recompute(self, idx, input_embeddings, attention_mask, max_new
             lps.append(_logprob_of(logits, self.vocab_size, tok))
         t = int(tok.item())
         result.append(torch.tensor(t, device=dev))
-        if eot_token is not None and t == eot_token:
+        ints.append(t)
+        if (eot_token is not None and t == eot_token) or (stops and _stop_len(ints, stops, None, step) is not None):
             break
         mask = _grow_mask(mask, L, 1)
         emb = torch.cat([emb, self.showo.model.embed_tokens.weight.detach().float()[tok].reshape(1, 1, -1)], dim=1).contiguous()

@@ -20,6 +20,10 @@ against the sequential calls' (same generator seed).
                                                # without repetition_penalty, alternating in this process, at batch 1 and n = 4 / 16,
                                                # greedy and top_k=5, and (with --slots 32) on 32 wide slots at n = 32: medians over
                                                # --reps calls; writes profiles/logit_adjust_bench.json
+  python tools/mmu_batch_bench.py --no-repeat-ngram 4,16   # cost of the sequence rules (csrc/seq_rules.hip): every leg without a keyword,
+                                               # with an adjustment alone and with no_repeat_ngram_size, alternating in this process,
+                                               # at batch 1 and n = 4 / 16, greedy and top_k=5, and (with --slots 32) on 32 wide slots
+                                               # at n = 32: medians over --reps calls; writes profiles/seq_rules_bench.json
   python tools/mmu_batch_bench.py --num-beams 4,8   # beam search (csrc/beam.hip) against mmu_generate_batch of as many greedy
                                                # sequences, alternating in this process: tokens/s of the best hypothesis, ms per step
                                                # of both legs and their difference; writes profiles/beam_bench.json
@@ -200,6 +204,55 @@ def penalty_legs(model, embs, masks, theta, reps, wide_slots=None):
     return res
 
 
+def seq_rule_legs(model, embs, masks, ngram, reps, wide_slots=None):
+    """tokens/s of every leg without a keyword ("off"), with banned_tokens alone ("adjust": the adjust launch the rules ride behind) and
+    with no_repeat_ngram_size=ngram ("on": the adjust launch as a bit copy plus the ban launch of csrc/seq_rules.hip), measured
+    alternately (off, adjust, on, off, ...) so that all see the same clocks; per leg the median and the min / max of `reps` whole calls
+    after one warm-up call each.  eot_token is None, so every leg emits the same number of tokens.  per_token_us: the difference of
+    the median call times of "on" and "off" over the tokens of the call; ban_per_token_us: that of "on" and "adjust", the ban launch
+    alone.  As with --repetition-penalty the batch-1 greedy "on" leg also trades the fused token seam for separate launches and the
+    n = 4 greedy one the all-greedy loop for the slot scheduler's; "adjust" makes the same trades."""
+    gen = lambda: torch.Generator(device="cuda").manual_seed(7)  # noqa: E731
+
+    def call(n, kw):
+        if n == 1:
+            return lambda: model.mmu_generate(input_embeddings=embs[0], attention_mask=masks[0], max_new_tokens=NEW, generator=gen(), **kw)
+        return lambda: model.mmu_generate_batch(input_embeddings=embs[:n], attention_mask=masks[:n], max_new_tokens=NEW, generator=gen(), **kw)
+
+    def once(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    res = {"shape": "cfg4: 631-embedding w_clip_vit prompts, 100 new tokens each, full-size seeded weights",
+           "unit": "tokens/s (whole call)", "reps": reps, "no_repeat_ngram_size": ngram}
+    shapes = [(1, {}), (4, {}), (16, {})] + ([(32, {"slots": wide_slots})] if wide_slots else [])
+    for n, extra in shapes:
+        for name, kw in (("greedy", GREEDY), ("topk5_t0.7", SAMPLED)):
+            kw = dict(kw, **extra)
+            legs = {"off": call(n, kw), "adjust": call(n, dict(kw, banned_tokens=[model.vocab_size - 1])),
+                    "on": call(n, dict(kw, no_repeat_ngram_size=ngram))}
+            for fn in legs.values():
+                fn()  # warm-up
+            times = {k: [] for k in legs}
+            for _ in range(reps):
+                for k, fn in legs.items():
+                    times[k].append(once(fn))
+            row = {}
+            for k, ts in times.items():
+                rate = sorted(n * NEW / t for t in ts)
+                row[k] = {"median": float(np.median(rate)), "min": rate[0], "max": rate[-1]}
+            med = {k: float(np.median(ts)) for k, ts in times.items()}
+            row["rules_overhead_percent"] = 100.0 * (med["on"] / med["off"] - 1.0)
+            row["per_token_us"] = 1e6 * (med["on"] - med["off"]) / (n * NEW)
+            row["ban_per_token_us"] = 1e6 * (med["on"] - med["adjust"]) / (n * NEW)
+            res[f"n{n}_{name}" + (f"_slots{wide_slots}" if extra else "")] = row
+            print(f"n={n} {name}: {row}", file=sys.stderr, flush=True)
+    return res
+
+
 def wide_legs(model, embs, masks, slot_counts, reps):
     """tokens/s of mmu_generate_batch without `slots` (the baseline: 8 slots of the dot2 kernels) and with slots=S for every S, measured
     alternately (None, S1, S2, None, ...) so that all legs see the same clocks; per leg the median and min / max of `reps` whole calls
@@ -312,7 +365,19 @@ def main():
     ap.add_argument("--profile-wide", type=int, default=None, help="one wide greedy call of 17 tokens on this many slots, for a kernel trace")
     ap.add_argument("--repetition-penalty", type=float, default=None,
                     help="measure repetition_penalty=THETA against the same legs without it (with --slots S: also n = 32 on S wide slots)")
+    ap.add_argument("--no-repeat-ngram", default=None,
+                    help="comma-separated sizes N (1..16): measure no_repeat_ngram_size=N against the same legs without it and with an adjustment alone (with --slots S: also "
+                         "n = 32 on S wide slots); writes profiles/seq_rules_bench.json")
     a = ap.parse_args()
+    if a.no_repeat_ngram is not None:
+        wide = int(a.slots.split(",")[0]) if a.slots else None
+        pkg, model, embs, masks = build(32 if wide else 16)
+        res = {f"no_repeat_ngram_{N}": seq_rule_legs(model, embs, masks, N, a.reps, wide) for N in (int(t) for t in a.no_repeat_ngram.split(","))}
+        out = a.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "seq_rules_bench.json")
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1)
+        print(json.dumps(res))
+        return
     if a.profile_beam is not None:
         pkg, model, embs, masks = build(1)
         for _ in range(2):
