@@ -1189,6 +1189,35 @@ int64_t showo_train_generation(showo_trainer* t);
 int showo_train_bind_param(showo_trainer* t, const char* key, float* param, float* exp_avg, float* exp_avg_sq, int64_t n);
 int showo_train_adamw_step(showo_trainer* t, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                            void* stream);
+/* ---- EMA of the weights (reference models/training_utils.py:61-296 `EMA`; csrc/ema.hip) --------------------------------------
+ * One step of a shadow value s against its parameter p is the reference's s.sub_(one_minus_decay * (s - p)): d = s - p,
+ * t = one_minus_decay * d, s' = s - t, three fp32 operations each rounded on its own (never an fma).  one_minus_decay is the
+ * Python float 1 - decay rounded to fp32, in [0, 1].
+ *
+ * Stand-alone table over `count` pairs of contiguous fp32 device tensors (shadow[k], param[k], n[k] elements; host arrays, read
+ * and uploaded by create; pointers 4-byte aligned, 16-byte aligned ones move four elements per access).  dst_bf16 / dst_f32
+ * (host arrays or NULL, entries NULL or at most one of the two set per pair): where swap also writes the bf16 cast / the fp32
+ * copy of the value that goes into param[k].
+ *   update  modes (host, count ints, NULL = all 0): 0 = the step above, 1 = shadow[k] = param[k] (the reference's branch for a
+ *           parameter that does not require grad).  One launch.  The modes are kept on the device; a call with other modes than
+ *           the one before waits for the stream and uploads them, and is refused inside a stream capture.
+ *   swap    exchanges param[k] and shadow[k] in place, one launch, no third copy; twice restores every bit. */
+typedef struct showo_ema_table showo_ema_table;
+int showo_ema_table_create(float* const* shadow, float* const* param, const int64_t* n, int count, uint16_t* const* dst_bf16,
+                           float* const* dst_f32, showo_ema_table** out);
+void showo_ema_table_destroy(showo_ema_table* h);
+int showo_ema_table_update(showo_ema_table* h, const int* modes, float one_minus_decay, void* stream);
+int showo_ema_table_swap(showo_ema_table* h, void* stream);
+/* On the trainer: showo_train_bind_ema registers the shadow of a key bound with showo_train_bind_param (NULL takes it away).
+ * showo_train_set_ema announces one_minus_decay for the NEXT showo_train_adamw_step alone: that step updates the shadow of every
+ * trainable parameter from the new master value inside the AdamW launch (every trainable parameter needs a shadow); negative = no
+ * EMA, the step is the plain one.  With SHOWO_TRAIN_ADAMW_MULTI=0 the per-tensor AdamW is followed by one table update: same bits.
+ * Frozen parameters are not touched by either.  showo_train_ema_swap exchanges every shadowed parameter, frozen ones included, with
+ * its shadow and rewrites the engine's weight images from the values that go into the parameters (version stamps as after an
+ * optimizer step).  The segment tables are rebuilt after a bind / trainable-set change, outside a stream capture only. */
+int showo_train_bind_ema(showo_trainer* t, const char* key, float* shadow, int64_t n);
+int showo_train_set_ema(showo_trainer* t, float one_minus_decay);
+int showo_train_ema_swap(showo_trainer* t, void* stream);
 /* torch.nn.utils.clip_grad_norm_ on a flat fp32 gradient buffer (reference training/train.py:614-615): g *= min(max_norm /
  * (||g||_2 + 1e-6), 1).  Fixed-order reduction (block partials in double, one block sums them in index order), the coefficient stays in
  * device memory: out2 (device, 2 floats) = {total norm, coefficient}; ws = showo_grad_clip_ws_doubles() doubles of scratch. */

@@ -103,6 +103,13 @@ _PROTOS = {
     "showo_train_losses": [c_p, c_p, c_p],
     "showo_train_bind_param": [c_p, C.c_char_p, c_p, c_p, c_p, c_i64],
     "showo_train_adamw_step": [c_p, c_f, c_f, c_f, c_f, c_f, c_i, c_p],
+    # EMA of the weights (csrc/ema.hip): the stand-alone segment table, and shadows on the trainer handle
+    "showo_ema_table_create": [c_p, c_p, c_p, c_i, c_p, c_p, c_p],
+    "showo_ema_table_update": [c_p, c_p, c_f, c_p],
+    "showo_ema_table_swap": [c_p, c_p],
+    "showo_train_bind_ema": [c_p, C.c_char_p, c_p, c_i64],
+    "showo_train_set_ema": [c_p, c_f],
+    "showo_train_ema_swap": [c_p, c_p],
     "showo_attn_fwd_lse": [c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_p],
     "showo_head_transpose": [c_p, c_p, c_i, c_i, c_i, c_i, c_i64, c_i64, c_i, c_p],
     "showo_attn_bwd": [c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_p, c_i, c_p, c_p, c_p, c_p, c_p, c_p, c_i, c_p, c_i, c_p, c_i,
@@ -284,7 +291,8 @@ _PROTOS = {
     "showo_prof_totals": [c_i, c_p, c_p],
 }
 _I64 = {"showo_kv_permute_stage_elems": [c_i, c_i, c_i, c_i], "showo_gemm_tiled_elems": [c_i, c_i],"showo_conv3t_launches": [], "showo_conv3t_split_launches": [], "showo_train_generation": [c_p]}
-_VOID = {"showo_engine_destroy": [c_p], "showo_vq_destroy": [c_p], "showo_train_destroy": [c_p], "showo_clip_destroy": [c_p], "showo_projector_destroy": [c_p]}
+_VOID = {"showo_engine_destroy": [c_p], "showo_vq_destroy": [c_p], "showo_train_destroy": [c_p], "showo_clip_destroy": [c_p], "showo_projector_destroy": [c_p],
+         "showo_ema_table_destroy": [c_p]}
 EXPORTED_SYMBOLS = sorted(list(_PROTOS) + list(_VOID) + list(_I64) + ["showo_last_error"])
 
 EPI_BF16, EPI_GELU_BF16, EPI_F32, EPI_RESID_F32 = 0, 1, 2, 3

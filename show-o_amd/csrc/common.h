@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <cstdlib>
+#include <vector>
 
 namespace showo {
 
@@ -317,10 +318,37 @@ int set_error_msg(int code, const char* msg);
 
 // multi-tensor AdamW (train_kernels.hip adamw_multi_kernel; table built by train_engine.hip)
 namespace showo {
-struct AdamSeg { float *p, *m, *v; const float* g; bf16_t* dst16; float* dst32; int64_t n; int decay; };
+// s: the EMA shadow of p (read and written by the EMA instance of the kernel only; NULL without one)
+struct AdamSeg { float *p, *m, *v; const float* g; bf16_t* dst16; float* dst32; int64_t n; int decay; float* s; };
 constexpr int64_t ADAM_CHUNK = 65536;  // elements per block
+// omd < 0: the plain instance.  omd >= 0 (1 - decay of this step): the EMA instance, every segment's s must be set
 int adamw_multi_launch(const AdamSeg* segs, const int* seg_of, const int64_t* start_of, int nchunks, float lr, float beta1, float beta2,
-                       float eps, float weight_decay, int step, hipStream_t s);
+                       float eps, float weight_decay, int step, float omd, hipStream_t s);
+
+// EMA of the weights (ema.hip).  One step of a shadow value against its parameter, the reference's s.sub_(omd * (s - p)): a
+// subtraction, a product and a subtraction, each rounded to fp32 on its own.  Contraction is switched off for this body: a - b * c
+// as one fma rounds once and gives other bits.
+__device__ __forceinline__ float ema_next(float s, float p, float omd) {
+#pragma clang fp contract(off)
+    const float d = s - p;
+    const float t = omd * d;
+    return s - t;
+}
+struct EmaSeg { float *s, *p; bf16_t* dst16; float* dst32; int64_t n; };
+// a segment table on the device, cut into chunks of ADAM_CHUNK elements; modes[k] = 1: segment k copies (s = p) instead of averaging
+struct EmaTable {
+    EmaSeg* segs = nullptr;
+    int* modes = nullptr;
+    int* seg_of = nullptr;
+    int64_t* start_of = nullptr;
+    int chunks = 0, count = 0;
+    std::vector<int> host_modes;
+    int build(const std::vector<EmaSeg>& host);
+    int set_modes(const int* m, hipStream_t s);
+    int update(float omd, hipStream_t s) const;
+    int swap(hipStream_t s) const;
+    void release();
+};
 // cross-entropy backward pass with the three loss weights read from device memory g3[3] (train_kernels.hip)
 int ce_loss_dev_weights(const float* logits, int ldl, const int64_t* labels, int B, int L, int V, int b_t2i, int b_lm, int b_mmu,
                         int max_seq_len, const float* g3, void* rows_ws, int* counts, float* rowloss, uint16_t* dlogits, int ldd,

@@ -46,7 +46,7 @@ struct LayerPlan {
     bool any = true;
     std::vector<Grad> clear;  // frozen members of a group that one launch writes whole (q/k/v, LayerNorm pairs): cleared after it
 };
-struct Bound { std::string key; float *p, *m, *v; int64_t n; bool decay; };
+struct Bound { std::string key; float *p, *m, *v; int64_t n; bool decay; float* s = nullptr; };  // s: EMA shadow (showo_train_bind_ema)
 
 // SHOWO_TRAIN_TN (default 1): weight gradients by showo_gemm_tn_bf16 on the token-major tensors the backward already holds (dY, and the
 // activations saved by the forward) + showo_colsum_bf16 for the bias gradients; 0 = transpose both operands and run the k-contiguous
@@ -76,6 +76,14 @@ struct showo_trainer {
     int adam_chunks = 0;
     bool adam_dirty = true;
     std::vector<std::pair<std::string, uint64_t*>> adam_keys;  // tensors the table updates + their engine version stamps
+    // EMA of the weights (ema.hip): shadows bound per key, 1 - decay announced for the next optimizer step (negative: none), and two
+    // tables rebuilt under the rule of adam_dirty -- every shadowed tensor with its engine destination (the swap), and the trainable
+    // ones alone (the table update behind the per-tensor AdamW of SHOWO_TRAIN_ADAMW_MULTI=0)
+    bool adam_shadowed = false;  // every segment of the AdamW table carries a shadow
+    float ema_omd = -1.f;
+    bool ema_dirty = true;
+    showo::EmaTable ema_all, ema_trainable;
+    std::vector<std::pair<std::string, uint64_t*>> ema_keys;  // tensors of ema_all + their engine version stamps
     // head
     float *logits = nullptr, *gembed = nullptr, *gfln = nullptr, *gwlm = nullptr, *gblm = nullptr;
     bf16_t *dlogits = nullptr, *bigT = nullptr;  // bigT: [max(Vp, F, 3H), Tp] transposed image of the dY side (SHOWO_TRAIN_TN=0 only)
@@ -269,6 +277,8 @@ extern "C" void showo_train_destroy(showo_trainer* t) {
     if (!t) return;
     for (void* p : t->allocs) hipFree(p);
     if (t->adam_segs) { hipFree(t->adam_segs); hipFree(t->adam_seg_of); hipFree(t->adam_start_of); }
+    t->ema_all.release();
+    t->ema_trainable.release();
     if (t->ev_tc) hipEventDestroy(t->ev_tc);
     if (t->tc_host) hipHostFree(t->tc_host);
     delete t;
@@ -374,6 +384,7 @@ extern "C" int showo_train_set_trainable(showo_trainer* t, const char* key, int 
     else { t->frozen.insert(k); t->pending_zero.insert(k); }
     t->plan_dirty = true;
     t->adam_dirty = true;
+    t->ema_dirty = true;
     return 0;
 }
 
@@ -943,9 +954,75 @@ extern "C" int showo_train_bind_param(showo_trainer* t, const char* key, float* 
     bool decay = true;
     for (const char* x : nd) decay = decay && k.find(x) == std::string::npos;
     t->adam_dirty = true;  // the optimizer's segment table is rebuilt by the next step
+    t->ema_dirty = true;
     for (auto& b : t->bound)
-        if (b.key == k) { b.p = param; b.m = exp_avg; b.v = exp_avg_sq; b.n = n; b.decay = decay; return 0; }
+        if (b.key == k) { b.p = param; b.m = exp_avg; b.v = exp_avg_sq; b.n = n; b.decay = decay; return 0; }  // (a bound shadow stays)
     t->bound.push_back(Bound{k, param, exp_avg, exp_avg_sq, n, decay});
+    return 0;
+}
+
+// ---- EMA of the weights: a shadow tensor per bound key (NULL takes it away again); the tables are rebuilt by their next user
+extern "C" int showo_train_bind_ema(showo_trainer* t, const char* key, float* shadow, int64_t n) {
+    if (!t || !key) return set_error_msg(1, "train_bind_ema: null argument");
+    std::string k(key);
+    for (auto& b : t->bound)
+        if (b.key == k) {
+            if (b.n != n) return set_error_msg(2, "train_bind_ema: element count mismatch");
+            if (shadow && shadow == b.p) return set_error_msg(1, "train_bind_ema: the shadow is the parameter itself");
+            b.s = shadow;
+            t->adam_dirty = true;
+            t->ema_dirty = true;
+            return 0;
+        }
+    return set_error_msg(3, "train_bind_ema: the key has no bound parameter (showo_train_bind_param first)");
+}
+
+extern "C" int showo_train_set_ema(showo_trainer* t, float one_minus_decay) {
+    if (!t) return set_error_msg(1, "train_set_ema: null handle");
+    if (one_minus_decay > 1.f || one_minus_decay != one_minus_decay) return set_error_msg(1, "train_set_ema: 1 - decay must lie in [0, 1] (negative: no EMA)");
+    t->ema_omd = one_minus_decay < 0.f ? -1.f : one_minus_decay;
+    return 0;
+}
+
+static int ema_tables_sync(showo_trainer* t, hipStream_t s) {
+    if (!t->ema_dirty) return 0;
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    hipStreamIsCapturing(s, &cs);
+    if (cs != hipStreamCaptureStatusNone) return set_error_msg(7, "train ema: the segment tables must be built outside a stream capture");
+    std::vector<showo::EmaSeg> all, trainable;
+    t->ema_keys.clear();
+    for (auto& b : t->bound) {
+        if (!b.s) continue;
+        showo::EmaSeg sg{b.s, b.p, nullptr, nullptr, b.n};
+        if (!t->frozen.count(b.key)) trainable.push_back(sg);
+        uint16_t* d16 = nullptr;
+        TRY(showo_engine_slot(t->e, b.key.c_str(), b.n, &d16, &sg.dst32));
+        sg.dst16 = d16;
+        all.push_back(sg);
+        t->ema_keys.push_back({b.key, showo::engine_version(t->e, b.key.c_str())});
+    }
+    TRY(t->ema_all.build(all));
+    TRY(t->ema_trainable.build(trainable));
+    t->ema_dirty = false;
+    return 0;
+}
+
+// Exchange every shadowed parameter (frozen ones included) with its shadow in place and write the engine's images from the values that
+// go into the parameters; same bookkeeping as the optimizer step for the rewritten tensors.  Twice = every bit as before.
+extern "C" int showo_train_ema_swap(showo_trainer* t, void* stream) {
+    if (!t) return set_error_msg(1, "train_ema_swap: null handle");
+    hipStream_t s = (hipStream_t)stream;
+    TRY(ema_tables_sync(t, s));
+    if (t->ema_all.count == 0) return set_error_msg(1, "train_ema_swap: no shadow bound (showo_train_bind_ema)");
+    TRY(t->ema_all.swap(s));
+    showo_engine* e = t->e;
+    for (auto& kv : t->ema_keys) {
+        if (kv.second) *kv.second = ++e->clock;
+        e->lo_loaded.erase(kv.first);
+    }
+    e->px3_valid = false;
+    e->head3_valid = false;
+    e->img_f16 = false;
     return 0;
 }
 
@@ -958,6 +1035,8 @@ extern "C" int showo_train_adamw_step(showo_trainer* t, float lr, float beta1, f
     if (t->bound.empty()) return set_error_msg(1, "train_adamw_step: no parameters bound");
     // SHOWO_TRAIN_ADAMW_MULTI (default 1): one launch over a segment table instead of one adamw + one image refresh per tensor
     static const bool multi = env_flag("SHOWO_TRAIN_ADAMW_MULTI", true);
+    const float omd = t->ema_omd;  // announced for this step alone (showo_train_set_ema)
+    t->ema_omd = -1.f;
     if (multi) {
         hipStream_t s = (hipStream_t)stream;
         if (t->adam_dirty) {  // (re)build the table: segments = bound tensors with their engine destinations, chunks of ADAM_CHUNK elements
@@ -965,10 +1044,12 @@ extern "C" int showo_train_adamw_step(showo_trainer* t, float lr, float beta1, f
             std::vector<int> seg_of;
             std::vector<int64_t> start_of;
             t->adam_keys.clear();
+            t->adam_shadowed = true;
             for (auto& b : t->bound) {
                 if (t->frozen.count(b.key)) continue;
                 t->adam_keys.push_back({b.key, showo::engine_version(t->e, b.key.c_str())});
-                showo::AdamSeg sg{b.p, b.m, b.v, t->grads[b.key].p, nullptr, nullptr, b.n, b.decay ? 1 : 0};
+                showo::AdamSeg sg{b.p, b.m, b.v, t->grads[b.key].p, nullptr, nullptr, b.n, b.decay ? 1 : 0, b.s};
+                t->adam_shadowed = t->adam_shadowed && b.s != nullptr;
                 uint16_t* d16 = nullptr;
                 TRY(showo_engine_slot(t->e, b.key.c_str(), b.n, &d16, &sg.dst32));
                 sg.dst16 = d16;
@@ -989,7 +1070,8 @@ extern "C" int showo_train_adamw_step(showo_trainer* t, float lr, float beta1, f
             t->adam_chunks = (int)seg_of.size();
             t->adam_dirty = false;
         }
-        TRY(showo::adamw_multi_launch(t->adam_segs, t->adam_seg_of, t->adam_start_of, t->adam_chunks, lr, beta1, beta2, eps, weight_decay, step, s));
+        if (omd >= 0.f && !t->adam_shadowed) return set_error_msg(1, "train_adamw_step: EMA announced, but a trainable parameter has no shadow bound");
+        TRY(showo::adamw_multi_launch(t->adam_segs, t->adam_seg_of, t->adam_start_of, t->adam_chunks, lr, beta1, beta2, eps, weight_decay, step, omd, s));
         // the bookkeeping of showo_engine_weights_touched, for the rewritten tensors only
         showo_engine* e = t->e;
         for (auto& kv : t->adam_keys) {
@@ -1006,6 +1088,12 @@ extern "C" int showo_train_adamw_step(showo_trainer* t, float lr, float beta1, f
         const Grad& g = t->grads[b.key];
         TRY(showo_adamw(b.p, g.p, b.m, b.v, b.n, lr, beta1, beta2, eps, b.decay ? weight_decay : 0.f, step, stream));
         TRY(showo_engine_load(t->e, b.key.c_str(), b.p, b.n, stream));
+    }
+    if (omd >= 0.f) {  // the table update over the trainable tensors, from the masters the loop above just wrote: the fused form's bits
+        TRY(ema_tables_sync(t, (hipStream_t)stream));
+        for (auto& b : t->bound)
+            if (!b.s && !t->frozen.count(b.key)) return set_error_msg(1, "train_adamw_step: EMA announced, but a trainable parameter has no shadow bound");
+        TRY(t->ema_trainable.update(omd, (hipStream_t)stream));
     }
     return 0;
 }

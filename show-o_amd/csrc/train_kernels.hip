@@ -800,9 +800,12 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
 // from the register that holds the new master value -- 437 adamw launches + 181 casts + 256 copies per step become one kernel, and the
 // 5.8 GB of master weights are not read a second time by the cast.  Same expressions as adamw_kernel element by element (same bits).
 // chunk c = (segment seg_of[c], elements [start_of[c], start_of[c] + ADAM_CHUNK)).
+// EMA = true: the segment's shadow takes one EMA step against the new master value while it sits in the register (showo::ema_next,
+// omd = 1 - decay): 8 more bytes per element instead of a second pass over p.  The AdamW expressions are the same text in both instances.
+template <bool EMA>
 __global__ __launch_bounds__(256) void adamw_multi_kernel(const showo::AdamSeg* __restrict__ segs, const int* __restrict__ seg_of,
                                                           const int64_t* __restrict__ start_of, float lr, float beta1, float beta2, float eps,
-                                                          float wd_all, float bc1, float bc2) {
+                                                          float wd_all, float bc1, float bc2, float omd) {
     const showo::AdamSeg sg = segs[seg_of[blockIdx.x]];
     const int64_t i0 = start_of[blockIdx.x];
     const int64_t i1 = i0 + showo::ADAM_CHUNK < sg.n ? i0 + showo::ADAM_CHUNK : sg.n;
@@ -820,6 +823,7 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const showo::AdamSeg* 
         sg.p[i] = pn;
         if (sg.dst16) sg.dst16[i] = f2bf(pn);
         else if (sg.dst32) sg.dst32[i] = pn;
+        if (EMA) sg.s[i] = showo::ema_next(sg.s[i], pn, omd);
     }
 }
 
@@ -1231,11 +1235,12 @@ extern "C" int showo_adamw(float* p, const float* g, float* m, float* v, int64_t
 
 namespace showo {
 int adamw_multi_launch(const AdamSeg* segs, const int* seg_of, const int64_t* start_of, int nchunks, float lr, float beta1, float beta2,
-                       float eps, float weight_decay, int step, hipStream_t s) {
+                       float eps, float weight_decay, int step, float omd, hipStream_t s) {
     if (nchunks <= 0) return 0;
     if (step < 1) return set_error_msg(1, "adamw: step counts from 1");
     const float bc1 = 1.0f - powf(beta1, (float)step), bc2 = 1.0f - powf(beta2, (float)step);
-    adamw_multi_kernel<<<dim3(nchunks), dim3(256), 0, s>>>(segs, seg_of, start_of, lr, beta1, beta2, eps, weight_decay, bc1, bc2);
+    if (omd >= 0.f) adamw_multi_kernel<true><<<dim3(nchunks), dim3(256), 0, s>>>(segs, seg_of, start_of, lr, beta1, beta2, eps, weight_decay, bc1, bc2, omd);
+    else adamw_multi_kernel<false><<<dim3(nchunks), dim3(256), 0, s>>>(segs, seg_of, start_of, lr, beta1, beta2, eps, weight_decay, bc1, bc2, 0.f);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return set_error_hip(e, "adamw_multi launch", __FILE__, __LINE__);
     return 0;

@@ -70,7 +70,33 @@ class PretrainedMixin:
         extra = self._extra_config()
         if extra:
             out["_extra"] = extra  # underscore keys are private to the writer: the reference's ConfigMixin skips them
+        registered = self.__dict__.get("_registered_config")
+        if registered:
+            out.update(registered)
+            out["_registered"] = sorted(registered)  # not constructor arguments: from_pretrained leaves them out
         return out
+
+    def register_to_config(self, **kwargs):
+        """further top-level entries of config.json (the reference's ConfigMixin.register_to_config; `EMA.save_pretrained` stores
+        its scalars this way).  They are written by save_config and read back by load_config(..., return_unused_kwargs=True)."""
+        self.__dict__.setdefault("_registered_config", {}).update(kwargs)
+
+    @classmethod
+    def from_config(cls, config, device=None, **kwargs):
+        """a fresh module from a config dict: constructor arguments by name, plus what `_config_dict()` / config.json keep under
+        `_extra`; underscore keys and registered entries are left out.  device: build on the meta device and materialise there,
+        uninitialised (the caller fills every parameter), instead of initialising on the host."""
+        cfg = {k: v for k, v in dict(config).items() if not k.startswith("_") and k not in config.get("_registered", ())}
+        cfg.update(config.get("_extra", {}))
+        cfg.update(kwargs)
+        if device is None:
+            return cls(**cfg)
+        with torch.device("meta"):
+            model = cls(**cfg)
+        model = model.to_empty(device=device)
+        if hasattr(model, "_reset_buffers"):
+            model._reset_buffers()
+        return model
 
     def _extra_config(self):
         """constructor arguments outside the reference's config (e.g. a non-default Phi geometry of a test model)"""
@@ -84,13 +110,21 @@ class PretrainedMixin:
             f.write(json.dumps(self._config_dict(), indent=2, sort_keys=True) + "\n")
 
     @classmethod
-    def load_config(cls, pretrained_model_name_or_path, subfolder=None, **kwargs):
+    def load_config(cls, pretrained_model_name_or_path, subfolder=None, return_unused_kwargs=False, **kwargs):
+        """return_unused_kwargs: (config, entries of the file that are no constructor arguments), the reference's contract --
+        what register_to_config added, or any other top-level key outside `_config_keys` and the constructor's signature"""
         d = pretrained_model_name_or_path if subfolder is None else os.path.join(pretrained_model_name_or_path, subfolder)
         path = d if os.path.isfile(d) else os.path.join(d, cls.config_name)
         if not os.path.isfile(path):
             raise EnvironmentError(f"{path} not found (hub downloads are not supported: pass a local directory)")
         with open(path, encoding="utf-8") as f:
-            return json.load(f)
+            raw = json.load(f)
+        if not return_unused_kwargs:
+            return raw
+        import inspect
+        known = set(cls._config_keys) | set(inspect.signature(cls.__init__).parameters)
+        unused = {k: v for k, v in raw.items() if not k.startswith("_") and (k in raw.get("_registered", ()) or k not in known)}
+        return raw, unused
 
     # ---- weights --------------------------------------------------------------------------------------------------
     def save_pretrained(self, save_directory, is_main_process=True, save_function=None, safe_serialization=True, variant=None,
@@ -162,7 +196,7 @@ class PretrainedMixin:
         if not os.path.isdir(d):
             raise EnvironmentError(f"{d} is not a local directory (hub downloads are not supported offline)")
         raw = cls.load_config(d)
-        cfg = {k: v for k, v in raw.items() if not k.startswith("_")}
+        cfg = {k: v for k, v in raw.items() if not k.startswith("_") and k not in raw.get("_registered", ())}
         cfg.update(raw.get("_extra", {}))
         cfg.update(kwargs)
         if device is None:

@@ -226,7 +226,7 @@ class SplicedImage(NamedTuple):
 class Trainer:
     def __init__(self, model, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, coeffs=(1.0, 0.1, 1.0), group=None,
                  wire="bf16", max_grad_norm=None, force_exchange=False, reserve_cus=None, gradient_accumulation_steps=1,
-                 loss_rows="all", projector=False):
+                 loss_rows="all", *, ema=None, projector=False):
         """gradient_accumulation_steps = k (every training YAML of the reference carries it): one step() call is one micro-batch;
         the first of a window overwrites the native gradient buffer, the others add into it (the accumulating kernel forms,
         showo_train_set_accumulate) with loss weights coeffs / k, and only the k-th runs the exchange, clipping, AdamW and the image
@@ -245,7 +245,16 @@ class Trainer:
         gradients are one more exchange bucket, clipping takes ONE norm over the Show-o and projector gradients, the native AdamW
         updates them (no decay for names containing "bias"), checkpoints carry their moments after the showo.* entries -- and
         step_clip_vit() runs the micro-batch with the projector's rows spliced in (DESIGN.md "CLIP-ViT training step").  A model
-        whose showo is wholly frozen (LLaVA-pretrain) is accepted when the projector trains."""
+        whose showo is wholly frozen (LLaVA-pretrain) is accepted when the projector trains.
+        ema: None (default, off), a float decay, or a dict of `training_utils.EMA` keyword arguments (decay, min_decay,
+        update_after_step, use_ema_warmup, inv_gamma, power).  `self.ema` is then an EMA whose `shadow_params` follow
+        `self.params + self.pparams`, initialised as clones of the parameters.  Every call that closes an accumulation window counts one
+        EMA step (the reference idiom `if accelerator.sync_gradients: ema.step(...)`) and the native AdamW launch updates the shadows of
+        the trainable Show-o tensors from the new master values it holds in registers; the projector's shadows take one table launch
+        behind their AdamW.  Frozen tensors get no update: their shadows are set equal to the parameters whenever the binding is
+        (re)built, so a hand edit of a frozen tensor needs `model.mark_weights_dirty()` and a new binding, as it does today.  Ranks
+        exchange nothing for it: identical parameters give identical shadows.  `with trainer.ema_weights():` evaluates on the averaged
+        weights; do not call `self.ema.step()` yourself (DESIGN.md "EMA of the weights")."""
         import os
         self._loss_rows_mode = loss_rows_mode(loss_rows)  # before anything touches the device
         self.loss_rows = loss_rows
@@ -292,13 +301,33 @@ class Trainer:
             self._pgrad = torch.zeros(cur, dtype=torch.float32, device=self.pparams[0][1].device)
             self._pviews = {n: self._pgrad[o:o + p.numel()].view(p.shape) for o, (n, p) in zip(offs, self.pparams)}
         self._wire, self._force_exchange = wire, force_exchange
+        self.ema = self._make_ema(ema)
+        self._pema = None      # segment table of the projector's shadows (training_utils.EmaTable)
+        self._in_ema = False   # inside `with self.ema_weights()`: parameters and shadows are exchanged
         self._bound = None
         self._bind()
+
+    def _make_ema(self, ema):
+        if ema is None:
+            return None
+        from .training_utils import EMA
+        if isinstance(ema, bool) or not isinstance(ema, (float, int, dict)):
+            raise TypeError(f"Trainer(ema=...) takes None, a float decay or a dict of EMA keyword arguments, got {ema!r}")
+        kw = dict(ema) if isinstance(ema, dict) else {"decay": float(ema)}
+        if "parameters" in kw:
+            raise TypeError("Trainer(ema={...}): the parameters are the trainer's own")
+        if not 0.0 <= kw.get("decay", 0.9999) <= 1.0:
+            raise ValueError("Trainer(ema=...): decay must be between 0 and 1")
+        kw.setdefault("model_cls", type(self.model))
+        if "model_config" not in kw and hasattr(self.model, "config") and hasattr(self.model, "arch"):
+            kw["model_config"] = dict(self.model.config, **self.model.arch)
+        return EMA([p for _, p in self.params + self.pparams], **kw)
 
     def _binding_key(self, params=None, pparams=None):
         params = self.params if params is None else params
         pparams = self.pparams if pparams is None else pparams
-        return (self.tr.value if hasattr(self.tr, "value") else int(self.tr),) + tuple(p.data_ptr() for _, p in params + pparams)
+        shadows = tuple(s.data_ptr() for s in self.ema.shadow_params) if self.ema is not None else ()
+        return (self.tr.value if hasattr(self.tr, "value") else int(self.tr),) + tuple(p.data_ptr() for _, p in params + pparams) + shadows
 
     def _bind(self):
         """(Re)create everything that holds raw pointers into the native trainer or the parameters: the gradient-bucket views, the
@@ -327,18 +356,97 @@ class Trainer:
         if self._ptrains:  # the projector's gradients: one more bucket, behind the head's
             self._pbucket = len(self.buckets)
             self.buckets.append(self._pgrad)
+        if self.ema is not None:
+            self._bind_ema()
         import torch.distributed as dist
         group = self.group
         active = dist.is_available() and dist.is_initialized() and (dist.get_world_size(group) > 1 or self._force_exchange)
         self.exchange = GradientExchange(self.buckets, dist, group, wire=self._wire) if active else None
         self._bound = self._binding_key()
 
+    # ---- EMA of the weights (DESIGN.md "EMA of the weights")
+    def _bind_ema(self):
+        """shadows -> the native trainer (Show-o tensors, next to showo_train_bind_param) and one stand-alone table (projector tensors).
+        A shadow that no longer matches its parameter's device / shape is re-made as a clone; a frozen tensor's shadow is set equal to
+        the parameter, here and nowhere else."""
+        from .training_utils import EmaTable
+        named = self.params + self.pparams
+        sh = self.ema.shadow_params
+        if len(sh) != len(named):
+            raise ValueError(f"Trainer: the EMA holds {len(sh)} shadows, the trainer has {len(named)} parameters")
+        trains = dict(self.trainable, **self.ptrainable)
+        with torch.no_grad():
+            for i, (n, p) in enumerate(named):
+                s = sh[i]
+                if s.device != p.device or s.shape != p.shape or s.dtype != torch.float32 or not s.is_contiguous():
+                    sh[i] = p.detach().clone()
+                elif not trains[n]:
+                    s.copy_(p)
+        for (n, p), s in zip(self.params, sh):
+            _lib.call("showo_train_bind_ema", self.tr, n.encode(), s.data_ptr(), p.numel())
+        if self._pema is not None:
+            torch.cuda.synchronize(self._pema.device)  # a launch over the old table may still be in flight
+            self._pema.close()
+            self._pema = None
+        if self.pparams:
+            self._pema = EmaTable(sh[len(self.params):], [p.detach() for _, p in self.pparams])
+            self._pmodes = [not self.ptrainable[n] for n, _ in self.pparams]
+
+    def _ema_swap(self):
+        """exchange parameters and shadows in place on the step's compute stream; the engine's and the projector's images follow"""
+        ms = self.compute_stream()
+        cur = torch.cuda.current_stream()
+        if ms is not None:
+            ms.wait_stream(cur)
+        with torch.cuda.stream(ms if ms is not None else cur):
+            _lib.call("showo_train_ema_swap", self.tr, _lib.stream())
+            if self._pema is not None:
+                self._pema.swap()
+                self._projector_refresh([n for n, _ in self.pparams])
+        if ms is not None:
+            cur.wait_stream(ms)
+
+    def ema_weights(self):
+        """`with trainer.ema_weights():` -- inside, the model's parameters ARE the averaged weights (and the shadows hold the raw
+        ones): `model.forward`, `t2i_generate`, `mmu_generate` and `score` run on them through the normal engine, whose weight images
+        the swap kernel rewrote.  No third copy of the weights exists at any time.  The exit swaps back, exceptions included, and
+        restores every bit.  Inside, step(), state_dict() and a nested ema_weights() raise RuntimeError."""
+        import contextlib
+
+        @contextlib.contextmanager
+        def scope():
+            if self.ema is None:
+                raise RuntimeError("Trainer.ema_weights needs Trainer(model, ema=...)")
+            if self._in_ema:
+                raise RuntimeError("Trainer.ema_weights: already inside ema_weights(); the parameters hold the averaged weights")
+            self.tr = self.model.trainer()
+            if self._binding_key() != self._bound:
+                if self.window.is_open:
+                    raise RuntimeError("Trainer.ema_weights: the native trainer or a tensor's storage changed inside an open accumulation window")
+                self.params = [("showo." + n, p) for n, p in self.model.showo.named_parameters()]
+                self.pparams = [("mm_projector." + n, p) for n, p in self.model.mm_projector.named_parameters()] if self.projector else []
+                self._bind()
+            self._ema_swap()
+            self._in_ema = True
+            try:
+                yield self
+            finally:
+                self._in_ema = False
+                self._ema_swap()
+        return scope()
+
+    def _refuse_inside_ema(self, what):
+        if self._in_ema:
+            raise RuntimeError(f"Trainer.{what} inside ema_weights(): the parameters hold the averaged weights; leave the context first")
+
     # ---- checkpoint / resume of the optimizer (reference: accelerator.save_state / load_state, training/train.py:851-889, 429-443)
     def state_dict(self):
         """torch.optim.AdamW layout: {'state': {i: {'step', 'exp_avg', 'exp_avg_sq'}}, 'param_groups': [...]} with the parameters
         numbered in `model.showo.named_parameters()` order, so the file is interchangeable with an AdamW built over that list.
         A projector=True trainer appends mm_projector.0.weight, .0.bias, .2.weight, .2.bias (the `model.named_parameters()` order).
-        Refused inside an open accumulation window: the partial gradient sum is not part of the file."""
+        Refused inside an open accumulation window: the partial gradient sum is not part of the file.
+        With EMA on, an "ema" entry holds `EMA.state_dict()` with the shadows cloned."""
+        self._refuse_inside_ema("state_dict")
         if self.window.is_open:
             raise RuntimeError(f"Trainer.state_dict inside an open accumulation window (micro-batch {self.window.position} of "
                                f"{self.window.steps}): the partial gradient sum is not saved; checkpoint when sync_gradients is True")
@@ -346,11 +454,18 @@ class Trainer:
                      "exp_avg_sq": self.v[n].detach().clone()} for i, (n, _) in enumerate(self.params + self.pparams)}
         group = {"lr": self.lr, "betas": tuple(self.betas), "eps": self.eps, "weight_decay": self.wd,
                  "params": list(range(len(self.params) + len(self.pparams)))}
-        return {"state": state, "param_groups": [group], "param_names": [n for n, _ in self.params + self.pparams]}
+        out = {"state": state, "param_groups": [group], "param_names": [n for n, _ in self.params + self.pparams]}
+        if self.ema is not None:
+            out["ema"] = dict(self.ema.state_dict(), shadow_params=[s.detach().clone() for s in self.ema.shadow_params])
+        return out
 
     def load_state_dict(self, sd):
         """moments are copied INTO the tensors bound to the native optimizer (showo_train_bind_param); lr / betas / eps / weight
-        decay / step count are taken from the file.  An open accumulation window is dropped: the next step() starts a new one."""
+        decay / step count are taken from the file.  An open accumulation window is dropped: the next step() starts a new one.
+        EMA: a file with an "ema" entry restores the scalars and copies the shadows into the bound tensors; a file without one, loaded
+        into an EMA trainer, resets the shadows to the current parameters and `optimization_step` to 0 (the averaging starts over);
+        a trainer without EMA ignores the entry."""
+        self._refuse_inside_ema("load_state_dict")
         self.window.reset()
         self.sync_gradients = False
         names = [n for n, _ in self.params + self.pparams]
@@ -375,6 +490,27 @@ class Trainer:
         g = sd["param_groups"][0]
         self.lr, self.betas, self.eps, self.wd = float(g["lr"]), tuple(g["betas"]), float(g["eps"]), float(g["weight_decay"])
         self.step_count = steps.pop() if steps else 0
+        self._load_ema(sd.get("ema"))
+
+    def _load_ema(self, esd):
+        if self.ema is None:
+            return
+        sh = self.ema.shadow_params
+        with torch.no_grad():
+            if esd is None:
+                for s, (_, p) in zip(sh, self.params + self.pparams):
+                    s.copy_(p)
+                self.ema.optimization_step, self.ema.cur_decay_value = 0, None
+                return
+            src = esd.get("shadow_params")
+            if src is not None:
+                if len(src) != len(sh) or any(tuple(a.shape) != tuple(b.shape) for a, b in zip(src, sh)):
+                    raise ValueError("EMA state was saved for a different parameter list")
+            self.ema.load_state_dict({k: v for k, v in esd.items() if k != "shadow_params"})
+            if src is not None:
+                for s, a in zip(sh, src):  # INTO the tensors bound to the native trainer
+                    s.copy_(a)
+        self.ema.cur_decay_value = self.ema.get_decay(self.ema.optimization_step) if self.ema.optimization_step > 0 else None
 
     def set_lr(self, lr):
         """learning-rate schedulers (training/train.py:303-310 `get_scheduler`) call this between steps; inside an accumulation
@@ -490,6 +626,7 @@ class Trainer:
         return out
 
     def _step(self, input_ids, attention_mask, labels, batch_size_t2i, batch_size_lm, batch_size_mmu, max_seq_length, image=None):
+        self._refuse_inside_ema("step")
         # model.trainer() re-uploads parameters whose (data_ptr, version) changed since the last call (load_state_dict, resume,
         # manual edits); the native AdamW below updates them through raw pointers and refreshes the engine images itself
         self.tr = self.model.trainer()
@@ -552,10 +689,17 @@ class Trainer:
             ex.finish()
         self.grad_norm = self.clip_grad_norm_(self.max_grad_norm) if self.max_grad_norm is not None else None
         self.step_count += 1
+        omd = None
+        if self.ema is not None:  # one EMA step per optimizer step, not per micro-batch
+            omd = self.ema.advance()[1]
         if self._showo_trains:
+            if omd is not None:  # announced for this launch alone: the shadows are updated from the new master values in registers
+                _lib.call("showo_train_set_ema", tr, omd)
             _lib.call("showo_train_adamw_step", tr, self.lr, self.betas[0], self.betas[1], self.eps, self.wd, self.step_count, _lib.stream())
         if self._ptrains:
             self._projector_adamw()
+        if omd is not None and self._pema is not None:
+            self._pema.update(omd, self._pmodes)
         self.sync_gradients = True
         return losses
 
@@ -563,12 +707,19 @@ class Trainer:
         """torch.optim.AdamW on the projector's trainable tensors (reference training/train_w_clip_vit.py:226-239: names containing
         `bias` take no decay), then their bf16 images go to the HIP projector from the updated masters -- what mark_weights_dirty()
         would make the next forward do, without its host wait"""
-        mm = self.model.mm_projector
         for n, p in self.pparams:
             if not self.ptrainable[n]:
                 continue
             _lib.call("showo_adamw", p.data_ptr(), self._pviews[n].data_ptr(), self.m[n].data_ptr(), self.v[n].data_ptr(), p.numel(),
                       self.lr, self.betas[0], self.betas[1], self.eps, 0.0 if "bias" in n else self.wd, self.step_count, _lib.stream())
+            self._projector_refresh([n])
+
+    def _projector_refresh(self, names):
+        """the HIP projector's images of these tensors, from masters that were rewritten through raw pointers"""
+        mm = self.model.mm_projector
+        for n, p in self.pparams:
+            if n not in names:
+                continue
             if getattr(mm, "_proj", None) is not None and mm._versions is not None:
                 k = n[len("mm_projector."):]
                 _lib.call("showo_projector_load", mm._proj, k.encode(), p.data_ptr(), p.numel(), _lib.stream())

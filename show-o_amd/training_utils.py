@@ -168,3 +168,205 @@ def labelled_rows(labels, batch_size_t2i, batch_size_lm, batch_size_mmu, max_seq
     in_mmu = torch.ones_like(in_lm) if batch_size_mmu == 0 else (b >= B - batch_size_mmu)
     live = t2i | (nxt & (in_lm | in_mmu))
     return torch.nonzero(live.reshape(-1)).reshape(-1).to(torch.int64)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# EMA of the weights (reference models/training_utils.py:61-296, itself adapted from torch-ema)
+# ---------------------------------------------------------------------------------------------------------------
+EMA_SCALAR_KEYS = ("decay", "min_decay", "optimization_step", "update_after_step", "use_ema_warmup", "inv_gamma", "power")
+
+
+def _ema_native_pairs(shadows, params):
+    """True when every (shadow, parameter) pair can go through the segment-table kernel: contiguous fp32 CUDA tensors of one
+    device and equal element counts"""
+    if not shadows or len(shadows) != len(params):
+        return False
+    dev = shadows[0].device
+    if dev.type != "cuda":
+        return False
+    for s, p in zip(shadows, params):
+        if s.device != dev or p.device != dev or s.dtype != torch.float32 or p.dtype != torch.float32:
+            return False
+        if not s.is_contiguous() or not p.is_contiguous() or s.numel() != p.numel():
+            return False
+    return True
+
+
+class EmaTable:
+    """showo_ema_table (include/showo_hip.h): one update / swap launch over pairs of contiguous fp32 CUDA tensors.  The table holds raw
+    pointers: the caller keeps the tensors alive and builds a new table when storage moves.  dst16 / dst32: optional lists of tensors
+    (or None entries) that swap() also writes the bf16 cast / fp32 copy of the new parameter values to."""
+
+    def __init__(self, shadows, params, dst16=None, dst32=None):
+        import ctypes as C
+        k = len(shadows)
+        arr = lambda ts: (C.c_void_p * k)(*[(t.data_ptr() if t is not None and t.numel() else None) for t in ts])
+        self.count = k
+        self.device = shadows[0].device
+        h = C.c_void_p()
+        _lib.call("showo_ema_table_create", arr(shadows), arr(params), (C.c_int64 * k)(*[int(s.numel()) for s in shadows]), k,
+                  arr(dst16) if dst16 is not None else None, arr(dst32) if dst32 is not None else None, C.byref(h))
+        self._h = h
+
+    def update(self, one_minus_decay, modes=None):
+        import ctypes as C
+        m = (C.c_int * self.count)(*[int(bool(v)) for v in modes]) if modes is not None else None
+        with torch.cuda.device(self.device):
+            _lib.call("showo_ema_table_update", self._h, m, float(one_minus_decay), _lib.stream())
+
+    def swap(self):
+        with torch.cuda.device(self.device):
+            _lib.call("showo_ema_table_swap", self._h, _lib.stream())
+
+    def close(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h is not None:
+            _lib.load().showo_ema_table_destroy(h)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class EMA:
+    """Exponential moving average of a model's weights; the reference class's constructor, attributes, methods and `state_dict`
+    keys.  `shadow_params[i]` follows `parameters[i]`:  shadow -= (1 - decay_t) * (shadow - parameter)  once per `step()`, with the
+    decay of `get_decay`; a parameter that does not require grad is copied instead.
+
+    `Trainer(model, ema=...)` owns one of these and updates it inside its AdamW launch; this class alone serves any list of tensors."""
+
+    def __init__(self, parameters, decay=0.9999, min_decay=0.0, update_after_step=0, use_ema_warmup=False, inv_gamma=1.0, power=2 / 3,
+                 model_cls=None, model_config=None, **kwargs):
+        """decay: the ceiling of the decay factor; min_decay: its floor; update_after_step: steps before averaging starts (the shadows
+        copy the parameters until then: decay 0); use_ema_warmup / inv_gamma / power: decay_t = 1 - (1 + t / inv_gamma) ** -power
+        instead of (1 + t) / (10 + t).  model_cls / model_config: what `save_pretrained` rebuilds the model from
+        (`model_cls.from_config(model_config)`; for a Showo, `dict(model.config, **model.arch)`)."""
+        self.shadow_params = [p.clone().detach() for p in parameters]
+        self.temp_stored_params = None
+        self.decay, self.min_decay, self.update_after_step = decay, min_decay, update_after_step
+        self.use_ema_warmup, self.inv_gamma, self.power = use_ema_warmup, inv_gamma, power
+        self.optimization_step = 0
+        self.cur_decay_value = None  # set by step()
+        self.model_cls, self.model_config = model_cls, model_config
+        self._table, self._table_key = None, None
+
+    # ---- the decay schedule
+    def get_decay(self, optimization_step):
+        t = optimization_step - self.update_after_step - 1
+        if t <= 0:
+            return 0.0
+        warm = 1 - (1 + t / self.inv_gamma) ** -self.power if self.use_ema_warmup else (1 + t) / (10 + t)
+        return max(min(warm, self.decay), self.min_decay)
+
+    def advance(self):
+        """count one optimization step and return (decay, 1 - decay) of it: the bookkeeping half of step(), for a caller that
+        updates the shadows itself (the Trainer's fused AdamW launch)"""
+        self.optimization_step += 1
+        self.cur_decay_value = self.get_decay(self.optimization_step)
+        return self.cur_decay_value, 1 - self.cur_decay_value
+
+    # ---- the update
+    @torch.no_grad()
+    def step(self, parameters):
+        """One EMA step of every shadow against `parameters` (same order as at construction).
+
+        When every shadow / parameter pair is a contiguous fp32 CUDA tensor this is ONE launch over a segment table (cached on the
+        data pointers and `requires_grad` flags; csrc/ema.hip), with the reference's three fp32 roundings per element.  Anything else
+        (CPU tensors, other dtypes after `to(dtype=...)`, non-contiguous tensors) runs the same expression in torch.
+        Unlike the reference this does not call `torch.cuda.empty_cache()`: that is a device-wide stall with no effect on results."""
+        parameters = list(parameters)
+        _, one_minus_decay = self.advance()
+        if _ema_native_pairs(self.shadow_params, parameters):
+            flags = tuple(not p.requires_grad for p in parameters)
+            self._native_table(parameters).update(one_minus_decay, flags)
+            return
+        for s, p in zip(self.shadow_params, parameters):
+            if p.requires_grad:
+                s.sub_(one_minus_decay * (s - p))
+            else:
+                s.copy_(p)
+
+    def _native_table(self, parameters):
+        key = tuple((s.data_ptr(), p.data_ptr(), s.numel(), bool(p.requires_grad)) for s, p in zip(self.shadow_params, parameters))
+        if self._table is None or self._table_key != key:
+            if self._table is not None:
+                torch.cuda.synchronize(self._table.device)  # a launch over the old table may still be in flight
+                self._table.close()
+            self._table = EmaTable(self.shadow_params, [p.detach() for p in parameters])
+            self._table_key = key
+        return self._table
+
+    # ---- moving the averages around
+    def copy_to(self, parameters):
+        """write the averaged weights into `parameters`.  On the parameters of a `Showo` follow it with `model.mark_weights_dirty()`:
+        a write through `.data` does not bump the version counter the engine watches (the rule for every manual edit)."""
+        for s, p in zip(self.shadow_params, list(parameters)):
+            p.data.copy_(s.to(p.device).data)
+
+    def to(self, device=None, dtype=None):
+        """move the shadows; `dtype` applies to floating-point shadows only.  Shadows that are not fp32 CUDA tensors afterwards take
+        the torch path of step()."""
+        self.shadow_params = [s.to(device=device, dtype=dtype) if s.is_floating_point() else s.to(device=device) for s in self.shadow_params]
+
+    def store(self, parameters):
+        """keep a CPU copy of `parameters` for restore() (validate with copy_to() in between)"""
+        self.temp_stored_params = [p.detach().cpu().clone() for p in parameters]
+
+    def restore(self, parameters):
+        if self.temp_stored_params is None:
+            raise RuntimeError("This ExponentialMovingAverage has no `store()`ed weights to `restore()`")
+        for c, p in zip(self.temp_stored_params, parameters):
+            p.data.copy_(c.data)
+        self.temp_stored_params = None
+
+    # ---- state
+    def state_dict(self):
+        """references, not copies (the torch convention)"""
+        sd = {k: getattr(self, k) for k in EMA_SCALAR_KEYS}
+        sd["shadow_params"] = self.shadow_params
+        return sd
+
+    def load_state_dict(self, state_dict):
+        import copy
+        sd = copy.deepcopy(state_dict)
+        self.decay = sd.get("decay", self.decay)
+        if self.decay < 0.0 or self.decay > 1.0:
+            raise ValueError("Decay must be between 0 and 1")
+        checks = (("min_decay", float), ("optimization_step", int), ("update_after_step", int), ("use_ema_warmup", bool),
+                  ("inv_gamma", (float, int)), ("power", (float, int)))
+        for k, kind in checks:
+            setattr(self, k, sd.get(k, getattr(self, k)))
+            if not isinstance(getattr(self, k), kind):
+                raise ValueError(f"Invalid {k}")
+        shadows = sd.get("shadow_params", None)
+        if shadows is not None:
+            self.shadow_params = shadows
+            if not isinstance(shadows, list):
+                raise ValueError("shadow_params must be a list")
+            if not all(isinstance(s, torch.Tensor) for s in shadows):
+                raise ValueError("shadow_params must all be Tensors")
+
+    # ---- a model directory with the averaged weights
+    def save_pretrained(self, path):
+        """writes a directory that `model_cls.from_pretrained(path)` loads with the shadows as its weights; the EMA scalars go into its
+        config.json under their state_dict names"""
+        if self.model_cls is None:
+            raise ValueError("`save_pretrained` can only be used if `model_cls` was defined at __init__.")
+        if self.model_config is None:
+            raise ValueError("`save_pretrained` can only be used if `model_config` was defined at __init__.")
+        dev = self.shadow_params[0].device if self.shadow_params else "cpu"
+        model = self.model_cls.from_config(self.model_config, device=dev)
+        model.register_to_config(**{k: getattr(self, k) for k in EMA_SCALAR_KEYS})
+        self.copy_to(model.parameters())
+        model.save_pretrained(path)
+
+    @classmethod
+    def from_pretrained(cls, path, model_cls):
+        _, scalars = model_cls.load_config(path, return_unused_kwargs=True)
+        model = model_cls.from_pretrained(path)
+        config = {k: v for k, v in model._config_dict().items() if k not in scalars}
+        ema = cls(model.parameters(), model_cls=model_cls, model_config=config)
+        ema.load_state_dict(scalars)
+        return ema
